@@ -3,7 +3,9 @@
 pipeline engine on Llama-3-70B Q4_K, PP = number of GPUs (BASELINE.json: "decode tokens/sec (whole
 node) + p50/token, Llama-3-70B PP=8 and 8B PP=1"; reference headline 2-3 tok/s for 70B, PDF p.12).
 
-    python bench.py --gpus 1 --steps 20 --warmup 5                  # PP=1 on one MI355X
+    python bench.py --gpus 1 --steps 20 --warmup 5                  # PP=1 on one MI355X: the headline only
+    python bench.py --gpus 1 --steps 20 --warmup 5 --full           # ... plus the secondary configs
+    python bench.py --gpus 1 --steps 20 --dump-outputs DIR          # ... plus the last round's tokens / logits (.npy)
     python bench.py --gpus 8 --steps 20 ...                          # PP=8 in ONE process (no launcher)
     torchrun --nproc-per-node 8 bench.py --gpus 8 --steps 20 ...     # PP=8, one rank per GPU
 
@@ -27,9 +29,12 @@ n_mb * mb_size sequences.  The timed region is exactly K decode rounds (every se
 token per round), bracketed by barrier + torch.cuda.synchronize() on both sides; the MAX over
 ranks is reported.
 
-At N > 1 (no replicas) it also measures BASELINE configs 3 and 5 on the same N-stage pipeline:
+A plain run sets up, warms up and times the headline configuration only.  `--dump-outputs DIR`
+then writes what the last timed round produced (inputs and weights are seeded, so two builds can
+be compared output for output).  The secondary configs run only with `--full`.
+At N > 1 (no replicas) `--full` also measures BASELINE configs 3 and 5 on the same N-stage pipeline:
 Llama-3-8B bf16 (64 sequences per micro-batch) and Mixtral 8x7B Q4_K_M (256), N + 1 micro-batches.
-At N = 1 the same run also measures, with the same bracket, the other named BASELINE configs at
+At N = 1 `--full` also measures, with the same bracket, the other named BASELINE configs at
 one GPU (Llama-3-8B Q4_K_M single stream, Mixtral 8x7B Q4_K_M at 256 sequences on the grouped MoE
 GEMM, Llama-3-8B bf16 at 64 sequences), the round-1 like-for-like point (70B, 64 sequences) and the
 headline shape at the reference's 2K context (256 sequences decoding at positions ~2000, after a
@@ -87,11 +92,35 @@ def parse_set(items):
     return out
 
 
+DUMP_LOGIT_BYTES = 48 << 20   # --dump-outputs: logits sample budget (the whole dump stays under 64 MB)
+
+
+def dump_outputs(eng, out_dir, vocab, mb_size):
+    """--dump-outputs: what a caller of the timed path holds after its last decode round, as float
+    .npy files (on the rank that owns the last stage): every sequence's generated tokens (the last
+    column is the last timed round's) and that round's logits of the micro-batch the last stage
+    computed last.  Logits beyond the byte budget are cut to a fixed seeded sample of rows, whose
+    indices go to logits_rows.npy."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    toks = eng.tokens()
+    n = min(len(t) for t in toks)
+    np.save(os.path.join(out_dir, "tokens.npy"), np.asarray([t[:n] for t in toks], dtype=np.float64))
+    logits = eng.logits(rows=mb_size, vocab=vocab)
+    rows = np.arange(mb_size)
+    keep = max(1, DUMP_LOGIT_BYTES // (vocab * 4))
+    if keep < mb_size:
+        rows = np.sort(np.random.default_rng(0).choice(mb_size, size=keep, replace=False))
+    np.save(os.path.join(out_dir, "logits.npy"), np.ascontiguousarray(logits[rows], dtype=np.float32))
+    np.save(os.path.join(out_dir, "logits_rows.npy"), rows.astype(np.float64))
+
+
 def run(eng_factory, vocab, n_seq, prompt_len, steps, warmup, world, pg_cpu, devices=(0,), dump_tokens=None,
-        trace=None):
+        trace=None, dump_dir=None, mb_size=0):
     """Start n_seq synthetic prompts, warm up, time exactly `steps` decode rounds; returns
     (ms, p50 ms, engine info) with ms and p50 the MAX over ranks.  dump_tokens: write the generated
-    tokens (where the last stage lives) to that JSON file, after the timed region.  trace: after the
+    tokens (where the last stage lives) to that JSON file, after the timed region.  dump_dir: write
+    the last timed round's outputs there (dump_outputs), before anything else runs.  trace: after the
     timed region, 5 more rounds with the engine's span trace on, written there (Chrome JSON)."""
     eng = eng_factory()
     try:
@@ -120,6 +149,8 @@ def run(eng_factory, vocab, n_seq, prompt_len, steps, warmup, world, pg_cpu, dev
             dist.all_reduce(vals, op=dist.ReduceOp.MAX)   # p50 only non-zero on the last stage
         from mipipe import _native as N
         info = N.jcall(N.lib().mp_engine_info, eng._h, what="engine info")
+        if dump_dir:
+            dump_outputs(eng, dump_dir, vocab, mb_size)
         if dump_tokens:
             with open(dump_tokens, "w") as f:
                 json.dump(eng.tokens(), f)
@@ -156,7 +187,14 @@ def main():
                     help="every stage on GPU 0: rehearses the N > 1 path on a 1-GPU box (in-process: local links; "
                          "torchrun: a gloo process group and TCP links, RCCL refuses two ranks of a communicator "
                          "on one GPU)")
-    ap.add_argument("--no-secondary", action="store_true", help="N = 1: skip the secondary configs")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline run, also measure the secondary configs (\"secondary\" in the JSON line); "
+                         "without it only the headline configuration is set up and timed")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the secondary configs after all")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the headline run's last-round outputs to DIR as .npy: "
+                         "tokens.npy (float64, sequences x generated tokens), logits.npy (float32, the last round's "
+                         "logits; a fixed seeded sample of rows, listed in logits_rows.npy, when they exceed 48 MB)")
     ap.add_argument("--dump-tokens", default=None, metavar="PATH",
                     help="write the headline run's generated tokens to PATH (JSON; A/B of e.g. the bf16 wire)")
     ap.add_argument("--trace", default=None, metavar="PATH",
@@ -214,12 +252,14 @@ def main():
                         n_mb * args.mb_size, args.prompt_len, args.steps, args.warmup, world, pg_cpu,
                         sorted(set(devices)),
                         dump_tokens=args.dump_tokens if rank == world - 1 else None,   # the last stage's rank
-                        trace=(args.trace if world == 1 else f"{args.trace}.rank{rank}") if args.trace else None)
+                        trace=(args.trace if world == 1 else f"{args.trace}.rank{rank}") if args.trace else None,
+                        dump_dir=args.dump_outputs if rank == world - 1 else None, mb_size=args.mb_size)
     n_tok = args.steps * n_mb * args.mb_size * replicas
     value = n_tok / (ms / 1e3)
 
     secondary = {}
-    if n_gpus == 1 and not args.no_secondary:
+    with_secondary = args.full and not args.no_secondary
+    if n_gpus == 1 and with_secondary:
         for label, model, ftype, mb, extra, plen in SECONDARY:
             plen = plen or args.prompt_len
             if model == args.model and ftype == args.ftype and mb == args.mb_size and not extra and plen == args.prompt_len:
@@ -229,7 +269,7 @@ def main():
             secondary[label] = dict(tok_s=round(args.steps * mb / (sms / 1e3), 2), ms_per_round=round(sms / args.steps, 4),
                                     p50_token_ms=round(sp50, 4))
 
-    elif n_gpus > 1 and replicas == 1 and not args.no_secondary:
+    elif n_gpus > 1 and replicas == 1 and with_secondary:
         for label, model, ftype, mb in SECONDARY_PP:
             if model == args.model and ftype == args.ftype:
                 continue

@@ -9,7 +9,7 @@ timeout -k 10 600 python -u -m pytest tests -q -m gpu -p no:cacheprovider --time
 grep -E "passed|failed|FAILED|Error" $O/tests.log | tail -12
 [ $rc -gt 1 ] && exit $rc
 step bench70b
-timeout -k 10 300 python bench.py --steps 20 --warmup 3 > $O/b70.log 2>&1 || { tail -5 $O/b70.log; exit 1; }
+timeout -k 10 300 python bench.py --full --steps 20 --warmup 3 > $O/b70.log 2>&1 || { tail -5 $O/b70.log; exit 1; }
 grep '"value"' $O/b70.log | tee $O/bench_default.json
 timeout -k 10 300 python bench.py --steps 20 --warmup 3 --mb-size 16 > $O/b70_16.log 2>&1 || { tail -5 $O/b70_16.log; exit 1; }
 grep '"value"' $O/b70_16.log | tee $O/bench_70b_mb16.json

@@ -148,6 +148,31 @@ def test_bench_py_inprocess_pipeline_cpu():
     assert d["link"]["kind"] == ["host"] and d["link"]["links_per_rank"] == 4
 
 
+def test_bench_py_dump_outputs_cpu(tmp_path):
+    """`bench.py --dump-outputs DIR` (CPU backend): after exactly --steps timed rounds it writes the
+    generated tokens (float64, one column per round after the prompt's own token) and the last
+    round's logits (float32), whose greedy argmax is the last token of every sequence; a plain run
+    carries no `secondary` object."""
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    out = tmp_path / "dump"
+    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--model", "tinyllama", "--ftype", "Q4_K_M",
+           "--steps", "2", "--warmup", "1", "--mb-size", "2", "--prompt-len", "4", "--set", "backend=cpu",
+           "--set", "threads=4", "--dump-outputs", str(out)]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, cwd=REPO, env=env)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["steps"] == 2 and d["ms_per_step"] > 0 and "secondary" not in d
+    assert sorted(os.listdir(out)) == ["logits.npy", "logits_rows.npy", "tokens.npy"]
+    toks, logits, rows = (np.load(out / f) for f in ("tokens.npy", "logits.npy", "logits_rows.npy"))
+    assert toks.dtype == np.float64 and toks.shape == (2, 1 + 1 + 2)   # prompt's token + warmup + steps
+    assert logits.dtype == np.float32 and logits.shape == (2, 32000) and np.isfinite(logits).all()
+    assert rows.tolist() == [0, 1]
+    assert ((toks >= 0) & (toks < 32000) & (toks == np.round(toks))).all()
+    assert logits.argmax(axis=1).tolist() == toks[:, -1].tolist()
+
+
 def test_bench_py_rejects_world_mismatch():
     env = dict(os.environ, WORLD_SIZE="2", RANK="0")
     r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "4"], capture_output=True,

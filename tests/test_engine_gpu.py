@@ -626,6 +626,33 @@ def test_bench_contract_line(cuda, native):
     assert d["config"]["parallelism"] == "pp1" and d["config"]["global_batch"] == 4
 
 
+def test_bench_dump_outputs(cuda, native, tmp_path):
+    """bench.py --dump-outputs DIR: a plain run (no `secondary`) of exactly --steps timed rounds, then
+    the generated tokens (float64) and the last round's logits (float32) as .npy; the logits' greedy
+    argmax is every sequence's last token."""
+    import json as _json
+    import os
+    import subprocess
+    import sys
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "1", "--model", "tinyllama",
+                        "--ftype", "Q4_K_M", "--steps", "3", "--warmup", "1", "--mb-size", "4", "--prompt-len", "16",
+                        "--dump-outputs", str(out)], capture_output=True, text=True, timeout=240, cwd=repo)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    d = _json.loads(lines[0])
+    assert d["steps"] == 3 and d["ms_per_step"] > 0 and "secondary" not in d
+    assert sorted(os.listdir(out)) == ["logits.npy", "logits_rows.npy", "tokens.npy"]
+    toks, logits, rows = (np.load(out / f) for f in ("tokens.npy", "logits.npy", "logits_rows.npy"))
+    assert toks.dtype == np.float64 and toks.shape == (4, 1 + 1 + 3)   # prompt's token + warmup + steps
+    assert logits.dtype == np.float32 and logits.shape == (4, 32000) and np.isfinite(logits).all()
+    assert rows.tolist() == [0, 1, 2, 3]
+    assert ((toks >= 0) & (toks < 32000) & (toks == np.round(toks))).all()
+    assert logits.argmax(axis=1).tolist() == toks[:, -1].tolist()
+
+
 def test_bench_two_ranks_torchrun(cuda, native):
     """The N > 1 bench path end to end on one GPU: torchrun with 2 ranks (both on GPU 0, gloo
     process group, TCP stage links -- RCCL refuses two ranks of one communicator on one GPU),
