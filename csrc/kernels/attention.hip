@@ -1161,9 +1161,9 @@ bool attn_decode_pre_ok(const DecodeAttnParams& p) {
 }
 
 template <bool F8, bool PRE>
-static void attn_decode_pf(const DecodeAttnParams& p, hipStream_t st) {
+static void attn_decode_pf(const DecodeAttnParams& p, bool nw8, hipStream_t st) {
   const dim3 grid(p.M, p.Hkv, 1);
-  if (p.M * p.Hkv <= knob(KNOB_ATTN_NW8_MAXWG)) {
+  if (nw8) {
     if (p.Dp == 128) hipLaunchKernelGGL((mpk::attn_decode_kernel8<128, F8, PRE>), grid, dim3(512), 0, st, p);
     else hipLaunchKernelGGL((mpk::attn_decode_kernel8<64, F8, PRE>), grid, dim3(512), 0, st, p);
   } else {
@@ -1172,30 +1172,45 @@ static void attn_decode_pf(const DecodeAttnParams& p, hipStream_t st) {
   }
 }
 
+// which device form a launch takes (a pure function of M, Hkv, n_split and the knobs):
+// the wave kernel where selected; else the next-chunk prefetch variant (2 workgroups per CU) for a
+// single split per (token, kv head) while the grid is small, with 8 waves on the smallest grids;
+// many workgroups (long contexts, or wide micro-batches: M * Hkv above MIPIPE_ATTN_PF_MAXWG) need
+// occupancy more than per-wave latency: the 3-per-CU variant
+AttnDecodeForm attn_decode_form(const DecodeAttnParams& p) {
+  if (attn_decode_wave_selected(p)) return ATTN_FORM_WAVE;
+  if (p.n_split == 1 && p.M * p.Hkv <= knob(KNOB_ATTN_PF_MAXWG))
+    return p.M * p.Hkv <= knob(KNOB_ATTN_NW8_MAXWG) ? ATTN_FORM_PF8 : ATTN_FORM_PF4;
+  return ATTN_FORM_NP;
+}
+
 void launch_attn_decode(const DecodeAttnParams& p, hipStream_t st) {
-  if (p.pre) {   // q rotated and K / V appended by the qkv GEMV (gemvs QkvAppend)
-    if (!attn_decode_pre_ok(p)) throw std::runtime_error("launch_attn_decode: pre-appended inputs need the one-split kernel");
-    return p.kv_fp8 ? attn_decode_pf<true, true>(p, st) : attn_decode_pf<false, true>(p, st);
-  }
-  if (attn_decode_wave_selected(p)) {
-    const int items = p.M * p.Hkv * p.n_split;
-    const dim3 grid((items + 3) / 4);
-    if (p.Dp == 128) {
-      if (p.kv_fp8) hipLaunchKernelGGL((mpk::attn_decode_wave_kernel<128, true>), grid, dim3(256), 0, st, p);
-      else hipLaunchKernelGGL((mpk::attn_decode_wave_kernel<128, false>), grid, dim3(256), 0, st, p);
-    } else {
-      if (p.kv_fp8) hipLaunchKernelGGL((mpk::attn_decode_wave_kernel<64, true>), grid, dim3(256), 0, st, p);
-      else hipLaunchKernelGGL((mpk::attn_decode_wave_kernel<64, false>), grid, dim3(256), 0, st, p);
+  // q rotated and K / V appended by the qkv GEMV (gemvs QkvAppend): the prefetch forms only
+  if (p.pre && !attn_decode_pre_ok(p))
+    throw std::runtime_error("launch_attn_decode: pre-appended inputs need the one-split kernel");
+  const AttnDecodeForm form = attn_decode_form(p);
+  switch (form) {
+    case ATTN_FORM_WAVE: {
+      const int items = p.M * p.Hkv * p.n_split;
+      const dim3 grid((items + 3) / 4);
+      if (p.Dp == 128) {
+        if (p.kv_fp8) hipLaunchKernelGGL((mpk::attn_decode_wave_kernel<128, true>), grid, dim3(256), 0, st, p);
+        else hipLaunchKernelGGL((mpk::attn_decode_wave_kernel<128, false>), grid, dim3(256), 0, st, p);
+      } else {
+        if (p.kv_fp8) hipLaunchKernelGGL((mpk::attn_decode_wave_kernel<64, true>), grid, dim3(256), 0, st, p);
+        else hipLaunchKernelGGL((mpk::attn_decode_wave_kernel<64, false>), grid, dim3(256), 0, st, p);
+      }
+      return;
     }
-    return;
+    case ATTN_FORM_PF4:
+    case ATTN_FORM_PF8: {
+      const bool nw8 = form == ATTN_FORM_PF8;
+      if (p.pre) return p.kv_fp8 ? attn_decode_pf<true, true>(p, nw8, st) : attn_decode_pf<false, true>(p, nw8, st);
+      return p.kv_fp8 ? attn_decode_pf<true, false>(p, nw8, st) : attn_decode_pf<false, false>(p, nw8, st);
+    }
+    case ATTN_FORM_NP:
+      return p.kv_fp8 ? attn_decode_go<true>(p, st) : attn_decode_go<false>(p, st);
   }
-  // the next-chunk prefetch variant (2 workgroups per CU) for a single split per (token, kv head)
-  // while the grid is small; many workgroups (long contexts, or wide micro-batches: M * Hkv above
-  // MIPIPE_ATTN_PF_MAXWG) need occupancy more than per-wave latency: the 3-per-CU variant
-  const int pf_max = knob(KNOB_ATTN_PF_MAXWG);
-  const bool pf = p.n_split == 1 && p.M * p.Hkv <= pf_max;
-  if (pf) return p.kv_fp8 ? attn_decode_pf<true, false>(p, st) : attn_decode_pf<false, false>(p, st);
-  p.kv_fp8 ? attn_decode_go<true>(p, st) : attn_decode_go<false>(p, st);
 }
 
 }  // namespace mp

@@ -403,13 +403,13 @@ int mp_op_embed(int type, const void* table, int64_t row_bytes, int d, const voi
 
 int mp_op_rope_kv(const void* qkv, int ldqkv, int M, int Hq, int Hkv, int hd, int Dp, const void* pos,
                   const void* slot, const void* block_table, int max_pages, const void* rope_cs, float q_scale,
-                  void* q_out, void* k_cache, void* v_cache, void* stream) {
+                  void* q_out, void* k_cache, void* v_cache, int kv_fp8, void* stream) {
   API_TRY
   RopeKvParams p{};
   p.qkv = (const float*)qkv; p.ldqkv = ldqkv; p.M = M; p.Hq = Hq; p.Hkv = Hkv; p.hd = hd; p.Dp = Dp;
   p.pos = (const int32_t*)pos; p.slot = (const int32_t*)slot; p.block_table = (const int32_t*)block_table;
   p.max_pages = max_pages; p.rope_cs = (const float2*)rope_cs; p.q_scale = q_scale; p.q_out = (f16*)q_out;
-  p.k_cache = (f16*)k_cache; p.v_cache = (f16*)v_cache;
+  p.k_cache = (f16*)k_cache; p.v_cache = (f16*)v_cache; p.kv_fp8 = kv_fp8;
   launch_rope_kv(p, (hipStream_t)stream);
   HIP_OK(hipGetLastError());
   return 0;
@@ -437,7 +437,7 @@ int mp_op_attention(const void* q, const void* kvlen, const void* slot, const vo
 int mp_op_attn_prefill(const void* q, const void* pos, const void* slot, const void* block_table, int max_pages,
                        const void* k_cache, const void* v_cache, int Hq, int Hkv, int hd, int Dp, const int32_t* segs,
                        int n_segs, void* out, int ldo, int n_split, int split_pages, void* o_part, void* ml_part,
-                       int M, void* stream) {
+                       int M, int kv_fp8, void* stream) {
   API_TRY
   PrefillAttnParams p{};
   p.q = (const f16*)q; p.pos = (const int32_t*)pos; p.slot = (const int32_t*)slot;
@@ -445,6 +445,7 @@ int mp_op_attn_prefill(const void* q, const void* pos, const void* slot, const v
   p.k_cache = (const f16*)k_cache; p.v_cache = (const f16*)v_cache;
   p.Hq = Hq; p.Hkv = Hkv; p.hd = hd; p.Dp = Dp; p.out = (f16*)out; p.ldo = ldo;
   p.M = M; p.n_split = n_split; p.split_pages = split_pages; p.o_part = (float*)o_part; p.ml_part = (float*)ml_part;
+  p.kv_fp8 = kv_fp8;
   const int bt = prefill_attn_rows_per_tile(Hq / Hkv);
   for (int s = 0; s < n_segs; ++s)
     for (int r = 0; r < segs[2 * s + 1]; r += bt) {
@@ -454,6 +455,90 @@ int mp_op_attn_prefill(const void* q, const void* pos, const void* slot, const v
   launch_attn_prefill(p, (hipStream_t)stream);
   HIP_OK(hipGetLastError());
   return 0;
+  API_CATCH(-1)
+}
+
+// The fused decode attention step at op level (attention.hip attn_decode_* / attn_o): every field
+// the engine sets in HipStage::decode_attn_params; probe stays 0.  The checks are the host's
+// contract for the kernels (what hip_stage.cpp guarantees by construction).
+static DecodeAttnParams decode_attn_args(const void* qkv, int ldqkv, const void* pos, const void* slot, int slot0,
+                                         const void* block_table, int max_pages, const void* rope_cs, float q_scale,
+                                         void* k_cache, void* v_cache, int M, int Hq, int Hkv, int hd, int Dp,
+                                         int split_len, int n_split, void* o_part, void* ml_part, void* counters,
+                                         void* out, int ldo, const void* ssq, float eps, int d_model, const void* bias,
+                                         int kv_fp8, int pre) {
+  auto need = [](bool ok, const char* what) {
+    if (!ok) throw std::runtime_error(std::string("attn_decode: ") + what);
+  };
+  need(M >= 1 && Hkv >= 1 && Hq >= Hkv && Hq % Hkv == 0, "M, Hq, Hkv");
+  need(Hq / Hkv <= 16, "at most 16 query heads per kv head (one MFMA column each)");
+  need((Dp == 64 || Dp == 128) && hd >= 2 && hd <= Dp && hd % 2 == 0, "head dim (even, <= Dp = 64 or 128)");
+  need(ldqkv >= (Hq + 2 * Hkv) * hd && ldqkv % 4 == 0 && ldo >= Hq * hd, "row strides");
+  need(max_pages >= 1 && split_len >= 32 && split_len % 32 == 0, "max_pages, split_len (multiple of 32)");
+  need(n_split >= 1 && n_split <= 128, "1 to 128 splits");
+  // (a position past the last split would make the kernels publish partials nobody merges)
+  need((int64_t)n_split * split_len >= (int64_t)max_pages * 64, "n_split * split_len covers max_pages * 64");
+  need(qkv && pos && block_table && rope_cs && k_cache && v_cache && out && counters, "null pointer");
+  need(slot0 >= 0 || slot, "slot or slot0");
+  need(n_split == 1 || (o_part && ml_part), "split partials");
+  need(!ssq || d_model > 0, "d_model with ssq");
+  need(ssq || !bias, "bias is part of the deferred norm (ssq)");
+  DecodeAttnParams p{};
+  p.qkv = (const float*)qkv; p.ldqkv = ldqkv; p.pos = (const int32_t*)pos; p.slot = (const int32_t*)slot;
+  p.slot0 = slot0 >= 0 ? slot0 : -1; p.block_table = (const int32_t*)block_table; p.max_pages = max_pages;
+  p.rope_cs = (const float2*)rope_cs; p.q_scale = q_scale; p.k_cache = (f16*)k_cache; p.v_cache = (f16*)v_cache;
+  p.M = M; p.Hq = Hq; p.Hkv = Hkv; p.hd = hd; p.Dp = Dp; p.split_len = split_len; p.n_split = n_split;
+  p.o_part = (float*)o_part; p.ml_part = (float*)ml_part; p.counters = (int32_t*)counters;
+  p.out = (f16*)out; p.ldo = ldo;
+  p.ssq = (const float*)ssq; p.eps = eps; p.d_model = d_model; p.bias = (const float*)bias;
+  p.kv_fp8 = kv_fp8 ? 1 : 0; p.pre = pre ? 1 : 0;
+  return p;
+}
+
+int mp_op_attn_decode(const void* qkv, int ldqkv, const void* pos, const void* slot, int slot0,
+                      const void* block_table, int max_pages, const void* rope_cs, float q_scale, void* k_cache,
+                      void* v_cache, int M, int Hq, int Hkv, int hd, int Dp, int split_len, int n_split, void* o_part,
+                      void* ml_part, void* counters, void* out, int ldo, const void* ssq, float eps, int d_model,
+                      const void* bias, int kv_fp8, int pre, void* stream) {
+  API_TRY
+  const DecodeAttnParams p = decode_attn_args(qkv, ldqkv, pos, slot, slot0, block_table, max_pages, rope_cs, q_scale,
+                                              k_cache, v_cache, M, Hq, Hkv, hd, Dp, split_len, n_split, o_part,
+                                              ml_part, counters, out, ldo, ssq, eps, d_model, bias, kv_fp8, pre);
+  launch_attn_decode(p, (hipStream_t)stream);
+  HIP_OK(hipGetLastError());
+  return 0;
+  API_CATCH(-1)
+}
+
+// attention + o-projection in one launch: Y [M][ldy] += attn [M][Hq * hd] . W_o^T (W T16-packed)
+int mp_op_attn_o(const void* qkv, int ldqkv, const void* pos, const void* slot, int slot0, const void* block_table,
+                 int max_pages, const void* rope_cs, float q_scale, void* k_cache, void* v_cache, int M, int Hq,
+                 int Hkv, int hd, int Dp, int split_len, int n_split, void* o_part, void* ml_part, void* counters,
+                 void* out, int ldo, const void* ssq, float eps, int d_model, const void* bias, int kv_fp8, int pre,
+                 const void* W, int ptype, int ntiles, int nsb, void* Y, int ldy, int n_valid, void* stream) {
+  API_TRY
+  const DecodeAttnParams p = decode_attn_args(qkv, ldqkv, pos, slot, slot0, block_table, max_pages, rope_cs, q_scale,
+                                              k_cache, v_cache, M, Hq, Hkv, hd, Dp, split_len, n_split, o_part,
+                                              ml_part, counters, out, ldo, ssq, eps, d_model, bias, kv_fp8, pre);
+  AttnOParams o{};
+  o.W = (const uint8_t*)W; o.ptype = ptype; o.ntiles = ntiles; o.nsb = nsb;
+  o.Y = (float*)Y; o.ldy = ldy; o.n_valid = n_valid;
+  if (!W || !Y || n_valid < 1 || n_valid > ntiles * 16 || ldy < n_valid || nsb * 256 < Hq * hd)
+    throw std::runtime_error("attn_o: W_o / Y arguments");
+  if (!attn_o_supported(p, o)) throw std::runtime_error("attn_o: unsupported shape");
+  launch_attn_o(p, o, (hipStream_t)stream);
+  HIP_OK(hipGetLastError());
+  return 0;
+  API_CATCH(-1)
+}
+
+// the device form launch_attn_decode would take (AttnDecodeForm: 0 prefetch 4 waves, 1 prefetch
+// 8 waves, 2 no prefetch, 3 wave) under the current knobs
+int mp_attn_decode_form(int M, int Hkv, int n_split) {
+  API_TRY
+  DecodeAttnParams p{};
+  p.M = M; p.Hkv = Hkv; p.n_split = n_split;
+  return (int)attn_decode_form(p);
   API_CATCH(-1)
 }
 

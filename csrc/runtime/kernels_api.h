@@ -215,6 +215,14 @@ struct DecodeAttnParams {
                                    // bit 1 the K append (results wrong; never in production runs)
 };
 void launch_attn_decode(const DecodeAttnParams& p, hipStream_t st);
+// the device form launch_attn_decode takes for p (host only: M, Hkv, n_split and the knobs decide)
+enum AttnDecodeForm {
+  ATTN_FORM_PF4 = 0,    // attn_decode_kernel: 4 waves, next-chunk prefetch (one split)
+  ATTN_FORM_PF8 = 1,    // attn_decode_kernel8: 8 waves (one split, tiny grids)
+  ATTN_FORM_NP = 2,     // attn_decode_kernel_np: no prefetch (several splits or wide grids)
+  ATTN_FORM_WAVE = 3,   // attn_decode_wave_kernel: one wave per (token, kv head, split)
+};
+AttnDecodeForm attn_decode_form(const DecodeAttnParams& p);
 // the launch would take the one-split workgroup kernel that accepts pre-appended inputs (p.pre)
 bool attn_decode_pre_ok(const DecodeAttnParams& p);
 // Fused decode attention + output projection (single stream, M <= 4, one KV split): workgroup

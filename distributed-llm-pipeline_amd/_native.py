@@ -67,13 +67,21 @@ _SIGS = {
     "mp_op_rmsnorm": ([c_void_p, c_int, c_void_p, c_int, c_float, c_void_p, c_int, c_int, c_void_p], c_int),
     "mp_op_embed": ([c_int, c_void_p, c_int64, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p], c_int),
     "mp_op_rope_kv": ([c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int,
-                       c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_void_p], c_int),
+                       c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_int, c_void_p], c_int),
+    "mp_op_attn_decode": ([c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_float, c_void_p,
+                           c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                           c_void_p, c_int, c_void_p, c_float, c_int, c_void_p, c_int, c_int, c_void_p], c_int),
+    "mp_op_attn_o": ([c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_float, c_void_p,
+                      c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                      c_void_p, c_int, c_void_p, c_float, c_int, c_void_p, c_int, c_int,
+                      c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p], c_int),
+    "mp_attn_decode_form": ([c_int, c_int, c_int], c_int),
     "mp_op_attention": ([c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int,
                          c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p], c_int),
     "mp_op_argmax": ([c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p], c_int),
     "mp_op_attn_prefill": ([c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int,
                             c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int,
-                            c_void_p], c_int),
+                            c_int, c_void_p], c_int),
     "mp_device_probe": ([c_int, c_void_p], c_int),
     "mp_op_gemv_fused": ([c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p,
                           c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_float, c_int, c_void_p, c_void_p,

@@ -278,10 +278,12 @@ def embed(raw_table: torch.Tensor, ggml_type: int, d: int, tokens: torch.Tensor)
     return x
 
 
-def attn_prefill(q, pos, slot, block_table, k_cache, v_cache, Hkv, hd, segs=None, n_split=1, split_pages=1):
+def attn_prefill(q, pos, slot, block_table, k_cache, v_cache, Hkv, hd, segs=None, n_split=1, split_pages=1,
+                 kv_fp8=False):
     """Prefill flash attention (attn_prefill.hip): q [M][Hq][Dp] f16 (q_scale applied), rows in
     `segs` = [(row0, T), ...] runs of consecutive positions of one sequence each (default: one run);
-    n_split > 1 splits every tile's pages (split_pages each) over workgroups, merged by attn_combine."""
+    n_split > 1 splits every tile's pages (split_pages each) over workgroups, merged by attn_combine.
+    kv_fp8: the caches hold e4m3 bytes (uint8 tensors of the same element layout)."""
     M, Hq, Dp = q.shape
     segs = segs or [(0, M)]
     sa = np.asarray(segs, np.int32).reshape(-1)
@@ -293,7 +295,7 @@ def attn_prefill(q, pos, slot, block_table, k_cache, v_cache, Hkv, hd, segs=None
     N.check(N.lib().mp_op_attn_prefill(_ptr(q), _ptr(pos), _ptr(slot), _ptr(block_table), block_table.shape[1],
                                        _ptr(k_cache), _ptr(v_cache), Hq, Hkv, hd, Dp,
                                        sa.ctypes.data, len(segs), _ptr(out), out.stride(0), n_split, split_pages,
-                                       _ptr(op), _ptr(ml), M, _stream()), "attn_prefill")
+                                       _ptr(op), _ptr(ml), M, int(kv_fp8), _stream()), "attn_prefill")
     return out
 
 
@@ -379,12 +381,13 @@ def rope_cs_table(max_pos: int, hd: int, base: float, freq_factors=None) -> torc
     return torch.from_numpy(cs)
 
 
-def rope_kv(qkv, pos, slot, block_table, rope_cs, Hq, Hkv, hd, Dp, q_scale, k_cache, v_cache):
+def rope_kv(qkv, pos, slot, block_table, rope_cs, Hq, Hkv, hd, Dp, q_scale, k_cache, v_cache, kv_fp8=False):
+    """kv_fp8: the caches hold e4m3 bytes (uint8 tensors of the same element layout)."""
     M = qkv.shape[0]
     q_out = torch.zeros(M, Hq, Dp, dtype=torch.float16, device=qkv.device)
     N.check(N.lib().mp_op_rope_kv(_ptr(qkv), qkv.stride(0), M, Hq, Hkv, hd, Dp, _ptr(pos), _ptr(slot),
                                   _ptr(block_table), block_table.shape[1], _ptr(rope_cs), q_scale, _ptr(q_out),
-                                  _ptr(k_cache), _ptr(v_cache), _stream()), "rope_kv")
+                                  _ptr(k_cache), _ptr(v_cache), int(kv_fp8), _stream()), "rope_kv")
     return q_out
 
 
@@ -397,3 +400,69 @@ def attention(q, kvlen, slot, block_table, k_cache, v_cache, Hkv, hd, tq=1, spli
                                     _ptr(k_cache), _ptr(v_cache), M, Hq, Hkv, hd, Dp, tq, split_len, n_split,
                                     _ptr(o_part), _ptr(ml_part), _ptr(out), out.stride(0), _stream()), "attention")
     return out
+
+
+ATTN_FORM_PF4, ATTN_FORM_PF8, ATTN_FORM_NP, ATTN_FORM_WAVE = 0, 1, 2, 3
+
+
+def attn_decode_form(M: int, Hkv: int, n_split: int) -> int:
+    """The device form launch_attn_decode takes for this grid under the current knobs (ATTN_FORM_*)."""
+    return N.check(N.lib().mp_attn_decode_form(M, Hkv, n_split), "attn_decode_form")
+
+
+class DecodeAttnScratch:
+    """Split partials and the self-resetting arrival counters of the fused decode attention; kept
+    across calls as the engine keeps them (o_part / ml_part poisoned with NaN: never read unwritten)."""
+
+    def __init__(self, M, Hq, Hkv, Dp, n_split, device="cuda"):
+        self.o_part = torch.full((n_split, M * Hq, Dp), float("nan"), dtype=torch.float32, device=device)
+        self.ml_part = torch.full((n_split, M * Hq, 2), float("nan"), dtype=torch.float32, device=device)
+        self.counters = torch.zeros(max(M, 16) * Hkv, dtype=torch.int32, device=device)
+
+
+def _decode_attn_args(qkv, pos, block_table, rope_cs, k_cache, v_cache, Hq, Hkv, hd, Dp, q_scale, split_len, n_split,
+                      scratch, out, slot, slot0, ssq, eps, d_model, bias, kv_fp8, pre):
+    M = qkv.shape[0]
+    assert qkv.dtype == torch.float32 and qkv.stride(1) == 1 and pos.dtype == torch.int32
+    assert block_table.dtype == torch.int32 and block_table.is_contiguous()
+    assert rope_cs.dtype == torch.float32 and rope_cs.is_contiguous()
+    assert k_cache.is_contiguous() and v_cache.is_contiguous()
+    assert k_cache.dtype == v_cache.dtype == (torch.uint8 if kv_fp8 else torch.float16)
+    assert (slot is None) != (slot0 is None), "exactly one of slot / slot0"
+    assert out.dtype == torch.float16 and out.stride(1) == 1
+    return (_ptr(qkv), qkv.stride(0), _ptr(pos), _ptr(slot), -1 if slot0 is None else int(slot0), _ptr(block_table),
+            block_table.shape[1], _ptr(rope_cs), q_scale, _ptr(k_cache), _ptr(v_cache), M, Hq, Hkv, hd, Dp, split_len,
+            n_split, _ptr(scratch.o_part), _ptr(scratch.ml_part), _ptr(scratch.counters), _ptr(out), out.stride(0),
+            _ptr(ssq), eps, d_model, _ptr(bias), int(kv_fp8), int(pre))
+
+
+def attn_decode(qkv, pos, block_table, rope_cs, k_cache, v_cache, Hq, Hkv, hd, Dp, q_scale, split_len, n_split,
+                scratch, *, slot=None, slot0=None, ssq=None, eps=0.0, d_model=0, bias=None, kv_fp8=False, pre=False,
+                out=None):
+    """The fused decode attention step (attention.hip: RoPE of q and the new k, KV append, split
+    flash-decoding, last-arriver merge) as the engine launches it: qkv f32 [M][>= (Hq + 2 Hkv) hd]
+    pre-RoPE (with ssq: before the deferred RMSNorm scale / bias), row t in slot slot0 + t or slot[t]
+    at position pos[t]; K pages [page][Hkv][64][Dp], V pages [page][Hkv][Dp][64], f16 or (kv_fp8)
+    e4m3 bytes.  pre: q rotated, the new K / V already in the cache.  Returns out f16 [M][Hq * hd];
+    the form is chosen by the launcher (attn_decode_form)."""
+    M = qkv.shape[0]
+    if out is None:
+        out = torch.zeros(M, Hq * hd, dtype=torch.float16, device=qkv.device)
+    a = _decode_attn_args(qkv, pos, block_table, rope_cs, k_cache, v_cache, Hq, Hkv, hd, Dp, q_scale, split_len,
+                          n_split, scratch, out, slot, slot0, ssq, eps, d_model, bias, kv_fp8, pre)
+    N.check(N.lib().mp_op_attn_decode(*a, _stream()), "attn_decode")
+    return out
+
+
+def attn_o(w: PackedWeight, y, qkv, pos, block_table, rope_cs, k_cache, v_cache, Hq, Hkv, hd, Dp, q_scale, split_len,
+           scratch, *, slot=None, slot0=None, ssq=None, eps=0.0, d_model=0, kv_fp8=False, pre=False):
+    """Fused decode attention + o-projection (attn_o_kernel): y f32 [M][n] += attn . W_o^T with
+    atomics; one split.  Raises where attn_o_supported is false."""
+    M = qkv.shape[0]
+    assert y.dtype == torch.float32 and y.stride(1) == 1 and y.shape == (M, w.n)
+    out = torch.zeros(M, Hq * hd, dtype=torch.float16, device=qkv.device)   # unused by the fused kernel
+    a = _decode_attn_args(qkv, pos, block_table, rope_cs, k_cache, v_cache, Hq, Hkv, hd, Dp, q_scale, split_len,
+                          1, scratch, out, slot, slot0, ssq, eps, d_model, None, kv_fp8, pre)
+    N.check(N.lib().mp_op_attn_o(*a, _ptr(w.dev), w.ptype, w.ntiles, w.nsb, _ptr(y), y.stride(0), w.n, _stream()),
+            "attn_o")
+    return y

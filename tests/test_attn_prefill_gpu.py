@@ -23,9 +23,10 @@ def _ref(q, K, V, pos):
     return torch.einsum("rhs,shd->rhd", torch.softmax(s, -1), Ve).float()
 
 
-def _setup(hd, Hq, Hkv, seqs, seed):
+def _setup(hd, Hq, Hkv, seqs, seed, fp8=False):
     """seqs: list of (slot, p0, T): prefill rows at positions p0..p0+T-1 of `slot` (KV of
-    positions < p0 + T already in the cache).  Returns the kernel inputs and per-slot K/V."""
+    positions < p0 + T already in the cache).  Returns the kernel inputs and per-slot K/V.
+    fp8: K / V are e4m3 values and the caches hold their bytes."""
     g = torch.Generator().manual_seed(seed)
     Dp = 64 if hd <= 64 else 128
     n_slots = max(s for s, _, _ in seqs) + 1
@@ -41,6 +42,8 @@ def _setup(hd, Hq, Hkv, seqs, seed):
         S = p0 + T
         K = (torch.randn(S, Hkv, hd, generator=g)).half()
         V = (torch.randn(S, Hkv, hd, generator=g)).half()
+        if fp8:
+            K, V = (t.float().to(torch.float8_e4m3fn).float().half() for t in (K, V))
         KV[s] = (K.float(), V.float())
         for p_ in range(S):
             page = int(bt[s, p_ // 64])
@@ -55,20 +58,37 @@ def _setup(hd, Hq, Hkv, seqs, seed):
     for _, _, T in seqs:
         segs.append((row, T))
         row += T
+    if fp8:   # every cached value (zeros included) is an e4m3 value: the bytes are exact
+        kc, vc = (t.float().to(torch.float8_e4m3fn).view(torch.uint8) for t in (kc, vc))
     return q, pos, slot, bt, kc, vc, KV, segs
 
 
-@pytest.mark.parametrize("hd,Hq,Hkv", [(128, 32, 8), (128, 64, 8), (64, 32, 4), (128, 8, 8), (48, 6, 6),
-                                       (128, 28, 4)])
-@pytest.mark.parametrize("seqs", [[(0, 0, 1)], [(0, 0, 37)], [(1, 0, 300)], [(0, 200, 130)],
-                                  [(2, 0, 20), (0, 100, 45), (1, 5, 3), (3, 0, 128)]])
+PREFILL_SHAPES = [(128, 32, 8), (128, 64, 8), (64, 32, 4), (128, 8, 8), (48, 6, 6), (128, 28, 4)]
+PREFILL_SEQS = [[(0, 0, 1)], [(0, 0, 37)], [(1, 0, 300)], [(0, 200, 130)],
+                [(2, 0, 20), (0, 100, 45), (1, 5, 3), (3, 0, 128)]]
+
+
+@pytest.mark.parametrize("hd,Hq,Hkv", PREFILL_SHAPES)
+@pytest.mark.parametrize("seqs", PREFILL_SEQS)
 @pytest.mark.parametrize("n_split", [1, 2])
 def test_attn_prefill_matches_reference(cuda, native, hd, Hq, Hkv, seqs, n_split):
+    _prefill_matches_reference(hd, Hq, Hkv, seqs, n_split, fp8=False)
+
+
+@pytest.mark.parametrize("hd,Hq,Hkv", PREFILL_SHAPES)
+@pytest.mark.parametrize("seqs", PREFILL_SEQS)
+@pytest.mark.parametrize("n_split", [1, 2])
+def test_attn_prefill_matches_reference_fp8(cuda, native, hd, Hq, Hkv, seqs, n_split):
+    """e4m3 pages; the reference attends the same e4m3 values, at the same tolerance."""
+    _prefill_matches_reference(hd, Hq, Hkv, seqs, n_split, fp8=True)
+
+
+def _prefill_matches_reference(hd, Hq, Hkv, seqs, n_split, fp8):
     from mipipe.ops.kernels import attn_prefill
-    q, pos, slot, bt, kc, vc, KV, segs = _setup(hd, Hq, Hkv, seqs, seed=hd + Hq + len(seqs))
+    q, pos, slot, bt, kc, vc, KV, segs = _setup(hd, Hq, Hkv, seqs, seed=hd + Hq + len(seqs), fp8=fp8)
     pages = max(p0 + T - 1 for _, p0, T in seqs) // 64 + 1
     out = attn_prefill(q.cuda(), pos.cuda(), slot.cuda(), bt.cuda(), kc.cuda(), vc.cuda(), Hkv, hd, segs,
-                       n_split=n_split, split_pages=-(-pages // n_split))
+                       n_split=n_split, split_pages=-(-pages // n_split), kv_fp8=fp8)
     out = out.float().cpu().view(-1, Hq, hd)
     row = 0
     for (s, p0, T), (r0, _) in zip(seqs, segs):

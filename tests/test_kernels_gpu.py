@@ -236,9 +236,26 @@ def _ref_attention(q, k, v, kvlen):
     return out
 
 
-@pytest.mark.parametrize("hd,Hq,Hkv", [(128, 32, 8), (64, 32, 4), (48, 6, 6), (128, 64, 8)])
+ROPE_KV_SHAPES = [(128, 32, 8), (64, 32, 4), (48, 6, 6), (128, 64, 8)]
+
+
+@pytest.mark.parametrize("hd,Hq,Hkv", ROPE_KV_SHAPES)
 @pytest.mark.parametrize("mode", ["decode", "prefill"])
 def test_rope_kv_attention(cuda, native, hd, Hq, Hkv, mode):
+    _rope_kv_attention(hd, Hq, Hkv, mode, fp8=False)
+
+
+@pytest.mark.parametrize("hd,Hq,Hkv", ROPE_KV_SHAPES)
+@pytest.mark.parametrize("mode", ["decode", "prefill"])
+def test_rope_kv_attention_fp8(cuda, native, hd, Hq, Hkv, mode):
+    """rope_kv writes e4m3 pages: every cached byte is the e4m3 rounding of the reference K / V
+    (one code off on at most 1 % of the elements: the kernel and this reference both rotate in f32,
+    in another order, so a value at a rounding boundary may land on the neighbouring code); the
+    attention kernel (f16 pages only) then runs on the decoded pages."""
+    _rope_kv_attention(hd, Hq, Hkv, mode, fp8=True)
+
+
+def _rope_kv_attention(hd, Hq, Hkv, mode, fp8):
     from mipipe.ops.kernels import rope_kv, attention, rope_cs_table
     torch.manual_seed(hd + Hq)
     Dp = 64 if hd <= 64 else 128
@@ -246,15 +263,16 @@ def test_rope_kv_attention(cuda, native, hd, Hq, Hkv, mode):
     pages = max_ctx // 64
     bt = torch.arange(n_slots * pages, dtype=torch.int32).reshape(n_slots, pages)
     bt = bt[:, torch.randperm(pages)].contiguous()          # non-trivial page order
-    kc = torch.zeros(n_slots * pages, Hkv, 64, Dp, dtype=torch.float16).cuda()
-    vc = torch.zeros(n_slots * pages, Hkv, Dp, 64, dtype=torch.float16).cuda()
+    kc = torch.zeros(n_slots * pages, Hkv, 64, Dp, dtype=torch.uint8 if fp8 else torch.float16).cuda()
+    vc = torch.zeros(n_slots * pages, Hkv, Dp, 64, dtype=torch.uint8 if fp8 else torch.float16).cuda()
     cs = rope_cs_table(max_ctx, hd, 10000.0).cuda()
     slot_id = 1
     S = 300                                                   # tokens in the sequence
     qkv = torch.randn(S, (Hq + 2 * Hkv) * hd)
     pos = torch.arange(S, dtype=torch.int32)
     slot = torch.full((S,), slot_id, dtype=torch.int32)
-    q = rope_kv(qkv.cuda(), pos.cuda(), slot.cuda(), bt.cuda(), cs, Hq, Hkv, hd, Dp, 1 / math.sqrt(hd), kc, vc)
+    q = rope_kv(qkv.cuda(), pos.cuda(), slot.cuda(), bt.cuda(), cs, Hq, Hkv, hd, Dp, 1 / math.sqrt(hd), kc, vc,
+                kv_fp8=fp8)
     # reference rope
     inv = 10000.0 ** (-torch.arange(0, hd, 2, dtype=torch.float64) / hd)
     ang = pos.double()[:, None] * inv[None]
@@ -271,6 +289,20 @@ def test_rope_kv_attention(cuda, native, hd, Hq, Hkv, mode):
     vr = qkv[:, (Hq + Hkv) * hd:].view(S, Hkv, hd)
     torch.testing.assert_close(q.float().cpu()[:, :, :hd], qr / math.sqrt(hd), rtol=2e-3, atol=2e-3)
     assert (q.float().cpu()[:, :, hd:] == 0).all()
+    if fp8:
+        e4m3 = lambda t: t.clamp(-448.0, 448.0).to(torch.float8_e4m3fn)
+        code = lambda b: torch.where(b >= 128, -(b.int() - 128), b.int())   # monotonic in the value
+        pg, ip = bt[slot_id, (pos // 64).long()].long(), (pos % 64).long()
+        kb, vb = kc.cpu(), vc.cpu()
+        dk = (code(kb[pg, :, ip, :][:, :, :hd]) - code(e4m3(kr).view(torch.uint8))).abs()
+        dv = (code(vb[pg, :, :, ip][:, :, :hd]) - code(e4m3(vr).view(torch.uint8))).abs()
+        assert int(dk.max()) <= 1 and int(dv.max()) <= 1
+        assert int(dk.sum()) + int(dv.sum()) <= 0.01 * (dk.numel() + dv.numel())
+        assert (kb[pg, :, ip, :][:, :, hd:] == 0).all() and (vb[pg, :, :, ip][:, :, hd:] == 0).all()
+        # the reference attends the e4m3 values; the kernel gets them as f16 pages
+        kr, vr = e4m3(kr).float(), e4m3(vr).float()
+        kc = kb.view(torch.float8_e4m3fn).float().half().cuda()
+        vc = vb.view(torch.float8_e4m3fn).float().half().cuda()
     # K/V pages hold the roped keys / values at the block-table positions
     kcc, vcc = kc.float().cpu(), vc.float().cpu()
     for p_ in [0, 63, 64, 200, 299]:

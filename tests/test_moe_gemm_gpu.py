@@ -6,7 +6,8 @@ engine's packer; the oracle dequantizes them with the unpack kernel (itself chec
 numpy dequantizer in test_kernels_gpu.py) and runs fp32 matmuls per routed expert.  M covers a
 65-token call (16 rows per expert), the 256-sequence decode micro-batch (64 rows per expert) and a
 512-token prompt chunk (128 per expert), with the default 128-row tiles and the opt-in 64- and 96-row
-ones (knob GEMM4_MOE64 1 / 2), plus a skewed routing."""
+ones (knob GEMM4_MOE64 1 / 2, and 3: the 96-row tiles with the down projection unsplit over K), plus a
+skewed routing."""
 import numpy as np
 import pytest
 import torch
@@ -53,12 +54,12 @@ def experts(native):
     return gu, dn, gu_all, dn_all
 
 
-@pytest.fixture(params=[0, 1, 2], ids=["tile128", "tile64", "tile96"])
+@pytest.fixture(params=[0, 1, 2, 3], ids=["tile128", "tile64", "tile96", "tile96-unsplit"])
 def moe64(request, native):
     from mipipe import _native as N
     N.check(N.lib().mp_set_knob(b"GEMM4_MOE64", request.param), "knob")
     yield request.param
-    N.lib().mp_set_knob(b"GEMM4_MOE64", 0)
+    N.check(N.lib().mp_reset_knob(b"GEMM4_MOE64"), "knob")   # the shipped default (2), not 0
 
 
 @pytest.mark.parametrize("M", [65, 256, 512, "256skew"])
