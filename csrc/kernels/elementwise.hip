@@ -313,6 +313,26 @@ __global__ __launch_bounds__(256) void rope_kv_kernel(const RopeKvParams p) {
   }
 }
 
+// ---------------------------------------------------------------- per-head Q/K RMSNorm (Qwen3)
+// In place on the f32 q|k|v rows, before RoPE.  grid (M tokens, head groups of 4 over [q heads |
+// k heads]); one wave per (token, head), lane l owns elements l and l + 64 of the head (hd <= 128:
+// one coalesced 256 B read per half).  The mean is over the hd real elements; v columns, row
+// padding and rows >= M are never written.
+__global__ __launch_bounds__(256) void qk_norm_kernel(const QkNormParams p) {
+  const int m = blockIdx.x;
+  const int hg = blockIdx.y * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (hg >= p.Hq + p.Hkv) return;   // whole waves: the wave_sum below stays convergent
+  const float* w = hg < p.Hq ? p.wq : p.wk;
+  float* h = p.qkv + (size_t)m * p.ldqkv + (size_t)hg * p.hd;   // k heads follow the q heads
+  const bool a0 = lane < p.hd, a1 = lane + 64 < p.hd;
+  const float x0 = a0 ? h[lane] : 0.f, x1 = a1 ? h[lane + 64] : 0.f;
+  const float w0 = a0 ? w[lane] : 0.f, w1 = a1 ? w[lane + 64] : 0.f;
+  const float ss = wave_sum(x0 * x0 + x1 * x1);
+  const float sc = rsqrtf(ss / (float)p.hd + p.eps);
+  if (a0) h[lane] = x0 * sc * w0;
+  if (a1) h[lane + 64] = x1 * sc * w1;
+}
+
 // ---------------------------------------------------------------- argmax
 __global__ __launch_bounds__(1024) void argmax_kernel(const float* logits, int ld, int n, int32_t* tok) {
   __shared__ float sv[16];
@@ -554,6 +574,14 @@ void launch_requant_i8(const f16* W, int ldw, int n, int n_pad, int nsb, uint8_t
 
 void launch_rope_kv(const RopeKvParams& p, hipStream_t st) {
   hipLaunchKernelGGL(mpk::rope_kv_kernel, dim3(p.M, (p.Hq + 2 * p.Hkv + 3) / 4), dim3(256), 0, st, p);
+}
+
+void launch_qk_norm(const QkNormParams& p, hipStream_t st) {
+  if (p.hd < 2 || p.hd > 128 || (p.hd & 1))
+    throw std::runtime_error("launch_qk_norm: needs an even head_dim <= 128");
+  if (p.M < 1 || p.Hq < 1 || p.Hkv < 1 || p.ldqkv < (p.Hq + 2 * p.Hkv) * p.hd || !p.qkv || !p.wq || !p.wk)
+    throw std::runtime_error("launch_qk_norm: bad shape");
+  hipLaunchKernelGGL(mpk::qk_norm_kernel, dim3(p.M, (p.Hq + p.Hkv + 3) / 4), dim3(256), 0, st, p);
 }
 
 void launch_argmax(const float* logits, int ld, int n, int M, int32_t* tokens, hipStream_t st, const ArgmaxScratch* sc) {

@@ -160,6 +160,7 @@ const char* mp_model_config_json(const char* gguf_path) {
   j["eps"] = (double)c.eps; j["n_expert"] = c.n_expert; j["n_expert_used"] = c.n_expert_used;
   j["rope_freqs"] = c.rope_freqs; j["tied_output"] = c.tied_output;
   j["arch"] = c.arch; j["rope_neox"] = c.rope_neox; j["qkv_bias"] = c.qkv_bias;
+  j["qk_norm"] = c.qk_norm;
   g_str = j.dump();
   return g_str.c_str();
   API_CATCH(nullptr)
@@ -411,6 +412,19 @@ int mp_op_rope_kv(const void* qkv, int ldqkv, int M, int Hq, int Hkv, int hd, in
   p.max_pages = max_pages; p.rope_cs = (const float2*)rope_cs; p.q_scale = q_scale; p.q_out = (f16*)q_out;
   p.k_cache = (f16*)k_cache; p.v_cache = (f16*)v_cache; p.kv_fp8 = kv_fp8;
   launch_rope_kv(p, (hipStream_t)stream);
+  HIP_OK(hipGetLastError());
+  return 0;
+  API_CATCH(-1)
+}
+
+// per-head Q/K RMSNorm (Qwen3), in place on the f32 q|k|v rows
+int mp_op_qk_norm(void* qkv, int ldqkv, int M, int Hq, int Hkv, int hd, const void* wq, const void* wk, float eps,
+                  void* stream) {
+  API_TRY
+  QkNormParams p{};
+  p.qkv = (float*)qkv; p.ldqkv = ldqkv; p.M = M; p.Hq = Hq; p.Hkv = Hkv; p.hd = hd;
+  p.wq = (const float*)wq; p.wk = (const float*)wk; p.eps = eps;
+  launch_qk_norm(p, (hipStream_t)stream);
   HIP_OK(hipGetLastError());
   return 0;
   API_CATCH(-1)

@@ -148,6 +148,12 @@ void CpuStage::load_gguf(const GgufFile& f) {
       L.bk = tensor_f32(need(p + "attn_k.bias"));
       L.bv = tensor_f32(need(p + "attn_v.bias"));
     }
+    if (cfg_.qk_norm) {
+      L.qn = tensor_f32(need(p + "attn_q_norm.weight"));
+      L.kn = tensor_f32(need(p + "attn_k_norm.weight"));
+      if ((int)L.qn.size() != cfg_.head_dim || (int)L.kn.size() != cfg_.head_dim)
+        throw std::runtime_error("attn_q_norm / attn_k_norm: expected head_dim weights");
+    }
     L.ffn_norm = tensor_f32(need(p + "ffn_norm.weight"));
     L.q = mat(p + "attn_q.weight");
     L.k = mat(p + "attn_k.weight");
@@ -204,6 +210,10 @@ void CpuStage::init_synthetic(const std::string& ftype, uint64_t seed) {
     const uint64_t s = seed * 1000003ULL + (uint64_t)li * 97;
     L.attn_norm.assign(d, 1.f);
     L.ffn_norm.assign(d, 1.f);
+    if (cfg_.qk_norm) {
+      L.qn.assign(cfg_.head_dim, 1.f);
+      L.kn.assign(cfg_.head_dim, 1.f);
+    }
     L.q = own_random(t.q, qd, d, s + 1);
     L.k = own_random(t.k, kvd, d, s + 2);
     L.v = own_random(t.v, kvd, d, s + 3);
@@ -337,6 +347,20 @@ void CpuStage::layer_forward(int li, int M, float* x, const int32_t* pos, const 
       float* row = qkv_.data() + (size_t)m * ldq;
       for (int i = 0; i < qd; ++i) row[i] += L.bq[i];
       for (int i = 0; i < kvd; ++i) row[qd + i] += L.bk[i], row[qd + kvd + i] += L.bv[i];
+    }
+  // Qwen3: RMSNorm of every q and k head (weights in GGUF order: NEOX pairs are rotated in place
+  // below, so nothing is permuted here), before the rotation
+  if (!L.qn.empty())
+    for (int m = 0; m < M; ++m) {
+      float* row = qkv_.data() + (size_t)m * ldq;
+      for (int h = 0; h < Hq + Hkv; ++h) {
+        float* v = row + (size_t)h * hd;
+        const float* w = h < Hq ? L.qn.data() : L.kn.data();
+        double ss = 0;
+        for (int j = 0; j < hd; ++j) ss += (double)v[j] * v[j];
+        const float r = 1.0f / std::sqrt((float)(ss / hd) + cfg_.eps);
+        for (int j = 0; j < hd; ++j) v[j] = v[j] * r * w[j];
+      }
     }
   // RoPE (GGUF Llama layout: adjacent pairs (2i, 2i+1); Qwen2 NEOX: (i, i + hd/2)) + KV append
   const int half = hd / 2, pstride = cfg_.rope_neox ? 1 : 2, poff = cfg_.rope_neox ? half : 1;

@@ -55,6 +55,7 @@ class CpuStage : public Stage {
     std::vector<float> attn_norm, ffn_norm;
     CpuMat q, k, v, o, gate, up, down;
     std::vector<float> bq, bk, bv;   // Qwen2 q/k/v biases (empty: none)
+    std::vector<float> qn, kn;       // Qwen3 per-head q / k RMSNorm weights [head_dim] (empty: none)
     bool moe = false;
     CpuMat router;
     std::vector<CpuMat> eg, eu, ed;   // experts

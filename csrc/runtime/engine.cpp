@@ -67,6 +67,7 @@ ModelConfig config_from_json(const Json& j) {
   c.n_expert = j.get_int("n_expert", 0);
   c.n_expert_used = j.get_int("n_expert_used", 0);
   c.n_ctx_train = j.get_int("n_ctx_train", 2048);
+  c.qk_norm = j.get_bool("qk_norm", false);   // Qwen3 shapes: all-ones per-head q / k norm weights
   if (!c.n_layer || !c.d_model || !c.n_head || !c.d_ff) throw std::runtime_error("synthetic config incomplete");
   return c;
 }
@@ -1856,6 +1857,8 @@ Json Engine::info() const {
   Json m = Json::object();
   m["n_layer"] = cfg_.n_layer; m["d_model"] = cfg_.d_model; m["vocab"] = cfg_.vocab;
   m["n_head"] = cfg_.n_head; m["n_head_kv"] = cfg_.n_head_kv; m["d_ff"] = cfg_.d_ff;
+  m["arch"] = cfg_.arch; m["head_dim"] = cfg_.head_dim; m["rope_neox"] = cfg_.rope_neox; m["qk_norm"] = cfg_.qk_norm;
+  m["describe"] = cfg_.describe();
   j["model"] = m;
   size_t wb = 0, kb = 0;
   for (auto& w : workers_) { wb += w->stage->weight_bytes(); kb += w->stage->kv_bytes(); }

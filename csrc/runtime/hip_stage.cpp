@@ -249,6 +249,19 @@ void HipStage::load_gguf(const GgufFile& f) {
       }
       L.qkv_bias = upload_f32(b.data(), b.size());
     }
+    if (cfg_.qk_norm) {
+      // the sum of squares is invariant under the per-head NEOX row permutation; the weight is not
+      const int hd = cfg_.head_dim;
+      float** dst[2] = {&L.q_norm, &L.k_norm};
+      const char* nm[2] = {"attn_q_norm.weight", "attn_k_norm.weight"};
+      for (int i = 0; i < 2; ++i) {
+        const std::vector<float> v = tensor_f32(need(p + nm[i]));
+        if ((int)v.size() != hd) throw std::runtime_error(p + nm[i] + ": expected head_dim weights");
+        std::vector<float> w(hd);
+        for (int r = 0; r < hd; ++r) w[r] = v[cfg_.rope_neox ? neox_src_row(r, hd) : r];
+        *dst[i] = upload_f32(w.data(), w.size());
+      }
+    }
     L.wo = pack_mat(need(p + "attn_output.weight"));
     if (cfg_.n_expert) {
       // Mixtral: router [E][d] + stacked experts (ffn_*_exps [E][F][d]) or legacy per-expert tensors
@@ -329,7 +342,7 @@ void HipStage::load_gguf(const GgufFile& f) {
 void HipStage::init_synthetic(const std::string& ftype, uint64_t seed) {
   HIP_OK(hipSetDevice(spec_.device));
   const int d = cfg_.d_model, qd = cfg_.q_dim(), kvd = cfg_.kv_dim(), F = cfg_.d_ff;
-  std::vector<float> ones(std::max(d, 1), 1.0f);
+  std::vector<float> ones(std::max({d, cfg_.head_dim, 1}), 1.0f);
   for (int li = spec_.layer_begin; li < spec_.layer_end; ++li) {
     LayerW& L = layers_[li - spec_.layer_begin];
     const SyntheticTypes t = SyntheticTypes::from_ftype(ftype, li, cfg_.n_layer);
@@ -346,6 +359,10 @@ void HipStage::init_synthetic(const std::string& ftype, uint64_t seed) {
       L.qkv.push_back({alloc_packed_random(t.q, qd, d, s + 1), off});
       L.qkv.push_back({alloc_packed_random(t.k, kvd, d, s + 2), qd});
       L.qkv.push_back({alloc_packed_random(t.v, kvd, d, s + 3), qd + kvd});
+    }
+    if (cfg_.qk_norm) {
+      L.q_norm = upload_f32(ones.data(), cfg_.head_dim);
+      L.k_norm = upload_f32(ones.data(), cfg_.head_dim);
     }
     L.wo = alloc_packed_random(t.o, d, qd, s + 4);
     if (cfg_.n_expert) {
@@ -917,7 +934,8 @@ void HipStage::layer_forward(int li, int M, float* x, const int32_t* pos, const 
     const bool two = knob(KNOB_GEMVS2) != 0;
     // decode: RoPE and the KV append in the qkv GEMV's epilogue (QkvAppend), so the attention starts
     // from rotated q and a complete cache (no dependent position -> page -> append chain of its own)
-    const bool pre = decode && opt_.fused_attn && knob(KNOB_ATTN_PRE) && !opt_.deterministic &&
+    // (a q/k-normed layer needs the complete projection before the rotation: no QkvAppend)
+    const bool pre = decode && opt_.fused_attn && knob(KNOB_ATTN_PRE) && !opt_.deterministic && !L.q_norm &&
                      attn_decode_pre_ok(decode_attn_params(li, M, pos, slot, false));
     QkvAppend qa{};
     if (pre) {
@@ -948,6 +966,7 @@ void HipStage::layer_forward(int li, int M, float* x, const int32_t* pos, const 
                    L.qkv_bias ? L.qkv_bias + s.y_off : nullptr, st, pre ? &q : nullptr);
       }
     }
+    qk_norm(L, M, st);
     if (!(decode && attention_o(li, M, pos, slot, x, st, pre))) {
       attention(li, M, pos, kvlen, slot, decode, st, false, pre);
       gemv_small(L.wo, EPI_ATOMIC, attn_, Ko_, nullptr, nullptr, M, x, d, nullptr, 0, d, nullptr, st);
@@ -975,7 +994,9 @@ void HipStage::layer_forward(int li, int M, float* x, const int32_t* pos, const 
   // q|k|v accumulator (invariant: zero outside [qkv GEMV, o-proj]; unfused forwards clear it after
   // their last layer).
   const bool small = fuse_norm(M);
-  const bool qkv_deferred = small && decode && opt_.fused_attn;
+  // (a q/k-normed layer normalises final q|k|v values: it takes the standalone attn_norm; the o-proj's
+  // zero side job below still clears the range, so the invariant holds for the next layer)
+  const bool qkv_deferred = small && decode && opt_.fused_attn && !L.q_norm;
   GemvParams nx{};
   nx.Xf = x; nx.ldxf = d; nx.eps = cfg_.eps; nx.d_norm = d;
   if (qkv_deferred) {
@@ -990,6 +1011,7 @@ void HipStage::layer_forward(int li, int M, float* x, const int32_t* pos, const 
     for (const MatSeg& s : L.qkv)
       gemv(s.m, EPI_ATOMIC, xn_, Kd_, M, qkv_ + s.y_off, qkv_n_, nullptr, 0, (int)s.m.dims.N, true, st);
   }
+  qk_norm(L, M, st);
   attention(li, M, pos, kvlen, slot, decode, st, qkv_deferred);
   if (small) {
     GemvParams z{};
@@ -1024,6 +1046,14 @@ void HipStage::layer_forward(int li, int M, float* x, const int32_t* pos, const 
   sk_defer_ = x;   // absorbed by the next layer's attention norm (or flushed after the last layer)
   gemv(L.down, EPI_ATOMIC, h_, Kff_, M, x, d, nullptr, 0, d, true, st);
   sk_defer_ = nullptr;
+}
+
+void HipStage::qk_norm(const LayerW& L, int M, hipStream_t st) {
+  if (!L.q_norm) return;
+  QkNormParams p{};
+  p.qkv = qkv_; p.ldqkv = qkv_n_; p.M = M; p.Hq = cfg_.n_head; p.Hkv = cfg_.n_head_kv; p.hd = cfg_.head_dim;
+  p.wq = L.q_norm; p.wk = L.k_norm; p.eps = cfg_.eps;
+  launch_qk_norm(p, st);
 }
 
 // single-stream decode: attention + o-projection in one launch (attention.hip attn_o_kernel) while

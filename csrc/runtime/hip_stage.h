@@ -62,6 +62,9 @@ struct LayerW {
   float* ffn_norm = nullptr;
   std::vector<MatSeg> qkv;
   float* qkv_bias = nullptr;  // [q | k | v] f32 (Qwen2), q/k rows NEOX-permuted like the weights
+  // Qwen3 per-head q / k RMSNorm weights, f32 [head_dim], NEOX-permuted like the q/k rows (null: none)
+  float* q_norm = nullptr;
+  float* k_norm = nullptr;
   PackedMat wo;
   bool fused_gateup = true;
   PackedMat gateup;           // interleaved (fused SwiGLU)
@@ -131,6 +134,8 @@ class HipStage : public Stage {
   void moe_ffn(const LayerW& L, int M, hipStream_t st, float* x);
   void moe_ffn_rows(const LayerW& L, int r0, int M, hipStream_t st, float* x, bool grouped = false);
   bool fuse_norm(int M) const;
+  // Qwen3: per-head RMSNorm of the q and k heads of the complete q|k|v rows in qkv_ (no-op without weights)
+  void qk_norm(const LayerW& L, int M, hipStream_t st);
   void build_i8_copies();
   int8_t* xq_ = nullptr; float* xqs_ = nullptr; int xq_ld_ = 0;   // int8_gemm: quantized activation rows
   const void* xq_src_ = nullptr; int xq_rows_ = 0;   // the f16 rows xq_ currently holds (set by norm_x / the quant)

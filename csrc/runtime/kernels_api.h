@@ -140,6 +140,19 @@ struct RopeKvParams {
   int kv_fp8 = 0;        // caches hold e4m3 bytes (same element layout, 1 byte each)
 };
 void launch_rope_kv(const RopeKvParams& p, hipStream_t st);
+
+// Qwen3: RMSNorm over each q and k head of the f32 projection rows, in place, before RoPE:
+// h[:] = h[:] * rsqrt(mean_j(h[j]^2) + eps) * w[:], mean over the hd real elements.  v, the row
+// padding and rows >= M are not written.  Even hd <= 128 (throws otherwise).
+struct QkNormParams {
+  float* qkv;            // [M][ldqkv]: q (Hq*hd) | k (Hkv*hd) | v (Hkv*hd) | padding
+  int ldqkv;
+  int M, Hq, Hkv, hd;
+  const float* wq;       // [hd] q-head norm weight (shared by every q head)
+  const float* wk;       // [hd] k-head norm weight
+  float eps;
+};
+void launch_qk_norm(const QkNormParams& p, hipStream_t st);
 // int8 rows for the P_I8 GEMM prototype: Q[m][k] = round(X[m][k] / xs[m]), xs[m] = max_k |X[m][k]| / 127
 void launch_quant_rows_i8(const f16* X, int ldx, int M, int K, int8_t* Q, int ldq, float* xs, hipStream_t st);
 // per-row int8 re-quantization of a dense f16 weight [n_pad][nsb * 256] (launch_unpack output) into

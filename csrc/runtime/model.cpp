@@ -15,9 +15,12 @@ ModelConfig ModelConfig::from_gguf(const GgufFile& f) {
   c.arch = f.get_str("general.architecture", "llama");
   c.name = f.get_str("general.name", "");
   const std::string a = c.arch + ".";
-  if (c.arch != "llama" && c.arch != "qwen2") throw std::runtime_error("unsupported architecture: " + c.arch);
-  c.rope_neox = c.arch == "qwen2";
+  if (c.arch != "llama" && c.arch != "qwen2" && c.arch != "qwen3")
+    throw std::runtime_error("unsupported architecture: " + c.arch);
+  c.rope_neox = c.arch == "qwen2" || c.arch == "qwen3";
   c.qkv_bias = f.tensor("blk.0.attn_q.bias") != nullptr;
+  c.qk_norm = f.tensor("blk.0.attn_q_norm.weight") != nullptr;
+  if (c.arch == "qwen3" && !c.qk_norm) throw std::runtime_error("qwen3: missing tensor blk.0.attn_q_norm.weight");
   c.n_layer = (int)f.get_int(a + "block_count", 0);
   c.d_model = (int)f.get_int(a + "embedding_length", 0);
   c.n_head = (int)f.get_int(a + "attention.head_count", 0);
@@ -28,7 +31,15 @@ ModelConfig ModelConfig::from_gguf(const GgufFile& f) {
   c.eps = (float)f.get_float(a + "attention.layer_norm_rms_epsilon", 1e-5);
   c.n_expert = (int)f.get_int(a + "expert_count", 0);
   c.n_expert_used = (int)f.get_int(a + "expert_used_count", 0);
-  c.head_dim = (int)f.get_int(a + "rope.dimension_count", c.n_head ? c.d_model / c.n_head : 0);
+  // head_dim: attention.key_length, else rope.dimension_count, else d_model / n_head
+  const int64_t rope_dim = f.get_int(a + "rope.dimension_count", 0);
+  const int64_t key_len = f.get_int(a + "attention.key_length", 0);
+  const int64_t val_len = f.get_int(a + "attention.value_length", 0);
+  c.head_dim = (int)(key_len ? key_len : rope_dim ? rope_dim : c.n_head ? c.d_model / c.n_head : 0);
+  if (val_len && val_len != c.head_dim)
+    throw std::runtime_error("attention.value_length != key_length unsupported (one head_dim per KV page)");
+  if (rope_dim && rope_dim != c.head_dim)
+    throw std::runtime_error("rope.dimension_count != head_dim unsupported (no partial rotary)");
   const GgufTensor* emb = f.tensor("token_embd.weight");
   if (!emb) throw std::runtime_error("missing token_embd.weight");
   c.vocab = (int)f.get_int(a + "vocab_size", emb->ne.size() > 1 ? emb->ne[1] : 0);
@@ -38,6 +49,7 @@ ModelConfig ModelConfig::from_gguf(const GgufFile& f) {
     throw std::runtime_error("incomplete llama hyper-parameters in GGUF");
   if (c.n_head % c.n_head_kv) throw std::runtime_error("n_head not a multiple of n_head_kv");
   if (c.head_dim > 128) throw std::runtime_error("head_dim > 128 unsupported");
+  if (c.qk_norm && (c.head_dim & 1)) throw std::runtime_error("per-head Q/K norm needs an even head_dim");
   if (c.n_head / c.n_head_kv > 16) throw std::runtime_error("GQA group > 16 unsupported");
   return c;
 }
@@ -50,6 +62,7 @@ std::string ModelConfig::describe() const {
   if (n_expert) o << " n_expert=" << n_expert << " n_expert_used=" << n_expert_used;
   if (rope_neox) o << " rope=neox";
   if (qkv_bias) o << " qkv_bias";
+  if (qk_norm) o << " qk_norm";
   return o.str();
 }
 

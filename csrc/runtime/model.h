@@ -29,6 +29,12 @@ struct ModelConfig {
   // invariant under the shared permutation and V is untouched, so no kernel changes.
   bool rope_neox = false;
   bool qkv_bias = false;
+  // Qwen3 family (arch "qwen3"): NEOX RoPE, no biases, and an RMSNorm over each q and k head
+  // (weights blk.N.attn_{q,k}_norm.weight, [head_dim], shared by the heads) between the projection
+  // and the rotation.  head_dim comes from attention.key_length and need not be d_model / n_head.
+  // The GPU stage permutes the norm weights like the q/k rows (neox_src_row); the mean of squares
+  // is invariant under the permutation.
+  bool qk_norm = false;
 
   int q_dim() const { return n_head * head_dim; }
   int kv_dim() const { return n_head_kv * head_dim; }

@@ -62,17 +62,22 @@ inline Json synthetic_arch(const std::string& name) {
   else if (name == "tinyllama") set("TinyLlama-1.1B", 22, 2048, 32, 4, 5632, 32000, 10000.0);
   else if (name == "mixtral-8x7b") set("Mixtral-8x7B", 32, 4096, 32, 8, 14336, 32000, 1000000.0, 8, 2);
   else if (name == "stories15m") set("stories15M", 6, 288, 6, 6, 768, 32000, 10000.0);
+  else if (name == "qwen3-8b") {
+    set("Qwen3-8B", 36, 4096, 32, 8, 12288, 151936, 1000000.0);
+    s["head_dim"] = 128; s["eps"] = 1e-6; s["n_ctx_train"] = 40960; s["qk_norm"] = true;
+  }
   else throw std::runtime_error("unknown synthetic model " + name +
-                                " (llama3-70b, llama3-8b, tinyllama, mixtral-8x7b, stories15m)");
+                                " (llama3-70b, llama3-8b, tinyllama, mixtral-8x7b, stories15m, qwen3-8b)");
   return s;
 }
 
 inline void print_common_usage(FILE* f) {
   fprintf(f,
           "model:\n"
-          "  -m, --model FILE          GGUF model (llama/mistral/mixtral architectures)\n"
+          "  -m, --model FILE          GGUF model (llama/mistral/mixtral/qwen2/qwen3 architectures)\n"
           "  --synthetic NAME          random-init model instead of -m (llama3-70b, llama3-8b, tinyllama,\n"
-          "                            mixtral-8x7b, stories15m); --ftype Q4_K_M|Q4_K|Q5_K_M|Q6_K|Q8_0|F16\n"
+          "                            mixtral-8x7b, stories15m, qwen3-8b); --ftype Q4_K_M|Q4_K|Q5_K_M|Q6_K|Q8_0|F16\n"
+          "  --no-qk-norm              synthetic Qwen3 shapes without the per-head Q/K RMSNorm (A/B of its cost)\n"
           "generation:\n"
           "  -p, --prompt TEXT         prompt (default \"Once upon a time\")\n"
           "  -f, --file FILE           read the prompt from a file\n"
@@ -116,6 +121,7 @@ inline CliOptions parse_cli(int argc, char** argv,
   Json& e = o.eng;
   e["max_ctx"] = 2048;
   std::string synthetic, devices, rpc, next, master;
+  bool no_qk_norm = false;
   int stages = 0, world = 0, rank = -1;
   for (int i = 1; i < argc; ++i) {
     const std::string a = argv[i];
@@ -125,6 +131,7 @@ inline CliOptions parse_cli(int argc, char** argv,
     };
     if (a == "-m" || a == "--model") e["gguf"] = val();
     else if (a == "--synthetic") synthetic = val();
+    else if (a == "--no-qk-norm") no_qk_norm = true;
     else if (a == "--ftype") e["ftype"] = val();
     else if (a == "-p" || a == "--prompt") o.prompt = val();
     else if (a == "-f" || a == "--file") o.prompt = read_file(val());
@@ -180,7 +187,11 @@ inline CliOptions parse_cli(int argc, char** argv,
     else if (extra_flag && extra_flag(a, val)) continue;
     else throw std::runtime_error("unknown flag " + a);
   }
-  if (!synthetic.empty()) e["synthetic"] = synthetic_arch(synthetic);
+  if (!synthetic.empty()) {
+    Json syn = synthetic_arch(synthetic);
+    if (no_qk_norm) syn["qk_norm"] = false;
+    e["synthetic"] = syn;
+  }
   if (!e.has("gguf") && !e.has("synthetic")) throw std::runtime_error("need -m FILE or --synthetic NAME");
   if (o.ngl == 0) e["backend"] = "cpu";
   else if (o.ngl > 0) e["gpu_layers"] = o.ngl;   // explicit -ngl only: >= n_layer puts every layer on the GPUs

@@ -68,6 +68,7 @@ _SIGS = {
     "mp_op_embed": ([c_int, c_void_p, c_int64, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p], c_int),
     "mp_op_rope_kv": ([c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int,
                        c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_int, c_void_p], c_int),
+    "mp_op_qk_norm": ([c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_float, c_void_p], c_int),
     "mp_op_attn_decode": ([c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_float, c_void_p,
                            c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
                            c_void_p, c_int, c_void_p, c_float, c_int, c_void_p, c_int, c_int, c_void_p], c_int),

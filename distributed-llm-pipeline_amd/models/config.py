@@ -29,8 +29,9 @@ class LlamaConfig:
     head_dim: int = 0           # 0 -> d_model // n_head
     tokenizer: str = "llama"    # "gpt2" (byte-level BPE) or "llama" (SPM)
     rope_freq_factors: bool = False   # Llama-3.1 rope_freqs.weight
-    arch: str = "llama"         # GGUF general.architecture: "llama" or "qwen2"
+    arch: str = "llama"         # GGUF general.architecture: "llama", "qwen2" or "qwen3"
     qkv_bias: bool = False      # Qwen2: attn_{q,k,v}.bias
+    qk_norm: bool = False       # Qwen3: per-head RMSNorm of q and k before RoPE (attn_{q,k}_norm.weight)
     tied_output: bool = False   # no output.weight (LM head = token_embd)
 
     @property
@@ -55,12 +56,19 @@ CONFIGS = {
                                 n_expert=8, n_expert_used=2),
     "qwen2-7b": LlamaConfig("qwen2-7b", 28, 3584, 28, 4, 18944, 152064, 1e6, 1e-6, 32768,
                             tokenizer="gpt2", arch="qwen2", qkv_bias=True),
+    "qwen3-8b": LlamaConfig("qwen3-8b", 36, 4096, 32, 8, 12288, 151936, 1e6, 1e-6, 40960, head_dim=128,
+                            tokenizer="gpt2", arch="qwen3", qk_norm=True),
     # small test shapes (same code paths, fast to generate)
     "tiny-gqa": LlamaConfig("tiny-gqa", 4, 512, 8, 2, 1024, 2048, 10000.0, 1e-5, 1024),
     "tiny-moe": LlamaConfig("tiny-moe", 3, 512, 8, 2, 768, 2048, 10000.0, 1e-5, 1024,
                             n_expert=4, n_expert_used=2),
     "tiny-qwen2": LlamaConfig("tiny-qwen2", 4, 512, 8, 2, 1024, 4096, 1e6, 1e-6, 1024,
                               tokenizer="gpt2", arch="qwen2", qkv_bias=True, tied_output=True),
+    # head_dim decoupled from d_model / n_head (q_dim 1024 != d_model 512), as in Qwen3-0.6B / 4B / 32B
+    "tiny-qwen3": LlamaConfig("tiny-qwen3", 4, 512, 8, 2, 1024, 4096, 1e6, 1e-6, 1024, head_dim=128,
+                              tokenizer="gpt2", arch="qwen3", qk_norm=True, tied_output=True),
+    "tiny-qwen3-hd64": LlamaConfig("tiny-qwen3-hd64", 4, 512, 8, 2, 1024, 4096, 1e6, 1e-6, 1024, head_dim=64,
+                                   tokenizer="gpt2", arch="qwen3", qk_norm=True, tied_output=True),
     "tiny-l3": LlamaConfig("tiny-l3", 4, 1024, 8, 2, 2048, 4096, 500000.0, 1e-5, 1024,
                            tokenizer="gpt2", rope_freq_factors=True),
 }

@@ -2,7 +2,8 @@
 
 Implements exactly the forward of SURVEY.md §3.5 (what llama.cpp's `llm_build_llama` computes for
 the reference run, upstream; not in mount): RMSNorm, RoPE "NORM" mode (adjacent pairs) with
-optional Llama-3.1 frequency factors, GQA attention with a KV cache, SwiGLU FFN or Mixtral top-k
+optional Llama-3.1 frequency factors (NEOX pairs for Qwen2 / Qwen3, Qwen3's per-head Q/K RMSNorm
+before the rotation), GQA attention with a KV cache, SwiGLU FFN or Mixtral top-k
 MoE, final norm + LM head.  Weights are dequantized from the GGUF with the numpy reference
 dequantizers, so engine-vs-oracle differences measure kernel numerics only.
 """
@@ -46,8 +47,8 @@ class RefLlama:
                   d_ff=int(g("feed_forward_length")), rope_base=float(g("rope.freq_base", 10000.0)),
                   eps=float(g("attention.layer_norm_rms_epsilon", 1e-5)),
                   n_expert=int(g("expert_count", 0)), n_expert_used=int(g("expert_used_count", 0)))
-        hp["head_dim"] = int(g("rope.dimension_count", hp["d_model"] // hp["n_head"]))
-        hp["rope_neox"] = a == "qwen2"   # llama.cpp LLM_ARCH_QWEN2 uses LLAMA_ROPE_TYPE_NEOX
+        hp["head_dim"] = int(g("attention.key_length", g("rope.dimension_count", hp["d_model"] // hp["n_head"])))
+        hp["rope_neox"] = a in ("qwen2", "qwen3")   # llama.cpp LLM_ARCH_QWEN2 / QWEN3 use LLAMA_ROPE_TYPE_NEOX
         tensors = {name: r.tensor_f32(name) for name in r.tensors}
         return cls(tensors, hp, dtype, device)
 
@@ -99,6 +100,8 @@ class RefLlama:
             if p + "attn_q.bias" in t:
                 q, k, v = q + t[p + "attn_q.bias"], k + t[p + "attn_k.bias"], v + t[p + "attn_v.bias"]
             q, k, v = q.view(T, H, hd), k.view(T, Hk, hd), v.view(T, Hk, hd)
+            if p + "attn_q_norm.weight" in t:   # Qwen3: per-head RMSNorm of q and k, before RoPE
+                q, k = self.rmsnorm(q, t[p + "attn_q_norm.weight"]), self.rmsnorm(k, t[p + "attn_k_norm.weight"])
             q, k = self.rope(q, pos), self.rope(k, pos)
             if self.kv_round is not None:   # e.g. the fp8 KV cache's rounding
                 k, v = self.kv_round(k), self.kv_round(v)

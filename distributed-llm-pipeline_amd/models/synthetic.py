@@ -35,6 +35,9 @@ def llama_tensor_specs(cfg: LlamaConfig, ftype: str):
             yield (p + "attn_q.bias", (cfg.n_head * hd,), Q.F32, "bias")
             yield (p + "attn_k.bias", (cfg.n_head_kv * hd,), Q.F32, "bias")
             yield (p + "attn_v.bias", (cfg.n_head_kv * hd,), Q.F32, "bias")
+        if cfg.qk_norm:
+            yield (p + "attn_q_norm.weight", (hd,), Q.F32, "qknorm")
+            yield (p + "attn_k_norm.weight", (hd,), Q.F32, "qknorm")
         yield (p + "attn_output.weight", (cfg.n_head * hd, d),
                tensor_type(ftype, "attn_output", i, L, cfg.n_head * hd), "wo")
         yield (p + "ffn_norm.weight", (d,), Q.F32, "norm")
@@ -56,6 +59,10 @@ def _float_init(rng, name, shape, kind, cfg: LlamaConfig, wscale: float):
     n = int(np.prod(shape))
     if kind == "norm":
         return (1.0 + 0.1 * rng.standard_normal(n)).astype(np.float32)
+    if kind == "qknorm":
+        # wide spread on purpose: a weight left un-permuted on the NEOX path, or a norm applied after
+        # RoPE, must show up against the oracle (the 1 +- 0.1 of "norm" would hide both)
+        return rng.uniform(0.5, 2.0, n).astype(np.float32)
     if kind == "rope":
         # Llama-3.1 style frequency factors: 1 for high freqs, up to 8 for low freqs
         i = np.arange(n)
@@ -91,6 +98,9 @@ def write_synthetic_gguf(path: str, cfg: LlamaConfig, ftype: str = "Q4_K_M", see
     w.add(f"{arch}.attention.head_count_kv", cfg.n_head_kv, U32)
     w.add(f"{arch}.rope.freq_base", float(cfg.rope_base), F32T)
     w.add(f"{arch}.rope.dimension_count", cfg.hd, U32)
+    if arch == "qwen3":
+        w.add(f"{arch}.attention.key_length", cfg.hd, U32)
+        w.add(f"{arch}.attention.value_length", cfg.hd, U32)
     w.add(f"{arch}.attention.layer_norm_rms_epsilon", float(cfg.eps), F32T)
     w.add(f"{arch}.vocab_size", cfg.vocab, U32)
     if cfg.n_expert:

@@ -391,6 +391,14 @@ def rope_kv(qkv, pos, slot, block_table, rope_cs, Hq, Hkv, hd, Dp, q_scale, k_ca
     return q_out
 
 
+def qk_norm(qkv, wq, wk, Hq, Hkv, hd, eps):
+    """Qwen3 per-head RMSNorm of the q and k heads of the f32 rows qkv [M, >= (Hq + 2 Hkv) hd], in
+    place, before RoPE; wq / wk: f32 [hd].  Returns qkv."""
+    N.check(N.lib().mp_op_qk_norm(_ptr(qkv), qkv.stride(0), qkv.shape[0], Hq, Hkv, hd, _ptr(wq), _ptr(wk),
+                                  float(eps), _stream()), "qk_norm")
+    return qkv
+
+
 def attention(q, kvlen, slot, block_table, k_cache, v_cache, Hkv, hd, tq=1, split_len=256, n_split=1):
     M, Hq, Dp = q.shape
     out = torch.zeros(M, Hq * hd, dtype=torch.float16, device=q.device)
