@@ -103,6 +103,157 @@ __global__ __launch_bounds__(1024) void moe_route_kernel(const MoeRouteParams p)
   for (int e = threadIdx.x; e < p.E; e += blockDim.x) p.counts[e] = cnt[e];
 }
 
+// Fused router for 64 < E <= 128 experts (Qwen3-MoE): one launch from the normalised activations to
+// every token's top-k selection; moe_bucket_kernel below then builds the per-expert lists.
+//
+// Workgroup = 16 token rows x all E experts, 8 waves.  Logits [16][K] x [K][E] on the 16x16x32 f16
+// MFMA: wave (ch, kp) owns the column tiles of experts 64 ch .. 64 ch + 63 and every 4th 64-wide K
+// chunk starting at chunk kp, so each slice of the dense router is read once per 16 rows (M / 16
+// workgroups in all; the one-row-per-workgroup kernel above re-reads the whole router per row:
+// 512 KB at E = 128, d = 2048).  Lane (g, r) of a chunk holds k = 64 c + 16 g + [0, 16) of x row r
+// and of router row e: the A and B operands of the two MFMAs carry the same k, and a row's four
+// lane groups read 128 contiguous bytes.  Rows >= M load nothing (zero A fragment); router rows
+// >= E re-read row E - 1 (in bounds and cached; those columns are never used).  The
+// four K partials of a logit are added in LDS in the fixed order kp = 0..3: no atomics, bitwise
+// repeatable.
+//
+// Top-k: wave w takes rows 2 w, 2 w + 1 of the block; lane l holds logits l and l + 64.  k rounds of
+// a wave arg-max, ties to the lower index (the rule of moe_route_kernel and CpuStage), pick the
+// experts in descending-logit order; the first round's maximum and one wave sum give the softmax
+// denominator.  Lane j < k then writes slot t k + j: its expert id into
+// sel[] and the renormalised weight.
+constexpr int RT_LDP = 128 + 4;   // padded LDS row: the 4 lane groups of a C tile (rows 4 apart) hit different banks
+
+__global__ __launch_bounds__(512) void moe_router_kernel(const f16* __restrict__ X, int ldx, const f16* __restrict__ R,
+                                                         int K, float* __restrict__ logits, const MoeRouteParams p) {
+  __shared__ float part[4][16][RT_LDP];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int ch = wave & 1, kp = wave >> 1;
+  const int r = lane & 15, g = lane >> 4;
+  const int m0 = blockIdx.x * 16;
+  const int E = p.E, M = p.M;
+  const bool x_ok = m0 + r < M;
+  const f16* xp = X + (size_t)min(m0 + r, M - 1) * ldx + 16 * g;
+  const f16* rp[4];
+#pragma unroll
+  for (int ct = 0; ct < 4; ++ct) rp[ct] = R + (size_t)min(64 * ch + 16 * ct + r, E - 1) * K + 16 * g;
+  f32x4 acc[4];
+#pragma unroll
+  for (int ct = 0; ct < 4; ++ct) acc[ct] = f32x4{0.f, 0.f, 0.f, 0.f};
+  // Two fragment sets in ping-pong, the next chunk's loads issued ahead of this chunk's MFMAs.  No
+  // uniform branch inside the K loop (the compiler then counts the loads in flight and waits for the
+  // current chunk only): every wave runs its 4 column tiles, tiles past E on the clamped row; a
+  // prefetch past the wave's last chunk re-reads that chunk with a zero A fragment.
+  struct Frag { half8_t a[2], b[4][2]; };
+  auto load = [&](Frag& f, const int k0, const bool a_ok) {
+#pragma unroll
+    for (int h = 0; h < 2; ++h) f.a[h] = a_ok ? *reinterpret_cast<const half8_t*>(xp + k0 + 8 * h) : half8_t{};
+#pragma unroll
+    for (int ct = 0; ct < 4; ++ct)
+#pragma unroll
+      for (int h = 0; h < 2; ++h) f.b[ct][h] = *reinterpret_cast<const half8_t*>(rp[ct] + k0 + 8 * h);
+  };
+  auto mac = [&](const Frag& f) {
+#pragma unroll
+    for (int ct = 0; ct < 4; ++ct)
+#pragma unroll
+      for (int h = 0; h < 2; ++h) acc[ct] = mfma16x16x32(f.a[h], f.b[ct][h], acc[ct]);
+  };
+  const int nch = (K / 64 - kp + 3) / 4;   // this wave's chunks kp, kp + 4, ..
+  auto chunk = [&](const int c) { return 64 * (kp + 4 * min(c, nch - 1)); };
+  if (nch > 0) {
+    Frag f0, f1;
+    load(f0, chunk(0), x_ok);
+    for (int c = 0; c < nch; c += 2) {
+      load(f1, chunk(c + 1), x_ok && c + 1 < nch);
+      __builtin_amdgcn_sched_barrier(0);   // (keeps the compiler from sinking the loads below the MFMAs)
+      mac(f0);
+      load(f0, chunk(c + 2), x_ok && c + 2 < nch);
+      __builtin_amdgcn_sched_barrier(0);
+      mac(f1);
+    }
+  }
+  // lane holds C[row 4 g + i][expert 64 ch + 16 ct + r]
+#pragma unroll
+  for (int ct = 0; ct < 4; ++ct)
+#pragma unroll
+    for (int i = 0; i < 4; ++i) part[kp][4 * g + i][64 * ch + 16 * ct + r] = acc[ct][i];
+  __syncthreads();
+
+  // The wave's two rows run side by side (two independent shuffle chains).  A logit travels as an
+  // order-preserving 32-bit key (f32 order, -0 folded into +0; 0 = taken or past E), so a round is
+  // one 6-step wave max of keys; the winner is the lowest lane holding the max key, lower half first.
+  auto to_key = [](float v) {
+    const uint32_t u = __float_as_uint(v == 0.f ? 0.f : v);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+  };
+  auto from_key = [](uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); };
+  const bool ok[2] = {lane < E, lane + 64 < E};
+  float v[2][2];
+  uint32_t key[2][2];
+#pragma unroll
+  for (int rr = 0; rr < 2; ++rr) {
+    const int row = 2 * wave + rr, t = m0 + row;   // rows past M: zero logits, nothing stored
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const int e = lane + 64 * h;
+      v[rr][h] = ok[h] ? ((part[0][row][e] + part[1][row][e]) + part[2][row][e]) + part[3][row][e] : -INFINITY;
+      if (ok[h] && t < M) logits[(size_t)t * p.ld + e] = v[rr][h];
+      key[rr][h] = ok[h] ? to_key(v[rr][h]) : 0u;
+    }
+  }
+  float mx[2] = {0.f, 0.f}, sum[2] = {1.f, 1.f}, my_p[2] = {0.f, 0.f};
+  int my_e[2] = {0, 0};
+  for (int j = 0; j < p.k; ++j) {
+    uint32_t best[2];
+#pragma unroll
+    for (int rr = 0; rr < 2; ++rr) best[rr] = max(key[rr][0], key[rr][1]);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1)
+#pragma unroll
+      for (int rr = 0; rr < 2; ++rr) best[rr] = max(best[rr], (uint32_t)__shfl_xor((int)best[rr], o));
+#pragma unroll
+    for (int rr = 0; rr < 2; ++rr) {
+      const unsigned long long b0 = __ballot(key[rr][0] == best[rr]), b1 = __ballot(key[rr][1] == best[rr]);
+      const int bi = b0 ? __builtin_ctzll(b0) : 64 + (b1 ? __builtin_ctzll(b1) : 0);
+      const float bv = from_key(best[rr]);
+      if (j == 0) {   // the row maximum: the softmax denominator from one wave sum (expf(-inf) = 0 past E)
+        mx[rr] = bv;
+        sum[rr] = wave_sum(expf(v[rr][0] - bv) + expf(v[rr][1] - bv));
+      }
+      if (bi == lane) key[rr][0] = 0u;
+      if (bi == lane + 64) key[rr][1] = 0u;
+      // (bi < E whenever the logits are finite; the clamp keeps a row of NaNs inside the lists)
+      if (lane == j) { my_e[rr] = min(bi, E - 1); my_p[rr] = expf(bv - mx[rr]) / sum[rr]; }
+    }
+  }
+#pragma unroll
+  for (int rr = 0; rr < 2; ++rr) {
+    const int t = m0 + 2 * wave + rr;
+    const float wsum = wave_sum(my_p[rr]);
+    if (lane < p.k && t < M) {
+      p.sel[t * p.k + lane] = my_e[rr];
+      p.weights[t * p.k + lane] = my_p[rr] / wsum;
+    }
+  }
+}
+
+// Bucket the n = M k selected slots by expert: one workgroup, list positions from LDS atomics (as
+// moe_route_kernel: global atomics on E addresses serialise at one L2 channel), counts out once.
+__global__ __launch_bounds__(1024) void moe_bucket_kernel(const MoeRouteParams p) {
+  __shared__ int cnt[128];
+  for (int e = threadIdx.x; e < p.E; e += blockDim.x) cnt[e] = 0;
+  __syncthreads();
+  const int n = p.M * p.k;
+  for (int s = threadIdx.x; s < n; s += blockDim.x) {
+    const int e = p.sel[s];
+    const int pos = atomicAdd(&cnt[e], 1);
+    p.lists[(size_t)e * p.list_cap + pos] = s;
+  }
+  __syncthreads();
+  for (int e = threadIdx.x; e < p.E; e += blockDim.x) p.counts[e] = cnt[e];
+}
+
 // Grouped skinny GEMV: grid (tiles, splits, experts).  Rows = the slots routed to expert e,
 // processed 16 at a time (one MFMA row tile); weights of expert e at W + e * estride.
 template <int PT, int EPI>
@@ -309,7 +460,17 @@ void launch_router_logits(const f16* X, int ldx, const f16* R, int K, int E, int
 }
 
 void launch_moe_route(const MoeRouteParams& p, hipStream_t st) {
+  if (p.E > 64) throw std::runtime_error("launch_moe_route: E <= 64 (launch_moe_router routes up to 128 experts)");
   hipLaunchKernelGGL(mpk::moe_route_kernel, dim3(1), dim3(1024), 0, st, p);
+}
+
+void launch_moe_router(const f16* X, int ldx, const f16* R, int K, float* logits, const MoeRouteParams& p, hipStream_t st) {
+  if (K < 64 || K % 64 || ldx < K || p.E < 1 || p.E > 128 || p.ld < p.E || p.M < 1 || p.k < 1 || p.k > 8 || p.k > p.E ||
+      p.list_cap < p.M * p.k || !p.sel)
+    throw std::runtime_error("launch_moe_router: K % 64, ldx >= K, 1 <= E <= 128, ld >= E, 1 <= k <= min(8, E), "
+                             "list_cap >= M k, sel != null");
+  hipLaunchKernelGGL(mpk::moe_router_kernel, dim3((p.M + 15) / 16), dim3(512), 0, st, X, ldx, R, K, logits, p);
+  hipLaunchKernelGGL(mpk::moe_bucket_kernel, dim3(1), dim3(1024), 0, st, p);
 }
 
 template <int PT, int EPI, int MT>

@@ -161,6 +161,7 @@ const char* mp_model_config_json(const char* gguf_path) {
   j["rope_freqs"] = c.rope_freqs; j["tied_output"] = c.tied_output;
   j["arch"] = c.arch; j["rope_neox"] = c.rope_neox; j["qkv_bias"] = c.qkv_bias;
   j["qk_norm"] = c.qk_norm;
+  j["expert_ff"] = c.expert_ff;
   g_str = j.dump();
   return g_str.c_str();
   API_CATCH(nullptr)
@@ -232,10 +233,41 @@ int mp_op_moe_gemm4(int ptype, int epi, const void* W, int64_t estride, int ntil
   API_CATCH(-1)
 }
 
+// grouped expert GEMV (moe.hip: M <= 64 the workgroup-shared kernel, above it one wave per tile):
+// same operands as mp_op_moe_gemm4; nsplit K splits of the ATOMIC (down) epilogue
+int mp_op_moe_gemv(int ptype, int epi, const void* W, int64_t estride, int ntiles, int nsb, const void* X, int ldx,
+                   int x_per_slot, int M, int E, int k, const void* counts, const void* lists, int list_cap,
+                   const void* weights, void* Y, int ldy, void* H, int ldh, int n_valid, int nsplit, void* stream) {
+  API_TRY
+  MoeGemvParams q{};
+  q.W = (const uint8_t*)W; q.estride = (size_t)estride; q.ntiles = ntiles; q.nsb = nsb;
+  q.X = (const f16*)X; q.ldx = ldx; q.x_per_slot = x_per_slot; q.M = M; q.E = E; q.k = k;
+  q.counts = (const int32_t*)counts; q.lists = (const int32_t*)lists; q.list_cap = list_cap;
+  q.weights = (const float*)weights; q.Y = (float*)Y; q.ldy = ldy; q.H = (f16*)H; q.ldh = ldh; q.n_valid = n_valid;
+  launch_moe_gemv(ptype, epi, q, nsplit, (hipStream_t)stream);
+  HIP_OK(hipGetLastError());
+  return 0;
+  API_CATCH(-1)
+}
+
 // router logits [M][ld] = X [M][ldx] . R [E][K]^T (dense f16 router)
 int mp_op_router_logits(const void* X, int ldx, const void* R, int K, int E, int M, void* out, int ld, void* stream) {
   API_TRY
   launch_router_logits((const f16*)X, ldx, (const f16*)R, K, E, M, (float*)out, ld, (hipStream_t)stream);
+  HIP_OK(hipGetLastError());
+  return 0;
+  API_CATCH(-1)
+}
+
+// fused router (E <= 128): logits + top-k selection + per-expert lists from x and the dense f16 router
+int mp_op_moe_router(const void* X, int ldx, const void* R, int K, int E, int M, int k, void* logits, int ld, void* counts,
+                     void* lists, int list_cap, void* weights, void* sel, void* stream) {
+  API_TRY
+  MoeRouteParams rp{};
+  rp.logits = (const float*)logits; rp.ld = ld; rp.M = M; rp.E = E; rp.k = k;
+  rp.counts = (int32_t*)counts; rp.lists = (int32_t*)lists; rp.list_cap = list_cap; rp.weights = (float*)weights;
+  rp.sel = (int32_t*)sel;
+  launch_moe_router((const f16*)X, ldx, (const f16*)R, K, (float*)logits, rp, (hipStream_t)stream);
   HIP_OK(hipGetLastError());
   return 0;
   API_CATCH(-1)

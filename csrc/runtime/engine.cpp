@@ -68,6 +68,9 @@ ModelConfig config_from_json(const Json& j) {
   c.n_expert_used = j.get_int("n_expert_used", 0);
   c.n_ctx_train = j.get_int("n_ctx_train", 2048);
   c.qk_norm = j.get_bool("qk_norm", false);   // Qwen3 shapes: all-ones per-head q / k norm weights
+  c.expert_ff = j.get_bool("expert_ff", false);   // Qwen3-MoE shapes: d_ff is the per-expert width
+  if (c.n_expert > 128 || (c.n_expert && (c.n_expert_used < 1 || c.n_expert_used > 8 || c.n_expert_used > c.n_expert)))
+    throw std::runtime_error("synthetic config: need n_expert <= 128 and 1 <= n_expert_used <= min(8, n_expert)");
   if (!c.n_layer || !c.d_model || !c.n_head || !c.d_ff) throw std::runtime_error("synthetic config incomplete");
   return c;
 }
@@ -1858,6 +1861,10 @@ Json Engine::info() const {
   m["n_layer"] = cfg_.n_layer; m["d_model"] = cfg_.d_model; m["vocab"] = cfg_.vocab;
   m["n_head"] = cfg_.n_head; m["n_head_kv"] = cfg_.n_head_kv; m["d_ff"] = cfg_.d_ff;
   m["arch"] = cfg_.arch; m["head_dim"] = cfg_.head_dim; m["rope_neox"] = cfg_.rope_neox; m["qk_norm"] = cfg_.qk_norm;
+  m["n_expert"] = cfg_.n_expert; m["n_expert_used"] = cfg_.n_expert_used;
+  // d_ff is the width of one expert where the file gives it separately (qwen3moe)
+  m["d_ff_kind"] = cfg_.expert_ff ? "expert" : "dense";
+  if (cfg_.expert_ff) m["expert_d_ff"] = cfg_.d_ff;
   m["describe"] = cfg_.describe();
   j["model"] = m;
   size_t wb = 0, kb = 0;

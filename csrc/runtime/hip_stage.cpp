@@ -479,11 +479,14 @@ void HipStage::alloc_runtime() {
   for (auto& L : layers_) any_unfused |= !L.fused_gateup;
   if (any_unfused) gu_ = (float*)zalloc((size_t)scratch_rows_ * 2 * cfg_.d_ff * 4);
   if (cfg_.n_expert) {
-    if (cfg_.n_expert > 64 || cfg_.n_expert_used > 8 || cfg_.n_expert_used < 1)
-      throw std::runtime_error("MoE: need n_expert <= 64 and 1 <= n_expert_used <= 8");
+    if (cfg_.n_expert > 128 || cfg_.n_expert_used > 8 || cfg_.n_expert_used < 1 || cfg_.n_expert_used > cfg_.n_expert)
+      throw std::runtime_error("MoE: need n_expert <= 128 and 1 <= n_expert_used <= min(8, n_expert)");
     const int k = cfg_.n_expert_used;
-    moe_logits_ = (float*)zalloc((size_t)scratch_rows_ * 64 * 4);
-    moe_counts_ = (int32_t*)zalloc(64 * 4);
+    // logits row stride: 64 up to 64 experts (moe_route_kernel), 128 above (moe_router_kernel)
+    moe_ld_ = (int)round_up(cfg_.n_expert, 64);
+    moe_logits_ = (float*)zalloc((size_t)scratch_rows_ * moe_ld_ * 4);
+    moe_counts_ = (int32_t*)zalloc((size_t)moe_ld_ * 4);
+    if (cfg_.n_expert > 64) moe_sel_ = (int32_t*)zalloc((size_t)scratch_rows_ * k * 4);
     moe_lists_ = (int32_t*)zalloc((size_t)cfg_.n_expert * scratch_rows_ * k * 4);
     moe_w_ = (float*)zalloc((size_t)scratch_rows_ * k * 4);
     moe_h_ = (f16*)zalloc((size_t)scratch_rows_ * k * Kff_ * 2);
@@ -872,17 +875,25 @@ void HipStage::moe_ffn(const LayerW& L, int M, hipStream_t st, float* x) {
 void HipStage::moe_ffn_rows(const LayerW& L, int r0, int M, hipStream_t st, float* x, bool grouped) {
   const int E = cfg_.n_expert, k = cfg_.n_expert_used, d = cfg_.d_model, F = cfg_.d_ff;
   const f16* xn = xn_ + (size_t)r0 * Kd_;
-  float* logits = moe_logits_ + (size_t)r0 * 64;
-  // router logits [M][E]: one 16-row tile, so split-K over the super-blocks (atomics into the
-  // buffer the ffn RMSNorm cleared) instead of one serial workgroup (28.5 us -> a few us per layer)
-  if (L.ex.router_dense && Kd_ >= (int)L.ex.router.dims.nsb * 256)
-    launch_router_logits(xn, Kd_, L.ex.router_dense, (int)L.ex.router.dims.nsb * 256, E, M, logits, 64, st);
-  else
-    gemv(L.ex.router, EPI_ATOMIC, xn, Kd_, M, logits, 64, nullptr, 0, E, true, st);
+  float* logits = moe_logits_ + (size_t)r0 * moe_ld_;
   MoeRouteParams rp{};
-  rp.logits = logits; rp.ld = 64; rp.M = M; rp.E = E; rp.k = k;
+  rp.logits = logits; rp.ld = moe_ld_; rp.M = M; rp.E = E; rp.k = k;
   rp.counts = moe_counts_; rp.lists = moe_lists_; rp.list_cap = scratch_rows_ * k; rp.weights = moe_w_;
-  launch_moe_route(rp, st);
+  const int Kr = (int)L.ex.router.dims.nsb * 256;
+  if (E > 64) {
+    // Qwen3-MoE: logits, top-k and lists from the fused router (16 token rows share each router slice)
+    if (!L.ex.router_dense || Kd_ < Kr) throw std::runtime_error("moe_ffn: the fused router needs the dense f16 router");
+    rp.sel = moe_sel_;
+    launch_moe_router(xn, Kd_, L.ex.router_dense, Kr, logits, rp, st);
+  } else {
+    // router logits [M][E]: one 16-row tile, so split-K over the super-blocks (atomics into the
+    // buffer the ffn RMSNorm cleared) instead of one serial workgroup (28.5 us -> a few us per layer)
+    if (L.ex.router_dense && Kd_ >= Kr)
+      launch_router_logits(xn, Kd_, L.ex.router_dense, Kr, E, M, logits, moe_ld_, st);
+    else
+      gemv(L.ex.router, EPI_ATOMIC, xn, Kd_, M, logits, moe_ld_, nullptr, 0, E, true, st);
+    launch_moe_route(rp, st);
+  }
   MoeGemvParams gp{};
   gp.W = L.ex.gateup.d; gp.estride = L.ex.gateup_stride;
   gp.ntiles = (int)L.ex.gateup.dims.ntiles; gp.nsb = (int)L.ex.gateup.dims.nsb;
@@ -972,7 +983,7 @@ void HipStage::layer_forward(int li, int M, float* x, const int32_t* pos, const 
       gemv_small(L.wo, EPI_ATOMIC, attn_, Ko_, nullptr, nullptr, M, x, d, nullptr, 0, d, nullptr, st);
     }
     if (L.moe) {
-      launch_rmsnorm(x, d, L.ffn_norm, d, cfg_.eps, xn_, Kd_, M, moe_logits_, (int64_t)M * 64, st);
+      launch_rmsnorm(x, d, L.ffn_norm, d, cfg_.eps, xn_, Kd_, M, moe_logits_, (int64_t)M * moe_ld_, st);
       xq_src_ = nullptr;
       moe_ffn(L, M, st, x);
       return;
@@ -1026,7 +1037,7 @@ void HipStage::layer_forward(int li, int M, float* x, const int32_t* pos, const 
   }
   const bool ffn_fused = small && !L.moe;
   // MoE: the same launch clears the router logits, which the router GEMV then accumulates split-K
-  if (!ffn_fused) norm_x(x, L.ffn_norm, M, L.moe ? moe_logits_ : nullptr, L.moe ? (int64_t)M * 64 : 0, st);
+  if (!ffn_fused) norm_x(x, L.ffn_norm, M, L.moe ? moe_logits_ : nullptr, L.moe ? (int64_t)M * moe_ld_ : 0, st);
   if (L.moe) {
     moe_ffn(L, M, st, x);
     return;

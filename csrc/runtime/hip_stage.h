@@ -219,6 +219,8 @@ class HipStage : public Stage {
   // MoE scratch
   float* moe_logits_ = nullptr; int32_t* moe_counts_ = nullptr; int32_t* moe_lists_ = nullptr;
   float* moe_w_ = nullptr; f16* moe_h_ = nullptr;
+  int moe_ld_ = 64;              // router logits row stride: round_up(n_expert, 64)
+  int32_t* moe_sel_ = nullptr;   // n_expert > 64: expert id per slot (fused router -> bucketing)
   // KV
   std::vector<f16*> kc_, vc_;
   int32_t* block_table_ = nullptr; int max_pages_ = 0; int n_pages_ = 0;   // paged KV (kvpager.h)

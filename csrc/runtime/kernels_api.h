@@ -295,13 +295,22 @@ void launch_f32_to_f16(const float* x, int ldx, int n, int M, f16* y, int ldy, h
 struct MoeRouteParams {
   const float* logits;   // [M][ld] router logits
   int ld;
-  int M, E, k;           // E <= 64, k <= 8
+  int M, E, k;           // k <= 8; E <= 64 for launch_moe_route, <= 128 for launch_moe_router
   int32_t* counts;       // [E]
   int32_t* lists;        // [E][list_cap] token-slot ids (token*k + j)
   int list_cap;
-  float* weights;        // [M*k] renormalised top-k softmax weights
+  float* weights;        // [M*k] renormalised top-k softmax weights, j in descending-logit order
+  int32_t* sel = nullptr;  // [M*k] expert id of every slot (launch_moe_router only: its selection kernel
+                           // writes it, its bucketing kernel reads it)
 };
+// E <= 64: one workgroup, a serial scan of the stored logits per token
 void launch_moe_route(const MoeRouteParams& p, hipStream_t st);
+// Fused router, E <= 128 (the stages use it for E > 64): logits [M][p.ld] (f32, stored; columns >= E
+// untouched) = x [M][ldx] f16 . R [E][K]^T on MFMA tiles of 16 token rows, then the wave-parallel
+// top-k (ties to the lower expert index) and the bucketing into p.counts / p.lists / p.weights.
+// Two launches, no atomics on global memory, bitwise repeatable except for the order of the slots
+// inside a list.  p.logits is not read; K % 64 == 0, p.list_cap >= M k.
+void launch_moe_router(const f16* X, int ldx, const f16* R, int K, float* logits, const MoeRouteParams& p, hipStream_t st);
 // router logits [M][ld] (f32, stored) from x [M][ldx] f16 and the dense f16 router R [E][K], E <= 64
 void launch_router_logits(const f16* X, int ldx, const f16* R, int K, int E, int M, float* out, int ld, hipStream_t st);
 struct MoeGemvParams {

@@ -15,12 +15,15 @@ ModelConfig ModelConfig::from_gguf(const GgufFile& f) {
   c.arch = f.get_str("general.architecture", "llama");
   c.name = f.get_str("general.name", "");
   const std::string a = c.arch + ".";
-  if (c.arch != "llama" && c.arch != "qwen2" && c.arch != "qwen3")
+  if (c.arch != "llama" && c.arch != "qwen2" && c.arch != "qwen3" && c.arch != "qwen3moe")
     throw std::runtime_error("unsupported architecture: " + c.arch);
-  c.rope_neox = c.arch == "qwen2" || c.arch == "qwen3";
+  const bool q3moe = c.arch == "qwen3moe";
+  c.rope_neox = c.arch == "qwen2" || c.arch == "qwen3" || q3moe;
   c.qkv_bias = f.tensor("blk.0.attn_q.bias") != nullptr;
   c.qk_norm = f.tensor("blk.0.attn_q_norm.weight") != nullptr;
-  if (c.arch == "qwen3" && !c.qk_norm) throw std::runtime_error("qwen3: missing tensor blk.0.attn_q_norm.weight");
+  if ((c.arch == "qwen3" || q3moe) && !c.qk_norm)
+    throw std::runtime_error(c.arch + ": missing tensor blk.0.attn_q_norm.weight");
+  if (q3moe && c.qkv_bias) throw std::runtime_error("qwen3moe: unexpected tensor blk.0.attn_q.bias");
   c.n_layer = (int)f.get_int(a + "block_count", 0);
   c.d_model = (int)f.get_int(a + "embedding_length", 0);
   c.n_head = (int)f.get_int(a + "attention.head_count", 0);
@@ -31,6 +34,29 @@ ModelConfig ModelConfig::from_gguf(const GgufFile& f) {
   c.eps = (float)f.get_float(a + "attention.layer_norm_rms_epsilon", 1e-5);
   c.n_expert = (int)f.get_int(a + "expert_count", 0);
   c.n_expert_used = (int)f.get_int(a + "expert_used_count", 0);
+  if (c.n_expert > 128)
+    throw std::runtime_error(a + "expert_count = " + std::to_string(c.n_expert) + ": at most 128 experts are supported");
+  if (c.n_expert && (c.n_expert_used < 1 || c.n_expert_used > 8))
+    throw std::runtime_error(a + "expert_used_count = " + std::to_string(c.n_expert_used) + ": need 1 .. 8 experts per token");
+  if (c.n_expert_used > c.n_expert)
+    throw std::runtime_error(a + "expert_used_count = " + std::to_string(c.n_expert_used) + " exceeds " + a +
+                             "expert_count = " + std::to_string(c.n_expert));
+  if (q3moe) {
+    // every layer is sparse, no shared experts; the expert FFN width has its own key (768 at 30B-A3B)
+    // and feed_forward_length, where a file carries it, is not the width of any tensor
+    if (!c.n_expert)   // e.g. a dense Qwen3 file relabelled: there is no dense qwen3moe
+      throw std::runtime_error("unsupported architecture: qwen3moe without " + a + "expert_count (every layer must be sparse)");
+    const int64_t key = f.get_int(a + "expert_feed_forward_length", 0);
+    const GgufTensor* ge = f.tensor("blk.0.ffn_gate_exps.weight");
+    const int64_t shape = ge && ge->ne.size() > 1 ? ge->ne[1] : 0;
+    if (key && shape && key != shape)
+      throw std::runtime_error(a + "expert_feed_forward_length = " + std::to_string(key) +
+                               " disagrees with blk.0.ffn_gate_exps.weight (" + std::to_string(shape) + " rows per expert)");
+    if (!key && !shape)
+      throw std::runtime_error("qwen3moe: neither " + a + "expert_feed_forward_length nor blk.0.ffn_gate_exps.weight");
+    c.d_ff = (int)(key ? key : shape);
+    c.expert_ff = true;
+  }
   // head_dim: attention.key_length, else rope.dimension_count, else d_model / n_head
   const int64_t rope_dim = f.get_int(a + "rope.dimension_count", 0);
   const int64_t key_len = f.get_int(a + "attention.key_length", 0);
@@ -57,7 +83,7 @@ ModelConfig ModelConfig::from_gguf(const GgufFile& f) {
 std::string ModelConfig::describe() const {
   std::ostringstream o;
   o << "arch=" << arch << " n_layer=" << n_layer << " d_model=" << d_model << " n_head=" << n_head
-    << " n_head_kv=" << n_head_kv << " head_dim=" << head_dim << " d_ff=" << d_ff << " vocab=" << vocab
+    << " n_head_kv=" << n_head_kv << " head_dim=" << head_dim << (expert_ff ? " expert_d_ff=" : " d_ff=") << d_ff << " vocab=" << vocab
     << " rope_base=" << rope_base;
   if (n_expert) o << " n_expert=" << n_expert << " n_expert_used=" << n_expert_used;
   if (rope_neox) o << " rope=neox";

@@ -35,6 +35,11 @@ struct ModelConfig {
   // The GPU stage permutes the norm weights like the q/k rows (neox_src_row); the mean of squares
   // is invariant under the permutation.
   bool qk_norm = false;
+  // Qwen3-MoE (arch "qwen3moe"): Qwen3 attention, every layer a sparse FFN of up to 128 experts with
+  // Mixtral's routing (softmax over all experts, top k <= 8, renormalised), no shared experts.  d_ff is
+  // the PER-EXPERT width, read from expert_feed_forward_length (else the shape of ffn_gate_exps);
+  // expert_ff records that, for describe() and Engine::info().
+  bool expert_ff = false;
 
   int q_dim() const { return n_head * head_dim; }
   int kv_dim() const { return n_head_kv * head_dim; }

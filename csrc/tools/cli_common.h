@@ -66,17 +66,22 @@ inline Json synthetic_arch(const std::string& name) {
     set("Qwen3-8B", 36, 4096, 32, 8, 12288, 151936, 1000000.0);
     s["head_dim"] = 128; s["eps"] = 1e-6; s["n_ctx_train"] = 40960; s["qk_norm"] = true;
   }
+  else if (name == "qwen3-30b-a3b") {   // d_ff = the width of one expert, every layer sparse
+    set("Qwen3-30B-A3B", 48, 2048, 32, 4, 768, 151936, 1000000.0, 128, 8);
+    s["head_dim"] = 128; s["eps"] = 1e-6; s["n_ctx_train"] = 40960; s["qk_norm"] = true; s["expert_ff"] = true;
+  }
   else throw std::runtime_error("unknown synthetic model " + name +
-                                " (llama3-70b, llama3-8b, tinyllama, mixtral-8x7b, stories15m, qwen3-8b)");
+                                " (llama3-70b, llama3-8b, tinyllama, mixtral-8x7b, stories15m, qwen3-8b, qwen3-30b-a3b)");
   return s;
 }
 
 inline void print_common_usage(FILE* f) {
   fprintf(f,
           "model:\n"
-          "  -m, --model FILE          GGUF model (llama/mistral/mixtral/qwen2/qwen3 architectures)\n"
+          "  -m, --model FILE          GGUF model (llama/mistral/mixtral/qwen2/qwen3/qwen3moe architectures)\n"
           "  --synthetic NAME          random-init model instead of -m (llama3-70b, llama3-8b, tinyllama,\n"
-          "                            mixtral-8x7b, stories15m, qwen3-8b); --ftype Q4_K_M|Q4_K|Q5_K_M|Q6_K|Q8_0|F16\n"
+          "                            mixtral-8x7b, stories15m, qwen3-8b, qwen3-30b-a3b);\n"
+          "                            --ftype Q4_K_M|Q4_K|Q5_K_M|Q6_K|Q8_0|F16\n"
           "  --no-qk-norm              synthetic Qwen3 shapes without the per-head Q/K RMSNorm (A/B of its cost)\n"
           "generation:\n"
           "  -p, --prompt TEXT         prompt (default \"Once upon a time\")\n"

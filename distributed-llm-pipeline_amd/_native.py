@@ -55,7 +55,12 @@ _SIGS = {
     "mp_op_moe_gemm4": ([c_int, c_int, c_void_p, ctypes.c_longlong, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int,
                          c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p],
                         c_int),
+    "mp_op_moe_gemv": ([c_int, c_int, c_void_p, ctypes.c_longlong, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int,
+                        c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int,
+                        c_void_p], c_int),
     "mp_op_router_logits": ([c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p], c_int),
+    "mp_op_moe_router": ([c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p,
+                          c_int, c_void_p, c_void_p, c_void_p], c_int),
     "mp_op_gemm4_splitk": ([c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p,
                             ctypes.c_longlong, c_void_p], c_int),
     "mp_op_quant_i8": ([c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p], c_int),

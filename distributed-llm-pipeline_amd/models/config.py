@@ -29,10 +29,15 @@ class LlamaConfig:
     head_dim: int = 0           # 0 -> d_model // n_head
     tokenizer: str = "llama"    # "gpt2" (byte-level BPE) or "llama" (SPM)
     rope_freq_factors: bool = False   # Llama-3.1 rope_freqs.weight
-    arch: str = "llama"         # GGUF general.architecture: "llama", "qwen2" or "qwen3"
+    arch: str = "llama"         # GGUF general.architecture: "llama", "qwen2", "qwen3" or "qwen3moe"
     qkv_bias: bool = False      # Qwen2: attn_{q,k,v}.bias
     qk_norm: bool = False       # Qwen3: per-head RMSNorm of q and k before RoPE (attn_{q,k}_norm.weight)
     tied_output: bool = False   # no output.weight (LM head = token_embd)
+    # standard deviation of the synthetic router weights.  With 0.5 and unit-RMS inputs the router
+    # logits have a standard deviation of 0.5 sqrt(d_model) (11 at d_model 512): a softmax over many
+    # experts then puts nearly all weight on one of them, and a wrong 2nd .. k-th expert would barely
+    # move the output.  1 / sqrt(d_model) gives logits of about unit standard deviation.
+    router_std: float = 0.5
 
     @property
     def hd(self) -> int:
@@ -58,6 +63,9 @@ CONFIGS = {
                             tokenizer="gpt2", arch="qwen2", qkv_bias=True),
     "qwen3-8b": LlamaConfig("qwen3-8b", 36, 4096, 32, 8, 12288, 151936, 1e6, 1e-6, 40960, head_dim=128,
                             tokenizer="gpt2", arch="qwen3", qk_norm=True),
+    # Qwen3-30B-A3B: d_ff is the width of ONE expert (expert_feed_forward_length), every layer sparse
+    "qwen3-30b-a3b": LlamaConfig("qwen3-30b-a3b", 48, 2048, 32, 4, 768, 151936, 1e6, 1e-6, 40960, head_dim=128,
+                                 n_expert=128, n_expert_used=8, tokenizer="gpt2", arch="qwen3moe", qk_norm=True),
     # small test shapes (same code paths, fast to generate)
     "tiny-gqa": LlamaConfig("tiny-gqa", 4, 512, 8, 2, 1024, 2048, 10000.0, 1e-5, 1024),
     "tiny-moe": LlamaConfig("tiny-moe", 3, 512, 8, 2, 768, 2048, 10000.0, 1e-5, 1024,
@@ -69,6 +77,10 @@ CONFIGS = {
                               tokenizer="gpt2", arch="qwen3", qk_norm=True, tied_output=True),
     "tiny-qwen3-hd64": LlamaConfig("tiny-qwen3-hd64", 4, 512, 8, 2, 1024, 4096, 1e6, 1e-6, 1024, head_dim=64,
                                    tokenizer="gpt2", arch="qwen3", qk_norm=True, tied_output=True),
+    # 128 experts, 8 per token, one-super-block experts; router logits of about unit standard deviation
+    "tiny-qwen3moe": LlamaConfig("tiny-qwen3moe", 2, 256, 4, 2, 256, 4096, 1e6, 1e-6, 1024, head_dim=128,
+                                 n_expert=128, n_expert_used=8, tokenizer="gpt2", arch="qwen3moe", qk_norm=True,
+                                 tied_output=True, router_std=1.0 / 16.0),
     "tiny-l3": LlamaConfig("tiny-l3", 4, 1024, 8, 2, 2048, 4096, 500000.0, 1e-5, 1024,
                            tokenizer="gpt2", rope_freq_factors=True),
 }

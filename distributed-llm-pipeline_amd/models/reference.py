@@ -3,8 +3,9 @@
 Implements exactly the forward of SURVEY.md §3.5 (what llama.cpp's `llm_build_llama` computes for
 the reference run, upstream; not in mount): RMSNorm, RoPE "NORM" mode (adjacent pairs) with
 optional Llama-3.1 frequency factors (NEOX pairs for Qwen2 / Qwen3, Qwen3's per-head Q/K RMSNorm
-before the rotation), GQA attention with a KV cache, SwiGLU FFN or Mixtral top-k
-MoE, final norm + LM head.  Weights are dequantized from the GGUF with the numpy reference
+before the rotation), GQA attention with a KV cache, SwiGLU FFN or Mixtral / Qwen3-MoE top-k
+MoE (softmax over all experts, top k, renormalised; ties to the lower expert index), final norm +
+LM head.  Weights are dequantized from the GGUF with the numpy reference
 dequantizers, so engine-vs-oracle differences measure kernel numerics only.
 """
 from __future__ import annotations
@@ -36,6 +37,10 @@ class RefLlama:
         self.cache_k = [None] * self.L
         self.cache_v = [None] * self.L
         self.kv_round = None   # optional f(t) applied to new K (after RoPE) and V before caching
+        # MoE: one (layer, start_pos, margin [T], rms [T]) per layer and forward() since reset():
+        # margin = the k-th minus the (k+1)-th largest router logit of each token, rms = the root mean
+        # square of its logit row (how close the selection is to flipping under a perturbed input)
+        self.router_margins = []
 
     @classmethod
     def from_gguf(cls, path: str, dtype=torch.float32, device="cpu"):
@@ -48,7 +53,8 @@ class RefLlama:
                   eps=float(g("attention.layer_norm_rms_epsilon", 1e-5)),
                   n_expert=int(g("expert_count", 0)), n_expert_used=int(g("expert_used_count", 0)))
         hp["head_dim"] = int(g("attention.key_length", g("rope.dimension_count", hp["d_model"] // hp["n_head"])))
-        hp["rope_neox"] = a in ("qwen2", "qwen3")   # llama.cpp LLM_ARCH_QWEN2 / QWEN3 use LLAMA_ROPE_TYPE_NEOX
+        # llama.cpp LLM_ARCH_QWEN2 / QWEN3 / QWEN3MOE use LLAMA_ROPE_TYPE_NEOX
+        hp["rope_neox"] = a in ("qwen2", "qwen3", "qwen3moe")
         tensors = {name: r.tensor_f32(name) for name in r.tensors}
         return cls(tensors, hp, dtype, device)
 
@@ -77,6 +83,7 @@ class RefLlama:
     def reset(self):
         self.cache_k = [None] * self.L
         self.cache_v = [None] * self.L
+        self.router_margins = []
 
     @torch.no_grad()
     def forward(self, tokens, start_pos: int, layers=None, x_in=None, want_logits=True):
@@ -124,7 +131,7 @@ class RefLlama:
             x = x + o @ t[p + "attn_output.weight"].T
             h = self.rmsnorm(x, t[p + "ffn_norm.weight"])
             if self.hp.get("n_expert", 0):
-                x = x + self._moe(h, p)
+                x = x + self._moe(h, p, i, start_pos)
             else:
                 g = h @ t[p + "ffn_gate.weight"].T
                 u = h @ t[p + "ffn_up.weight"].T
@@ -134,13 +141,19 @@ class RefLlama:
         h = self.rmsnorm(x, t["output_norm.weight"])
         return h @ t["output.weight"].T
 
-    def _moe(self, h, p):
+    def _moe(self, h, p, layer=0, start_pos=0):
         t = self.t
         E, k = self.hp["n_expert"], self.hp["n_expert_used"]
         logits = h @ t[p + "ffn_gate_inp.weight"].T          # [T, E]
         probs = torch.softmax(logits, -1)
-        w, idx = torch.topk(probs, k, dim=-1)
+        # a stable descending sort keeps equal logits in index order: ties go to the lower expert
+        srt, order = torch.sort(logits, dim=-1, descending=True, stable=True)
+        idx = order[:, :k]
+        w = torch.gather(probs, -1, idx)
         w = w / w.sum(-1, keepdim=True)
+        margin = srt[:, k - 1] - srt[:, k] if k < E else torch.full_like(srt[:, 0], float("inf"))
+        rms = torch.sqrt((logits * logits).mean(-1))
+        self.router_margins.append((layer, start_pos, margin.double().cpu().numpy(), rms.double().cpu().numpy()))
         out = torch.zeros_like(h)
         G, U, D = t[p + "ffn_gate_exps.weight"], t[p + "ffn_up_exps.weight"], t[p + "ffn_down_exps.weight"]
         for ti in range(h.shape[0]):

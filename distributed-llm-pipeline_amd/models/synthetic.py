@@ -70,7 +70,7 @@ def _float_init(rng, name, shape, kind, cfg: LlamaConfig, wscale: float):
     if kind == "bias":
         return (rng.standard_normal(n) * 0.5).astype(np.float32)
     if kind == "router":
-        return (rng.standard_normal(n) * 0.5).astype(np.float32)
+        return (rng.standard_normal(n) * cfg.router_std).astype(np.float32)
     if kind == "embd":
         return (rng.standard_normal(n) * 1.0).astype(np.float32)
     fan_in = shape[0]
@@ -94,11 +94,13 @@ def write_synthetic_gguf(path: str, cfg: LlamaConfig, ftype: str = "Q4_K_M", see
     w.add(f"{arch}.context_length", cfg.n_ctx_train, U32)
     w.add(f"{arch}.embedding_length", cfg.d_model, U32)
     w.add(f"{arch}.feed_forward_length", cfg.d_ff, U32)
+    if arch == "qwen3moe" and cfg.n_expert:   # cfg.d_ff is the per-expert width
+        w.add(f"{arch}.expert_feed_forward_length", cfg.d_ff, U32)
     w.add(f"{arch}.attention.head_count", cfg.n_head, U32)
     w.add(f"{arch}.attention.head_count_kv", cfg.n_head_kv, U32)
     w.add(f"{arch}.rope.freq_base", float(cfg.rope_base), F32T)
     w.add(f"{arch}.rope.dimension_count", cfg.hd, U32)
-    if arch == "qwen3":
+    if arch in ("qwen3", "qwen3moe"):
         w.add(f"{arch}.attention.key_length", cfg.hd, U32)
         w.add(f"{arch}.attention.value_length", cfg.hd, U32)
     w.add(f"{arch}.attention.layer_norm_rms_epsilon", float(cfg.eps), F32T)

@@ -192,6 +192,18 @@ def moe_gemm(w_dev: torch.Tensor, estride: int, ptype: int, ntiles: int, nsb: in
                                     h.stride(0) if h is not None else 0, n_valid, _stream()), "moe_gemm4")
 
 
+def moe_gemv(w_dev: torch.Tensor, estride: int, ptype: int, ntiles: int, nsb: int, n_valid: int, epi: int,
+             x: torch.Tensor, M: int, E: int, k: int, counts, lists, weights=None, *, x_per_slot: bool = False,
+             h: torch.Tensor | None = None, y: torch.Tensor | None = None, nsplit: int = 1) -> None:
+    """Grouped expert GEMV (the decode route of the stages, M <= 64 tokens per call on the
+    workgroup-shared kernel); operands as moe_gemm, `nsplit` K splits for the EPI_ATOMIC epilogue."""
+    assert x.dtype == torch.float16 and x.is_contiguous()
+    N.check(N.lib().mp_op_moe_gemv(ptype, epi, _ptr(w_dev), estride, ntiles, nsb, _ptr(x), x.stride(0),
+                                   int(x_per_slot), M, E, k, _ptr(counts), _ptr(lists), lists.shape[1],
+                                   _ptr(weights), _ptr(y), y.stride(0) if y is not None else 0, _ptr(h),
+                                   h.stride(0) if h is not None else 0, n_valid, nsplit, _stream()), "moe_gemv")
+
+
 def router_logits(x: torch.Tensor, r_dense: torch.Tensor) -> torch.Tensor:
     """logits [M][E] f32 = x [M][K] f16 . r_dense [E][K]^T (the dense-router kernel, E <= 64)."""
     M, K = x.shape[0], r_dense.shape[1]
@@ -200,6 +212,28 @@ def router_logits(x: torch.Tensor, r_dense: torch.Tensor) -> torch.Tensor:
     N.check(N.lib().mp_op_router_logits(_ptr(x), x.stride(0), _ptr(r_dense.contiguous()), K, E, M, _ptr(out), 64,
                                         _stream()), "router_logits")
     return out[:, :E]
+
+
+def moe_router(x: torch.Tensor, r_dense: torch.Tensor, k: int, *, ld: int | None = None, list_cap: int | None = None,
+               logits: torch.Tensor | None = None, lists: torch.Tensor | None = None):
+    """Fused router for up to 128 experts: x [M][K] f16 and the dense f16 router r_dense [E][K] ->
+    (logits [M][ld] f32, counts [E], lists [E][list_cap] of slot ids t * k + j, weights [M * k]).
+    `logits` / `lists` may be passed pre-filled (the kernel leaves columns >= E and the list tails
+    untouched); otherwise the padding columns are 0 and the list tails -1."""
+    assert x.dtype == torch.float16 and r_dense.dtype == torch.float16 and x.stride(1) == 1
+    M, (E, K) = x.shape[0], r_dense.shape
+    r_dense = r_dense.contiguous()
+    if logits is None:
+        logits = torch.zeros(M, ld or (E + 63) // 64 * 64, dtype=torch.float32, device=x.device)
+    if lists is None:
+        lists = torch.full((E, list_cap or M * k), -1, dtype=torch.int32, device=x.device)
+    counts = torch.zeros(E, dtype=torch.int32, device=x.device)
+    weights = torch.zeros(M * k, dtype=torch.float32, device=x.device)
+    sel = torch.zeros(M * k, dtype=torch.int32, device=x.device)
+    N.check(N.lib().mp_op_moe_router(_ptr(x), x.stride(0), _ptr(r_dense), K, E, M, k, _ptr(logits), logits.stride(0),
+                                     _ptr(counts), _ptr(lists), lists.stride(0), _ptr(weights), _ptr(sel), _stream()),
+            "moe_router")
+    return logits, counts, lists, weights
 
 
 class I8Weight:
