@@ -588,6 +588,33 @@ int mp_attn_decode_form(int M, int Hkv, int n_split) {
   API_CATCH(-1)
 }
 
+// gemm4 launch plans (host only: shape, type and knobs decide).  out[10] = ok, bm, nwv, tw, nsplit,
+// per, wnt, grid_x, grid_y, grid_z.  Returns 1 when the kernel geometry table holds the plan's
+// geometry (or the plan is not ok: nothing would launch), else 0.
+static int plan_out(const Gemm4Plan& pl, int ptype, bool moe, int* out) {
+  const int v[10] = {pl.ok, pl.bm, pl.nwv, pl.tw, pl.nsplit, pl.per, pl.wnt, pl.grid_x, pl.grid_y, pl.grid_z};
+  std::copy(v, v + 10, out);
+  return !pl.ok || gemm4_has_geometry(ptype, pl.bm, pl.nwv, pl.tw, moe);
+}
+
+int mp_gemm4_plan(int ptype, int epi, int M, int ntiles, int nsb, int allow_split, int partial_stores, int* out) {
+  API_TRY
+  return plan_out(plan_gemm4(ptype, epi, M, ntiles, nsb, allow_split != 0, partial_stores != 0), ptype, false, out);
+  API_CATCH(-1)
+}
+
+int mp_moe_gemm4_plan(int ptype, int epi, int M, int k, int E, int ntiles, int nsb, int per_slot, int* out) {
+  API_TRY
+  return plan_out(plan_moe_gemm4(ptype, epi, M, k, E, ntiles, nsb, per_slot != 0), ptype, true, out);
+  API_CATCH(-1)
+}
+
+int mp_gemm4_geometry_count() { return gemm4_geometry_count(); }
+
+int mp_gemm4_has_geometry(int ptype, int bm, int nwv, int tw, int moe) {
+  return gemm4_has_geometry(ptype, bm, nwv, tw, moe != 0);
+}
+
 int mp_op_argmax(const void* logits, int ld, int n, int M, void* tokens, void* part, void* counters, void* stream) {
   API_TRY
   // part [M][kArgmaxChunks][2] f32 + counters [M] zeroed int32 select the two-level kernel

@@ -529,8 +529,9 @@ void HipStage::alloc_runtime() {
       if (!m.d || is16(m.ptype)) return;
       for (int M : {opt_.mb_size, opt_.prefill_chunk}) {
         if (M <= 64) continue;
-        const int ns = gemm4_splits(m.ptype, (int)m.dims.ntiles, (int)m.dims.nsb, M);
-        if (ns > 1) need = std::max(need, (size_t)ns * M * m.dims.ntiles * 16);
+        // the plan launch_gemm4_splitk will run (ok: it splits)
+        const Gemm4Plan pl = plan_gemm4(m.ptype, EPI_ATOMIC, M, (int)m.dims.ntiles, (int)m.dims.nsb, true, true);
+        if (pl.ok) need = std::max(need, (size_t)pl.nsplit * M * m.dims.ntiles * 16);
       }
     };
     for (const LayerW& L : layers_) {
@@ -729,93 +730,76 @@ void HipStage::set_history(int mb, const std::vector<std::vector<int32_t>>& seqs
   HIP_OK(hipMemcpy(hist_cnt_ + (size_t)mb * B, cnt.data(), cnt.size() * 4, hipMemcpyHostToDevice));
 }
 
+// the GemvParams fields every launch on a packed matrix shares
+static GemvParams mat_params(const PackedMat& m, const f16* X, int ldx, int M, float* Y, int ldy, f16* H, int ldh,
+                             int n_valid) {
+  GemvParams p{};
+  p.W = m.d; p.X = X; p.ldx = ldx; p.M = M; p.Y = Y; p.ldy = ldy; p.H = H; p.ldh = ldh;
+  p.ntiles = (int)m.dims.ntiles; p.nsb = (int)m.dims.nsb; p.n_valid = n_valid;
+  return p;
+}
+
+// Up to 64 rows (decode micro-batches, short prompt chunks): the dequant GEMV.  Above: gemm4 for the
+// types it takes, gemm3 for 16-bit weights, the 64 x 64 GEMM for the rest (Q4_0) -- except its wide
+// gate/up (>= 192 workgroups of 16 tiles), which the two-tile GEMV beats per 64 rows
+// (profiles/r1g_prefill_gemm_vs_gemv.txt).  How the selection got here: docs/PERFORMANCE.md, 3.1.
+HipStage::GemmRoute HipStage::gemm_route(const PackedMat& m, int epi, int M, bool have_x) const {
+  if (M <= 64 || !opt_.prefill_gemm) return GemmRoute::GEMV;
+  if (m.i8 && xq_ && have_x) return GemmRoute::I8;
+  const int gv = opt_.prefill_gemm_v == 2 ? 4 : opt_.prefill_gemm_v != 0 ? opt_.prefill_gemm_v : is16(m.ptype) ? 3 : 4;
+  if (gv == 4 && gemm4_supported(m.ptype)) return GemmRoute::GEMM4;
+  if (gv == 3) return GemmRoute::GEMM3;
+  const bool wide_swiglu = epi == EPI_SWIGLU && m.dims.ntiles / 16 >= 192;
+  return wide_swiglu ? GemmRoute::GEMV : GemmRoute::GEMM1;
+}
+
 void HipStage::gemv(const PackedMat& m, int epi, const f16* X, int ldx, int M, float* Y, int ldy, f16* H, int ldh,
                     int n_valid, bool allow_split, hipStream_t st, const GemvParams* extras) {
-  // up to 64 rows (decode micro-batches, short prompt chunks): the dequant GEMV, 1-4 MFMA row
-  // groups per weight fragment; longer prompt chunks: MFMA GEMM, weights read once per 64 rows
-  // exception: the large gate/up GEMVs that run two tiles per wave (>= 192 workgroups of 16
-  // tiles) beat the 64x64-tile GEMM per 64 rows (70B: 4 x 73.6 us vs 410 us per 256-row chunk;
-  // profiles/r1g_prefill_gemm_vs_gemv.txt)
-  // v2 GEMM (128 rows x 256 columns per workgroup, the decode GEMV's dequant + LDS-shared rows):
-  // every shape, f16 weights excepted (they take the 64 x 64 GEMM)
-  // v3 GEMM (gemm3.hip: 128|256 x 128|256 workgroup tiles, each weight element dequantized once
-  // per workgroup, cross-stage MFMA stream): every type, 16-bit weights included
-  // (round 3, before v4) v2 for the quantized types, v3 for 16-bit weights (v2 has no 16-bit path).  Measured in
-  // the 70B mb256 round: v3 wins the gate/up on some boxes and loses it on others (212 vs 249 us in
-  // profiles/r6h_engine_gemm_v2_v3.txt, 268 us in r6j_gemm_select.txt), and loses o/down (114 vs 98),
-  // qkv (72 vs 69) and the Q6_K LM head (1162 vs 639) everywhere; bench.py A/B in one run:
-  // v2 5402 tok/s, v3 for gate/up only 5204-5217, v3 everywhere 4867 (r6j)
-  // auto for quantized weights, per epilogue (r8a, profiles/r8a_gemm_microbench.txt, 70B at M = 256):
-  // the whole-K SwiGLU / store GEMMs (gate/up, LM head) take v4 (gate/up 297 vs 316 us, Q6_K head
-  // 724 vs 820), the split-K accumulating ones (qkv, o, down) keep v2.  (v4 there too,
-  // prefill_gemm_v=4, ran 70B mb256 at 5953-5970 vs 5764 tok/s but 8B mb256 at 27.3k vs 29.4k, prompt
-  // processing 2-5 % slower, and missed the 70B-width oracle at row 128 after two decode rounds
-  // (NMSE 1.1e-3): profiles/r8s_v4_everywhere.txt -- not the default)
-  // round 5: with the tail-stage hazard gone (tools/isa_lint.py) and the saddr DMA, gemm4 takes the
-  // split-K shapes too: 70B mb256 a tie (5797 / 5786 vs 5800 / 5776), 8B mb256 30401 vs 29709
-  // (profiles/r10d_splitk_ab_and_prof.txt)
-  // (round 6: the 128-row gemm2 form is retired; prefill_gemm_v = 2 takes gemm4)
-  const int gv = opt_.prefill_gemm_v == 2 ? 4 : opt_.prefill_gemm_v != 0 ? opt_.prefill_gemm_v : is16(m.ptype) ? 3 : 4;
-  const bool wide_swiglu = epi == EPI_SWIGLU && m.dims.ntiles / 16 >= 192;
-  const bool v3 = gv == 3;
-  if (M > 64 && opt_.prefill_gemm && m.i8 && xq_ && X) {
-    // int8_gemm: x rows quantized per row, int8 MFMA against the re-quantized copy (gemm3<P_I8>)
-    const int K = (int)m.dims.nsb * 256;
-    if (X != xq_src_ || M != xq_rows_) {   // not already quantized by norm_x / the previous GEMM on X
-      launch_quant_rows_i8(X, ldx, M, K, xq_, xq_ld_, xqs_, st);
-      xq_src_ = X;
-      xq_rows_ = M;
+  switch (gemm_route(m, epi, M, X != nullptr)) {
+    case GemmRoute::I8: {
+      // int8_gemm: x rows quantized per row, int8 MFMA against the re-quantized copy (gemm3<P_I8>)
+      const int K = (int)m.dims.nsb * 256;
+      if (X != xq_src_ || M != xq_rows_) {   // not already quantized by norm_x / the previous GEMM on X
+        launch_quant_rows_i8(X, ldx, M, K, xq_, xq_ld_, xqs_, st);
+        xq_src_ = X;
+        xq_rows_ = M;
+      }
+      GemvParams p = mat_params(m, reinterpret_cast<const f16*>(xq_), xq_ld_, M, Y, ldy, H, ldh, n_valid);
+      p.W = m.i8; p.xscale = xqs_; p.wscale = m.i8_ws;
+      launch_gemm3(P_I8, epi, p, st, allow_split && !opt_.deterministic);
+      return;
     }
-    GemvParams p{};
-    p.W = m.i8; p.X = reinterpret_cast<const f16*>(xq_); p.ldx = xq_ld_; p.M = M; p.Y = Y; p.ldy = ldy; p.H = H; p.ldh = ldh;
-    p.ntiles = (int)m.dims.ntiles; p.nsb = (int)m.dims.nsb; p.n_valid = n_valid;
-    p.xscale = xqs_; p.wscale = m.i8_ws;
-    launch_gemm3(P_I8, epi, p, st, allow_split && !opt_.deterministic);
-    return;
-  }
-  if (M > 64 && opt_.prefill_gemm && gv == 4 && gemm4_supported(m.ptype)) {
-    // v4 GEMM (gemm4.hip: 32x32x16 MFMA): split-K shapes store per-split partials like v2 (into the
-    // residual x: absorbed by the next RMSNorm), the rest run whole-K
-    GemvParams p{};
-    p.W = m.d; p.X = X; p.ldx = ldx; p.M = M; p.Y = Y; p.ldy = ldy; p.H = H; p.ldh = ldh;
-    p.ntiles = (int)m.dims.ntiles; p.nsb = (int)m.dims.nsb; p.n_valid = n_valid;
-    const bool sk = opt_.gemm_splitk_store && sk_part_ && epi == EPI_ATOMIC && allow_split;
-    const bool defer = sk && Y == sk_defer_;
-    if (sk) flush_sk(st);
-    int ns = 0;
-    if (sk && launch_gemm4_splitk(m.ptype, p, sk_part_, sk_part_n_, st, !defer, &ns)) {
-      if (defer) sk_pend_ = SkPending{Y, M, n_valid, ldy, ns, p.ntiles * 16, (int64_t)M * p.ntiles * 16};
-    } else {
-      launch_gemm4(m.ptype, epi, p, st, allow_split && !opt_.deterministic);
+    case GemmRoute::GEMM4: {
+      // split-K shapes store per-split partials (into the residual x: absorbed by the next RMSNorm),
+      // the rest run whole-K
+      const GemvParams p = mat_params(m, X, ldx, M, Y, ldy, H, ldh, n_valid);
+      const bool sk = opt_.gemm_splitk_store && sk_part_ && epi == EPI_ATOMIC && allow_split;
+      const bool defer = sk && Y == sk_defer_;
+      if (sk) flush_sk(st);
+      int ns = 0;
+      if (sk && launch_gemm4_splitk(m.ptype, p, sk_part_, sk_part_n_, st, !defer, &ns)) {
+        if (defer) sk_pend_ = SkPending{Y, M, n_valid, ldy, ns, p.ntiles * 16, (int64_t)M * p.ntiles * 16};
+      } else {
+        launch_gemm4(m.ptype, epi, p, st, allow_split && !opt_.deterministic);
+      }
+      return;
     }
-    return;
-  }
-  if (M > 64 && opt_.prefill_gemm && (v3 || !wide_swiglu)) {
-    GemvParams p{};
-    p.W = m.d; p.X = X; p.ldx = ldx; p.M = M; p.Y = Y; p.ldy = ldy; p.H = H; p.ldh = ldh;
-    p.ntiles = (int)m.dims.ntiles; p.nsb = (int)m.dims.nsb; p.n_valid = n_valid;
-    if (v3) launch_gemm3(m.ptype, epi, p, st, allow_split && !opt_.deterministic);
-    else launch_gemm(m.ptype, epi, p, st);   // the types gemm4 does not take (Q4_0), or prefill_gemm_v = 1
-    return;
+    case GemmRoute::GEMM3:
+      launch_gemm3(m.ptype, epi, mat_params(m, X, ldx, M, Y, ldy, H, ldh, n_valid), st, allow_split && !opt_.deterministic);
+      return;
+    case GemmRoute::GEMM1:
+      launch_gemm(m.ptype, epi, mat_params(m, X, ldx, M, Y, ldy, H, ldh, n_valid), st);
+      return;
+    case GemmRoute::GEMV: break;
   }
   for (int r0 = 0; r0 < M; r0 += 64) {
-    GemvParams p{};
+    GemvParams p = mat_params(m, X + (size_t)r0 * ldx, ldx, std::min(64, M - r0), Y ? Y + (size_t)r0 * ldy : nullptr, ldy,
+                              H ? H + (size_t)r0 * ldh : nullptr, ldh, n_valid);
     if (extras) {   // fused norm / bias / zero-fill: small M only (one pass of this loop)
       p.Xf = extras->Xf; p.ldxf = extras->ldxf; p.gamma = extras->gamma; p.eps = extras->eps;
       p.d_norm = extras->d_norm; p.bias = extras->bias; p.zero = extras->zero; p.zero_n = extras->zero_n;
       p.ssq = extras->ssq;
     }
-    p.W = m.d;
-    p.X = X + (size_t)r0 * ldx;
-    p.ldx = ldx;
-    p.M = std::min(64, M - r0);
-    p.Y = Y ? Y + (size_t)r0 * ldy : nullptr;
-    p.ldy = ldy;
-    p.H = H ? H + (size_t)r0 * ldh : nullptr;
-    p.ldh = ldh;
-    p.ntiles = (int)m.dims.ntiles;
-    p.nsb = (int)m.dims.nsb;
-    p.n_valid = n_valid;
     const int nsplit = allow_split ? gemv_auto_split(p.ntiles, p.nsb, p.M, epi) : 1;
     const int ns = det_splits(p.ntiles, p.nsb, p.M, epi, allow_split);
     if (opt_.deterministic && epi == EPI_ATOMIC && ns > 1) {
@@ -900,22 +884,17 @@ void HipStage::moe_ffn_rows(const LayerW& L, int r0, int M, hipStream_t st, floa
   gp.X = xn; gp.ldx = Kd_; gp.x_per_slot = 0; gp.k = k;
   gp.counts = moe_counts_; gp.lists = moe_lists_; gp.list_cap = rp.list_cap; gp.E = E;
   gp.H = moe_h_; gp.ldh = Kff_; gp.n_valid = F; gp.M = M;
-  if (grouped) {
-    MoeGemvParams dp = gp;
-    dp.W = L.ex.down.d; dp.estride = L.ex.down_stride;
-    dp.ntiles = (int)L.ex.down.dims.ntiles; dp.nsb = (int)L.ex.down.dims.nsb;
-    dp.X = moe_h_; dp.ldx = Kff_; dp.x_per_slot = 1; dp.H = nullptr; dp.ldh = 0;
-    dp.Y = x + (size_t)r0 * d; dp.ldy = d; dp.weights = moe_w_; dp.n_valid = d;
-    if (!launch_moe_gemm4(L.ex.gateup.ptype, EPI_SWIGLU, gp, st) || !launch_moe_gemm4(L.ex.down.ptype, EPI_ATOMIC, dp, st))
-      throw std::runtime_error("moe_ffn: grouped GEMM does not support the expert weight type");
-    return;
-  }
-  launch_moe_gemv(L.ex.gateup.ptype, EPI_SWIGLU, gp, 1, st);
   MoeGemvParams dp = gp;
   dp.W = L.ex.down.d; dp.estride = L.ex.down_stride;
   dp.ntiles = (int)L.ex.down.dims.ntiles; dp.nsb = (int)L.ex.down.dims.nsb;
   dp.X = moe_h_; dp.ldx = Kff_; dp.x_per_slot = 1; dp.H = nullptr; dp.ldh = 0;
   dp.Y = x + (size_t)r0 * d; dp.ldy = d; dp.weights = moe_w_; dp.n_valid = d;
+  if (grouped) {
+    if (!launch_moe_gemm4(L.ex.gateup.ptype, EPI_SWIGLU, gp, st) || !launch_moe_gemm4(L.ex.down.ptype, EPI_ATOMIC, dp, st))
+      throw std::runtime_error("moe_ffn: grouped GEMM does not support the expert weight type");
+    return;
+  }
+  launch_moe_gemv(L.ex.gateup.ptype, EPI_SWIGLU, gp, 1, st);
   if (opt_.deterministic) dp.Yslot = moe_yslot_;   // per-slot outputs, combined in expert-rank order below
   // only ~k/E of the expert grid is busy: size the split for the active experts
   const int active = std::min(E, M * k);
@@ -1074,16 +1053,10 @@ bool HipStage::attention_o(int li, int M, const int32_t* pos, const int32_t* slo
   const LayerW& L = layers_[li];
   if (!opt_.fused_attn || opt_.deterministic || opt_.attn_o_max_ctx <= 0 || opt_.max_ctx > opt_.attn_o_max_ctx)
     return false;
-  DecodeAttnParams dp{};
-  dp.qkv = qkv_; dp.ldqkv = qkv_n_; dp.pos = pos; dp.slot = slot; dp.block_table = block_table_;
-    dp.slot0 = dec_slot0_;   // decode only
-  dp.max_pages = max_pages_; dp.rope_cs = rope_cs_; dp.q_scale = 1.0f / std::sqrt((float)cfg_.head_dim);
-  dp.k_cache = kc_[li]; dp.v_cache = vc_[li]; dp.M = M; dp.Hq = cfg_.n_head; dp.Hkv = cfg_.n_head_kv;
-  dp.kv_fp8 = opt_.kv_fp8;
-  dp.pre = pre;   // q rotated and K / V appended by the qkv GEMV
   // one split over the whole context (every workgroup of a kv head runs that head's attention)
-  dp.hd = cfg_.head_dim; dp.Dp = Dp_; dp.split_len = (int)round_up(opt_.max_ctx, 128); dp.n_split = 1;
-  dp.o_part = o_part_; dp.ml_part = ml_part_; dp.counters = attn_cnt_; dp.out = attn_; dp.ldo = Ko_;
+  DecodeAttnParams dp = decode_attn_params(li, M, pos, slot, false);
+  dp.split_len = (int)round_up(opt_.max_ctx, 128); dp.n_split = 1;
+  dp.pre = pre;   // q rotated and K / V appended by the qkv GEMV
   AttnOParams op{};
   op.W = L.wo.d; op.ptype = L.wo.ptype; op.ntiles = (int)L.wo.dims.ntiles; op.nsb = (int)L.wo.dims.nsb;
   op.Y = x; op.ldy = cfg_.d_model; op.n_valid = cfg_.d_model;
@@ -1196,10 +1169,9 @@ void HipStage::attention(int li, int M, const int32_t* pos, const int32_t* kvlen
 void HipStage::gemv_small(const PackedMat& m, int epi, const f16* X, int ldx, const float* Xf, const float* gamma,
                           int M, float* Y, int ldy, f16* H, int ldh, int n_valid, const float* bias, hipStream_t st,
                           const QkvAppend* qa) {
-  GemvParams p{};
+  GemvParams p = mat_params(m, X, ldx, M, Y, ldy, H, ldh, n_valid);
   if (qa) p.qa = *qa;
-  p.W = m.d; p.X = X; p.ldx = ldx; p.M = M; p.Y = Y; p.ldy = ldy; p.H = H; p.ldh = ldh;
-  p.ntiles = (int)m.dims.ntiles; p.nsb = (int)m.dims.nsb; p.n_valid = n_valid; p.bias = bias;
+  p.bias = bias;
   if (Xf) { p.Xf = Xf; p.ldxf = cfg_.d_model; p.gamma = gamma; p.eps = cfg_.eps; p.d_norm = cfg_.d_model; }
   const GemvsPlan pl = plan_gemvs(p.ntiles, p.nsb, M, epi, false, opt_.deterministic);
   if (!Xf && pl.lds + (size_t)pl.sb_per_split * 64 > 150 * 1024) {   // (+ the single-row form's table)

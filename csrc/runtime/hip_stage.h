@@ -154,6 +154,9 @@ class HipStage : public Stage {
   // RMSNorm of the residual x into xn_ (absorbing pending split-K partials of x first)
   void norm_x(float* x, const float* w, int M, float* zero, int64_t zero_n, hipStream_t st, const float* bias = nullptr,
               int bias_n = 0);
+  // the kernel family gemv() launches for a matrix, an epilogue and a row count
+  enum class GemmRoute { I8, GEMM4, GEMM3, GEMM1, GEMV };
+  GemmRoute gemm_route(const PackedMat& m, int epi, int M, bool have_x) const;
   void gemv(const PackedMat& m, int epi, const f16* X, int ldx, int M, float* Y, int ldy, f16* H, int ldh,
             int n_valid, bool allow_split, hipStream_t st,
             const GemvParams* extras = nullptr);

@@ -5,6 +5,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "gemm4_plan.h"   // Gemm4Plan, plan_gemm4, plan_moe_gemm4
+
 typedef _Float16 f16;
 
 namespace mp {
@@ -52,7 +54,6 @@ struct GemvParams {
   const float* bias = nullptr;   // [n] added once (split 0) to STORE / ATOMIC outputs
   float* zero = nullptr;         // side job after the GEMV: zero_n floats cleared
   int64_t zero_n = 0;
-  int m_blocks = 1;              // (unused: the retired 128-row gemm2 form)
   // P_I8 (launch_gemm3): X holds int8 rows (ldx in bytes), y = xscale[m] * wscale[n] * sum(xq * wq)
   const float* xscale = nullptr;
   const float* wscale = nullptr;
@@ -92,11 +93,16 @@ void launch_gemm(int ptype, int epi, GemvParams p, hipStream_t st);
 // X and the raw quants staged by global_load_lds, 16x16x32 f16 MFMA; EPI_ATOMIC splits K over
 // blockIdx.y (allow_split).  A/B overrides: knobs GEMM3_BM / GEMM3_BN / GEMM3_SPLIT (tuning.h).
 void launch_gemm3(int ptype, int epi, GemvParams p, hipStream_t st, bool allow_split = true);
-// Prompt / wide-decode GEMM v4 (gemm4.hip): gemm3's LDS-DMA stream on v_mfma_f32_32x32x16 (BM 128 |
-// 256 rows x 256 columns, each wave owning 32 columns).  Q4_K, Q6_K, F16, BF16; false = type not
-// supported (nothing launched).  _splitk: split-K partial stores like launch_gemm2_splitk.
+// Prompt / wide-decode GEMM v4 (gemm4*.hip): gemm3's LDS-DMA stream on v_mfma_f32_32x32x16 (BM 128 |
+// 256 rows x 256 columns, each wave owning 32 columns, and the opt-in forms of the geometry table).
+// Q4_K, Q5_K, Q6_K, Q8_0, F16, BF16; false = type not supported (nothing launched).  Every launch
+// runs plan_gemm4 / plan_moe_gemm4 (gemm4_plan.h).  _splitk: split-K partial stores, split s into
+// scratch + s * M * ntiles * 16 (false: the shape does not split or scratch_n floats are too few),
+// then (reduce) added into p.Y in split order.
 bool gemm4_supported(int ptype);
-int gemm4_splits(int ptype, int ntiles, int nsb, int M);   // K splits of a splittable launch
+// the kernel geometry table: its size, and whether it holds (bm, nwv, tw, moe) for the weight type
+int gemm4_geometry_count();
+bool gemm4_has_geometry(int ptype, int bm, int nwv, int tw, bool moe);
 bool launch_gemm4(int ptype, int epi, GemvParams p, hipStream_t st, bool allow_split = true);
 bool launch_gemm4_splitk(int ptype, GemvParams p, float* scratch, size_t scratch_n, hipStream_t st,
                          bool reduce = true, int* nsplit_out = nullptr);
@@ -332,7 +338,6 @@ struct MoeGemvParams {
 };
 // Y[t][n] += sum_{j < k} Yslot[t*k + j][n], j ascending (deterministic MoE combine)
 void launch_moe_combine(const float* Yslot, int ld_slot, int k, int M, int n, float* Y, int ldy, hipStream_t st);
-void launch_moe_route(const MoeRouteParams& p, hipStream_t st);
 void launch_moe_gemv(int ptype, int epi, MoeGemvParams p, int nsplit, hipStream_t st);
 // Grouped MoE dequant GEMM (gemm4.hip, any M): every routed expert's rows as one 32x32x16 MFMA GEMM
 // (rows gathered by the A staging, epilogues scattered by slot).  SWIGLU (gate/up) or ATOMIC (down,

@@ -452,6 +452,29 @@ def attn_decode_form(M: int, Hkv: int, n_split: int) -> int:
     return N.check(N.lib().mp_attn_decode_form(M, Hkv, n_split), "attn_decode_form")
 
 
+GEMM4_PLAN_FIELDS = ("ok", "bm", "nwv", "tw", "nsplit", "per", "wnt", "grid_x", "grid_y", "grid_z")
+
+
+def _gemm4_plan(fn, what, *args) -> dict:
+    out = (ctypes.c_int * len(GEMM4_PLAN_FIELDS))()
+    in_table = N.check(fn(*args, out), what)
+    return dict(zip(GEMM4_PLAN_FIELDS, out), in_table=in_table)
+
+
+def gemm4_plan(ptype: int, epi: int, M: int, ntiles: int, nsb: int, allow_split: bool = True,
+               partial_stores: bool = False) -> dict:
+    """The launch launch_gemm4 (partial_stores: launch_gemm4_splitk) runs for this shape under the
+    current knobs (host only): GEMM4_PLAN_FIELDS, plus in_table = 1 when the kernel geometry table
+    holds the plan's (bm, nwv, tw)."""
+    return _gemm4_plan(N.lib().mp_gemm4_plan, "gemm4_plan", ptype, epi, M, ntiles, nsb, int(allow_split),
+                       int(partial_stores))
+
+
+def moe_gemm4_plan(ptype: int, epi: int, M: int, k: int, E: int, ntiles: int, nsb: int, per_slot: bool = False) -> dict:
+    """The same for launch_moe_gemm4 (M tokens, k of E experts each; per_slot: the deterministic down)."""
+    return _gemm4_plan(N.lib().mp_moe_gemm4_plan, "moe_gemm4_plan", ptype, epi, M, k, E, ntiles, nsb, int(per_slot))
+
+
 class DecodeAttnScratch:
     """Split partials and the self-resetting arrival counters of the fused decode attention; kept
     across calls as the engine keeps them (o_part / ml_part poisoned with NaN: never read unwritten)."""

@@ -1,8 +1,9 @@
-"""tools/isa_lint.py: the counted-wait LDS kernels (gemm3.hip / gemm4.hip) compiled for gfx950 must
+"""tools/isa_lint.py: the counted-wait LDS kernels (gemm3.hip / gemm4_<type>.hip) compiled for gfx950 must
 have no VGPR hazard on an in-flight inline-asm LDS read and no -Winline-asm warning (the VERDICT r4
 gemm4 root cause: dead next-stage reads of a split's last stage had their registers recycled while
 the LDS data was still in flight).  CPU only: hipcc cross-compiles the device assembly."""
 import os
+import re
 import shutil
 import subprocess
 import sys
@@ -80,13 +81,16 @@ def test_lint_accepts_counted_waits(tmp_path):
 @pytest.mark.skipif(shutil.which("/opt/rocm/bin/hipcc") is None and shutil.which("hipcc") is None,
                     reason="hipcc not available")
 def test_gemm_kernels_isa_clean(tmp_path):
-    """Compile gemm3.hip and gemm4.hip to gfx950 assembly (in parallel, ~3 min) and lint every
-    kernel instantiation: zero findings, zero -Winline-asm warnings."""
-    srcs = [os.path.join(REPO, "csrc/kernels", f) for f in ("gemm4.hip", "gemm3.hip")]
-    with ThreadPoolExecutor(2) as ex:
+    """Compile gemm3.hip and the per-type gemm4 units to gfx950 assembly (in parallel, ~3 min) and
+    lint every kernel instantiation: zero findings, zero -Winline-asm warnings."""
+    srcs = L.default_sources()
+    assert len(srcs) == 7, srcs   # gemm3 + the six weight types of gemm4
+    with ThreadPoolExecutor(4) as ex:
         outs = list(ex.map(lambda s: L.compile_asm(s, str(tmp_path)), srcs))
     assert sum(w for _, w in outs) == 0, "-Winline-asm warnings"
     total = 0
     for path, _ in outs:
+        with open(path) as f:
+            assert re.search(r"gemm[34]_kernel", f.read()), path + ": no kernel to lint"
         total += L.lint_file(path, r"gemm[34]_kernel", verbose=False)
     assert total == 0

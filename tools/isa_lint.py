@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""ISA lint for the counted-wait LDS kernels (gemm3.hip / gemm4.hip).
+"""ISA lint for the counted-wait LDS kernels (gemm3.hip / gemm4_kernel.h through gemm4_<type>.hip).
 
 The wide dequant GEMMs issue their LDS reads as inline asm and retire them with their own counted
 ``s_waitcnt lgkmcnt(N)`` (csrc/kernels/gemm_lds.h).  The compiler believes an asm read's result
@@ -22,8 +22,8 @@ retires all but the N most recent.  LDS reads that return in order may overwrite
 (write-after-write by a later LDS read of the same register is allowed).  The ``-Winline-asm``
 warnings of the same compile are counted too (the ``m0`` clobber of the LDS-DMA helper).
 
-Usage:  python tools/isa_lint.py [--asm FILE.s ...] [--src csrc/kernels/gemm4.hip ...] [-v]
-With ``--src`` it runs ``hipcc --cuda-device-only -S`` itself (2-3 min for gemm4.hip).
+Usage:  python tools/isa_lint.py [--asm FILE.s ...] [--src csrc/kernels/gemm4_q4_k.hip ...] [-v]
+With ``--src`` it runs ``hipcc --cuda-device-only -S`` itself (1-2 min per quantized gemm4 unit).
 Exit status 1 when there is any finding.
 """
 from __future__ import annotations
@@ -214,6 +214,12 @@ def analyse(insns, labels, max_states=256):
     return findings, infos, overflow
 
 
+def default_sources() -> list:
+    """The units the CPU suite lints: gemm3 and the per-type gemm4 kernel units."""
+    kdir = os.path.join(ROOT, "csrc", "kernels")
+    return [os.path.join(kdir, f) for f in sorted(os.listdir(kdir)) if re.fullmatch(r"gemm4_\w+\.hip|gemm3\.hip", f)]
+
+
 def compile_asm(src: str, out_dir: str) -> tuple:
     os.makedirs(out_dir, exist_ok=True)
     out = os.path.join(out_dir, os.path.basename(src).replace(".hip", ".s"))
@@ -259,8 +265,8 @@ def main(argv=None) -> int:
     ap.add_argument("--kernels", default=r"gemm[34]_kernel", help="regex on the mangled kernel name")
     ap.add_argument("-v", "--verbose", action="store_true")
     a = ap.parse_args(argv)
-    if not a.asm and not a.src:   # no arguments: the two kernels the CPU suite lints
-        a.src = [os.path.join(ROOT, "csrc", "kernels", f) for f in ("gemm4.hip", "gemm3.hip")]
+    if not a.asm and not a.src:   # no arguments: the kernels the CPU suite lints
+        a.src = default_sources()
     files, warns = list(a.asm), 0
     for s in a.src:
         out, w = compile_asm(s, a.out_dir)
