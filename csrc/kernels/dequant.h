@@ -280,6 +280,104 @@ template <> struct Deq<P_Q4_0> {
   }
 };
 
+// ------------------------------------------------------------------ 2-bit fields (Q3_K, Q2_K)
+// A lane's 64 quants of the super-block are ONE 16-B piece: fragment (h, s) sits in dword
+// 2 (s >> 1) + h, byte pair s & 1 of each 16-bit half, element j at bit 16 (j & 1) + 8 (s & 1) +
+// 2 (j >> 1).  With v = dword >> 8 (s & 1), the field at bit p = 2i of each half is the f16 pair
+// (j = 2i, 2i + 1): it reads as q exactly under the exponent 2^(10 - p), i.e. OR-ed with 0x6400,
+// 0x5C00, 0x5400, 0x4C00 (1024 + q, 256 + q, 64 + q, 16 + q): four masks on w and four on w >> 8
+// give the dword's 16 weights.
+// Q2_K: w = S q + M with S = f16(d sc), M = f16(-dmin m) (one rounding each, as Q4_K), one fma.
+__device__ __forceinline__ half8_t k2_frag(uint32_t v, half2_t S, half2_t M) {
+  return pack8(as_u32(__builtin_elementwise_fma(as_h2((v & 0x00030003u) | 0x64006400u) - h2c(1024.f), S, M)),
+               as_u32(__builtin_elementwise_fma(as_h2((v & 0x000C000Cu) | 0x5C005C00u) - h2c(256.f), S, M)),
+               as_u32(__builtin_elementwise_fma(as_h2((v & 0x00300030u) | 0x54005400u) - h2c(64.f), S, M)),
+               as_u32(__builtin_elementwise_fma(as_h2((v & 0x00C000C0u) | 0x4C004C00u) - h2c(16.f), S, M)));
+}
+// Q3_K: hb = the fragment's 8 high bits (bit 4 (j & 1) + (j >> 1), the Q5_K order), OR-ed in at the
+// field's bit + 2 (= 4); q = lo + 4 hi - 4; w = S q with S = f16(d s_k) (one rounding, as Q6_K)
+__device__ __forceinline__ half8_t k3_frag(uint32_t v, uint32_t hb, half2_t S) {
+  const uint32_t x = hb | (hb << 12);   // (x >> i): hi(2i) at bit 0, hi(2i+1) at bit 16
+  const uint32_t h0 = ((x << 2) & 0x00040004u) | 0x64006400u, h1 = ((x << 3) & 0x00100010u) | 0x5C005C00u;
+  const uint32_t h2 = ((x << 4) & 0x00400040u) | 0x54005400u, h3 = ((x << 5) & 0x01000100u) | 0x4C004C00u;
+  return pack8(as_u32((as_h2((v & 0x00030003u) | h0) - h2c(1028.f)) * S),   // 1024 + 4 zero point
+               as_u32((as_h2((v & 0x000C000Cu) | h1) - h2c(260.f)) * S),
+               as_u32((as_h2((v & 0x00300030u) | h2) - h2c(68.f)) * S),
+               as_u32((as_h2((v & 0x00C000C0u) | h3) - h2c(20.f)) * S));
+}
+// Q2_K scale byte (sc | m << 4) pair in bits 0-7 / 16-23 of u -> (d sc, d sc'), (-dmin m, -dmin m')
+__device__ __forceinline__ void k2_scales(uint32_t u, uint32_t dm, half2_t& S, half2_t& M) {
+  const half2_t d2 = h2lo(as_h2(dm)), n2 = -h2hi(as_h2(dm));
+  S = (as_h2((u & 0x000F000Fu) | 0x64006400u) - h2c(1024.f)) * d2;
+  M = (as_h2((u & 0x00F000F0u) | 0x54005400u) - h2c(64.f)) * n2;
+}
+// Q3_K 6-bit scale (s_k + 32) -> f16(d s_k)
+__device__ __forceinline__ f16 k3_scale(uint32_t s6, f16 d) { return (as_h2(0x6400u | s6).x - (f16)1056.f) * d; }
+
+// ------------------------------------------------------------------ Q3_K (110 B / 256 w)
+// chunk: quants [lane] 16 B | high bits [lane] 8 B (dword h, byte s) | scales [r] 12 B (byte b of
+// lane group g's 24-bit word of four 6-bit scales at 4 b + g) | d [r] 2 B   (csrc/runtime/qtypes.h)
+template <> struct Deq<P_Q3_K> {
+  static constexpr int CB = chunk_bytes(P_Q3_K);
+  struct Raw { u32x4 q; u32x2 hm; uint32_t s0, s1, s2, d; };
+  __device__ static __forceinline__ void load(Raw& r, const uint8_t* c, int lane) { load(r, PtrSrc{c}, lane); }
+  template <class S>
+  __device__ static __forceinline__ void load(Raw& r, const S& c, int lane) {
+    r.q = c.q16nt(lane * 16);
+    r.hm = c.q8nt(1024 + lane * 8);
+    r.s0 = c.q4(1536 + (lane & 15) * 12);
+    r.s1 = c.q4(1536 + (lane & 15) * 12 + 4);
+    r.s2 = c.q4(1536 + (lane & 15) * 12 + 8);
+    r.d = c.q2(1728 + (lane & 15) * 2);
+  }
+  template <int H>
+  __device__ static __forceinline__ void dequant(const Raw& r, half8_t b[4], int lane, const Consts&) { dequant<H>(r, b, lane); }
+  template <int H>
+  __device__ static __forceinline__ void dequant(const Raw& r, half8_t b[4], int lane) {
+    const f16 dh = __builtin_bit_cast(f16, (uint16_t)r.d);
+    const uint32_t g = (uint32_t)lane >> 4;
+    // the lane group's 24-bit scale word: byte g of each of the three dwords
+    const uint32_t lo = __builtin_amdgcn_perm(r.s1, r.s0, g | ((g + 4) << 8) | 0x0C0C0000u);
+    const uint32_t v = __builtin_amdgcn_perm(r.s2, lo, 0x0C000100u | ((g + 4) << 16));
+    // sub-blocks 4g + 2H, 4g + 2H + 1 (MFMA s >> 1): (1024 + s6) pair, minus 1056, times d
+    const uint32_t a = ((v >> (12 * H)) & 0x3Fu) | (((v >> (12 * H + 6)) & 0x3Fu) << 16) | 0x64006400u;
+    const half2_t S2 = (as_h2(a) - h2c(1056.f)) * half2_t{dh, dh};
+    const uint32_t qh = r.hm[H];
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+      const uint32_t w = r.q[2 * (s >> 1) + H];
+      b[s] = k3_frag((s & 1) ? w >> 8 : w, (qh >> (8 * s)) & 0xFFu, (s >> 1) ? h2hi(S2) : h2lo(S2));
+    }
+  }
+};
+
+// ------------------------------------------------------------------ Q2_K (84 B / 256 w)
+// chunk: quants [lane] 16 B | scale bytes [r] 16 B (dword g = sub-blocks 4g..4g+3) | (d, dmin) [r] 4 B
+template <> struct Deq<P_Q2_K> {
+  static constexpr int CB = chunk_bytes(P_Q2_K);
+  struct Raw { u32x4 q; uint32_t sc, dm; };
+  __device__ static __forceinline__ void load(Raw& r, const uint8_t* c, int lane) { load(r, PtrSrc{c}, lane); }
+  template <class S>
+  __device__ static __forceinline__ void load(Raw& r, const S& c, int lane) {
+    r.q = c.q16nt(lane * 16);
+    r.sc = c.q4(1024 + (lane & 15) * 16 + 4 * (lane >> 4));
+    r.dm = c.q4(1280 + (lane & 15) * 4);
+  }
+  template <int H>
+  __device__ static __forceinline__ void dequant(const Raw& r, half8_t b[4], int lane, const Consts&) { dequant<H>(r, b, lane); }
+  template <int H>
+  __device__ static __forceinline__ void dequant(const Raw& r, half8_t b[4], int lane) {
+    // sub-blocks 4g + 2H, 4g + 2H + 1: bytes 2H, 2H + 1 of r.sc into the two halves
+    half2_t S2, M2;
+    k2_scales(__builtin_amdgcn_perm(0u, r.sc, H ? 0x0C030C02u : 0x0C010C00u), r.dm, S2, M2);
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+      const uint32_t w = r.q[2 * (s >> 1) + H];
+      b[s] = k2_frag((s & 1) ? w >> 8 : w, (s >> 1) ? h2hi(S2) : h2lo(S2), (s >> 1) ? h2hi(M2) : h2lo(M2));
+    }
+  }
+};
+
 // bf16 pair (low, high halves of w) -> f16 pair (dense unpack only: the GEMV/GEMM kernels keep bf16):
 // exact inside f16's normal range; v_cvt_pkrtz rounds toward zero, so a bf16 beyond 65504 becomes
 // +-65504 (saturation) instead of an infinity

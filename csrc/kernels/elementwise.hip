@@ -155,6 +155,22 @@ __device__ float deq_elem(int t, const uint8_t* row, int e) {
       if (t == T_Q5_K) q += ((b[16 + (l & 31)] >> (2 * c + (l >= 32))) & 1) << 4;
       return d * sc * q - dmin * m;
     }
+    case T_Q2_K: case T_Q3_K: {   // element w = 128 n + 32 j + l: 2-bit field (qs[32 n + l] >> 2 j) & 3
+      const uint8_t* b = row + (e / 256) * (t == T_Q2_K ? 84 : 110);
+      const int w = e % 256, n = w / 128, j = (w % 128) / 32, l = w % 32, k = w / 16;
+      const int lo = (b[(t == T_Q2_K ? 16 : 32) + 32 * n + l] >> (2 * j)) & 3;
+      if (t == T_Q2_K) {
+        const float d = h2f(*reinterpret_cast<const uint16_t*>(b + 80));
+        const float dmin = h2f(*reinterpret_cast<const uint16_t*>(b + 82));
+        return d * (float)(b[k] & 15) * (float)lo - dmin * (float)(b[k] >> 4);
+      }
+      const int hi = (b[l] >> (4 * n + j)) & 1;
+      const uint8_t* sc = b + 96;
+      const int low4 = k < 8 ? (sc[k] & 15) : (sc[k - 8] >> 4);
+      const int high2 = (sc[8 + k % 4] >> (2 * (k / 4))) & 3;
+      const float d = h2f(*reinterpret_cast<const uint16_t*>(b + 108));
+      return d * (float)((low4 | (high2 << 4)) - 32) * (float)(lo + 4 * hi - 4);
+    }
     case T_Q6_K: {
       const uint8_t* b = row + (e / 256) * 210;
       const int w = e % 256, n = w / 128, r = w % 128, k = r / 32, l = r % 32;

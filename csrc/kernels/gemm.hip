@@ -130,6 +130,8 @@ void launch_gemm(int ptype, int epi, GemvParams p, hipStream_t st) {
     case P_Q6_K: gemm_pt<P_Q6_K>(epi, p, st); break;
     case P_Q8_0: gemm_pt<P_Q8_0>(epi, p, st); break;
     case P_Q4_0: gemm_pt<P_Q4_0>(epi, p, st); break;
+    case P_Q3_K: gemm_pt<P_Q3_K>(epi, p, st); break;
+    case P_Q2_K: gemm_pt<P_Q2_K>(epi, p, st); break;
     case P_F16: gemm_pt<P_F16>(epi, p, st); break;
     case P_BF16: gemm_pt<P_BF16>(epi, p, st); break;
   }

@@ -5,7 +5,8 @@
 namespace mp {
 
 bool gemm4_supported(int ptype) {
-  return ptype == P_Q4_K || ptype == P_Q5_K || ptype == P_Q6_K || ptype == P_Q8_0 || ptype == P_F16 || ptype == P_BF16;
+  return ptype == P_Q4_K || ptype == P_Q5_K || ptype == P_Q6_K || ptype == P_Q8_0 || ptype == P_F16 || ptype == P_BF16 ||
+         ptype == P_Q3_K || ptype == P_Q2_K;
 }
 
 bool gemm4_has_geometry(int ptype, int bm, int nwv, int tw, bool moe) {
@@ -27,6 +28,8 @@ static void run(int ptype, const Gemm4Plan& pl, int epi, const GemvParams& p, co
     case P_Q5_K: return gemm4_run<P_Q5_K>(pl, epi, p, mo, st);
     case P_Q6_K: return gemm4_run<P_Q6_K>(pl, epi, p, mo, st);
     case P_Q8_0: return gemm4_run<P_Q8_0>(pl, epi, p, mo, st);
+    case P_Q3_K: return gemm4_run<P_Q3_K>(pl, epi, p, mo, st);
+    case P_Q2_K: return gemm4_run<P_Q2_K>(pl, epi, p, mo, st);
     case P_F16: return gemm4_run<P_F16>(pl, epi, p, mo, st);
     case P_BF16: return gemm4_run<P_BF16>(pl, epi, p, mo, st);
     default: throw std::runtime_error("gemm4: weight type " + std::to_string(ptype));

@@ -1,5 +1,6 @@
 // gemm4: from a launch plan (csrc/runtime/gemm4_plan.h) to the kernel instantiation it names.
-// gemm4_<type>.hip instantiate gemm4_run for one weight type each; gemm4.hip switches on the type.
+// gemm4_<type>.hip instantiate gemm4_run per weight type (Q3_K beside Q5_K, Q2_K beside Q6_K);
+// gemm4.hip switches on the type.
 #pragma once
 #include "gemm4_kernel.h"
 #include "../runtime/tuning.h"   // the probe-build knobs only: every launch decision is the plan's
@@ -103,6 +104,8 @@ extern template void gemm4_run<P_Q4_K>(const Gemm4Plan&, int, const GemvParams&,
 extern template void gemm4_run<P_Q5_K>(const Gemm4Plan&, int, const GemvParams&, const mpk::G4Moe*, hipStream_t);
 extern template void gemm4_run<P_Q6_K>(const Gemm4Plan&, int, const GemvParams&, const mpk::G4Moe*, hipStream_t);
 extern template void gemm4_run<P_Q8_0>(const Gemm4Plan&, int, const GemvParams&, const mpk::G4Moe*, hipStream_t);
+extern template void gemm4_run<P_Q3_K>(const Gemm4Plan&, int, const GemvParams&, const mpk::G4Moe*, hipStream_t);
+extern template void gemm4_run<P_Q2_K>(const Gemm4Plan&, int, const GemvParams&, const mpk::G4Moe*, hipStream_t);
 extern template void gemm4_run<P_F16>(const Gemm4Plan&, int, const GemvParams&, const mpk::G4Moe*, hipStream_t);
 extern template void gemm4_run<P_BF16>(const Gemm4Plan&, int, const GemvParams&, const mpk::G4Moe*, hipStream_t);
 

@@ -182,6 +182,61 @@ template <> struct W4<P_Q5_K> {
   }
 };
 
+// Q3_K / Q2_K: the row's ONE 16-B quant piece of the quarter: dwords 2h, 2h + 1 = k-halves kk = 0, 1
+// of this lane's g = 2h + e (one b64), byte pair e; the sub-block of MFMA t is 2 kk + h
+template <> struct W4<P_Q3_K> {
+  static constexpr int NR = 6;
+  static constexpr bool kParts = false;
+  template <int P, class RW, class PR>   // (unused: kParts false) the whole fragment's dword P
+  __device__ static __forceinline__ uint32_t fragp(const RW& w, const PR& p, int t, int h, const Consts& k) {
+    return __builtin_bit_cast(u32x4, frag(w, p, t, h, k))[P];
+  }
+  struct Raw { uint32_t s[3], d; u32x2 q, hm; };
+  struct Prep { uint32_t v; f16 d; };
+  template <int TW>
+  __device__ static __forceinline__ void load(const char* R, int lane, int pair, Raw& w) {
+    const int c = lane & 31, u = 2 * pair + (c >> 4), r = c & 15, h = lane >> 5;
+#pragma unroll
+    for (int b = 0; b < 3; ++b) ds_b32(w.s[b], R + TW * 384 + (u * 16 + r) * 12 + 4 * b);
+    ds_u16(w.d, R + TW * 576 + (u * 16 + r) * 2);
+    ds_b64(w.q, R + (u * 16 + r) * 16 + 8 * h);
+    ds_b64(w.hm, R + TW * 256 + (u * 16 + r) * 8);
+  }
+  __device__ static __forceinline__ Prep prep(const Raw& w, int q) {
+    return Prep{W3<P_Q3_K>::qword(w.s[0], w.s[1], w.s[2], (uint32_t)q), __builtin_bit_cast(f16, (uint16_t)w.d)};
+  }
+  __device__ static __forceinline__ half8_t frag(const Raw& w, const Prep& p, int t, int h, const Consts&) {
+    const int kk = t >> 1, e = t & 1, g = 2 * h + e;
+    const f16 sf = k3_scale((p.v >> (6 * (2 * kk + h))) & 0x3Fu, p.d);
+    return k3_frag(e ? w.q[kk] >> 8 : w.q[kk], (w.hm[kk] >> (8 * g)) & 0xFFu, half2_t{sf, sf});
+  }
+};
+
+template <> struct W4<P_Q2_K> {
+  static constexpr int NR = 3;
+  static constexpr bool kParts = false;
+  template <int P, class RW, class PR>   // (unused: kParts false) the whole fragment's dword P
+  __device__ static __forceinline__ uint32_t fragp(const RW& w, const PR& p, int t, int h, const Consts& k) {
+    return __builtin_bit_cast(u32x4, frag(w, p, t, h, k))[P];
+  }
+  struct Raw { uint32_t sc, dm; u32x2 q; };
+  using Prep = W3<P_Q2_K>::Prep;
+  template <int TW>
+  __device__ static __forceinline__ void load(const char* R, int lane, int pair, Raw& w) {
+    const int c = lane & 31, u = 2 * pair + (c >> 4), r = c & 15, h = lane >> 5;
+    ds_b32(w.sc, R + TW * 256 + (u * 16 + r) * 4);
+    ds_b32(w.dm, R + TW * 320 + (u * 16 + r) * 4);
+    ds_b64(w.q, R + (u * 16 + r) * 16 + 8 * h);
+  }
+  __device__ static __forceinline__ Prep prep(const Raw& w, int) { return Prep{w.sc, w.dm}; }
+  __device__ static __forceinline__ half8_t frag(const Raw& w, const Prep& p, int t, int h, const Consts&) {
+    const int kk = t >> 1, e = t & 1;
+    half2_t S, M;
+    W3<P_Q2_K>::scales(p, 2 * kk + h, S, M);
+    return k2_frag(e ? w.q[kk] >> 8 : w.q[kk], S, M);
+  }
+};
+
 // Q8_0: piece (u, kk, r) = 32 int8 (+128) at R + ((u*2 + kk)*16 + r)*32; bytes 16h .. 16h+15 hold
 // dwords g = 2h, 2h+1 of the 16x16 map (one b128 per kk); block scales [u][r] = (d(2q), d(2q+1))
 template <> struct W4<P_Q8_0> {
@@ -243,7 +298,8 @@ template <> struct W4<P_F16> : W4_16<P_F16> {};
 template <> struct W4<P_BF16> : W4_16<P_BF16> {};
 
 template <int PT> constexpr bool g4_supported() {
-  return PT == P_Q4_K || PT == P_Q5_K || PT == P_Q6_K || PT == P_Q8_0 || PT == P_F16 || PT == P_BF16;
+  return PT == P_Q4_K || PT == P_Q5_K || PT == P_Q6_K || PT == P_Q8_0 || PT == P_F16 || PT == P_BF16 ||
+         PT == P_Q3_K || PT == P_Q2_K;
 }
 
 // MoE mode (grouped GEMM over the routed experts): blockIdx.z = expert e, whose rows are

@@ -378,6 +378,98 @@ template <> struct W3<P_Q6_K> {
   }
 };
 
+// Q3_K: quants [u][r] 16 B (the row's ONE piece of quarter q: dword 2 (g >> 1) + kk, byte pair
+// g & 1), high bits [u][r] 8 B (dword kk, byte g), the tile's 192 scale bytes [u] (every quarter's:
+// contiguous per tile), d [u][r] 2 B
+template <> struct W3<P_Q3_K> {
+  static constexpr int CB = chunk_bytes(P_Q3_K);
+  static constexpr int RAW(int TW) { return TW * 608; }
+  static constexpr int NI(int TW) { return wi(16 * TW) + wi(8 * TW) + wi(12 * TW) + wi(2 * TW); }
+  static constexpr int NR(int TW) { return 6 * TW; }
+  template <int TW> struct Raw { uint32_t s[TW][3], d[TW]; u32x2 q[TW], hm[TW]; };
+  struct Prep { uint32_t v; f16 d; };
+  template <int TW, class E>
+  __device__ static __forceinline__ void issue(char* R, const W3Src& c, E&& em) {
+    em.template go<16>(R, 16 * TW, [&](int e) { return c.chunk(e >> 4, CB) + (16 * c.q + (e & 15)) * 16; });
+    em.template go<16>(R + TW * 256, 8 * TW, [&](int f) {   // 16 rows x 8 B contiguous
+      return c.chunk(f >> 3, CB) + 1024 + 16 * c.q * 8 + (f & 7) * 16;
+    });
+    em.template go<16>(R + TW * 384, 12 * TW, [&](int f) { return c.chunk(f / 12, CB) + 1536 + (f % 12) * 16; });
+    em.template go<16>(R + TW * 576, 2 * TW, [&](int f) { return c.chunk(f >> 1, CB) + 1728 + (f & 1) * 16; });
+  }
+  template <int TW>
+  __device__ static __forceinline__ void load(const char* R, int lane, Raw<TW>& w) {
+    const int r = lane & 15, g = lane >> 4;
+#pragma unroll
+    for (int u = 0; u < TW; ++u) {
+#pragma unroll
+      for (int b = 0; b < 3; ++b) ds_b32(w.s[u][b], R + TW * 384 + (u * 16 + r) * 12 + 4 * b);
+      ds_u16(w.d[u], R + TW * 576 + (u * 16 + r) * 2);
+      ds_b64(w.q[u], R + (u * 16 + r) * 16 + 8 * (g >> 1));
+      ds_b64(w.hm[u], R + TW * 256 + (u * 16 + r) * 8);
+    }
+  }
+  // the 24-bit scale word of quarter q: byte q of each of the row's three scale dwords
+  __device__ static __forceinline__ uint32_t qword(uint32_t s0, uint32_t s1, uint32_t s2, uint32_t q) {
+    const uint32_t lo = __builtin_amdgcn_perm(s1, s0, q | ((q + 4) << 8) | 0x0C0C0000u);
+    return __builtin_amdgcn_perm(s2, lo, 0x0C000100u | ((q + 4) << 16));
+  }
+  template <int TW>
+  __device__ static __forceinline__ Prep prep(const Raw<TW>& w, int u, int q, int) {
+    return Prep{qword(w.s[u][0], w.s[u][1], w.s[u][2], (uint32_t)q), __builtin_bit_cast(f16, (uint16_t)w.d[u])};
+  }
+  template <int TW>
+  __device__ static __forceinline__ half8_t frag(const Raw<TW>& w, const Prep& p, int u, int kk, int lane, const Consts&) {
+    const int g = lane >> 4;
+    // sub-block 4q + 2kk + (g >> 1) of the quarter's four 6-bit scales
+    const f16 sf = k3_scale((p.v >> (6 * (2 * kk + (g >> 1)))) & 0x3Fu, p.d);
+    return k3_frag(w.q[u][kk] >> (8 * (g & 1)), (w.hm[u][kk] >> (8 * g)) & 0xFFu, half2_t{sf, sf});
+  }
+};
+
+// Q2_K: quants [u][r] 16 B (as Q3_K), scale bytes [u][r] 4 B (dword q of the row's 16),
+// (d, dmin) [u][r] 4 B
+template <> struct W3<P_Q2_K> {
+  static constexpr int CB = chunk_bytes(P_Q2_K);
+  static constexpr int RAW(int TW) { return TW * 384; }
+  static constexpr int NI(int TW) { return wi(16 * TW) + wi(16 * TW) + wi(4 * TW); }
+  static constexpr int NR(int TW) { return 3 * TW; }
+  template <int TW> struct Raw { uint32_t sc[TW], dm[TW]; u32x2 q[TW]; };
+  struct Prep { uint32_t sc, dm; };
+  template <int TW, class E>
+  __device__ static __forceinline__ void issue(char* R, const W3Src& c, E&& em) {
+    em.template go<16>(R, 16 * TW, [&](int e) { return c.chunk(e >> 4, CB) + (16 * c.q + (e & 15)) * 16; });
+    em.template go<4>(R + TW * 256, 16 * TW, [&](int e) { return c.chunk(e >> 4, CB) + 1024 + (e & 15) * 16 + 4 * c.q; });
+    em.template go<16>(R + TW * 320, 4 * TW, [&](int f) { return c.chunk(f >> 2, CB) + 1280 + (f & 3) * 16; });
+  }
+  template <int TW>
+  __device__ static __forceinline__ void load(const char* R, int lane, Raw<TW>& w) {
+    const int r = lane & 15, g = lane >> 4;
+#pragma unroll
+    for (int u = 0; u < TW; ++u) {
+      ds_b32(w.sc[u], R + TW * 256 + (u * 16 + r) * 4);
+      ds_b32(w.dm[u], R + TW * 320 + (u * 16 + r) * 4);
+      ds_b64(w.q[u], R + (u * 16 + r) * 16 + 8 * (g >> 1));
+    }
+  }
+  template <int TW>
+  __device__ static __forceinline__ Prep prep(const Raw<TW>& w, int u, int, int) { return Prep{w.sc[u], w.dm[u]}; }
+  // sub-block sub (0..3 of the quarter): S = d sc, M = -dmin m as splat pairs
+  __device__ static __forceinline__ void scales(const Prep& p, int sub, half2_t& S, half2_t& M) {
+    const uint32_t sb = (p.sc >> (8 * sub)) & 0xFFu;
+    half2_t S2, M2;
+    k2_scales(sb, p.dm, S2, M2);
+    S = h2lo(S2); M = h2lo(M2);
+  }
+  template <int TW>
+  __device__ static __forceinline__ half8_t frag(const Raw<TW>& w, const Prep& p, int u, int kk, int lane, const Consts&) {
+    const int g = lane >> 4;
+    half2_t S, M;
+    scales(p, 2 * kk + (g >> 1), S, M);
+    return k2_frag(w.q[u][kk] >> (8 * (g & 1)), S, M);
+  }
+};
+
 // Q8_0: quants [u][h][r] 32 B (int8 + 128), block scales [u][r] 4 B = (d(2q), d(2q+1))
 template <> struct W3<P_Q8_0> {
   static constexpr int CB = chunk_bytes(P_Q8_0);

@@ -611,6 +611,8 @@ void launch_gemvs(int ptype, int epi, GemvParams p, bool deterministic, hipStrea
     case P_Q6_K: gemvs_pt<P_Q6_K>(epi, p, pl, st); break;
     case P_Q8_0: gemvs_pt<P_Q8_0>(epi, p, pl, st); break;
     case P_Q4_0: gemvs_pt<P_Q4_0>(epi, p, pl, st); break;
+    case P_Q3_K: gemvs_pt<P_Q3_K>(epi, p, pl, st); break;
+    case P_Q2_K: gemvs_pt<P_Q2_K>(epi, p, pl, st); break;
     case P_F16: gemvs_pt<P_F16>(epi, p, pl, st); break;
     case P_BF16: gemvs_pt<P_BF16>(epi, p, pl, st); break;
     default: throw std::runtime_error("launch_gemvs: unknown packed type");

@@ -68,6 +68,23 @@ __global__ void init_packed_kernel(uint8_t* W, size_t nbytes, int pt, float scal
         v[k] = (uint32_t)h | ((uint32_t)h << 16);
       }
     }
+  } else if (pt == P_Q3_K) {
+    // quants, high bits and the 6-bit scales are all random (every bit pattern is valid); d for 8
+    // rows per 16 B: rms(s_k) ~ 18.5, rms(q) ~ 2.3
+    if (in_chunk >= 1728) {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const uint16_t h = f2h(scale / 43.f);
+        v[k] = (uint32_t)h | ((uint32_t)h << 16);
+      }
+    }
+  } else if (pt == P_Q2_K) {
+    // random quants and scale / min nibbles; (d, dmin) per row with dmin = 1.5 d (mean q = 1.5), so
+    // the weights are roughly zero-mean
+    if (in_chunk >= 1280) {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) v[k] = (uint32_t)f2h(scale / 13.5f) | ((uint32_t)f2h(scale / 9.f) << 16);
+    }
   } else if (pt == P_Q4_0) {
     if (in_chunk >= 2048) {
 #pragma unroll
@@ -99,6 +116,11 @@ __global__ void init_raw_kernel(uint8_t* W, int64_t nblocks, int t, float scale,
       for (int i = 0; i < 4; ++i) p[8 + i] = p[4 + i];
       break;
     }
+    case T_Q3_K: *reinterpret_cast<uint16_t*>(p + 108) = f2h(scale / 43.f); break;
+    case T_Q2_K:
+      *reinterpret_cast<uint16_t*>(p + 80) = f2h(scale / 13.5f);
+      *reinterpret_cast<uint16_t*>(p + 82) = f2h(scale / 9.f);
+      break;
     case T_Q6_K: *reinterpret_cast<uint16_t*>(p + 208) = f2h(scale * 3.4f / (32.f * 127.f)); break;
     case T_F16: h[0] = f2h(((hash32(seed + b) & 0xFFFF) / 65536.f - 0.5f) * 3.4f * scale); break;
     case T_BF16: h[0] = (uint16_t)(__float_as_uint(((hash32(seed + b) & 0xFFFF) / 65536.f - 0.5f) * 3.4f * scale) >> 16); break;

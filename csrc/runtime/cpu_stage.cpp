@@ -74,6 +74,11 @@ void fill_random(int type, int64_t nblocks, float scale, uint64_t seed, uint8_t*
         put_f16(p + 2, scale / 300.f);
         break;
       case T_Q6_K: put_f16(p + bb - 2, scale / 2000.f); break;
+      case T_Q3_K: put_f16(p + 108, scale / 75.f); break;   // random 6-bit scales, q in [-4, 3]
+      case T_Q2_K:   // dmin = 1.5 d centres the weights (mean q = 1.5, scale and min nibbles alike)
+        put_f16(p + 80, scale / 24.f);
+        put_f16(p + 82, scale / 16.f);
+        break;
       default: throw std::runtime_error("cpu synthetic: unsupported type");
     }
   }

@@ -38,6 +38,18 @@ SyntheticTypes SyntheticTypes::from_ftype(const std::string& ftype_in, int layer
     all(T_Q4_K);
     t.out = T_Q6_K;
     if (more_bits(layer, n_layer)) { t.v = T_Q6_K; t.down = T_Q6_K; }
+  } else if (f == "Q3_K" || f == "Q3_K_S") { all(T_Q3_K); t.out = T_Q6_K; }
+  else if (f == "Q3_K_M" || f == "Q3_K_L") {   // the mixes of models/config.py tensor_type
+    const bool large = f == "Q3_K_L";
+    all(T_Q3_K);
+    t.out = T_Q6_K;
+    t.v = large || layer < 2 ? T_Q5_K : T_Q4_K;
+    t.o = large ? T_Q5_K : T_Q4_K;
+    t.down = large || layer < n_layer / 16 ? T_Q5_K : T_Q4_K;
+  } else if (f == "Q2_K") {
+    all(T_Q2_K);
+    t.out = T_Q6_K;
+    t.v = t.o = t.down = T_Q3_K;
   } else throw std::runtime_error("unknown synthetic ftype " + ftype_in);
   if (f == "Q5_K_M" && more_bits(layer, n_layer)) { t.v = T_Q6_K; t.down = T_Q6_K; }
   return t;

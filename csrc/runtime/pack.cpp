@@ -62,6 +62,21 @@ static inline int q6k_val(const uint8_t* b, int w) {
   return lo | (hi << 4);
 }
 
+// Q2_K / Q3_K: element w = 128 n + 32 j + l, 2-bit field (qs[32 n + l] >> 2 j) & 3
+static inline int k2_field(const uint8_t* qs, int w) {
+  const int n = w / 128, j = (w % 128) / 32, l = w % 32;
+  return (qs[32 * n + l] >> (2 * j)) & 3;
+}
+// Q3_K: lo + 4 hi (0..7, the weight's q + 4), hi = (hmask[l] >> (4 n + j)) & 1
+static inline int q3k_val(const uint8_t* b, int w) {
+  return k2_field(b + 32, w) | (((b[w % 32] >> (w / 32)) & 1) << 2);
+}
+// Q3_K: the 6-bit scale of sub-block k as stored (s_k + 32)
+static inline int q3k_scale6(const uint8_t* sc, int k) {
+  const int low4 = k < 8 ? (sc[k] & 15) : (sc[k - 8] >> 4);
+  const int high2 = (sc[8 + k % 4] >> (2 * (k / 4))) & 3;
+  return low4 | (high2 << 4);
+}
 // Position of weight w (0..255 of a super-block) of tile row r: MFMA i = 4h + s of lane 16g + r,
 // element j, with w = 64g + 32h + 8s + j (the T16 k-mapping, csrc/kernels/dequant.h): lane group
 // g owns the quarter [64g, 64g + 64) of the super-block.
@@ -93,6 +108,13 @@ static inline void put_nib(uint8_t* chunk, const Pos& p, int v) {
   const int pos = (p.j & 1) * 4 + (p.j >> 1);   // nibble position inside the dword
   uint8_t& byte = dw[pos / 2];
   byte |= (uint8_t)((v & 15) << ((pos & 1) * 4));
+}
+
+// 2-bit field of (h, s, j) inside the lane's ONE 16-B piece: dword 2 (s >> 1) + h, bit
+// 16 (j & 1) + 8 (s & 1) + 2 (j >> 1)
+static inline void put_2bit(uint8_t* chunk, const Pos& p, int v) {
+  const int bit = 32 * (2 * (p.s >> 1) + p.h) + 16 * (p.j & 1) + 8 * (p.s & 1) + 2 * (p.j >> 1);
+  chunk[p.lane * 16 + bit / 8] |= (uint8_t)((v & 3) << (bit % 8));
 }
 
 static void pack_chunk(int t, int pt, const uint8_t* src, int64_t K, int64_t k0, uint8_t* chunk, int r) {
@@ -127,6 +149,30 @@ static void pack_chunk(int t, int pt, const uint8_t* src, int64_t K, int64_t k0,
       }
       std::memcpy(chunk + 3072 + 16 * r, src + 192, 16);
       std::memcpy(chunk + 3328 + 2 * r, src + 208, 2);
+      break;
+    }
+    case P_Q3_K: {
+      for (int w = 0; w < 256; ++w) {
+        const Pos p = pos_of(w, r);
+        const int v = q3k_val(src, w);
+        put_2bit(chunk, p, v & 3);
+        uint8_t* qh = chunk + 1024 + p.lane * 8 + p.h * 4;
+        const int bit = 8 * p.s + (p.j & 1) * 4 + (p.j >> 1);
+        qh[bit / 8] |= (uint8_t)((v >> 2) << (bit % 8));
+      }
+      // lane group g's scales 4g..4g+3 as one 24-bit word, byte b at 4 b + g of the row's 12
+      for (int g = 0; g < 4; ++g) {
+        uint32_t v = 0;
+        for (int i = 0; i < 4; ++i) v |= (uint32_t)q3k_scale6(src + 96, 4 * g + i) << (6 * i);
+        for (int b = 0; b < 3; ++b) chunk[1536 + 12 * r + 4 * b + g] = (uint8_t)(v >> (8 * b));
+      }
+      std::memcpy(chunk + 1728 + 2 * r, src + 108, 2);
+      break;
+    }
+    case P_Q2_K: {
+      for (int w = 0; w < 256; ++w) put_2bit(chunk, pos_of(w, r), k2_field(src + 16, w));
+      std::memcpy(chunk + 1024 + 16 * r, src, 16);
+      std::memcpy(chunk + 1280 + 4 * r, src + 80, 4);
       break;
     }
     case P_Q8_0: {
@@ -276,6 +322,28 @@ MP_HOST_AVX2_CLONES void dequant_row(int t, const uint8_t* src, float* dst, int6
               o[64 * c + 32 + l] = d1 * ((q[l] >> 4) | (((qh[l] >> (2 * c + 1)) & 1) << 4)) - n1;
             }
           }
+        }
+      }
+      return;
+    case T_Q2_K:
+      for (int64_t b = 0; b < K / 256; ++b) {
+        const uint8_t* blk = src + 84 * b;
+        const float d = f16_to_f32(rd16(blk + 80)), dmin = f16_to_f32(rd16(blk + 82));
+        float* __restrict__ o = dst + 256 * b;
+        for (int w = 0; w < 256; ++w) {
+          const int sm = blk[w / 16];
+          o[w] = d * (float)(sm & 15) * (float)k2_field(blk + 16, w) - dmin * (float)(sm >> 4);
+        }
+      }
+      return;
+    case T_Q3_K:
+      for (int64_t b = 0; b < K / 256; ++b) {
+        const uint8_t* blk = src + 110 * b;
+        const float d = f16_to_f32(rd16(blk + 108));
+        float* __restrict__ o = dst + 256 * b;
+        for (int k = 0; k < 16; ++k) {
+          const float ds = d * (float)(q3k_scale6(blk + 96, k) - 32);
+          for (int l = 0; l < 16; ++l) o[16 * k + l] = ds * (float)(q3k_val(blk, 16 * k + l) - 4);
         }
       }
       return;

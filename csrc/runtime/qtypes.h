@@ -9,6 +9,25 @@
 // inside a dword lets ((w >> 4i) & 0x000F000F) | 0x64006400 produce a packed f16 pair (1024+q)
 // directly.  Bytes per chunk equal 16 x the ggml block bytes (no bandwidth overhead), except F16
 // which stores plain f16.
+//
+// The two low-bit K-quants (GGUF side, 256 weights per block; element e = 128 n + 32 j + l with
+// n = 0..1, j = 0..3, l = 0..31, 16-wide sub-block e / 16 = 8 n + 2 j + l / 16):
+//   Q2_K, 84 B:  scales[16], qs[64], f16 d, f16 dmin.  q = (qs[32 n + l] >> 2 j) & 3,
+//                sc = scales[e / 16] & 15, m = scales[e / 16] >> 4, w = d sc q - dmin m.
+//   Q3_K, 110 B: hmask[32], qs[64], scales[12], f16 d.  lo = (qs[32 n + l] >> 2 j) & 3,
+//                hi = (hmask[l] >> (4 n + j)) & 1, q = lo + 4 hi - 4 in [-4, 3]; the 6-bit scale of
+//                sub-block k: low4 = k < 8 ? scales[k] & 15 : scales[k - 8] >> 4,
+//                high2 = (scales[8 + k % 4] >> (2 (k / 4))) & 3, s_k = (low4 | high2 << 4) - 32,
+//                w = d s_k q.
+// Packed, both keep the k-mapping above with 2-bit fields: ONE 16-B piece per lane holds the lane's
+// 64 quants of the super-block, fragment (h, s) in dword 2 (s >> 1) + h, element j at bit
+// 16 (j & 1) + 8 (s & 1) + 2 (j >> 1), so that four masks on w and on w >> 8 give 16 weights
+// (csrc/kernels/dequant.h).  Chunk sections:
+//   P_Q3_K (1760 B): quants [lane] 16 B | high bits [lane] 8 B (dword h, bit 8 s + 4 (j & 1) + (j >> 1))
+//                    | scales [r] 12 B: byte b of v_g at 4 b + g, v_g = the four 6-bit (s_k + 32) of
+//                    lane group g's sub-blocks 4g..4g+3, 6 bits each | d [r] 2 B
+//   P_Q2_K (1344 B): quants [lane] 16 B | scale bytes [r] 16 B (dword g = sub-blocks 4g..4g+3, as
+//                    in GGUF) | (d, dmin) [r] 4 B
 #pragma once
 #include <stdint.h>
 #include <stddef.h>
@@ -30,7 +49,8 @@ inline const char* type_name(int t) {
   switch (t) {
     case T_F32: return "F32"; case T_F16: return "F16"; case T_BF16: return "BF16";
     case T_Q8_0: return "Q8_0"; case T_Q4_0: return "Q4_0"; case T_Q4_K: return "Q4_K";
-    case T_Q5_K: return "Q5_K"; case T_Q6_K: return "Q6_K"; default: return "?";
+    case T_Q5_K: return "Q5_K"; case T_Q6_K: return "Q6_K";
+    case T_Q2_K: return "Q2_K"; case T_Q3_K: return "Q3_K"; default: return "?";
   }
 }
 
@@ -39,7 +59,7 @@ MP_HD inline int block_elems(int t) {
   switch (t) {
     case T_F32: case T_F16: case T_BF16: return 1;
     case T_Q8_0: case T_Q4_0: return 32;
-    case T_Q4_K: case T_Q5_K: case T_Q6_K: return 256;
+    case T_Q2_K: case T_Q3_K: case T_Q4_K: case T_Q5_K: case T_Q6_K: return 256;
     default: return 0;
   }
 }
@@ -47,6 +67,7 @@ MP_HD inline int block_bytes(int t) {
   switch (t) {
     case T_F32: return 4; case T_F16: case T_BF16: return 2;
     case T_Q8_0: return 34; case T_Q4_0: return 18;
+    case T_Q2_K: return 84; case T_Q3_K: return 110;
     case T_Q4_K: return 144; case T_Q5_K: return 176; case T_Q6_K: return 210;
     default: return 0;
   }
@@ -57,7 +78,8 @@ inline size_t row_bytes(int t, int64_t n) { return (size_t)(n / block_elems(t)) 
 // weights stay bf16 (P_BF16, same chunk layout as F16): no narrowing at pack time, the kernels run
 // the bf16 MFMA on them.  P_I8 is not a GGUF type: per-row int8 re-quantized weights (one f32 scale
 // per output row, kept beside the matrix) for the int8-activation GEMM prototype (gemm3.hip, K15).
-enum PackType : int { P_F16 = 0, P_Q8_0 = 1, P_Q4_K = 2, P_Q5_K = 3, P_Q6_K = 4, P_Q4_0 = 5, P_BF16 = 6, P_I8 = 7 };
+enum PackType : int { P_F16 = 0, P_Q8_0 = 1, P_Q4_K = 2, P_Q5_K = 3, P_Q6_K = 4, P_Q4_0 = 5, P_BF16 = 6, P_I8 = 7,
+                      P_Q3_K = 8, P_Q2_K = 9 };
 constexpr bool is16(int p) { return p == P_F16 || p == P_BF16; }
 
 inline int pack_type_of(int ggml_type) {
@@ -66,6 +88,7 @@ inline int pack_type_of(int ggml_type) {
     case T_BF16: return P_BF16;
     case T_Q8_0: return P_Q8_0; case T_Q4_0: return P_Q4_0;
     case T_Q4_K: return P_Q4_K; case T_Q5_K: return P_Q5_K; case T_Q6_K: return P_Q6_K;
+    case T_Q3_K: return P_Q3_K; case T_Q2_K: return P_Q2_K;
     default: return -1;
   }
 }
@@ -73,7 +96,8 @@ inline int pack_type_of(int ggml_type) {
 // bytes of one (16-row tile, 256-k super-block) chunk
 constexpr int chunk_bytes(int p) {
   return is16(p) ? 8192 : p == P_Q8_0 ? 4352 : p == P_Q4_K ? 2304 : p == P_Q5_K ? 2816
-       : p == P_Q6_K ? 3360 : p == P_Q4_0 ? 2304 : p == P_I8 ? 4096 : 0;
+       : p == P_Q6_K ? 3360 : p == P_Q4_0 ? 2304 : p == P_I8 ? 4096
+       : p == P_Q3_K ? 1760 : p == P_Q2_K ? 1344 : 0;
 }
 
 inline int64_t round_up(int64_t a, int64_t b) { return (a + b - 1) / b * b; }

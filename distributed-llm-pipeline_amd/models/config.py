@@ -122,4 +122,25 @@ def tensor_type(ftype: str, name: str, layer: int, n_layer: int, k_dim: int) -> 
         if name in ("attn_v", "ffn_down") and use_more_bits(layer, n_layer):
             return Q.Q6_K
         return Q.Q5_K
+    if ftype in ("Q3_K", "Q3_K_S", "Q3_K_M", "Q3_K_L", "Q2_K"):
+        # the low-bit K-quant mixes (as recalled from upstream): the base type beside Q4_K / Q5_K / Q6_K
+        if name == "output":
+            t = Q.Q6_K
+        elif ftype == "Q2_K":
+            t = Q.Q3_K if name in ("attn_v", "attn_output", "ffn_down") else Q.Q2_K
+        elif ftype in ("Q3_K", "Q3_K_S"):
+            t = Q.Q3_K
+        else:
+            large = ftype == "Q3_K_L"
+            if name == "attn_v":
+                t = Q.Q5_K if large or layer < 2 else Q.Q4_K
+            elif name == "attn_output":
+                t = Q.Q5_K if large else Q.Q4_K
+            elif name == "ffn_down":
+                t = Q.Q5_K if large or layer < n_layer // 16 else Q.Q4_K
+            else:
+                t = Q.Q3_K
+        if not kq:   # upstream's rule for the two low-bit types; the others as above
+            return Q.Q4_0 if t in (Q.Q2_K, Q.Q3_K) else Q.Q8_0
+        return t
     raise ValueError(ftype)

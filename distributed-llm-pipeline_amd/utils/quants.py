@@ -5,7 +5,7 @@ synthetic-GGUF generator.  The block layouts follow the GGUF/ggml spec recorded 
 SURVEY.md §2.8 (the reference delegates these formats to its llama.cpp submodule,
 `.gitmodules:1-3`, which is not in the mount; the spec is reconstructed there).
 
-Formats: F32, F16, BF16, Q8_0, Q4_0, Q4_K, Q5_K, Q6_K.  Quantizers are simple
+Formats: F32, F16, BF16, Q8_0, Q4_0, Q2_K, Q3_K, Q4_K, Q5_K, Q6_K.  Quantizers are simple
 (min/max based) but produce valid blocks; dequantizers are exact implementations of
 the block math, so `dequant(bytes)` is the ground truth a kernel must reproduce.
 """
@@ -21,13 +21,14 @@ BF16 = 30
 QK_K = 256
 
 TYPE_NAMES = {F32: "F32", F16: "F16", BF16: "BF16", Q8_0: "Q8_0", Q4_0: "Q4_0",
-              Q4_K: "Q4_K", Q5_K: "Q5_K", Q6_K: "Q6_K"}
+              Q2_K: "Q2_K", Q3_K: "Q3_K", Q4_K: "Q4_K", Q5_K: "Q5_K", Q6_K: "Q6_K"}
 NAME_TO_TYPE = {v: k for k, v in TYPE_NAMES.items()}
 
 # (block_elems, block_bytes)
 BLOCK = {
     F32: (1, 4), F16: (1, 2), BF16: (1, 2),
     Q8_0: (32, 34), Q4_0: (32, 18),
+    Q2_K: (256, 84), Q3_K: (256, 110),
     Q4_K: (256, 144), Q5_K: (256, 176), Q6_K: (256, 210),
 }
 
@@ -285,6 +286,126 @@ def dequantize_q6_k(b: np.ndarray) -> np.ndarray:
     return y.reshape(-1)
 
 
+# ----------------------------------------------------------------------------- Q2_K / Q3_K
+# Both: 256 weights per block, element e = 128 n + 32 j + l (n = 0..1, j = 0..3, l = 0..31), whose
+# 16-wide sub-block is e // 16 = 8 n + 2 j + l // 16.  The 2-bit field of e is
+# (qs[32 n + l] >> 2 j) & 3.  (Written from memory of ggml, like the SURVEY.md section 2.8 formats:
+# this text is the specification the kernels and tests follow.)
+def _pack_2bit(q: np.ndarray) -> np.ndarray:
+    """q [nb, 256] (only bits 0-1 used) -> qs [nb, 64]."""
+    q4 = (q.reshape(-1, 2, 4, 32) & 3).astype(np.uint8)
+    qs = np.zeros((q4.shape[0], 2, 32), np.uint8)
+    for j in range(4):
+        qs |= q4[:, :, j, :] << (2 * j)
+    return qs.reshape(-1, 64)
+
+
+def _unpack_2bit(qs: np.ndarray) -> np.ndarray:
+    """qs [nb, 64] -> the 2-bit fields [nb, 256] in element order."""
+    qs = qs.reshape(-1, 2, 1, 32)
+    sh = (2 * np.arange(4, dtype=np.uint8)).reshape(1, 1, 4, 1)
+    return ((qs >> sh) & 3).reshape(-1, 256)
+
+
+def quantize_q2_k(x: np.ndarray) -> np.ndarray:
+    """Q2_K, 84 bytes: scales[16] (sc | m << 4), qs[64], f16 d, f16 dmin.
+    w = d * sc * q - dmin * m with q the 2-bit field, sc / m the nibbles of scales[e // 16].
+    Plain min/max per 16-wide sub-block."""
+    x = np.asarray(x, np.float32).reshape(-1, 16, 16)
+    nb = x.shape[0]
+    mn = np.minimum(x.min(axis=2), 0.0)
+    mx = x.max(axis=2)
+    scale = np.maximum(mx - mn, 0.0) / 3.0
+    mins = -mn
+    d16 = (scale.max(axis=1) / 15.0).astype(np.float16).astype(np.float32)
+    dmin16 = (mins.max(axis=1) / 15.0).astype(np.float16).astype(np.float32)
+    inv_d = np.where(d16 > 0, 1.0 / np.where(d16 > 0, d16, 1), 0.0)
+    inv_dm = np.where(dmin16 > 0, 1.0 / np.where(dmin16 > 0, dmin16, 1), 0.0)
+    sc = np.clip(np.rint(scale * inv_d[:, None]), 0, 15).astype(np.uint8)
+    m = np.clip(np.rint(mins * inv_dm[:, None]), 0, 15).astype(np.uint8)
+    eff_s = d16[:, None] * sc.astype(np.float32)
+    eff_m = dmin16[:, None] * m.astype(np.float32)
+    inv_s = np.where(eff_s > 0, 1.0 / np.where(eff_s > 0, eff_s, 1), 0.0)
+    q = np.clip(np.rint((x + eff_m[:, :, None]) * inv_s[:, :, None]), 0, 3).astype(np.uint8).reshape(nb, 256)
+    out = np.zeros((nb, 84), np.uint8)
+    out[:, 0:16] = sc | (m << 4)
+    out[:, 16:80] = _pack_2bit(q)
+    out[:, 80:82] = d16.astype(np.float16).reshape(-1, 1).view(np.uint8)
+    out[:, 82:84] = dmin16.astype(np.float16).reshape(-1, 1).view(np.uint8)
+    return out.reshape(-1)
+
+
+def dequantize_q2_k(b: np.ndarray) -> np.ndarray:
+    b = np.asarray(b, np.uint8).reshape(-1, 84)
+    sc = np.repeat((b[:, 0:16] & 15).astype(np.float32), 16, axis=1)      # [nb, 256] by e // 16
+    m = np.repeat((b[:, 0:16] >> 4).astype(np.float32), 16, axis=1)
+    q = _unpack_2bit(b[:, 16:80]).astype(np.float32)
+    d = b[:, 80:82].copy().view(np.float16).astype(np.float32)
+    dmin = b[:, 82:84].copy().view(np.float16).astype(np.float32)
+    return (d * sc * q - dmin * m).reshape(-1)
+
+
+def pack_scales_q3_k(s: np.ndarray) -> np.ndarray:
+    """16 signed 6-bit scales s_k in [-32, 31] -> scales[12]: u = s + 32, low nibble of u_k in
+    scales[k] & 15 (k < 8) or scales[k - 8] >> 4, its high 2 bits at scales[8 + k % 4] >> 2 (k // 4)."""
+    u = (s.astype(np.int32) + 32).astype(np.uint8)
+    out = np.zeros((u.shape[0], 12), np.uint8)
+    for k in range(16):
+        out[:, k % 8] |= (u[:, k] & 15) << (4 * (k // 8))
+        out[:, 8 + k % 4] |= (u[:, k] >> 4) << (2 * (k // 4))
+    return out
+
+
+def unpack_scales_q3_k(sc: np.ndarray) -> np.ndarray:
+    sc = sc.astype(np.uint8)
+    s = np.zeros((sc.shape[0], 16), np.int32)
+    for k in range(16):
+        low4 = (sc[:, k] & 15) if k < 8 else (sc[:, k - 8] >> 4)
+        high2 = (sc[:, 8 + k % 4] >> (2 * (k // 4))) & 3
+        s[:, k] = (low4 | (high2 << 4)).astype(np.int32) - 32
+    return s
+
+
+def quantize_q3_k(x: np.ndarray) -> np.ndarray:
+    """Q3_K, 110 bytes: hmask[32], qs[64], scales[12], f16 d.
+    q = lo + 4 hi - 4 in [-4, 3] with lo the 2-bit field and hi = (hmask[l] >> (4 n + j)) & 1;
+    w = d * s_k * q with s_k the signed 6-bit scale of sub-block k = e // 16 (pack_scales_q3_k).
+    Plain: the signed maximum magnitude of a sub-block divided by -4."""
+    x = np.asarray(x, np.float32).reshape(-1, 16, 16)
+    nb = x.shape[0]
+    idx = np.abs(x).argmax(axis=2)
+    mx = np.take_along_axis(x, idx[:, :, None], axis=2)[:, :, 0]
+    scale = mx / -4.0
+    d16 = (np.abs(scale).max(axis=1) / 31.0).astype(np.float16).astype(np.float32)
+    inv_d = np.where(d16 > 0, 1.0 / np.where(d16 > 0, d16, 1), 0.0)
+    s = np.clip(np.rint(scale * inv_d[:, None]), -32, 31).astype(np.int32)
+    eff = d16[:, None] * s.astype(np.float32)
+    inv = np.where(eff != 0, 1.0 / np.where(eff != 0, eff, 1), 0.0)
+    q = (np.clip(np.rint(x * inv[:, :, None]), -4, 3) + 4).astype(np.uint8).reshape(nb, 256)
+    hi = (q >> 2).reshape(nb, 8, 32)                                         # [nb, 4 n + j, l]
+    hmask = np.zeros((nb, 32), np.uint8)
+    for bit in range(8):
+        hmask |= hi[:, bit, :] << bit
+    out = np.zeros((nb, 110), np.uint8)
+    out[:, 0:32] = hmask
+    out[:, 32:96] = _pack_2bit(q)
+    out[:, 96:108] = pack_scales_q3_k(s)
+    out[:, 108:110] = d16.astype(np.float16).reshape(-1, 1).view(np.uint8)
+    return out.reshape(-1)
+
+
+def dequantize_q3_k(b: np.ndarray) -> np.ndarray:
+    b = np.asarray(b, np.uint8).reshape(-1, 110)
+    nb = b.shape[0]
+    lo = _unpack_2bit(b[:, 32:96]).astype(np.int32)
+    bits = (2 ** np.arange(8)).astype(np.uint8).reshape(1, 8, 1)
+    hi = ((b[:, None, 0:32] & bits) != 0).astype(np.int32).reshape(nb, 256)  # [nb, 4 n + j, l]
+    q = (lo + 4 * hi - 4).astype(np.float32)
+    s = np.repeat(unpack_scales_q3_k(b[:, 96:108]).astype(np.float32), 16, axis=1)
+    d = b[:, 108:110].copy().view(np.float16).astype(np.float32)
+    return (d * s * q).reshape(-1)
+
+
 # ----------------------------------------------------------------------------- dispatch
 def quantize(x: np.ndarray, qtype: int) -> np.ndarray:
     x = np.ascontiguousarray(x, np.float32)
@@ -294,7 +415,7 @@ def quantize(x: np.ndarray, qtype: int) -> np.ndarray:
         return x.astype(np.float16).reshape(-1).view(np.uint8).copy()
     if qtype == BF16:
         return f32_to_bf16_bits(x.reshape(-1)).view(np.uint8).copy()
-    return {Q8_0: quantize_q8_0, Q4_0: quantize_q4_0, Q4_K: quantize_q4_k,
+    return {Q8_0: quantize_q8_0, Q4_0: quantize_q4_0, Q2_K: quantize_q2_k, Q3_K: quantize_q3_k, Q4_K: quantize_q4_k,
             Q5_K: quantize_q5_k, Q6_K: quantize_q6_k}[qtype](x)
 
 
@@ -307,7 +428,8 @@ def dequantize(b: np.ndarray, qtype: int, shape=None) -> np.ndarray:
     elif qtype == BF16:
         y = bf16_bits_to_f32(b.view(np.uint16))
     else:
-        y = {Q8_0: dequantize_q8_0, Q4_0: dequantize_q4_0, Q4_K: dequantize_q4_k,
+        y = {Q8_0: dequantize_q8_0, Q4_0: dequantize_q4_0, Q2_K: dequantize_q2_k, Q3_K: dequantize_q3_k,
+             Q4_K: dequantize_q4_k,
              Q5_K: dequantize_q5_k, Q6_K: dequantize_q6_k}[qtype](b)
     return y.reshape(shape) if shape is not None else y
 
@@ -337,4 +459,11 @@ def random_blocks(rng: np.random.Generator, qtype: int, n_rows: int, n_cols: int
     elif qtype == Q6_K:
         raw[:, 192:208] = rng.integers(40, 100, size=(nblk, 16)).astype(np.int8).view(np.uint8)
         raw[:, 208:210] = np.full((nblk, 1), scale / (32.0 * 70.0), np.float16).view(np.uint8)
+    elif qtype == Q2_K:
+        # random scale / min nibbles and quants; dmin = 1.5 d centres the weights (mean q = 1.5)
+        raw[:, 80:82] = np.full((nblk, 1), scale / 13.5, np.float16).view(np.uint8)
+        raw[:, 82:84] = np.full((nblk, 1), scale / 9.0, np.float16).view(np.uint8)
+    elif qtype == Q3_K:
+        # every hmask / quant / 6-bit scale bit random: |s_k| averages 16, q deviation ~2.3
+        raw[:, 108:110] = np.full((nblk, 1), scale / 42.0, np.float16).view(np.uint8)
     return raw.reshape(-1)

@@ -11,9 +11,11 @@ import numpy as np
 from . import quants as Q
 
 P_F16, P_Q8_0, P_Q4_K, P_Q5_K, P_Q6_K, P_Q4_0, P_BF16 = 0, 1, 2, 3, 4, 5, 6
-CHUNK = {P_F16: 8192, P_Q8_0: 4352, P_Q4_K: 2304, P_Q5_K: 2816, P_Q6_K: 3360, P_Q4_0: 2304, P_BF16: 8192}
+P_Q3_K, P_Q2_K = 8, 9   # (7 is P_I8, which has no GGUF type)
+CHUNK = {P_F16: 8192, P_Q8_0: 4352, P_Q4_K: 2304, P_Q5_K: 2816, P_Q6_K: 3360, P_Q4_0: 2304, P_BF16: 8192,
+         P_Q3_K: 1760, P_Q2_K: 1344}
 PACK_OF = {Q.F32: P_F16, Q.F16: P_F16, Q.BF16: P_BF16, Q.Q8_0: P_Q8_0, Q.Q4_0: P_Q4_0,
-           Q.Q4_K: P_Q4_K, Q.Q5_K: P_Q5_K, Q.Q6_K: P_Q6_K}
+           Q.Q4_K: P_Q4_K, Q.Q5_K: P_Q5_K, Q.Q6_K: P_Q6_K, Q.Q3_K: P_Q3_K, Q.Q2_K: P_Q2_K}
 
 
 def _f16(b2):
@@ -60,6 +62,27 @@ def unpack_t16(packed: np.ndarray, ptype: int, n: int, k: int) -> np.ndarray:
                                 qh = c[2048 + h * 256 + lane * 4 + (8 * s + pos) // 8]
                                 q = q + (((qh >> ((8 * s + pos) % 8)) & 1) << 4)
                             v = d * sc * q - dmin * mn
+                        elif ptype in (P_Q3_K, P_Q2_K):
+                            # quants [lane] 16 B: dword 2 (s >> 1) + h, field at bit 16 (j & 1) + 8 (s & 1) + 2 (j >> 1)
+                            bit = 32 * (2 * (s >> 1) + h) + 16 * (j & 1) + 8 * (s & 1) + 2 * (j >> 1)
+                            q = ((c[lane * 16 + bit // 8] >> (bit % 8)) & 3).astype(np.float32)
+                            sub = 2 * h + (s >> 1)                            # of the lane group's 4 sub-blocks
+                            if ptype == P_Q2_K:
+                                # scale bytes [r] 16 B (sc | m << 4 of sub-block 4g + sub), (d, dmin) [r] 4 B
+                                sm = c[1024 + 16 * r + 4 * g + sub]
+                                d = _f16(np.stack([c[1280 + 4 * rr: 1280 + 4 * rr + 2] for rr in r]))
+                                dmin = _f16(np.stack([c[1282 + 4 * rr: 1282 + 4 * rr + 2] for rr in r]))
+                                v = d * (sm & 15) * q - dmin * (sm >> 4)
+                            else:
+                                # high bits [lane] 8 B: dword h, bit 8 s + 4 (j & 1) + (j >> 1); scales [r] 12 B:
+                                # byte b of v_g = u(4g) | u(4g+1) << 6 | u(4g+2) << 12 | u(4g+3) << 18 (u = s_k + 32)
+                                # at byte 4 b + g; d [r] 2 B
+                                hb = 8 * s + pos
+                                hi = (c[1024 + lane * 8 + 4 * h + hb // 8] >> (hb % 8)) & 1
+                                vg = sum(c[1536 + 12 * r + 4 * b + g].astype(np.int64) << (8 * b) for b in range(3))
+                                sk = ((vg >> (6 * sub)) & 63).astype(np.float32) - 32
+                                d = _f16(np.stack([c[1728 + 2 * rr: 1728 + 2 * rr + 2] for rr in r]))
+                                v = d * sk * (q + 4 * hi - 4)
                         elif ptype == P_Q6_K:
                             i = j >> 1
                             bit = 16 * s + ((8 + 2 * i) if (j & 1) else 2 * i)
