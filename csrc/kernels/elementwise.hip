@@ -451,22 +451,30 @@ __global__ __launch_bounds__(256) void argmax2_kernel(const float* logits, int l
   }
 }
 
-// deterministic reductions: a fixed summation order per element, no atomics
+// deterministic reductions: a fixed summation order per element, no atomics.  INIT: Y is written,
+// not accumulated into: it starts from the bias (or 0.f, not from the first partial, so a sum of
+// signed zeros comes out as it does on a zero-filled Y)
+template <bool INIT>
 __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restrict__ part, int nsplit, int64_t ss, int ldp,
-                                                            int n, float* __restrict__ Y, int ldy) {
+                                                            int n, float* __restrict__ Y, int ldy,
+                                                            const float* __restrict__ bias) {
   const int m = blockIdx.y, j = blockIdx.x * 256 + threadIdx.x;
   if (j >= n) return;
-  float acc = Y[(size_t)m * ldy + j];
+  float acc = INIT ? (bias ? bias[j] : 0.f) : Y[(size_t)m * ldy + j];
   for (int s = 0; s < nsplit; ++s) acc += part[(size_t)s * ss + (size_t)m * ldp + j];
   Y[(size_t)m * ldy + j] = acc;
 }
 
-// 4 consecutive columns per thread (n, ldp, ldy multiples of 4)
+// 4 consecutive columns per thread (n, ldp, ldy multiples of 4; INIT: a 16-B aligned bias)
+template <bool INIT>
 __global__ __launch_bounds__(256) void splitk_reduce4_kernel(const float* __restrict__ part, int nsplit, int64_t ss, int ldp,
-                                                             int n, float* __restrict__ Y, int ldy) {
+                                                             int n, float* __restrict__ Y, int ldy,
+                                                             const float* __restrict__ bias) {
   const int m = blockIdx.y, j = (blockIdx.x * 256 + threadIdx.x) * 4;
   if (j >= n) return;
-  float4 acc = *reinterpret_cast<const float4*>(Y + (size_t)m * ldy + j);
+  float4 acc;
+  if constexpr (INIT) acc = bias ? *reinterpret_cast<const float4*>(bias + j) : make_float4(0.f, 0.f, 0.f, 0.f);
+  else acc = *reinterpret_cast<const float4*>(Y + (size_t)m * ldy + j);
   for (int s = 0; s < nsplit; ++s) {
     const float4 v = *reinterpret_cast<const float4*>(part + (size_t)s * ss + (size_t)m * ldp + j);
     acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w;
@@ -615,13 +623,17 @@ void launch_argmax(const float* logits, int ld, int n, int M, int32_t* tokens, h
 }
 
 void launch_splitk_reduce(const float* part, int nsplit, int64_t split_stride, int ldp, int M, int n, float* Y, int ldy,
-                          hipStream_t st) {
-  if ((n & 3) == 0 && (ldp & 3) == 0 && (ldy & 3) == 0 && (split_stride & 3) == 0)
-    hipLaunchKernelGGL(mpk::splitk_reduce4_kernel, dim3((n / 4 + 255) / 256, M), dim3(256), 0, st, part, nsplit,
-                       split_stride, ldp, n, Y, ldy);
-  else
-    hipLaunchKernelGGL(mpk::splitk_reduce_kernel, dim3((n + 255) / 256, M), dim3(256), 0, st, part, nsplit, split_stride,
-                       ldp, n, Y, ldy);
+                          hipStream_t st, bool init, const float* bias) {
+  if (bias && !init) throw std::runtime_error("launch_splitk_reduce: a bias needs the init form");
+  const bool v4 = (n & 3) == 0 && (ldp & 3) == 0 && (ldy & 3) == 0 && (split_stride & 3) == 0 &&
+                  (reinterpret_cast<uintptr_t>(bias) & 15) == 0;
+  const dim3 grid(((v4 ? n / 4 : n) + 255) / 256, M);
+#define SKR_LAUNCH(K) hipLaunchKernelGGL(K, grid, dim3(256), 0, st, part, nsplit, split_stride, ldp, n, Y, ldy, bias)
+  if (v4 && init) SKR_LAUNCH(mpk::splitk_reduce4_kernel<true>);
+  else if (v4) SKR_LAUNCH(mpk::splitk_reduce4_kernel<false>);
+  else if (init) SKR_LAUNCH(mpk::splitk_reduce_kernel<true>);
+  else SKR_LAUNCH(mpk::splitk_reduce_kernel<false>);
+#undef SKR_LAUNCH
 }
 
 void launch_moe_combine(const float* Yslot, int ld_slot, int k, int M, int n, float* Y, int ldy, hipStream_t st) {

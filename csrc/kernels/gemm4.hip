@@ -44,18 +44,21 @@ bool launch_gemm4(int ptype, int epi, GemvParams p, hipStream_t st, bool allow_s
 }
 
 // split-K partial stores: split s writes scratch + s * M * ldp; false (nothing launched) when the
-// shape does not split or the partials do not fit scratch_n floats
+// shape does not split or the partials do not fit scratch_n floats.  init: the reduction writes
+// Y = p.bias + the partials instead of adding them onto Y (which then needs no fill)
 bool launch_gemm4_splitk(int ptype, GemvParams p, float* scratch, size_t scratch_n, hipStream_t st, bool reduce,
-                         int* nsplit_out) {
-  if (p.bias) return false;
+                         int* nsplit_out, bool init) {
+  if (init && !reduce) throw std::runtime_error("gemm4 split-K: the init form reduces at once");
+  if (p.bias && !init) return false;
   const Gemm4Plan pl = plan_gemm4(ptype, EPI_ATOMIC, p.M, p.ntiles, p.nsb, true, true);
   const int ldp = p.ntiles * 16;
   if (!pl.ok || (size_t)pl.nsplit * p.M * ldp > scratch_n) return false;
   GemvParams q = p;
   q.Y = scratch; q.ldy = ldp; q.split_stride = (int64_t)p.M * ldp;
+  q.bias = nullptr;   // (init: added by the reduction)
   run(ptype, pl, EPI_STORE, q, nullptr, st);
   if (nsplit_out) *nsplit_out = pl.nsplit;
-  if (reduce) launch_splitk_reduce(scratch, pl.nsplit, q.split_stride, ldp, p.M, p.n_valid, p.Y, p.ldy, st);
+  if (reduce) launch_splitk_reduce(scratch, pl.nsplit, q.split_stride, ldp, p.M, p.n_valid, p.Y, p.ldy, st, init, p.bias);
   return true;
 }
 

@@ -39,8 +39,11 @@ static void gemm4_go(const Gemm4Plan& pl, const GemvParams& p, const mpk::G4Moe&
   const dim3 grid(pl.grid_x, pl.grid_y, pl.grid_z), block(64 * NWV);
 #define G4_LAUNCH(F) hipLaunchKernelGGL((mpk::gemm4_kernel<PT, EPI, BM, MOE, NWV, F, TW>), grid, block, 0, st, p, n_mb, per, n_stages, mo)
 #ifdef MIPIPE_TIMING_PROBES
-  // timing probes (knob GEMM4_PROBE): Q4_K dense gate/up (SwiGLU, 256 rows) and split-K stores
-  if constexpr (PT == P_Q4_K && ((!MOE && ((EPI == EPI_SWIGLU && BM == 256) || (EPI == EPI_STORE && BM == 128))) ||
+  // timing probes (knob GEMM4_PROBE): Q4_K dense gate/up (SwiGLU, 256 rows), split-K stores and the
+  // 256-row store.  Bits 0-2 are FL bits 3-5; bit 3 (no epilogue stores, FL bit 6) goes alone or on
+  // top of the whole skeleton (8, 15)
+  if constexpr (PT == P_Q4_K && ((!MOE && ((EPI == EPI_SWIGLU && BM == 256) || (EPI == EPI_STORE && BM == 128) ||
+                                           (EPI == EPI_STORE && BM == 256 && NWV == 4))) ||
                                  (MOE && EPI == EPI_SWIGLU && BM == 128 && NWV == 8))) {
     const int pk = knob(KNOB_GEMM4_PROBE);
     if (pk) {
@@ -52,8 +55,18 @@ static void gemm4_go(const Gemm4Plan& pl, const GemvParams& p, const mpk::G4Moe&
         case 4: if (w4) G4_LAUNCH(4 | 32); else G4_LAUNCH(32); return;
         case 5: if (w4) G4_LAUNCH(4 | 40); else G4_LAUNCH(40); return;
         case 6: if (w4) G4_LAUNCH(4 | 48); else G4_LAUNCH(48); return;
-        default: if (w4) G4_LAUNCH(4 | 56); else G4_LAUNCH(56); return;
+        case 7: if (w4) G4_LAUNCH(4 | 56); else G4_LAUNCH(56); return;
+        case 8: if (w4) G4_LAUNCH(4 | 64); else G4_LAUNCH(64); return;
+        case 15: if (w4) G4_LAUNCH(4 | 56 | 64); else G4_LAUNCH(56 | 64); return;
+        default: throw std::runtime_error("gemm4: GEMM4_PROBE bit 3 goes alone (8) or with bits 0-2 all set (15)");
       }
+    }
+  }
+  // the LM head of a Q4_K file is Q6_K (dense 256-row store, 4 waves x 64 columns): bit 3 only
+  if constexpr (PT == P_Q6_K && !MOE && EPI == EPI_STORE && BM == 256 && NWV == 4) {
+    if (knob(KNOB_GEMM4_PROBE) == 8) {
+      if (wnt) G4_LAUNCH(4 | 64); else G4_LAUNCH(64);
+      return;
     }
   }
   // the LDS-DMA spread schedules (knob GEMM4_SPREAD, measured no faster: PERFORMANCE.md) exist in

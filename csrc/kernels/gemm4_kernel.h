@@ -20,6 +20,9 @@
 //   C:            column c, row 8 (v >> 2) + 4 h + (v & 3) of the 16 accumulators v
 // The k permutation inside a 32-k half (A and B index it the same way) is all a dot product needs,
 // and the sub-block scale of MFMA t (k-half kk) is uniform over the lanes.
+// The dense STORE and SwiGLU epilogues regroup C across lanes (DPP, no LDS) into 16 contiguous bytes
+// of one row per lane and store those (lane_transpose4 below); the atomics and the MoE scatters
+// store by element.
 //
 // The x image, the raw weight images and the 3-stage counted-vmcnt / counted-lgkmcnt stream are
 // gemm3's (gemm_lds.h); see gemm3.hip for the pipeline's invariants.
@@ -333,9 +336,46 @@ struct G4Geom {
   static constexpr int A_INSTR = (NP + NWV - 1) / NWV;        // per wave (uniform: vmcnt accounting)
 };
 
-// FL (compile-time flags): bits 0-1 LDS-DMA spread mode, bit 2 non-temporal weights; bits 3-5 timing
+// Wide epilogue stores: the C fragment is regrouped across lanes in registers (DPP moves: no LDS
+// round trip, nothing for the counted waits), so that a lane holds 16 contiguous bytes of one row.
+// DPP controls whose source lane is the destination lane xor d inside a row of 16 (all symmetric)
+constexpr int kDppXor1 = 0xB1, kDppXor2 = 0x4E, kDppXor3 = 0x1B, kDppHalfMirror = 0x141, kDppRor8 = 0x128;
+template <int CTRL>
+__device__ __forceinline__ uint32_t dpp_u32(uint32_t x) {
+  return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, CTRL, 0xf, 0xf, true);
+}
+// lane xor D (1, 2, 4 or 8); 4 = reverse the 8 lanes (xor 7), then the quad (xor 3)
+template <int D>
+__device__ __forceinline__ uint32_t lane_xor(uint32_t x) {
+  static_assert(D == 1 || D == 2 || D == 4 || D == 8, "lane_xor: 1, 2, 4 or 8");
+  if constexpr (D == 1) return dpp_u32<kDppXor1>(x);
+  else if constexpr (D == 2) return dpp_u32<kDppXor2>(x);
+  else if constexpr (D == 4) return dpp_u32<kDppXor3>(dpp_u32<kDppHalfMirror>(x));
+  else return dpp_u32<kDppRor8>(x);
+}
+// The lanes l and l ^ D (hi: this lane has bit D set) hold the 2 x 2 block [[a, b], [a', b']];
+// transpose it: the low lane's b and the high lane's a trade places
+template <int D>
+__device__ __forceinline__ void lane_swap(uint32_t& a, uint32_t& b, bool hi) {
+  const uint32_t pa = lane_xor<D>(a), pb = lane_xor<D>(b);
+  a = hi ? pb : a;
+  b = hi ? b : pa;
+}
+// 4 x 4 transpose over the lanes {l, l ^ D0, l ^ D1, l ^ D0 ^ D1} (index j = bit D0 + 2 bit D1 of the
+// lane): r[k] of lane j becomes r[j] of lane k
+template <int D0, int D1>
+__device__ __forceinline__ void lane_transpose4(uint32_t (&r)[4], int lane) {
+  const bool h0 = (lane & D0) != 0, h1 = (lane & D1) != 0;
+  lane_swap<D0>(r[0], r[1], h0);
+  lane_swap<D0>(r[2], r[3], h0);
+  lane_swap<D1>(r[0], r[2], h1);
+  lane_swap<D1>(r[1], r[3], h1);
+}
+
+// FL (compile-time flags): bits 0-1 LDS-DMA spread mode, bit 2 non-temporal weights; bits 3-6 timing
 // probes (probe builds only, wrong results): 3 raw bits as B fragments (no dequant VALU), 4 no MFMAs
-// (operands kept live), 5 no LDS-DMA (the stage images keep stale bytes).  Compile-time
+// (operands kept live), 5 no LDS-DMA (the stage images keep stale bytes), 6 no epilogue stores (the
+// values kept live).  Compile-time
 // because every weight DMA of a stage branched on them at run time: the 2-stage loop body of the MoE
 // gate/up kernel carried 485 scalar instructions (36 of them 64-bit compares, 44 s_nop) against 32
 // MFMAs.
@@ -350,7 +390,7 @@ __global__ __launch_bounds__(64 * NWV) __attribute__((amdgpu_waves_per_eu(NWV ==
   using Q3 = W3<PT>;
   using Q = W4<PT>;
   using G = G4Geom<PT, BM, NWV, TW>;
-  constexpr bool PR_NODQ = (FL & 8) != 0, PR_NOMMA = (FL & 16) != 0, PR_NODMA = (FL & 32) != 0;
+  constexpr bool PR_NODQ = (FL & 8) != 0, PR_NOMMA = (FL & 16) != 0, PR_NODMA = (FL & 32) != 0, PR_NOST = (FL & 64) != 0;
   constexpr int NB = G::NB, FR = BM / 32, BN = 16 * TW * NWV;
   constexpr bool BF = PT == P_BF16;
   static_assert(NB >= 3 && NB <= 5, "gemm4: 3-5 stage buffers");
@@ -618,10 +658,65 @@ __global__ __launch_bounds__(64 * NWV) __attribute__((amdgpu_waves_per_eu(NWV ==
   // epilogue: lane holds C[row 32 i + 8 (v >> 2) + 4 h + (v & 3)][col cl] of each of the wave's
   // 32-column pairs
   const int rowb = m0 + 4 * h;
+  // 16-byte stores when every row of the output starts 16-B aligned (uniform over the launch);
+  // otherwise, the MoE scatters and the atomics store by element
+  const bool wide_y = EPI == EPI_STORE && !MOE && (reinterpret_cast<uintptr_t>(p.Y) & 15) == 0 && (p.ldy & 3) == 0 &&
+                      (p.split_stride & 3) == 0;
+  const bool wide_h = EPI == EPI_SWIGLU && !MOE && (reinterpret_cast<uintptr_t>(p.H) & 15) == 0 && (p.ldh & 7) == 0;
 #pragma unroll
   for (int pp = 0; pp < NPR; ++pp) {
   const int n = cg * BN + wave * 16 * TW + 32 * pp + cl;
   if constexpr (EPI == EPI_SWIGLU) {
+    if constexpr (!MOE) {
+      // dense, H rows 16-B aligned: 16-B stores.  The gate lane (h, c) and the up lane (h, c + 8) share
+      // each register pair: the gate lane takes the up value of register 2 w, the up lane the gate
+      // value of 2 w + 1, so lane (k = c & 7, up) holds output k of its tile at the fragment rows
+      // 8 (w >> 1) + 4 h + 2 (w & 1) + up, w = 0 .. 7.  An 8 x 8 transpose over the lanes k then gives
+      // lane k the tile's 8 outputs (contiguous in H) of its row w = k.
+      if (wide_h) {   // wave-uniform
+        const bool up = (cl & 8) != 0;
+        const int k = cl & 7;
+        const int o0 = ((n >> 4) << 3);   // the tile's first output
+        const int rk = rowb + 8 * (k >> 1) + 2 * (k & 1) + (up ? 1 : 0);
+#pragma unroll
+        for (int i = 0; i < FR; ++i) {
+          uint32_t d[4];
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            f16 o2[2];
+#pragma unroll
+            for (int t = 0; t < 2; ++t) {
+              const float a0 = acc[i][pp][4 * q + 2 * t], a1 = acc[i][pp][4 * q + 2 * t + 1];
+              const float recv = __builtin_bit_cast(float, lane_xor<8>(__builtin_bit_cast(uint32_t, up ? a0 : a1)));
+              o2[t] = sat_f16(silu(up ? recv : a0) * (up ? a1 : recv));
+            }
+            d[q] = as_u32(half2_t{o2[0], o2[1]});   // rows w = 2 q, 2 q + 1 of output k
+          }
+          // 16-bit step: the even lane keeps row 2 q of outputs (k, k + 1), the odd lane row 2 q + 1
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            const uint32_t pd = lane_xor<1>(d[q]);
+            d[q] = (k & 1) ? (pd >> 16) | (d[q] & 0xFFFF0000u) : (d[q] & 0xFFFFu) | (pd << 16);
+          }
+          // dword q of lane k: row 2 q + (k & 1), output pair k >> 1  ->  row k, output pair q
+          lane_transpose4<2, 4>(d, lane);
+          const int m = rk + 32 * i;
+          if constexpr (PR_NOST) {
+            asm volatile("" :: "v"(d[0]), "v"(d[1]), "v"(d[2]), "v"(d[3]));
+          } else if (m < M) {
+            f16* hp = p.H + (size_t)m * p.ldh + o0;
+            if (o0 + 8 <= p.n_valid) {
+              *reinterpret_cast<u32x4*>(hp) = u32x4{d[0], d[1], d[2], d[3]};
+            } else {   // the tile straddles n_valid
+#pragma unroll
+              for (int e = 0; e < 8; ++e)
+                if (o0 + e < p.n_valid) hp[e] = __builtin_bit_cast(f16, (uint16_t)(d[e >> 1] >> (16 * (e & 1))));
+            }
+          }
+        }
+        continue;
+      }
+    }
     const int o = (n >> 4) * 8 + (cl & 15);   // tile rows 0-7 gate, 8-15 up of the same 8 outputs
 #pragma unroll
     for (int i = 0; i < FR; ++i)
@@ -631,10 +726,45 @@ __global__ __launch_bounds__(64 * NWV) __attribute__((amdgpu_waves_per_eu(NWV ==
         const int m = rowb + 32 * i + 8 * (v >> 2) + (v & 3);
         if ((cl & 8) == 0 && m < M && o < p.n_valid) {
           const int hr = MOE ? list[m] : m;   // MoE: the slot's row of H
-          p.H[(size_t)hr * p.ldh + o] = sat_f16(silu(acc[i][pp][v]) * other);
+          const f16 hv = sat_f16(silu(acc[i][pp][v]) * other);
+          if constexpr (PR_NOST) asm volatile("" :: "v"(hv));
+          else p.H[(size_t)hr * p.ldh + o] = hv;
         }
       }
   } else {
+    if constexpr (EPI == EPI_STORE && !MOE) {
+      // dense, Y rows 16-B aligned: the 4 x 4 block that the registers 4 b .. 4 b + 3 form in a quad of
+      // lanes (rows 8 b + 4 h + 0 .. 3, columns 4 g .. 4 g + 3) is transposed, so lane 4 g + j holds
+      // row 8 b + 4 h + j, columns 4 g .. 4 g + 3: one 16-B store, 8 rows x 128 B per instruction
+      if (wide_y) {   // wave-uniform
+        const int j = cl & 3, n0 = n - j;
+        const float bias = (p.bias && blockIdx.y == 0 && n < p.n_valid) ? p.bias[n] : 0.f;
+        float* Yq = p.Y + (size_t)blockIdx.y * p.split_stride + n0;
+#pragma unroll
+        for (int i = 0; i < FR; ++i)
+#pragma unroll
+          for (int b4 = 0; b4 < 4; ++b4) {
+            uint32_t r[4];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) r[e] = __builtin_bit_cast(uint32_t, acc[i][pp][4 * b4 + e] + bias);
+            lane_transpose4<1, 2>(r, lane);
+            const int m = rowb + 32 * i + 8 * b4 + j;
+            if constexpr (PR_NOST) {
+              asm volatile("" :: "v"(r[0]), "v"(r[1]), "v"(r[2]), "v"(r[3]));
+            } else if (m < M) {
+              float* y = Yq + (size_t)m * p.ldy;
+              if (n0 + 4 <= p.n_valid) {
+                *reinterpret_cast<u32x4*>(y) = u32x4{r[0], r[1], r[2], r[3]};
+              } else {   // the group straddles n_valid
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+                  if (n0 + e < p.n_valid) y[e] = __builtin_bit_cast(float, r[e]);
+              }
+            }
+          }
+        continue;
+      }
+    }
     if (n < p.n_valid) {
       const float bias = (p.bias && blockIdx.y == 0) ? p.bias[n] : 0.f;
       float* Y = p.Y + (size_t)blockIdx.y * p.split_stride + n;
@@ -651,6 +781,8 @@ __global__ __launch_bounds__(64 * NWV) __attribute__((amdgpu_waves_per_eu(NWV ==
               else unsafeAtomicAdd(p.Y + (size_t)(slot / mo.k) * p.ldy + n, wv);
             } else if constexpr (EPI == EPI_ATOMIC) {
               unsafeAtomicAdd(Y + (size_t)m * p.ldy, acc[i][pp][v] + bias);
+            } else if constexpr (PR_NOST) {
+              asm volatile("" :: "v"(acc[i][pp][v] + bias));
             } else {
               Y[(size_t)m * p.ldy] = acc[i][pp][v] + bias;
             }

@@ -784,13 +784,16 @@ void HipStage::gemv(const PackedMat& m, int epi, const f16* X, int ldx, int M, f
     case GemmRoute::GEMM4: {
       // split-K shapes store per-split partials (into the residual x: absorbed by the next RMSNorm),
       // the rest run whole-K
-      const GemvParams p = mat_params(m, X, ldx, M, Y, ldy, H, ldh, n_valid);
+      GemvParams p = mat_params(m, X, ldx, M, Y, ldy, H, ldh, n_valid);
       const bool sk = opt_.gemm_splitk_store && sk_part_ && epi == EPI_ATOMIC && allow_split;
       const bool defer = sk && Y == sk_defer_;
       if (sk) flush_sk(st);
       int ns = 0;
-      if (sk && launch_gemm4_splitk(m.ptype, p, sk_part_, sk_part_n_, st, !defer, &ns)) {
+      if (sk_init_) p.bias = sk_init_bias_;
+      if (sk && launch_gemm4_splitk(m.ptype, p, sk_part_, sk_part_n_, st, !defer, &ns, sk_init_)) {
         if (defer) sk_pend_ = SkPending{Y, M, n_valid, ldy, ns, p.ntiles * 16, (int64_t)M * p.ntiles * 16};
+      } else if (sk_init_) {   // Y holds no fill to accumulate onto
+        throw std::runtime_error("gemv: the split-K plan took the partial-store route, the launch did not");
       } else {
         launch_gemm4(m.ptype, epi, p, st, allow_split && !opt_.deterministic);
       }
@@ -826,6 +829,14 @@ void HipStage::gemv(const PackedMat& m, int epi, const f16* X, int ldx, int M, f
     }
     launch_gemv(m.ptype, epi, p, nsplit, st);
   }
+}
+
+// Whether gemv(m, EPI_ATOMIC, M rows, allow_split) will store split-K partials and reduce them: the
+// launcher's own plan call and scratch bound (launch_gemm4_splitk)
+bool HipStage::splitk_store_route(const PackedMat& m, int M) const {
+  if (!opt_.gemm_splitk_store || !sk_part_ || gemm_route(m, EPI_ATOMIC, M, true) != GemmRoute::GEMM4) return false;
+  const Gemm4Plan pl = plan_gemm4(m.ptype, EPI_ATOMIC, M, (int)m.dims.ntiles, (int)m.dims.nsb, true, true);
+  return pl.ok && (size_t)pl.nsplit * M * m.dims.ntiles * 16 <= sk_part_n_;
 }
 
 void HipStage::flush_sk(hipStream_t st) {
@@ -1009,9 +1020,24 @@ void HipStage::layer_forward(int li, int M, float* x, const int32_t* pos, const 
       gemv(s.m, EPI_ATOMIC, nullptr, 0, M, qkv_ + s.y_off, qkv_n_, nullptr, 0, (int)s.m.dims.N, true, st, &e);
     }
   } else {
-    norm_x(x, L.attn_norm, M, qkv_, (int64_t)M * qkv_n_, st, L.qkv_bias, qkv_n_);
-    for (const MatSeg& s : L.qkv)
+    // When every qkv segment stores split-K partials, their reductions write q|k|v = bias + partials
+    // and the norm launch fills nothing; any other route accumulates onto the zero / bias fill
+    int covered = 0;
+    bool init = !L.qkv.empty();
+    for (const MatSeg& s : L.qkv) {
+      init = init && s.y_off == covered && splitk_store_route(s.m, M);
+      covered += (int)s.m.dims.N;
+    }
+    init = init && covered == qkv_n_;
+    if (init) norm_x(x, L.attn_norm, M, nullptr, 0, st);
+    else norm_x(x, L.attn_norm, M, qkv_, (int64_t)M * qkv_n_, st, L.qkv_bias, qkv_n_);
+    for (const MatSeg& s : L.qkv) {
+      sk_init_ = init;
+      sk_init_bias_ = init && L.qkv_bias ? L.qkv_bias + s.y_off : nullptr;
       gemv(s.m, EPI_ATOMIC, xn_, Kd_, M, qkv_ + s.y_off, qkv_n_, nullptr, 0, (int)s.m.dims.N, true, st);
+      sk_init_ = false;
+      sk_init_bias_ = nullptr;
+    }
   }
   qk_norm(L, M, st);
   attention(li, M, pos, kvlen, slot, decode, st, qkv_deferred);

@@ -217,6 +217,11 @@ class HipStage : public Stage {
   struct SkPending { float* x = nullptr; int M = 0, n = 0, ldy = 0, ns = 0, ldp = 0; int64_t ss = 0; };
   SkPending sk_pend_;
   float* sk_defer_ = nullptr;   // gemv(): ATOMIC GEMMs into this buffer defer their reduction
+  // gemv(): the split-K GEMM must take the partial-store route and its reduction writes Y = bias +
+  // partials (the caller left Y unfilled); sk_init_bias_: the bias of the GEMM's columns, or nullptr
+  bool sk_init_ = false;
+  const float* sk_init_bias_ = nullptr;
+  bool splitk_store_route(const PackedMat& m, int M) const;
   float* o_part_ = nullptr; float* ml_part_ = nullptr; int n_split_ = 1;
   int32_t* attn_cnt_ = nullptr;   // fused decode attention: split arrival counters
   // MoE scratch

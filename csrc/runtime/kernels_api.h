@@ -105,12 +105,13 @@ int gemm4_geometry_count();
 bool gemm4_has_geometry(int ptype, int bm, int nwv, int tw, bool moe);
 bool launch_gemm4(int ptype, int epi, GemvParams p, hipStream_t st, bool allow_split = true);
 bool launch_gemm4_splitk(int ptype, GemvParams p, float* scratch, size_t scratch_n, hipStream_t st,
-                         bool reduce = true, int* nsplit_out = nullptr);
+                         bool reduce = true, int* nsplit_out = nullptr, bool init = false);
 
 // Y[m][n] += sum_{s < nsplit} part[s][m][n], s ascending: the fixed-order split-K reduction of the
 // deterministic mode (part rows of ldp floats, splits split_stride floats apart)
+// init: Y[m][n] = (bias ? bias[n] : 0) + the same sum instead (Y is not read)
 void launch_splitk_reduce(const float* part, int nsplit, int64_t split_stride, int ldp, int M, int n, float* Y, int ldy,
-                          hipStream_t st);
+                          hipStream_t st, bool init = false, const float* bias = nullptr);
 
 // x f32 [M][ldx] -> out f16 [M][ldo] = rmsnorm(x) * w ; also zero `zero_n` floats at `zero`
 // `zero` is filled with 0, or with `bias` repeated every `bias_n` floats when bias != nullptr (the
