@@ -372,7 +372,7 @@ __global__ __launch_bounds__(1024) void argmax_kernel(const float* logits, int l
   if (threadIdx.x == 0) {
     for (int i = 1; i < 16; ++i)
       if (sv[i] > bv || (sv[i] == bv && si[i] < bi)) { bv = sv[i]; bi = si[i]; }
-    tok[blockIdx.x] = bi;
+    tok[blockIdx.x] = bi == 0x7fffffff ? 0 : bi;   // no comparable maximum (all -inf / NaN): token 0, as argmax2
   }
 }
 

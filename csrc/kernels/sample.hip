@@ -52,7 +52,7 @@ __global__ __launch_bounds__(ST) void sample_kernel(const SampleParams p) {
     __syncthreads();
     if (mx == gmx) atomicMin(&best, am);
     __syncthreads();
-    if (threadIdx.x == 0) p.tokens[row] = best;
+    if (threadIdx.x == 0) p.tokens[row] = best == 0x7fffffff ? 0 : best;   // all -inf / NaN: token 0, as argmax
     return;
   }
   const float invT = 1.f / p.temp;

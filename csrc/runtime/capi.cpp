@@ -424,6 +424,89 @@ int mp_op_rmsnorm(const void* x, int ldx, const void* w, int d, float eps, void*
   API_CATCH(-1)
 }
 
+// Test bindings of the row kernels (tests/test_row_kernels_gpu.py): each one is its launcher and
+// nothing else -- every buffer is the caller's, so a test can put canaries around what is written.
+int mp_op_rmsnorm_fill(const void* x, int ldx, const void* w, int d, float eps, void* out, int ldo, int M, void* zero,
+                       int64_t zero_n, const void* bias, int bias_n, void* stream) {
+  API_TRY
+  launch_rmsnorm((const float*)x, ldx, (const float*)w, d, eps, (f16*)out, ldo, M, (float*)zero, zero_n,
+                 (hipStream_t)stream, (const float*)bias, bias_n);
+  HIP_OK(hipGetLastError());
+  return 0;
+  API_CATCH(-1)
+}
+
+int mp_op_rmsnorm_acc(void* x, int ldx, const void* w, int d, float eps, void* out, int ldo, int M, void* zero,
+                      int64_t zero_n, const void* part, int nsplit, int64_t ss, int ldp, const void* bias, int bias_n,
+                      void* q8, int ldq8, void* q8s, void* stream) {
+  API_TRY
+  launch_rmsnorm_acc((float*)x, ldx, (const float*)w, d, eps, (f16*)out, ldo, M, (float*)zero, zero_n,
+                     (const float*)part, nsplit, ss, ldp, (hipStream_t)stream, (const float*)bias, bias_n, (int8_t*)q8,
+                     ldq8, (float*)q8s);
+  HIP_OK(hipGetLastError());
+  return 0;
+  API_CATCH(-1)
+}
+
+int mp_op_splitk_reduce(const void* part, int nsplit, int64_t ss, int ldp, int M, int n, void* Y, int ldy, int init,
+                        const void* bias, void* stream) {
+  API_TRY
+  launch_splitk_reduce((const float*)part, nsplit, ss, ldp, M, n, (float*)Y, ldy, (hipStream_t)stream, init != 0,
+                       (const float*)bias);
+  HIP_OK(hipGetLastError());
+  return 0;
+  API_CATCH(-1)
+}
+
+int mp_op_moe_combine(const void* ys, int lds, int k, int M, int n, void* Y, int ldy, void* stream) {
+  API_TRY
+  launch_moe_combine((const float*)ys, lds, k, M, n, (float*)Y, ldy, (hipStream_t)stream);
+  HIP_OK(hipGetLastError());
+  return 0;
+  API_CATCH(-1)
+}
+
+int mp_op_swiglu(const void* gu, int ld, int F, int M, void* h, int ldh, void* stream) {
+  API_TRY
+  launch_swiglu((const float*)gu, ld, F, M, (f16*)h, ldh, (hipStream_t)stream);
+  HIP_OK(hipGetLastError());
+  return 0;
+  API_CATCH(-1)
+}
+
+int mp_op_f32_to_f16(const void* x, int ldx, int n, int M, void* y, int ldy, void* stream) {
+  API_TRY
+  launch_f32_to_f16((const float*)x, ldx, n, M, (f16*)y, ldy, (hipStream_t)stream);
+  HIP_OK(hipGetLastError());
+  return 0;
+  API_CATCH(-1)
+}
+
+// dtype: ACT_F16 (1) or ACT_BF16 (2), the engine's "act_dtype" wire formats
+int mp_op_act_pack(const void* x, void* y, int64_t n, int dtype, void* stream) {
+  API_TRY
+  launch_act_pack((const float*)x, y, n, dtype, (hipStream_t)stream);
+  HIP_OK(hipGetLastError());
+  return 0;
+  API_CATCH(-1)
+}
+
+int mp_op_act_unpack(const void* y, void* x, int64_t n, int dtype, void* stream) {
+  API_TRY
+  launch_act_unpack(y, (float*)x, n, dtype, (hipStream_t)stream);
+  HIP_OK(hipGetLastError());
+  return 0;
+  API_CATCH(-1)
+}
+
+int mp_op_advance(void* pos, void* kvlen, int M, void* step, void* stream) {
+  API_TRY
+  launch_advance((int32_t*)pos, (int32_t*)kvlen, M, (int32_t*)step, (hipStream_t)stream);
+  HIP_OK(hipGetLastError());
+  return 0;
+  API_CATCH(-1)
+}
+
 int mp_op_embed(int type, const void* table, int64_t row_bytes, int d, const void* tokens, int M, void* x, int ldx,
                 void* stream) {
   API_TRY

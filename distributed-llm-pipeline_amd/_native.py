@@ -70,6 +70,18 @@ _SIGS = {
     "mp_reset_knob": ([c_char_p], c_int),
     "mp_op_unpack": ([c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p], c_int),
     "mp_op_rmsnorm": ([c_void_p, c_int, c_void_p, c_int, c_float, c_void_p, c_int, c_int, c_void_p], c_int),
+    "mp_op_rmsnorm_fill": ([c_void_p, c_int, c_void_p, c_int, c_float, c_void_p, c_int, c_int, c_void_p, c_int64,
+                            c_void_p, c_int, c_void_p], c_int),
+    "mp_op_rmsnorm_acc": ([c_void_p, c_int, c_void_p, c_int, c_float, c_void_p, c_int, c_int, c_void_p, c_int64,
+                           c_void_p, c_int, c_int64, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p], c_int),
+    "mp_op_splitk_reduce": ([c_void_p, c_int, c_int64, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p,
+                             c_void_p], c_int),
+    "mp_op_moe_combine": ([c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p], c_int),
+    "mp_op_swiglu": ([c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p], c_int),
+    "mp_op_f32_to_f16": ([c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p], c_int),
+    "mp_op_act_pack": ([c_void_p, c_void_p, c_int64, c_int, c_void_p], c_int),
+    "mp_op_act_unpack": ([c_void_p, c_void_p, c_int64, c_int, c_void_p], c_int),
+    "mp_op_advance": ([c_void_p, c_void_p, c_int, c_void_p, c_void_p], c_int),
     "mp_op_embed": ([c_int, c_void_p, c_int64, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p], c_int),
     "mp_op_rope_kv": ([c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int,
                        c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_int, c_void_p], c_int),

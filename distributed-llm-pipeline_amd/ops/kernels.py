@@ -305,6 +305,61 @@ def rmsnorm(x: torch.Tensor, w: torch.Tensor, eps: float, k_pad: int | None = No
     return out
 
 
+# Raw bindings of the row kernels for the kernel tests: every tensor is the caller's (nothing is
+# allocated here), shapes are explicit, and a launcher's own argument check surfaces as RuntimeError.
+ACT_F16, ACT_BF16 = 1, 2
+
+
+def rmsnorm_fill(x, ldx, w, d, eps, out, ldo, M, zero=None, zero_n=0, bias=None, bias_n=0) -> None:
+    """launch_rmsnorm: out f16 [M][ldo] = norm(x f32 [M][ldx]) * w; the same launch clears zero[:zero_n]
+    (or, with bias, sets zero[i] = bias[i % bias_n])."""
+    N.check(N.lib().mp_op_rmsnorm_fill(_ptr(x), ldx, _ptr(w), d, eps, _ptr(out), ldo, M, _ptr(zero), zero_n,
+                                       _ptr(bias), bias_n, _stream()), "rmsnorm_fill")
+
+
+def rmsnorm_acc(x, ldx, w, d, eps, out, ldo, M, zero=None, zero_n=0, part=None, nsplit=0, ss=0, ldp=0, bias=None,
+                bias_n=0, q8=None, ldq8=0, q8s=None) -> None:
+    """launch_rmsnorm_acc: x += part[0] + ... + part[nsplit - 1] (split s at part + s * ss, rows ldp
+    apart) is written back, then normalised as rmsnorm_fill; q8 / q8s: the f16 row also as int8 + scale."""
+    N.check(N.lib().mp_op_rmsnorm_acc(_ptr(x), ldx, _ptr(w), d, eps, _ptr(out), ldo, M, _ptr(zero), zero_n, _ptr(part),
+                                      nsplit, ss, ldp, _ptr(bias), bias_n, _ptr(q8), ldq8, _ptr(q8s), _stream()),
+            "rmsnorm_acc")
+
+
+def splitk_reduce(part, nsplit, ss, ldp, M, n, y, ldy, init=False, bias=None) -> None:
+    """y[m][j] (+)= sum_s part[s * ss + m * ldp + j] in split order; init: y starts from bias[j] or 0."""
+    N.check(N.lib().mp_op_splitk_reduce(_ptr(part), nsplit, ss, ldp, M, n, _ptr(y), ldy, int(init), _ptr(bias),
+                                        _stream()), "splitk_reduce")
+
+
+def moe_combine(ys, lds, k, M, n, y, ldy) -> None:
+    """y[t][j] += sum_{e < k} ys[(t * k + e) * lds + j], e ascending."""
+    N.check(N.lib().mp_op_moe_combine(_ptr(ys), lds, k, M, n, _ptr(y), ldy, _stream()), "moe_combine")
+
+
+def swiglu(gu, ld, F, M, h, ldh) -> None:
+    """h f16 [M][ldh] = sat_f16(silu(gu[m][j]) * gu[m][F + j]) for j < F (gu f32 [M][ld])."""
+    N.check(N.lib().mp_op_swiglu(_ptr(gu), ld, F, M, _ptr(h), ldh, _stream()), "swiglu")
+
+
+def f32_to_f16(x, ldx, n, M, y, ldy) -> None:
+    N.check(N.lib().mp_op_f32_to_f16(_ptr(x), ldx, n, M, _ptr(y), ldy, _stream()), "f32_to_f16")
+
+
+def act_pack(x, y, n, dtype) -> None:
+    """Stage-boundary wire format: n f32 elements of x -> f16 / bf16 (ACT_F16 / ACT_BF16) in y."""
+    N.check(N.lib().mp_op_act_pack(_ptr(x), _ptr(y), n, dtype, _stream()), "act_pack")
+
+
+def act_unpack(y, x, n, dtype) -> None:
+    N.check(N.lib().mp_op_act_unpack(_ptr(y), _ptr(x), n, dtype, _stream()), "act_unpack")
+
+
+def advance(pos, kvlen, M, step=None) -> None:
+    """Decode-step advance: pos[i] += 1, kvlen[i] = pos[i] + 1 for i < M; step[0] += 1 when given."""
+    N.check(N.lib().mp_op_advance(_ptr(pos), _ptr(kvlen), M, _ptr(step), _stream()), "advance")
+
+
 def embed(raw_table: torch.Tensor, ggml_type: int, d: int, tokens: torch.Tensor) -> torch.Tensor:
     M = tokens.numel()
     x = torch.empty(M, d, dtype=torch.float32, device=tokens.device)
