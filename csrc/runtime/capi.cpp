@@ -23,6 +23,7 @@
 #include "kernels_api.h"
 #include "log.h"
 #include "pack.h"
+#include "perplexity.h"
 #include "tokenizer.h"
 #include "transport.h"
 
@@ -720,6 +721,47 @@ int mp_op_sample(const void* logits, int ld, int n, int M, float temp, int top_k
   API_CATCH(-1)
 }
 
+int mp_op_logprob(const void* logits, int ld, int n, int M, const void* target, int top_n, void* lse, void* target_lp,
+                  void* top_id, void* top_lp, int ld_top, void* stream) {
+  API_TRY
+  LogprobParams p{};
+  p.logits = (const float*)logits; p.ld = ld; p.n = n; p.M = M; p.target = (const int32_t*)target; p.top_n = top_n;
+  p.lse = (float*)lse; p.target_lp = (float*)target_lp; p.top_id = (int32_t*)top_id; p.top_lp = (float*)top_lp;
+  p.ld_top = ld_top;
+  launch_logprob(p, (hipStream_t)stream);
+  HIP_OK(hipGetLastError());
+  return 0;
+  API_CATCH(-1)
+}
+
+// the generation pair: stats (+ raw logits of the penalty window) before the penalties, the chosen
+// token's logprob after the sampler
+int mp_op_logprob_chosen(const void* logits, int ld, int n, int M, const void* tokens, const void* lse, const void* hist,
+                         int last_n, const void* hist_raw, void* chosen_lp, void* stream) {
+  API_TRY
+  LogprobChosenParams p{};
+  p.logits = (const float*)logits; p.ld = ld; p.n = n; p.M = M; p.tokens = (const int32_t*)tokens;
+  p.lse = (const float*)lse; p.hist = (const int32_t*)hist; p.last_n = last_n; p.hist_raw = (const float*)hist_raw;
+  p.chosen_lp = (float*)chosen_lp;
+  launch_logprob_chosen(p, (hipStream_t)stream);
+  HIP_OK(hipGetLastError());
+  return 0;
+  API_CATCH(-1)
+}
+
+int mp_op_logprob_stats(const void* logits, int ld, int n, int M, int top_n, void* lse, void* top_id, void* top_lp,
+                        int ld_top, const void* hist, int last_n, void* hist_raw, void* stream) {
+  API_TRY
+  LogprobParams p{};
+  p.logits = (const float*)logits; p.ld = ld; p.n = n; p.M = M; p.top_n = top_n; p.lse = (float*)lse;
+  p.top_id = (int32_t*)top_id; p.top_lp = (float*)top_lp; p.ld_top = ld_top;
+  p.hist = (const int32_t*)hist; p.last_n = last_n; p.hist_raw = (float*)hist_raw;
+  launch_logprob(p, (hipStream_t)stream);
+  HIP_OK(hipGetLastError());
+  return 0;
+  API_CATCH(-1)
+}
+
 int mp_op_penalize(void* logits, int ld, int n, int M, const void* hist, int last_n, float repeat, float freq,
                    float presence, void* stream) {
   API_TRY
@@ -777,6 +819,13 @@ int mp_tok_info(void* h, int32_t* out) {  // vocab, bos, eos, eot
   auto* t = static_cast<Tokenizer*>(h);
   out[0] = t->n_vocab(); out[1] = t->bos(); out[2] = t->eos(); out[3] = t->eot();
   return 0;
+  API_CATCH(-1)
+}
+// 1 when the vocabulary puts BOS in front of a prompt by default (tokenizer.ggml.add_bos_token)
+int mp_tok_add_bos(void* h) {
+  API_TRY
+  if (!h) throw std::runtime_error("tokenizer handle is null");
+  return static_cast<Tokenizer*>(h)->add_bos_default() ? 1 : 0;
   API_CATCH(-1)
 }
 // pre-tokenizer split (tests): returns pieces joined by '\x1f'
@@ -932,6 +981,73 @@ int mp_engine_tokens(void* h, int32_t* out, int n_seq, int cap) {
     for (int j = 0; j < cap; ++j) out[(size_t)i * cap + j] = j < (int)t[i].size() ? t[i][j] : -1;
   }
   return n;
+  API_CATCH(-1)
+}
+// log-probabilities of the generated tokens (engine config n_probs != 0), aligned with
+// mp_engine_tokens: lp[n_seq][cap] (NaN past a sequence's tokens), top_id / top_lp
+// [n_seq][cap][n_top] with n_top = max(n_probs, 0) (null allowed when n_top = 0).  Returns the
+// longest sequence's token count.
+int mp_engine_logprobs(void* h, float* lp, int32_t* top_id, float* top_lp, int n_seq, int cap) {
+  API_TRY
+  Engine* e = static_cast<Engine*>(h);
+  const auto& g = e->logprobs();
+  const int nt = e->n_top();
+  int n = 0;
+  for (int i = 0; i < n_seq && i < (int)g.size(); ++i) {
+    const int have = (int)g[i].lp.size();
+    n = std::max(n, std::min(cap, have));
+    for (int j = 0; j < cap; ++j) {
+      lp[(size_t)i * cap + j] = j < have ? g[i].lp[j] : NAN;
+      for (int k = 0; k < nt && top_id && top_lp; ++k) {
+        top_id[((size_t)i * cap + j) * nt + k] = j < have ? g[i].top_id[(size_t)j * nt + k] : -1;
+        top_lp[((size_t)i * cap + j) * nt + k] = j < have ? g[i].top_lp[(size_t)j * nt + k] : NAN;
+      }
+    }
+  }
+  return n;
+  API_CATCH(-1)
+}
+// prompt scoring: prompts as in mp_engine_start; lp holds, prompt after prompt, the len - 1 values
+// log p(prompt[t + 1] | prompt[:t + 1]); top_id / top_lp the n_top alternatives per position
+// ([sum(len - 1)][n_top], null allowed when n_top = 0)
+int mp_engine_score(void* h, const int32_t* prompt_tokens, const int32_t* lens, int n_seq, int n_top, float* lp,
+                    int32_t* top_id, float* top_lp) {
+  API_TRY
+  std::vector<std::vector<int32_t>> prompts;
+  size_t off = 0;
+  for (int i = 0; i < n_seq; ++i) {
+    prompts.emplace_back(prompt_tokens + off, prompt_tokens + off + lens[i]);
+    off += lens[i];
+  }
+  if (n_top > 0 && (!top_id || !top_lp)) throw std::runtime_error("score: top-n buffers missing");
+  std::vector<Engine::SeqLogprobs> out;
+  static_cast<Engine*>(h)->score(prompts, n_top, &out);
+  size_t o = 0;
+  for (const auto& s : out) {
+    std::copy(s.lp.begin(), s.lp.end(), lp + o);
+    if (n_top > 0) {
+      std::copy(s.top_id.begin(), s.top_id.end(), top_id + o * n_top);
+      std::copy(s.top_lp.begin(), s.top_lp.end(), top_lp + o * n_top);
+    }
+    o += s.lp.size();
+  }
+  return 0;
+  API_CATCH(-1)
+}
+// the --perplexity procedure's helpers (perplexity.h) for tests and Python callers.
+// mp_ppl_windows: the number of n_ctx-token windows of a stream, -1 when it has fewer than 2 * n_ctx
+// tokens.  mp_ppl_estimate: lp = [n_windows][n_ctx - 1] window scores -> out4 = {mean NLL, PPL, +-,
+// positions counted}
+long mp_ppl_windows(long n_tokens, int n_ctx) {
+  return ppl_enough_tokens((size_t)std::max(0L, n_tokens), n_ctx) ? ppl_n_windows((size_t)n_tokens, n_ctx) : -1;
+}
+int mp_ppl_estimate(const float* lp, int n_windows, int n_ctx, double* out4) {
+  API_TRY
+  if (n_ctx < 2) throw std::runtime_error("perplexity: n_ctx must be at least 2");
+  PplEstimate est;
+  for (int w = 0; w < n_windows; ++w) est.add_window(lp + (size_t)w * (n_ctx - 1), n_ctx);
+  out4[0] = est.mean_nll(); out4[1] = est.ppl(); out4[2] = est.err(); out4[3] = (double)est.count;
+  return 0;
   API_CATCH(-1)
 }
 // debug: logits of the last decode/prefill of a micro-batch (last stage, rank-local)

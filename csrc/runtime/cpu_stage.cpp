@@ -549,13 +549,72 @@ void CpuStage::set_history(int mb, const std::vector<std::vector<int32_t>>& seqs
   }
 }
 
+// Host counterpart of logprob_kernel (logprob.hip), accumulated in double: the row's log-sum-exp
+// (NaN counts as -inf; -inf without a finite maximum) and its top_n (id, logprob) by descending
+// logit, ties to the lower id, -1 / -inf past the finite entries.
+static double row_logprob(const float* lg, int n, int top_n, int32_t* top_id, float* top_lp) {
+  auto val = [&](int i) { return lg[i] == lg[i] ? lg[i] : -INFINITY; };
+  float mx = -INFINITY;
+  for (int i = 0; i < n; ++i) mx = std::max(mx, val(i));
+  const bool dead = !std::isfinite(mx);
+  double s = 0;
+  if (!dead)
+    for (int i = 0; i < n; ++i) s += std::exp((double)val(i) - (double)mx);
+  const double lse = dead ? -INFINITY : (double)mx + std::log(s);
+  if (top_n > 0) {
+    std::vector<int32_t> ids;
+    if (!dead)
+      for (int i = 0; i < n; ++i)
+        if (val(i) > -INFINITY) ids.push_back(i);
+    const size_t k = std::min(ids.size(), (size_t)top_n);
+    std::partial_sort(ids.begin(), ids.begin() + k, ids.end(),
+                      [&](int32_t a, int32_t b) { return lg[a] > lg[b] || (lg[a] == lg[b] && a < b); });
+    for (int j = 0; j < top_n; ++j) {
+      top_id[j] = (size_t)j < k ? ids[j] : -1;
+      top_lp[j] = (size_t)j < k ? (float)((double)lg[ids[j]] - lse) : -INFINITY;
+    }
+  }
+  return lse;
+}
+
+void CpuStage::set_score_targets(int mb, const int32_t* host, int n, int top_n) {
+  if (!spec_.last()) return;
+  if (n > opt_.prefill_chunk || top_n < 0 || top_n > kMaxProbs) throw std::runtime_error("set_score_targets: bad size");
+  if (sc_tgt_.size() < (size_t)opt_.n_mb) {
+    sc_tgt_.resize(opt_.n_mb); sc_lp_.resize(opt_.n_mb); sc_top_id_.resize(opt_.n_mb); sc_top_lp_.resize(opt_.n_mb);
+  }
+  sc_tgt_[mb].assign(host, host + n);
+  sc_top_n_ = top_n;
+}
+
+void CpuStage::copy_scores(int mb, int n, float* target_lp, int32_t* top_id, float* top_lp) {
+  if ((size_t)mb >= sc_lp_.size() || (int)sc_lp_[mb].size() < n) throw std::runtime_error("no scores");
+  std::memcpy(target_lp, sc_lp_[mb].data(), (size_t)n * 4);
+  if (sc_top_n_ > 0 && top_id && top_lp) {
+    std::memcpy(top_id, sc_top_id_[mb].data(), (size_t)n * sc_top_n_ * 4);
+    std::memcpy(top_lp, sc_top_lp_[mb].data(), (size_t)n * sc_top_n_ * 4);
+  }
+}
+
 void CpuStage::head(int mb, int M, const float* x, int32_t* tok_out, uint64_t salt) {
   rmsnorm(x, out_norm_, xn_.data(), M);
   matmul(out_, xn_.data(), cfg_.d_model, M, logits_.data(), cfg_.vocab, false);
   const bool pen = penalties_on();
   if (pen && hist_.empty()) hist_.resize((size_t)opt_.n_mb * opt_.mb_size);
+  // token logprobs: log-softmax of the RAW logits (before the in-place penalty), Stage::logprob_rec layout
+  const bool lp = n_probs_ != 0;
+  const int B = opt_.mb_size, top_n = std::max(n_probs_, 0);
+  if (lp && lp_rec_.size() < (size_t)opt_.n_mb) lp_rec_.assign(opt_.n_mb, std::vector<uint32_t>(logprob_rec_words(B), 0xFFFFFFFFu));
+  std::unordered_map<int32_t, float> raw;   // raw logits of the ids the penalty rewrites
   for (int m = 0; m < M; ++m) {
     float* lg = logits_.data() + (size_t)m * cfg_.vocab;
+    double lse = 0;
+    if (lp) {
+      uint32_t* rec = lp_rec_[mb].data();
+      lse = row_logprob(lg, cfg_.vocab, top_n, reinterpret_cast<int32_t*>(rec + B) + (size_t)m * kMaxProbs,
+                        reinterpret_cast<float*>(rec + B + (size_t)B * kMaxProbs) + (size_t)m * kMaxProbs);
+      raw.clear();
+    }
     std::vector<int32_t>* h = pen ? &hist_[(size_t)mb * opt_.mb_size + m] : nullptr;
     if (pen) {
       std::unordered_map<int32_t, int> cnt;
@@ -563,11 +622,22 @@ void CpuStage::head(int mb, int M, const float* x, int32_t* tok_out, uint64_t sa
       for (const auto& [t, c] : cnt) {
         if (t < 0 || t >= cfg_.vocab) continue;
         float l = lg[t];
+        if (lp) raw[t] = l;
         l = l > 0.f ? l / pen_repeat_ : l * pen_repeat_;
         lg[t] = l - (float)c * pen_freq_ - pen_presence_;
       }
     }
     tok_out[m] = sample_row(lg, salt, m);
+    if (lp) {
+      const int32_t t = tok_out[m];
+      float v = -INFINITY;
+      if (t >= 0 && t < cfg_.vocab && std::isfinite(lse)) {
+        const auto it = raw.find(t);
+        const float r = it != raw.end() ? it->second : lg[t];
+        if (r == r) v = (float)((double)r - lse);
+      }
+      reinterpret_cast<float*>(lp_rec_[mb].data())[m] = v;
+    }
     if (pen) {
       h->push_back(tok_out[m]);
       if ((int)h->size() > pen_last_n_) h->erase(h->begin());
@@ -608,6 +678,22 @@ void CpuStage::prefill(int mb, const std::vector<PrefillSeg>& segs, hipStream_t)
     for (int m = 0; m < T; ++m) {
       const float* r = lg.data() + (size_t)m * cfg_.vocab;
       vtok_[mb][m] = (int32_t)(std::max_element(r, r + cfg_.vocab) - r);
+    }
+  } else if (spec_.last() && !segs.empty() && segs[0].score) {
+    // prompt scoring: the log-probability of each row's target token (and the top-n)
+    if ((size_t)mb >= sc_tgt_.size() || (int)sc_tgt_[mb].size() < T) throw std::runtime_error("score chunk without targets");
+    std::vector<float> xn((size_t)T * d), lg((size_t)T * cfg_.vocab);
+    rmsnorm(x, out_norm_, xn.data(), T);
+    matmul(out_, xn.data(), d, T, lg.data(), cfg_.vocab, false);
+    sc_lp_[mb].assign(T, -INFINITY);
+    sc_top_id_[mb].assign((size_t)T * sc_top_n_, -1);
+    sc_top_lp_[mb].assign((size_t)T * sc_top_n_, -INFINITY);
+    for (int m = 0; m < T; ++m) {
+      const float* r = lg.data() + (size_t)m * cfg_.vocab;
+      const double lse = row_logprob(r, cfg_.vocab, sc_top_n_, sc_top_id_[mb].data() + (size_t)m * sc_top_n_,
+                                     sc_top_lp_[mb].data() + (size_t)m * sc_top_n_);
+      const int32_t t = sc_tgt_[mb][m];
+      if (t >= 0 && t < cfg_.vocab && std::isfinite(lse) && r[t] == r[t]) sc_lp_[mb][m] = (float)((double)r[t] - lse);
     }
   } else if (spec_.last()) {
     int row = 0;

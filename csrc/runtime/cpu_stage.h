@@ -44,6 +44,11 @@ class CpuStage : public Stage {
   void prefill(int mb, const std::vector<PrefillSeg>& segs, hipStream_t st) override;
   void prefill_finish(int mb, hipStream_t st, const std::vector<int>* rows = nullptr) override;
   void copy_verify_tokens(int mb, int32_t* host, int n) override;
+  const void* logprob_rec(int mb) const override {
+    return n_probs_ != 0 && (size_t)mb < lp_rec_.size() ? lp_rec_[mb].data() : nullptr;
+  }
+  void set_score_targets(int mb, const int32_t* host, int n, int top_n) override;
+  void copy_scores(int mb, int n, float* target_lp, int32_t* top_id, float* top_lp) override;
   void decode(int mb, hipStream_t st) override;
   const float* logits_ptr() const override { return logits_.data(); }
   int logits_ld() const override { return cfg_.vocab; }
@@ -97,6 +102,11 @@ class CpuStage : public Stage {
   std::vector<std::vector<int32_t>> tok_, pos_;
   std::vector<int32_t> prompt_;
   std::vector<std::vector<float>> last_h_;   // last stage: [mb][B][d] final prompt rows
+  std::vector<std::vector<uint32_t>> lp_rec_;   // last stage, n_probs != 0: [mb] record words (Stage::logprob_rec)
+  std::vector<std::vector<int32_t>> sc_tgt_;    // prompt scoring: [mb] targets, then results of the chunk
+  std::vector<std::vector<float>> sc_lp_, sc_top_lp_;
+  std::vector<std::vector<int32_t>> sc_top_id_;
+  int sc_top_n_ = 0;
   std::vector<std::vector<int32_t>> vtok_;   // last stage: [mb][rows] greedy tokens of a verify chunk
   std::vector<float> logits_;
   // scratch

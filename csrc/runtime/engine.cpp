@@ -406,6 +406,9 @@ Engine::Engine(const Json& j) : jcfg_(j) {
   so.moe_gemm = j.get_bool("moe_gemm", true);
   packed_prefill_ = j.get_bool("packed_prefill", true);
   prefix_cache_ = j.get_bool("prefix_cache", true);
+  n_probs_ = j.get_int("n_probs", 0);
+  if (n_probs_ < -1 || n_probs_ > Stage::kMaxProbs)
+    throw std::runtime_error("n_probs must be -1 (chosen token only) or 0.." + std::to_string(Stage::kMaxProbs));
 
   // ---- stages this process owns
   for (int s = 0; s < S_; ++s) {
@@ -426,6 +429,7 @@ Engine::Engine(const Json& j) : jcfg_(j) {
                            (float)j.get_num("min_p", 0.0), seed);
     w->stage->set_penalties(j.get_int("repeat_last_n", 64), (float)j.get_num("repeat_penalty", 1.0),
                             (float)j.get_num("frequency_penalty", 0.0), (float)j.get_num("presence_penalty", 0.0));
+    if (n_probs_ != 0) w->stage->set_n_probs(n_probs_);
     if (w->cpu) {
       w->ring_pending.assign(M_, false);
       workers_.push_back(std::move(w));
@@ -493,6 +497,17 @@ Engine::Engine(const Json& j) : jcfg_(j) {
     HIP_OK(hipHostMalloc((void**)&out_host_, (size_t)rounds_cap_ * M_ * B_ * 4, hipHostMallocDefault));
   }
   std::memset(out_host_, 0xff, (size_t)rounds_cap_ * M_ * B_ * 4);
+  if (n_probs_ != 0) {   // the rounds' logprob records travel beside the tokens
+    lp_words_ = Stage::logprob_rec_words(B_);
+    const size_t words = (size_t)rounds_cap_ * M_ * lp_words_;
+    if (cpu_) {
+      lp_vec_.resize(words);
+      lp_host_ = lp_vec_.data();
+    } else {
+      HIP_OK(hipHostMalloc((void**)&lp_host_, words * 4, hipHostMallocDefault));
+    }
+    std::memset(lp_host_, 0xff, words * 4);
+  }
   load_ms_ = now_ms() - t0;
   MP_LOGI("engine ready: %d stage(s), %d micro-batch(es) x %d seq, ctx %d, load %.1f ms", S_, M_, B_, max_ctx_,
           load_ms_);
@@ -522,6 +537,7 @@ Engine::~Engine() {
   }
   links_.clear();
   if (out_host_ && !cpu_) (void)hipHostFree(out_host_);
+  if (lp_host_ && !cpu_) (void)hipHostFree(lp_host_);
 }
 
 bool Engine::owns_last() const {
@@ -725,6 +741,7 @@ void Engine::run_items_cpu(Worker& w, const std::vector<Item>& items) {
         if (last) {
           span(w, nullptr, 0, "prefill_head mb" + std::to_string(mb), [&] { st.prefill_finish(mb, nullptr, it.rows.empty() ? nullptr : &it.rows); });
           std::memcpy(out_host_ + (size_t)mb * B_, st.tokens(mb), (size_t)B_ * 4);
+          if (lp_host_) std::memcpy(lp_host_ + (size_t)mb * lp_words_, st.logprob_rec(mb), lp_words_ * 4);
         }
         if (S_ > 1) {
           if (last) send(mb, st.tokens(mb), (size_t)B_ * 4, "tok");
@@ -742,6 +759,8 @@ void Engine::run_items_cpu(Worker& w, const std::vector<Item>& items) {
         if (last) {
           w.tok_t.push_back(now_ms());
           std::memcpy(out_host_ + ((size_t)((it.round + 1) % rounds_cap_) * M_ + mb) * B_, st.tokens(mb), (size_t)B_ * 4);
+          if (lp_host_)
+            std::memcpy(lp_host_ + ((size_t)((it.round + 1) % rounds_cap_) * M_ + mb) * lp_words_, st.logprob_rec(mb), lp_words_ * 4);
         }
         if (S_ > 1) {
           if (!last) send(mb, st.act(mb), (size_t)B_ * d4, "act");
@@ -836,6 +855,8 @@ void Engine::run_items(Worker& w, const std::vector<Item>& items) {
           span(w, cs, 0, "prefill_head mb" + std::to_string(mb), [&] { st.prefill_finish(mb, cs, it.rows.empty() ? nullptr : &it.rows); });
           HIP_OK(hipMemcpyAsync(out_host_ + (size_t)mb * B_, st.tokens(mb), (size_t)B_ * 4, hipMemcpyDeviceToHost,
                                 cs));
+          if (lp_host_)
+            HIP_OK(hipMemcpyAsync(lp_host_ + (size_t)mb * lp_words_, st.logprob_rec(mb), lp_words_ * 4, hipMemcpyDeviceToHost, cs));
         }
         if (S_ > 1) {
           if (last) send_from(mb, st.tokens(mb), (size_t)B_ * 4);
@@ -853,6 +874,9 @@ void Engine::run_items(Worker& w, const std::vector<Item>& items) {
           if (ev_i < w.tok_ev.size()) HIP_OK(hipEventRecord(w.tok_ev[ev_i], cs));
           HIP_OK(hipMemcpyAsync(out_host_ + ((size_t)((it.round + 1) % rounds_cap_) * M_ + mb) * B_, st.tokens(mb), (size_t)B_ * 4,
                                 hipMemcpyDeviceToHost, cs));
+          if (lp_host_)
+            HIP_OK(hipMemcpyAsync(lp_host_ + ((size_t)((it.round + 1) % rounds_cap_) * M_ + mb) * lp_words_, st.logprob_rec(mb),
+                                  lp_words_ * 4, hipMemcpyDeviceToHost, cs));
         }
         if (S_ > 1) {
           if (!last) send_act(mb, st.act(mb), (size_t)B_ * d4);
@@ -1104,6 +1128,7 @@ void Engine::start(const std::vector<std::vector<int32_t>>& prompts) {
   if ((int)prompts.size() > M_ * B_) throw std::runtime_error("more prompts than micro-batch slots");
   prompts_ = prompts;
   gen_.assign(prompts.size(), {});
+  gen_lp_.assign(prompts.size(), {});
   rounds_done_ = 0;
   resumable_ = true;
   base_round_.assign((size_t)M_ * B_, 0);
@@ -1152,7 +1177,10 @@ void Engine::start(const std::vector<std::vector<int32_t>>& prompts) {
   run_all(items);
   started_ = true;
   if (owns_last())
-    for (size_t i = 0; i < prompts.size(); ++i) gen_[i].push_back(out_host_[i]);
+    for (size_t i = 0; i < prompts.size(); ++i) {
+      gen_[i].push_back(out_host_[i]);
+      take_logprobs(i, 0);
+    }
   slot_toks_ = prompts;
 }
 
@@ -1486,6 +1514,7 @@ void Engine::admit(const std::vector<int>& slots, const std::vector<std::vector<
   if (slots.size() != prompts.size()) throw std::runtime_error("admit: one prompt per slot");
   const size_t NS = (size_t)M_ * B_;
   if (prompts_.size() < NS) { prompts_.resize(NS); gen_.resize(NS); }
+  gen_lp_.resize(gen_.size());
   base_round_.resize(NS, 0);
   active_.resize(NS, 0);
   std::vector<size_t> seqs;
@@ -1498,6 +1527,7 @@ void Engine::admit(const std::vector<int>& slots, const std::vector<std::vector<
     kv_grant((size_t)i, (int)prompts[k].size() + 1);
     prompts_[i] = prompts[k];
     gen_[i].clear();
+    gen_lp_[i] = {};
     base_round_[i] = rounds_done_;
     active_[i] = 1;
     seqs.push_back((size_t)i);
@@ -1520,7 +1550,10 @@ void Engine::admit(const std::vector<int>& slots, const std::vector<std::vector<
   slot_toks_.clear();
   run_all(items);
   if (owns_last())
-    for (size_t i : seqs) gen_[i].push_back(out_host_[i]);
+    for (size_t i : seqs) {
+      gen_[i].push_back(out_host_[i]);
+      take_logprobs(i, 0);
+    }
   // the head pushed a token into the penalty window of every row of these micro-batches: re-seed
   // them from the host (prompt + accepted tokens)
   for (auto& w : workers_)
@@ -1594,6 +1627,9 @@ StepStats Engine::decode_steps(int k) {
       for (size_t i = 0; i < prompts_.size(); ++i) {
         const int32_t t = out_host_[(size_t)((rounds_done_ + r + 1) % rounds_cap_) * M_ * B_ + i];
         gen_[i].push_back(t);
+        // (released slots too, like their tokens just above: gen_lp_ stays aligned with gen_, which is
+        // what logprobs() checks; admit() resets both when the slot gets its next sequence)
+        take_logprobs(i, (size_t)((rounds_done_ + r + 1) % rounds_cap_));
         if (on_token) on_token((int)i, t);
       }
   rounds_done_ += k;
@@ -1602,6 +1638,136 @@ StepStats Engine::decode_steps(int k) {
 }
 
 std::vector<std::vector<int32_t>> Engine::tokens() const { return gen_; }
+
+// sequence i's record of the round stored at ring slot `round_slot` -> gen_lp_[i]
+void Engine::take_logprobs(size_t i, size_t round_slot) {
+  if (!lp_host_) return;
+  if (gen_lp_.size() <= i) gen_lp_.resize(i + 1);
+  const size_t mb = i / B_, b = i % B_;
+  const uint32_t* rec = lp_host_ + (round_slot * M_ + mb) * lp_words_;
+  const float* chosen = reinterpret_cast<const float*>(rec);
+  const int32_t* ids = reinterpret_cast<const int32_t*>(rec + B_) + b * Stage::kMaxProbs;
+  const float* lps = reinterpret_cast<const float*>(rec + B_ + (size_t)B_ * Stage::kMaxProbs) + b * Stage::kMaxProbs;
+  SeqLogprobs& g = gen_lp_[i];
+  g.lp.push_back(chosen[b]);
+  g.top_id.insert(g.top_id.end(), ids, ids + n_top());
+  g.top_lp.insert(g.top_lp.end(), lps, lps + n_top());
+}
+
+bool Engine::last_logprob(int slot, float* lp, std::vector<int32_t>* top_id, std::vector<float>* top_lp) const {
+  if (n_probs_ == 0 || slot < 0 || (size_t)slot >= gen_lp_.size() || (size_t)slot >= gen_.size()) return false;
+  const SeqLogprobs& g = gen_lp_[slot];
+  if (g.lp.empty() || g.lp.size() != gen_[slot].size()) return false;
+  const size_t nt = (size_t)n_top();
+  *lp = g.lp.back();
+  if (top_id) top_id->assign(g.top_id.end() - nt, g.top_id.end());
+  if (top_lp) top_lp->assign(g.top_lp.end() - nt, g.top_lp.end());
+  return true;
+}
+
+const std::vector<Engine::SeqLogprobs>& Engine::logprobs() const {
+  if (n_probs_ == 0) throw std::runtime_error("logprobs: the engine was built with n_probs = 0");
+  if (!owns_last()) throw std::runtime_error("logprobs live where the last stage does");
+  for (size_t i = 0; i < gen_.size(); ++i)
+    if (i >= gen_lp_.size() || gen_lp_[i].lp.size() != gen_[i].size())
+      throw std::runtime_error("logprobs were not recorded for every token (speculative decoding and restored "
+                               "checkpoints do not record them)");
+  return gen_lp_;
+}
+
+// Prompt scoring.  Each pass sends at most one packed chunk per micro-batch through the pipeline
+// on the prefill path (rows of several prompts in one chunk, prompts spanning chunks), with the
+// last stage keeping log p(next token) per row; the targets of a chunk are uploaded to the last
+// stage before the pass and the rows' results read back after it (the verify-chunk pattern of
+// spec_generate).  The last token of a prompt has no target and is not sent.
+void Engine::score(const std::vector<std::vector<int32_t>>& prompts, int n_top, std::vector<SeqLogprobs>* out) {
+  if (mode_ == "mp" && S_ > 1)
+    throw std::runtime_error("score: needs every stage in this process (mode \"mp\" is not supported)");
+  if ((int)workers_.size() != S_) throw std::runtime_error("score: needs every stage in this process");
+  if (n_top < 0 || n_top > Stage::kMaxProbs) throw std::runtime_error("score: n_probs must be 0.." + std::to_string(Stage::kMaxProbs));
+  const size_t n = prompts.size();
+  if ((int)n > M_ * B_) throw std::runtime_error("more prompts than micro-batch slots");
+  for (auto& p : prompts) {
+    if (p.empty() || (int)p.size() > max_ctx_) throw std::runtime_error("bad prompt length");
+    for (int32_t t : p)
+      if (t < 0 || t >= cfg_.vocab) throw std::runtime_error("token id out of range");
+  }
+  Worker* wf = nullptr;
+  Worker* wl = nullptr;
+  for (auto& w : workers_) {
+    if (w->stage->spec().first()) wf = w.get();
+    if (w->stage->spec().last()) wl = w.get();
+  }
+  // the slots' KV is overwritten: whatever ran before is over
+  started_ = false;
+  slot_toks_.clear();
+  prompts_.clear();
+  gen_.clear();
+  gen_lp_.clear();
+  rounds_done_ = 0;
+  base_round_.assign((size_t)M_ * B_, 0);
+  active_.assign((size_t)M_ * B_, 0);
+  for (size_t i = n; i < (size_t)M_ * B_; ++i) pager_.release((int)i);
+  for (size_t i = 0; i < n; ++i)
+    if (prompts[i].size() > 1) kv_grant(i, (int)prompts[i].size() - 1);
+  kv_sync();
+  for (size_t i = 0; i < n; ++i) {
+    if (wf->cpu) std::memcpy(wf->stage->prompt_buf() + i * max_ctx_, prompts[i].data(), prompts[i].size() * 4);
+    else {
+      HIP_OK(hipSetDevice(wf->device));
+      HIP_OK(hipMemcpy(wf->stage->prompt_buf() + i * max_ctx_, prompts[i].data(), prompts[i].size() * 4, hipMemcpyHostToDevice));
+    }
+  }
+  out->assign(n, {});
+  for (size_t i = 0; i < n; ++i) {
+    (*out)[i].lp.assign(prompts[i].size() - 1, 0.f);
+    (*out)[i].top_id.assign((prompts[i].size() - 1) * n_top, -1);
+    (*out)[i].top_lp.assign((prompts[i].size() - 1) * n_top, 0.f);
+  }
+  std::vector<int> done(n, 0);   // rows of each prompt already scored
+  std::vector<int32_t> tgt;
+  std::vector<float> lp((size_t)chunk_), tl((size_t)chunk_ * std::max(1, n_top));
+  std::vector<int32_t> ti((size_t)chunk_ * std::max(1, n_top));
+  for (;;) {
+    std::vector<Item> items;
+    for (int mb = 0; mb < M_; ++mb) {
+      Item it{Item::PREFILL};
+      it.mb = mb;
+      tgt.clear();
+      for (int b = 0; b < B_ && it.T < chunk_; ++b) {
+        const size_t i = (size_t)mb * B_ + b;
+        if (i >= n) break;
+        const int rows = (int)prompts[i].size() - 1;
+        if (done[i] >= rows) continue;
+        PrefillSeg sg;
+        sg.b = b; sg.p0 = done[i]; sg.T = std::min(chunk_ - it.T, rows - done[i]); sg.score = true;
+        for (int t = 0; t < sg.T; ++t) tgt.push_back(prompts[i][sg.p0 + t + 1]);
+        it.segs.push_back(sg);
+        it.T += sg.T;
+        if (!packed_prefill_) break;
+      }
+      if (it.T == 0) continue;
+      if (!wl->cpu) HIP_OK(hipSetDevice(wl->device));
+      wl->stage->set_score_targets(mb, tgt.data(), it.T, n_top);
+      items.push_back(it);
+    }
+    if (items.empty()) break;
+    run_all(items);
+    for (const Item& it : items) {
+      if (!wl->cpu) HIP_OK(hipSetDevice(wl->device));
+      wl->stage->copy_scores(it.mb, it.T, lp.data(), ti.data(), tl.data());
+      int row = 0;
+      for (const PrefillSeg& sg : it.segs) {
+        const size_t i = (size_t)it.mb * B_ + sg.b;
+        std::copy(lp.begin() + row, lp.begin() + row + sg.T, (*out)[i].lp.begin() + sg.p0);
+        std::copy(ti.begin() + (size_t)row * n_top, ti.begin() + (size_t)(row + sg.T) * n_top, (*out)[i].top_id.begin() + (size_t)sg.p0 * n_top);
+        std::copy(tl.begin() + (size_t)row * n_top, tl.begin() + (size_t)(row + sg.T) * n_top, (*out)[i].top_lp.begin() + (size_t)sg.p0 * n_top);
+        done[i] += sg.T;
+        row += sg.T;
+      }
+    }
+  }
+}
 
 Json Engine::generate(const std::vector<std::vector<int32_t>>& prompts, int n_predict,
                       std::vector<std::vector<int32_t>>* out) {

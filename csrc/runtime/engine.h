@@ -74,6 +74,22 @@ class Engine {
   StepStats decode_steps(int k);
   // generated tokens so far per sequence (valid where the last stage lives)
   std::vector<std::vector<int32_t>> tokens() const;
+  // Token log-probabilities (config "n_probs": 0 off, -1 chosen token only, 1..20 plus that many
+  // alternatives): log-softmax of the raw logits, one entry per token of tokens()
+  struct SeqLogprobs {
+    std::vector<float> lp;           // [tokens]
+    std::vector<int32_t> top_id;     // [tokens][n_top]
+    std::vector<float> top_lp;       // [tokens][n_top]
+  };
+  int n_probs() const { return n_probs_; }
+  int n_top() const { return n_probs_ > 0 ? n_probs_ : 0; }
+  const std::vector<SeqLogprobs>& logprobs() const;
+  // the record of last_token(slot): false when none was taken (n_probs = 0, speculative decoding)
+  bool last_logprob(int slot, float* lp, std::vector<int32_t>* top_id, std::vector<float>* top_lp) const;
+  // Prompt scoring: out[i].lp[t] = log p(prompts[i][t + 1] | prompts[i][:t + 1]), t < len - 1, with
+  // the top n_top (id, logprob) pairs per position.  At most n_mb * mb_size prompts; every stage in
+  // this process.  Ends any running generation (the slots' KV is overwritten).
+  void score(const std::vector<std::vector<int32_t>>& prompts, int n_top, std::vector<SeqLogprobs>* out);
 
   // Continuous batching: between decode rounds, prefill new sequences into the
   // given sequence slots (slot = mb * mb_size + row) while the other slots keep their state; each
@@ -167,6 +183,14 @@ class Engine {
   std::vector<std::vector<int32_t>> gen_;          // generated tokens per sequence
   int32_t* out_host_ = nullptr;                    // pinned [rounds_cap][M*B]
   std::vector<int32_t> out_vec_;                   // CPU backend storage of out_host_
+  // n_probs != 0: the rounds' logprob records beside the tokens, [rounds_cap][M] records of
+  // lp_words_ 4-byte words (Stage::logprob_rec), and what has been collected from them per sequence
+  int n_probs_ = 0;
+  size_t lp_words_ = 0;
+  uint32_t* lp_host_ = nullptr;
+  std::vector<uint32_t> lp_vec_;
+  std::vector<SeqLogprobs> gen_lp_;
+  void take_logprobs(size_t seq, size_t round_slot);
   bool cpu_ = false;          // every stage on the CPU backend
   bool hybrid_ = false;       // gpu_layers (-ngl N) < n_layer: stage 0 on the CPU, the rest on GPUs
   bool stage_cpu(int s) const { return cpu_ || (hybrid_ && s == 0); }

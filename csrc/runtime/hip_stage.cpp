@@ -713,6 +713,7 @@ void HipStage::set_penalties(int last_n, float repeat, float freq, float presenc
   Stage::set_penalties(last_n, repeat, freq, presence);
   if (!spec_.last()) return;
   ensure_hist();
+  ensure_logprob();
   if (changed && !graphs_.empty()) capture_graphs();
 }
 
@@ -726,9 +727,78 @@ void HipStage::ensure_hist() {
   hist_n_ = pen_last_n_;
 }
 
+// token logprob buffers (last stage, n_probs != 0): allocated when recording is switched on and when
+// the penalty window changes size; nothing exists, and head() enqueues nothing more, with n_probs 0
+void HipStage::ensure_logprob() {
+  if (!spec_.last() || n_probs_ == 0) return;
+  const int B = opt_.mb_size;
+  if (lp_rec_.empty()) {
+    HIP_OK(hipSetDevice(spec_.device));
+    for (int mb = 0; mb < opt_.n_mb; ++mb) {
+      lp_rec_.push_back((float*)dmalloc(logprob_rec_words(B) * 4));
+      HIP_OK(hipMemset(lp_rec_.back(), 0xFF, logprob_rec_words(B) * 4));
+    }
+    lp_lse_ = (float*)dmalloc((size_t)B * 4);
+  }
+  if (hist_ && lp_hist_n_ != hist_n_) {
+    lp_hist_raw_ = (float*)dmalloc((size_t)B * hist_n_ * 4);
+    lp_hist_n_ = hist_n_;
+  }
+}
+
+void HipStage::set_n_probs(int n) {
+  if (n < -1 || n > kMaxProbs) throw std::runtime_error("n_probs must be -1 (chosen token only) or 0.." + std::to_string(kMaxProbs));
+  const bool changed = n != n_probs_;
+  n_probs_ = n;
+  if (!spec_.last()) return;
+  ensure_logprob();
+  if (changed && !graphs_.empty()) capture_graphs();
+}
+
+// the buffers of a chunk whose every row goes through the LM head (speculative verify chunks and
+// score chunks share them): the chunk's logits and, per micro-batch, the greedy token after each row
+void HipStage::ensure_chunk_head() {
+  if (!vlogits_) vlogits_ = (float*)dmalloc((size_t)opt_.prefill_chunk * logits_ld_ * 4);
+  if (!vtok_) vtok_ = (int32_t*)dmalloc((size_t)opt_.n_mb * opt_.prefill_chunk * 4);
+}
+
+void HipStage::set_score_targets(int mb, const int32_t* host, int n, int top_n) {
+  if (!spec_.last()) return;
+  if (n > opt_.prefill_chunk || top_n < 0 || top_n > kMaxProbs) throw std::runtime_error("set_score_targets: bad size");
+  HIP_OK(hipSetDevice(spec_.device));
+  const size_t rows = (size_t)opt_.n_mb * opt_.prefill_chunk;
+  if (!sc_tgt_) {
+    sc_tgt_ = (int32_t*)dmalloc(rows * 4);
+    sc_lp_ = (float*)dmalloc(rows * 4);
+    sc_lse_ = (float*)dmalloc(rows * 4);
+  }
+  if (top_n > 0 && !sc_top_id_) {
+    sc_top_id_ = (int32_t*)dmalloc(rows * kMaxProbs * 4);
+    sc_top_lp_ = (float*)dmalloc(rows * kMaxProbs * 4);
+  }
+  ensure_chunk_head();
+  sc_top_n_ = top_n;
+  HIP_OK(hipMemcpy(sc_tgt_ + (size_t)mb * opt_.prefill_chunk, host, (size_t)n * 4, hipMemcpyHostToDevice));
+}
+
+void HipStage::copy_scores(int mb, int n, float* target_lp, int32_t* top_id, float* top_lp) {
+  if (!sc_lp_ || n > opt_.prefill_chunk) throw std::runtime_error("no scores");
+  HIP_OK(hipSetDevice(spec_.device));
+  HIP_OK(hipStreamSynchronize(stream_));
+  const size_t off = (size_t)mb * opt_.prefill_chunk;
+  HIP_OK(hipMemcpy(target_lp, sc_lp_ + off, (size_t)n * 4, hipMemcpyDeviceToHost));
+  if (sc_top_n_ > 0 && top_id && top_lp) {
+    HIP_OK(hipMemcpy2D(top_id, (size_t)sc_top_n_ * 4, sc_top_id_ + off * kMaxProbs, (size_t)kMaxProbs * 4,
+                       (size_t)sc_top_n_ * 4, n, hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy2D(top_lp, (size_t)sc_top_n_ * 4, sc_top_lp_ + off * kMaxProbs, (size_t)kMaxProbs * 4,
+                       (size_t)sc_top_n_ * 4, n, hipMemcpyDeviceToHost));
+  }
+}
+
 void HipStage::set_history(int mb, const std::vector<std::vector<int32_t>>& seqs) {
   if (!spec_.last() || !penalties_on()) return;
   ensure_hist();
+  ensure_logprob();
   const int B = opt_.mb_size, n = hist_n_;
   std::vector<int32_t> h((size_t)B * n, -1), cnt(B, 0);
   for (int b = 0; b < B && b < (int)seqs.size(); ++b) {
@@ -1236,6 +1306,19 @@ void HipStage::head(int mb, int M, const float* x, int32_t* tok_out, uint64_t sa
   }
   const bool pen = penalties_on() && hist_;
   int32_t* hist = pen ? hist_ + (size_t)mb * opt_.mb_size * hist_n_ : nullptr;
+  // token logprobs are those of the RAW logits: the statistics (and the raw logits of the ids the
+  // penalty is about to rewrite) are taken here, the chosen token's value after the sampler
+  const bool lp = n_probs_ != 0 && !lp_rec_.empty();
+  float* rec = lp ? lp_rec_[mb] : nullptr;
+  if (lp) {
+    const int B = opt_.mb_size;
+    LogprobParams q{};
+    q.logits = logits_; q.ld = logits_ld_; q.n = cfg_.vocab; q.M = M;
+    q.top_n = std::max(n_probs_, 0); q.lse = lp_lse_;
+    q.top_id = (int32_t*)(rec + B); q.top_lp = rec + B + (size_t)B * kMaxProbs; q.ld_top = kMaxProbs;
+    if (pen) { q.hist = hist; q.last_n = hist_n_; q.hist_raw = lp_hist_raw_; }
+    launch_logprob(q, st);
+  }
   if (pen) {
     PenaltyParams pp{};
     pp.logits = logits_; pp.ld = logits_ld_; pp.n = cfg_.vocab; pp.M = M;
@@ -1250,6 +1333,13 @@ void HipStage::head(int mb, int M, const float* x, int32_t* tok_out, uint64_t sa
     launch_sample(sp, st);
   } else {
     launch_argmax(logits_, logits_ld_, cfg_.vocab, M, tok_out, st, &am_);
+  }
+  if (lp) {
+    LogprobChosenParams c{};
+    c.logits = logits_; c.ld = logits_ld_; c.n = cfg_.vocab; c.M = M; c.tokens = tok_out; c.lse = lp_lse_;
+    if (pen) { c.hist = hist; c.last_n = hist_n_; c.hist_raw = lp_hist_raw_; }
+    c.chosen_lp = rec;
+    launch_logprob_chosen(c, st);
   }
   if (pen) launch_hist_push(hist, hist_cnt_ + (size_t)mb * opt_.mb_size, hist_n_, tok_out, M, st);
 }
@@ -1275,14 +1365,24 @@ void HipStage::prefill(int mb, const std::vector<PrefillSeg>& segs, hipStream_t 
   segs_ = nullptr;
   if (spec_.last() && !segs.empty() && segs[0].verify) {
     // speculative verification: LM head over every row of the chunk, greedy next token per row
-    if (!vlogits_) {
-      vlogits_ = (float*)dmalloc((size_t)opt_.prefill_chunk * logits_ld_ * 4);
-      vtok_ = (int32_t*)dmalloc((size_t)opt_.n_mb * opt_.prefill_chunk * 4);
-    }
+    ensure_chunk_head();
     launch_rmsnorm(x, d, out_norm_, d, cfg_.eps, xn_, Kd_, T, nullptr, 0, st);
     xq_src_ = nullptr;
     gemv(out_, EPI_STORE, xn_, Kd_, T, vlogits_, logits_ld_, nullptr, 0, cfg_.vocab, false, st);
     launch_argmax(vlogits_, logits_ld_, cfg_.vocab, T, vtok_ + (size_t)mb * opt_.prefill_chunk, st, &am_);
+  } else if (spec_.last() && !segs.empty() && segs[0].score) {
+    // prompt scoring: LM head over every row of the chunk, then each row's target logprob
+    if (!sc_tgt_ || !vlogits_) throw std::runtime_error("score chunk without targets");
+    launch_rmsnorm(x, d, out_norm_, d, cfg_.eps, xn_, Kd_, T, nullptr, 0, st);
+    xq_src_ = nullptr;
+    gemv(out_, EPI_STORE, xn_, Kd_, T, vlogits_, logits_ld_, nullptr, 0, cfg_.vocab, false, st);
+    const size_t off = (size_t)mb * opt_.prefill_chunk;
+    LogprobParams q{};
+    q.logits = vlogits_; q.ld = logits_ld_; q.n = cfg_.vocab; q.M = T;
+    q.target = sc_tgt_ + off; q.top_n = sc_top_n_; q.lse = sc_lse_ + off; q.target_lp = sc_lp_ + off;
+    if (sc_top_n_ > 0) { q.top_id = sc_top_id_ + off * kMaxProbs; q.top_lp = sc_top_lp_ + off * kMaxProbs; }
+    q.ld_top = kMaxProbs;
+    launch_logprob(q, st);
   } else if (spec_.last()) {
     int row = 0;
     for (const PrefillSeg& s : segs) {

@@ -103,6 +103,10 @@ class HipStage : public Stage {
   void prefill(int mb, const std::vector<PrefillSeg>& segs, hipStream_t st) override;
   void prefill_finish(int mb, hipStream_t st, const std::vector<int>* rows = nullptr) override;
   void copy_verify_tokens(int mb, int32_t* host, int n) override;
+  void set_n_probs(int n) override;
+  const void* logprob_rec(int mb) const override { return lp_rec_.empty() ? nullptr : lp_rec_[mb]; }
+  void set_score_targets(int mb, const int32_t* host, int n, int top_n) override;
+  void copy_scores(int mb, int n, float* target_lp, int32_t* top_id, float* top_lp) override;
 
   // One decode step for micro-batch mb (graph replay if captured).
   void decode(int mb, hipStream_t st) override;
@@ -162,6 +166,8 @@ class HipStage : public Stage {
             const GemvParams* extras = nullptr);
   void head(int mb, int M, const float* x, int32_t* tok_out, uint64_t salt, hipStream_t st);
   void ensure_hist();
+  void ensure_logprob();
+  void ensure_chunk_head();
   // pinned double-buffered weight staging (load_gguf)
   struct Staging {
     uint8_t* buf[2] = {nullptr, nullptr};
@@ -251,6 +257,15 @@ class HipStage : public Stage {
   std::vector<float*> last_h_;                       // last stage: [mb][B][d] final prompt rows
   float* vlogits_ = nullptr;                          // last stage, speculative verify: [chunk][logits_ld_]
   int32_t* vtok_ = nullptr;                           // [n_mb][chunk] greedy token after each verify row
+  // token logprobs (last stage, n_probs != 0): per micro-batch record (Stage::logprob_rec), the rows'
+  // log-sum-exp and the raw logits of the penalty window's ids saved before the in-place penalty
+  std::vector<float*> lp_rec_;
+  float* lp_lse_ = nullptr;                           // [mb_size]
+  float* lp_hist_raw_ = nullptr; int lp_hist_n_ = 0;  // [mb_size][hist_n_]
+  // prompt scoring (last stage): per micro-batch targets and results of a score chunk
+  int32_t* sc_tgt_ = nullptr; float* sc_lp_ = nullptr; float* sc_lse_ = nullptr;   // [n_mb][chunk]
+  int32_t* sc_top_id_ = nullptr; float* sc_top_lp_ = nullptr;                      // [n_mb][chunk][kMaxProbs]
+  int sc_top_n_ = 0;
   const std::vector<PrefillSeg>* segs_ = nullptr;    // segments of the prefill in progress
   // graphs
   std::vector<hipGraphExec_t> graphs_;

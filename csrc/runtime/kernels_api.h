@@ -274,6 +274,33 @@ struct SampleParams {
   int32_t* tokens;
 };
 void launch_sample(const SampleParams& p, hipStream_t st);
+// token log-probabilities of the RAW logits (log-softmax; NaN counts as -inf), one workgroup per
+// row: lse[m], the target's logprob (-inf without a target, or with one outside [0, n)) and the
+// top_n (id, logprob) pairs by descending logit, exact ties to the lower id; slots past the
+// finite entries are -1 / -inf, and so is everything for a row without a finite maximum.
+constexpr int kLogprobMaxTop = 20;
+struct LogprobParams {
+  const float* logits; int ld; int n; int M;   // read-only; columns n..ld-1 are never read
+  const int32_t* target;                       // [M] or null
+  int top_n;                                   // 0..kLogprobMaxTop
+  float* lse;                                  // [M]
+  float* target_lp;                            // [M] or null
+  int32_t* top_id; float* top_lp; int ld_top;  // [M][ld_top], the first top_n of a row are written
+  // optional: save the raw logits at the ids of each row's penalty window (hist [M][last_n], -1 =
+  // empty) into hist_raw [M][last_n], before launch_penalize edits them in place
+  const int32_t* hist; int last_n; float* hist_raw;
+};
+void launch_logprob(const LogprobParams& p, hipStream_t st);
+// after the sampler: chosen_lp[m] = raw logit of tokens[m] - lse[m]; the raw logit of an id of the
+// penalty window comes from hist_raw (hist as it was when launch_logprob ran, i.e. before
+// launch_hist_push), every other one from the logits
+struct LogprobChosenParams {
+  const float* logits; int ld; int n; int M;
+  const int32_t* tokens; const float* lse;
+  const int32_t* hist; int last_n; const float* hist_raw;   // null without penalties
+  float* chosen_lp;
+};
+void launch_logprob_chosen(const LogprobChosenParams& p, hipStream_t st);
 // repetition penalties (llama.cpp penalties sampler semantics) over each row's ring of the last
 // `last_n` accepted tokens (-1 = empty): every distinct token t of the window with count c gets
 // l = l > 0 ? l / repeat : l * repeat, then l -= c * freq + presence.  In place, before sampling.

@@ -50,6 +50,32 @@ std::vector<int32_t> Session::encode(const std::string& text) const {
   return o;
 }
 
+std::vector<int32_t> Session::encode_raw(const std::string& text) const {
+  if (tok_) return tok_->encode(text, false, false);
+  std::vector<int32_t> o;
+  const int V = eng_->model().vocab;
+  for (unsigned char c : text) o.push_back((int32_t)((c + 3) % V));
+  return o;
+}
+
+int Session::bos() const {
+  if (tok_) return tok_->add_bos_default() ? tok_->bos() : -1;
+  return 1;   // the stand-in tokenizer's encode() starts with 1
+}
+
+// the engine's logprob record of slot's newest token t -> r.probs
+void Session::push_prob(GenResult& r, int slot, int32_t t) const {
+  float lp = 0;
+  std::vector<int32_t> ids;
+  std::vector<float> lps;
+  if (!eng_->last_logprob(slot, &lp, &ids, &lps)) return;
+  TokenProb tp;
+  tp.id = t; tp.piece = piece(t); tp.logprob = lp;
+  for (size_t k = 0; k < ids.size(); ++k)
+    if (ids[k] >= 0) tp.top.push_back({ids[k], piece(ids[k]), lps[k]});
+  r.probs.push_back(std::move(tp));
+}
+
 std::string Session::piece(int32_t id) const {
   if (tok_) return tok_->piece(id);
   return "[" + std::to_string(id) + "]";
@@ -88,6 +114,7 @@ std::vector<GenResult> Session::run(std::vector<GenRequest>& reqs) {
     if (is_eog(t)) { active[i] = false; r.stop = "eog"; return; }
     r.tokens.push_back(t);
     r.n_gen++;
+    push_prob(r, (int)i, t);
     const std::string p = acc[i].push(piece(t));
     r.text += p;
     if (emit && !p.empty() && reqs[i].on_piece && !reqs[i].on_piece(p)) { active[i] = false; r.stop = "cancelled"; }
@@ -201,6 +228,7 @@ void Session::serve(const std::function<std::vector<Served>(int free)>& next) {
     if (is_eog(t)) { r.stop = "eog"; return false; }
     r.tokens.push_back(t);
     r.n_gen++;
+    push_prob(r, slot, t);
     const std::string p = L.acc.push(piece(t));
     r.text += p;
     ++L.step;

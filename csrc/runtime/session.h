@@ -27,12 +27,23 @@ struct GenRequest {
   std::function<bool(const std::string& piece)> on_piece;
 };
 
+// one generated token with its log-probability (log-softmax of the raw logits) and the engine's
+// n_probs most likely alternatives at that step (engine config n_probs != 0)
+struct TokenProb {
+  int32_t id = -1;
+  std::string piece;
+  float logprob = 0;
+  struct Alt { int32_t id; std::string piece; float logprob; };
+  std::vector<Alt> top;
+};
+
 struct GenResult {
   int n_prompt = 0, n_gen = 0;
   double prefill_ms = 0, decode_ms = 0;
   std::string text;
   std::string stop;   // "eog" | "length" | "cancelled" | "context"
   std::vector<int32_t> tokens;
+  std::vector<TokenProb> probs;   // one per token of `tokens` when the engine records logprobs
 };
 
 class Session {
@@ -52,6 +63,9 @@ class Session {
   }
   int failovers() const { return failovers_; }
   std::vector<int32_t> encode(const std::string& text) const;
+  // text as a bare token stream (no BOS), and the BOS id the vocabulary puts in front (-1: none)
+  std::vector<int32_t> encode_raw(const std::string& text) const;
+  int bos() const;
   std::string piece(int32_t id) const;
   bool is_eog(int32_t id) const;
 
@@ -71,6 +85,7 @@ class Session {
   static std::string perf_summary(const GenResult& r, double load_ms);
 
  private:
+  void push_prob(GenResult& r, int slot, int32_t t) const;
   Engine* eng_;
   std::function<Engine*(const std::string&)> on_fault_;
   int max_failovers_ = 0, failovers_ = 0;

@@ -52,6 +52,8 @@ struct PrefillSeg {
   int p0 = 0;         // first position of this segment
   int T = 0;          // tokens
   bool last = false;  // ends the prompt
+  bool score = false;   // prompt scoring chunk: the last stage runs the LM head over EVERY row and keeps the
+                        // log-probability of each row's target token (set_score_targets -> copy_scores)
   bool verify = false;  // speculative verification chunk: the last stage scores EVERY row (greedy
                         // argmax after each row -> verify_tokens), nothing is kept for prefill_finish
 };
@@ -86,6 +88,20 @@ class Stage {
   // last stage, after a prefill() of verify segments of micro-batch mb: the greedy next token after
   // each of the chunk's n rows (row order = segment order) -> host
   virtual void copy_verify_tokens(int mb, int32_t* host, int n) = 0;
+  // Token log-probabilities (log-softmax of the RAW logits: before penalties, temperature and cuts).
+  // n_probs: 0 = off (nothing is recorded or enqueued), -1 = the chosen token's logprob only,
+  // 1..kMaxProbs = plus that many most likely tokens.  Last stage: every head() then leaves one
+  // record per row of micro-batch mb, logprob_rec(mb) (device memory for HIP, host for CPU):
+  //   f32 chosen_lp[mb_size] | i32 top_id[mb_size][kMaxProbs] | f32 top_lp[mb_size][kMaxProbs]
+  static constexpr int kMaxProbs = 20;
+  static size_t logprob_rec_words(int mb_size) { return (size_t)mb_size * (1 + 2 * kMaxProbs); }
+  virtual void set_n_probs(int n) { n_probs_ = n; }
+  virtual const void* logprob_rec(int mb) const { (void)mb; return nullptr; }
+  // prompt scoring, last stage: the target token of each of the n rows of micro-batch mb's next
+  // score chunk (-1 = none) and how many alternatives to keep; after that prefill(), the rows'
+  // target logprobs (and top_n ids / logprobs, [n][top_n]) -> host
+  virtual void set_score_targets(int mb, const int32_t* host, int n, int top_n) = 0;
+  virtual void copy_scores(int mb, int n, float* target_lp, int32_t* top_id, float* top_lp) = 0;
   virtual const float* logits_ptr() const = 0;   // last computed logits (device/host)
   virtual int logits_ld() const = 0;
   virtual size_t weight_bytes() const = 0;
@@ -127,6 +143,7 @@ class Stage {
   int top_k_ = 0;
   uint64_t seed_ = 0;
   int pen_last_n_ = 64;
+  int n_probs_ = 0;
   float pen_repeat_ = 1.f, pen_freq_ = 0.f, pen_presence_ = 0.f;
 };
 

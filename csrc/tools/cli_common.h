@@ -25,6 +25,7 @@ struct CliOptions {
   bool verbose = false;
   bool echo_prompt = true;
   bool bench = false;
+  bool perplexity = false;    // --perplexity: llama.cpp's perplexity procedure over the -f file
   int bench_prompt = 128, bench_warmup = 3, bench_steps = 20;
   std::string trace;
   std::string rpc;            // --rpc host:port,... (without --world): stage workers to attach to (rpc.h)
@@ -92,6 +93,10 @@ inline void print_common_usage(FILE* f) {
           "  --repeat-penalty R --repeat-last-n N --frequency-penalty F --presence-penalty P\n"
           "                            penalties over the last N tokens (default 1.0 / 64 / 0 / 0)\n"
           "  --sampling greedy         force greedy\n"
+          "  --n-probs N               record token log-probabilities (raw log-softmax): -1 the chosen token's\n"
+          "                            only, 1..20 plus that many alternatives (default 0: off)\n"
+          "  --perplexity -f FILE      perplexity of a text file, llama.cpp's procedure: windows of -c tokens,\n"
+          "                            the second half of each window counts\n"
           "  --draft-max K             speculative decoding by prompt lookup: up to K drafted tokens per\n"
           "                            verify round (greedy; --lookup-ngram N, default 3)\n"
           "placement / pipeline:\n"
@@ -186,6 +191,8 @@ inline CliOptions parse_cli(int argc, char** argv,
     else if (a == "--trace") o.trace = val();
     else if (a == "--no-display-prompt") o.echo_prompt = false;
     else if (a == "--bench") o.bench = true;
+    else if (a == "--perplexity") o.perplexity = true;
+    else if (a == "--n-probs") e["n_probs"] = std::atoi(val().c_str());
     else if (a == "--bench-prompt") o.bench_prompt = std::atoi(val().c_str());
     else if (a == "--bench-warmup") o.bench_warmup = std::atoi(val().c_str());
     else if (a == "--bench-steps") o.bench_steps = std::atoi(val().c_str());

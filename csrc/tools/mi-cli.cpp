@@ -15,6 +15,7 @@
 #include "cli_common.h"
 #include "engine.h"
 #include "log.h"
+#include "perplexity.h"
 #include "rpc.h"
 #include "session.h"
 
@@ -25,6 +26,7 @@ static void usage() {
   print_common_usage(stderr);
   fprintf(stderr,
           "mi-cli:\n"
+          "  --perplexity -f FILE      prints a running estimate and `Final estimate: PPL = x +/- y`\n"
           "  --bench [--bench-prompt L --bench-warmup W --bench-steps K]   decode throughput of full batches\n"
           "  --daemon                  read {\"prompt\":..,\"n_predict\":..} lines on stdin, answer with JSON lines\n"
           "  --no-display-prompt       do not echo the prompt\n"
@@ -32,6 +34,39 @@ static void usage() {
           "  --state-load DIR          resume a checkpoint: continue its sequence for -n more tokens\n"
           "  --rpc-server PORT [-m LOCAL.gguf] [--device D] [--rpc-jobs N]\n"
           "                            stage worker (llama.cpp rpc-server role): serve --rpc clients, N jobs (0 = forever)\n");
+}
+
+// --perplexity -f FILE: llama.cpp's default procedure (perplexity.h) on the engine's prompt scoring;
+// the windows go through Engine::score capacity() at a time
+static int run_perplexity(Engine& eng, Session& s, const std::string& text) {
+  const int c = eng.max_ctx();
+  const std::vector<int32_t> toks = s.encode_raw(text);
+  if (!ppl_enough_tokens(toks.size(), c)) {
+    fprintf(stderr, "mi-cli: --perplexity needs at least %d tokens (2 x the context of %d), the file has %zu\n", 2 * c, c,
+            toks.size());
+    return 1;
+  }
+  const long n_win = ppl_n_windows(toks.size(), c);
+  const int bos = s.bos();
+  MP_LOGI("perplexity: %zu tokens, %ld windows of %d, %d at a time", toks.size(), n_win, c, s.capacity());
+  PplEstimate est;
+  const double t0 = session_now_ms();
+  for (long w0 = 0; w0 < n_win; w0 += s.capacity()) {
+    std::vector<std::vector<int32_t>> wins;
+    for (long w = w0; w < std::min(n_win, w0 + (long)s.capacity()); ++w) wins.push_back(ppl_window(toks, w, c, bos));
+    std::vector<Engine::SeqLogprobs> sc;
+    eng.score(wins, 0, &sc);
+    for (size_t i = 0; i < wins.size(); ++i) {
+      est.add_window(sc[i].lp.data(), c);
+      printf("[%ld]%.4lf,", w0 + (long)i + 1, est.ppl());
+    }
+    fflush(stdout);
+  }
+  printf("\n");
+  MP_LOGI("perplexity: %.1f ms, %ld positions counted", session_now_ms() - t0, est.count);
+  printf("Final estimate: PPL = %.4lf +/- %.5lf\n", est.ppl(), est.err());
+  fflush(stdout);
+  return 0;
 }
 
 static int run_daemon(Session& s) {
@@ -140,6 +175,7 @@ int main(int argc, char** argv) {
     }
     Session s(eng, o.eng.get_str("gguf", ""));
     if (daemon) return run_daemon(s);
+    if (o.perplexity) return run_perplexity(eng, s, o.prompt);
     if (!state_load.empty()) {
       // resume: continue sequence 0 of the checkpoint token by token
       eng.load_state(state_load);

@@ -617,7 +617,7 @@ void serve_static(Server& S, int fd, const Request& r) {
 
 // axum Json<ChatRequest> extractor semantics (main.rs:18-21)
 bool parse_prompt_body(int fd, const Request& r, std::string* prompt, int* n_predict, int def_n,
-                       std::string* model = nullptr) {
+                       std::string* model = nullptr, Json* body = nullptr) {
   if (lower(r.header("content-type")).find("application/json") == std::string::npos) {
     respond_text(fd, 415, "Expected request with `Content-Type: application/json`");
     return false;
@@ -637,6 +637,7 @@ bool parse_prompt_body(int fd, const Request& r, std::string* prompt, int* n_pre
   *n_predict = j.get_int("n_predict", def_n);
   if (*n_predict < 0) *n_predict = def_n;
   if (model) *model = j.get_str("model", "");
+  if (body) *body = j;
   return true;
 }
 
@@ -829,7 +830,24 @@ void handle_completion(Server& S, int fd, const Request& r) {
   std::string prompt;
   int n = 128;   // PDF p.10: n_predict 128
   std::string model;
-  if (!parse_prompt_body(fd, r, &prompt, &n, 128, &model) || !known_model(S, fd, &model)) return;
+  Json body;
+  if (!parse_prompt_body(fd, r, &prompt, &n, 128, &model, &body) || !known_model(S, fd, &model)) return;
+  // "n_probs": k alternatives per generated token, at most what the engine records (--n-probs)
+  const int n_probs = body.get_int("n_probs", 0);
+  int have = 0;
+  {
+    std::lock_guard<std::mutex> l(S.eng_mu);
+    if (S.eng) have = std::max(0, S.eng->n_probs());
+  }
+  if (n_probs < 0) {
+    respond_text(fd, 400, "n_probs must not be negative");
+    return;
+  }
+  if (n_probs > have) {
+    respond_text(fd, 400, "n_probs " + std::to_string(n_probs) + " exceeds what this server records (--n-probs " +
+                              std::to_string(have) + ")");
+    return;
+  }
   auto job = submit(S, prompt, n, model);
   {
     std::unique_lock<std::mutex> l(job->mu);
@@ -840,6 +858,22 @@ void handle_completion(Server& S, int fd, const Request& r) {
   o["content"] = g.text;
   o["response"] = g.text;
   o["tokens_predicted"] = g.n_gen;
+  if (n_probs > 0) {   // llama.cpp's field: one entry per generated token, n_probs alternatives each
+    Json cp = Json::array();
+    for (const TokenProb& tp : g.probs) {
+      Json e = Json::object();
+      e["id"] = (int)tp.id; e["token"] = tp.piece; e["logprob"] = (double)tp.logprob;
+      Json top = Json::array();
+      for (size_t k = 0; k < tp.top.size() && (int)k < n_probs; ++k) {
+        Json a = Json::object();
+        a["id"] = (int)tp.top[k].id; a["token"] = tp.top[k].piece; a["logprob"] = (double)tp.top[k].logprob;
+        top.push(a);
+      }
+      e["top_logprobs"] = top;
+      cp.push(e);
+    }
+    o["completion_probabilities"] = cp;
+  }
   o["tokens_evaluated"] = g.n_prompt;
   o["stop_reason"] = g.stop;
   Json t = Json::object();

@@ -111,11 +111,18 @@ _SIGS = {
     "mp_op_gemvs": ([c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_int,
                      c_int, c_void_p, c_int, c_void_p, c_float, c_int, c_void_p, c_int, c_int, c_int, c_void_p], c_int),
     "mp_op_penalize": ([c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_float, c_float, c_float, c_void_p], c_int),
+    "mp_op_logprob": ([c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                       c_void_p], c_int),
+    "mp_op_logprob_stats": ([c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int,
+                             c_void_p, c_void_p], c_int),
+    "mp_op_logprob_chosen": ([c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
+                              c_void_p], c_int),
     "mp_op_hist_push": ([c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p], c_int),
     "mp_op_sample": ([c_void_p, c_int, c_int, c_int, c_float, c_int, c_float, c_float, ctypes.c_uint64, c_void_p,
                       c_void_p, c_void_p], c_int),
     "mp_tok_open": ([c_char_p], c_void_p),
     "mp_tok_close": ([c_void_p], None),
+    "mp_tok_add_bos": ([c_void_p], c_int),
     "mp_tok_encode": ([c_void_p, c_char_p, c_int, c_int, c_void_p, c_int], c_int),
     "mp_tok_piece": ([c_void_p, c_int, c_void_p, c_int], c_int),
     "mp_tok_decode": ([c_void_p, c_void_p, c_int, c_void_p, c_int], c_int),
@@ -136,6 +143,10 @@ _SIGS = {
     "mp_engine_release": ([c_void_p, c_int], c_int),
     "mp_engine_decode": ([c_void_p, c_int], c_char_p),
     "mp_engine_tokens": ([c_void_p, c_void_p, c_int, c_int], c_int),
+    "mp_engine_logprobs": ([c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int], c_int),
+    "mp_engine_score": ([c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p], c_int),
+    "mp_ppl_windows": ([ctypes.c_long, c_int], ctypes.c_long),
+    "mp_ppl_estimate": ([c_void_p, c_int, c_int, c_void_p], c_int),
     "mp_engine_logits": ([c_void_p, c_int, c_void_p, c_int], c_int),
     "mp_rccl_unique_id": ([c_void_p], c_int),
     "mp_local_link_selftest": ([c_int, c_int, c_int64, c_int, c_int], c_int),

@@ -12,7 +12,8 @@ frequency_penalty/presence_penalty (penalties over the last n tokens, prompt inc
 threads (CPU backend), trace, watchdog_s, link_timeout_s, fault (fault injection), verbose, log_file,
 kv_dtype ("f16" | "fp8"), kv_pool_tokens (paged KV pool), prefill_gemm_v (0 auto | 1 | 2 | 3 | 4), prefill_flash,
 deterministic, fused_norm, small_gemv, act_dtype (stage-boundary wire: "auto" | "f32" | "bf16" | "f16"),
-device_speed ("probe" or a list; Halda-style partition weights).
+device_speed ("probe" or a list; Halda-style partition weights), n_probs (token logprobs: 0 off, -1 the
+chosen token's only, 1..20 plus that many alternatives; read with logprobs()).
 """
 from __future__ import annotations
 
@@ -61,6 +62,7 @@ class Engine:
     def generate(self, prompts, n_predict: int):
         flat, lens = self._flat(prompts)
         out = np.full((len(prompts), n_predict), -1, np.int32)
+        self._n_seq = len(prompts)
         stats = N.jcall(N.lib().mp_engine_generate, self._h, flat.ctypes.data, lens.ctypes.data, len(prompts),
                         n_predict, out.ctypes.data, what="generate")
         return out.tolist(), stats
@@ -105,6 +107,46 @@ class Engine:
         n = N.check(N.lib().mp_engine_tokens(self._h, out.ctypes.data, self._n_seq, cap), "tokens")
         return [[t for t in row if t >= 0] for row in out[:, :n].tolist()]
 
+    def logprobs(self):
+        """Log-probabilities of the generated tokens (engine built with n_probs != 0): the log-softmax
+        of the RAW logits (before penalties, temperature and cuts; llama.cpp's server default).
+        Returns per sequence (lp, top_id, top_lp): float32 [n_tokens] aligned with tokens(), and
+        [n_tokens][n_probs] alternatives by descending probability (empty with n_probs = -1)."""
+        nt = max(int(self.cfg.get("n_probs", 0)), 0)
+        # one record per token: the buffers are sized by the longest sequence, the counts are tokens()'s
+        counts = [len(t) for t in self.tokens(cap=self.info["max_ctx"] + 2)]
+        cap = max(counts + [1])
+        lp = np.zeros((self._n_seq, cap), np.float32)
+        tid = np.zeros((self._n_seq, cap, nt), np.int32)
+        tlp = np.zeros((self._n_seq, cap, nt), np.float32)
+        N.check(N.lib().mp_engine_logprobs(self._h, lp.ctypes.data, tid.ctypes.data if nt else None,
+                                           tlp.ctypes.data if nt else None, self._n_seq, cap), "logprobs")
+        return [(lp[i, :n].copy(), tid[i, :n].copy(), tlp[i, :n].copy()) for i, n in enumerate(counts)]
+
+    def score(self, prompts, n_probs: int = 0):
+        """Prompt scoring: per prompt a float32 array of length len(prompt) - 1 whose entry t is
+        log p(prompt[t + 1] | prompt[:t + 1]).  With n_probs > 0 returns (lp, top_id, top_lp) per
+        prompt instead, the top arrays [len - 1][n_probs].  Prompts are batched over the engine's
+        n_mb x mb_size slots; a running generation ends (its KV is overwritten)."""
+        res = []
+        for g in range(0, len(prompts), self.n_seq_cap):
+            grp = prompts[g:g + self.n_seq_cap]
+            flat, lens = self._flat(grp)
+            rows = int(sum(len(p) - 1 for p in grp))
+            lp = np.zeros(max(rows, 1), np.float32)
+            tid = np.zeros((max(rows, 1), n_probs), np.int32)
+            tlp = np.zeros((max(rows, 1), n_probs), np.float32)
+            N.check(N.lib().mp_engine_score(self._h, flat.ctypes.data, lens.ctypes.data, len(grp), n_probs,
+                                            lp.ctypes.data, tid.ctypes.data if n_probs else None,
+                                            tlp.ctypes.data if n_probs else None), "score")
+            o = 0
+            for p in grp:
+                n = len(p) - 1
+                res.append((lp[o:o + n].copy(), tid[o:o + n].copy(), tlp[o:o + n].copy()) if n_probs
+                           else lp[o:o + n].copy())
+                o += n
+        return res
+
     def bench(self, prompt_len: int, warmup: int, steps: int):
         return N.jcall(N.lib().mp_engine_bench, self._h, prompt_len, warmup, steps, what="bench")
 
@@ -136,6 +178,29 @@ class Engine:
         out = np.zeros((rows, vocab), np.float32)
         N.check(N.lib().mp_engine_logits(self._h, 0, out.ctypes.data, rows), "logits")
         return out
+
+
+def perplexity_windows(tokens, n_ctx: int, bos: int = -1):
+    """llama.cpp's perplexity windows of a token stream: consecutive n_ctx-token pieces (the tail
+    that fills no window is dropped), BOS in the first slot when bos >= 0.  Raises when the stream
+    has fewer than 2 * n_ctx tokens."""
+    n = N.lib().mp_ppl_windows(len(tokens), n_ctx)
+    if n < 0:
+        raise ValueError(f"perplexity needs at least {2 * n_ctx} tokens, got {len(tokens)}")
+    wins = [list(tokens[w * n_ctx:(w + 1) * n_ctx]) for w in range(n)]
+    if bos >= 0:
+        for w in wins:
+            w[0] = bos
+    return wins
+
+
+def perplexity_estimate(window_scores, n_ctx: int) -> dict:
+    """Perplexity from the windows' score() arrays (n_ctx - 1 values each): only positions
+    [n_ctx / 2, n_ctx - 1) count; err is the standard error of the mean NLL times the PPL."""
+    lp = np.ascontiguousarray(np.asarray(window_scores, np.float32).reshape(-1, n_ctx - 1))
+    out = (ctypes.c_double * 4)()
+    N.check(N.lib().mp_ppl_estimate(lp.ctypes.data, lp.shape[0], n_ctx, out), "perplexity estimate")
+    return {"nll": out[0], "ppl": out[1], "err": out[2], "count": int(out[3])}
 
 
 def device_probe(device: int = 0) -> dict:

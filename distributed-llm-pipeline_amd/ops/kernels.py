@@ -456,6 +456,52 @@ def penalize(logits: torch.Tensor, hist: torch.Tensor, repeat: float = 1.0, freq
     return logits
 
 
+LOGPROB_MAX_TOP = 20
+
+
+def logprob(logits: torch.Tensor, n: int | None = None, target: torch.Tensor | None = None, top_n: int = 0,
+            rows: int | None = None, out: tuple | None = None):
+    """Log-softmax statistics of the first `rows` rows of f32 logits [M][ld] (columns n.. are padding):
+    returns (lse [M], target_lp [M], top_id [M][w], top_lp [M][w]); the kernel writes the first `rows`
+    rows and the first top_n slots of a row.  out: pre-filled buffers of those shapes (w >= top_n)."""
+    assert logits.dtype == torch.float32 and logits.stride(1) == 1
+    M = logits.shape[0] if rows is None else rows
+    n = logits.shape[1] if n is None else n
+    dev = logits.device
+    if out is None:
+        out = (torch.empty(M, dtype=torch.float32, device=dev), torch.empty(M, dtype=torch.float32, device=dev),
+               torch.empty(M, max(top_n, 1), dtype=torch.int32, device=dev),
+               torch.empty(M, max(top_n, 1), dtype=torch.float32, device=dev))
+    lse, tlp, tid, tl = out
+    assert tid.dtype == torch.int32 and tid.is_contiguous() and tl.is_contiguous() and tid.shape == tl.shape
+    assert lse.numel() >= M and tlp.numel() >= M and tid.shape[0] >= M
+    if target is not None:
+        assert target.dtype == torch.int32 and target.numel() >= M and target.is_contiguous()
+    N.check(N.lib().mp_op_logprob(_ptr(logits), logits.stride(0), n, M, _ptr(target), top_n, _ptr(lse), _ptr(tlp),
+                                  _ptr(tid), _ptr(tl), tid.shape[1], _stream()), "logprob")
+    return out
+
+
+def logprob_generation(logits: torch.Tensor, hist: torch.Tensor | None, top_n: int, step):
+    """The engine's generation sequence on f32 logits [M][n]: statistics of the raw logits (saving
+    those of the penalty window `hist`), then step(logits) -> int32 tokens [M] (penalties in place
+    and a sampler), then the chosen tokens' raw logprobs.  Returns (tokens, chosen_lp, top_id, top_lp)."""
+    M, n = logits.shape
+    dev = logits.device
+    lse = torch.empty(M, dtype=torch.float32, device=dev)
+    tid = torch.empty(M, max(top_n, 1), dtype=torch.int32, device=dev)
+    tl = torch.empty(M, max(top_n, 1), dtype=torch.float32, device=dev)
+    last_n = 0 if hist is None else hist.shape[1]
+    raw = None if hist is None else torch.empty(M, last_n, dtype=torch.float32, device=dev)
+    N.check(N.lib().mp_op_logprob_stats(_ptr(logits), logits.stride(0), n, M, top_n, _ptr(lse), _ptr(tid), _ptr(tl),
+                                        tid.shape[1], _ptr(hist), last_n, _ptr(raw), _stream()), "logprob_stats")
+    tokens = step(logits)
+    clp = torch.empty(M, dtype=torch.float32, device=dev)
+    N.check(N.lib().mp_op_logprob_chosen(_ptr(logits), logits.stride(0), n, M, _ptr(tokens), _ptr(lse), _ptr(hist),
+                                         last_n, _ptr(raw), _ptr(clp), _stream()), "logprob_chosen")
+    return tokens, clp, tid[:, :top_n], tl[:, :top_n]
+
+
 def hist_push(hist: torch.Tensor, cnt: torch.Tensor, tokens: torch.Tensor) -> None:
     """hist[m][cnt[m] % last_n] = tokens[m]; cnt[m] += 1 (int32 device tensors)."""
     M, last_n = hist.shape

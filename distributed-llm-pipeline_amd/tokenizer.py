@@ -20,6 +20,7 @@ class Tokenizer:
         info = np.zeros(4, np.int32)
         N.check(L.mp_tok_info(self._h, info.ctypes.data), "tokenizer info")
         self.n_vocab, self.bos, self.eos, self.eot = (int(v) for v in info)
+        self.add_bos = bool(N.check(L.mp_tok_add_bos(self._h), "tokenizer add_bos"))   # BOS in front of a prompt by default
 
     def close(self):
         if getattr(self, "_h", None):
