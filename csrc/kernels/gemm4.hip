@@ -36,29 +36,38 @@ static void run(int ptype, const Gemm4Plan& pl, int epi, const GemvParams& p, co
   }
 }
 
-bool launch_gemm4(int ptype, int epi, GemvParams p, hipStream_t st, bool allow_split) {
-  const Gemm4Plan pl = plan_gemm4(ptype, epi, p.M, p.ntiles, p.nsb, allow_split, false);
-  if (!pl.ok) return false;
+void run_gemm4(int ptype, const Gemm4Plan& pl, int epi, const GemvParams& p, hipStream_t st) {
   run(ptype, pl, epi, p, nullptr, st);
-  return true;
 }
 
-// split-K partial stores: split s writes scratch + s * M * ldp; false (nothing launched) when the
-// shape does not split or the partials do not fit scratch_n floats.  init: the reduction writes
-// Y = p.bias + the partials instead of adding them onto Y (which then needs no fill)
-bool launch_gemm4_splitk(int ptype, GemvParams p, float* scratch, size_t scratch_n, hipStream_t st, bool reduce,
-                         int* nsplit_out, bool init) {
+bool launch_gemm4(int ptype, int epi, GemvParams p, hipStream_t st, bool allow_split) {
+  const Gemm4Plan pl = plan_gemm4(ptype, epi, p.M, p.ntiles, p.nsb, allow_split, false);
+  if (pl.ok) run_gemm4(ptype, pl, epi, p, st);
+  return pl.ok;
+}
+
+// split-K partial stores of a partial-store plan: split s writes scratch + s * M * ldp.  init: the
+// reduction writes Y = p.bias + the partials instead of adding them onto Y (which then needs no fill)
+void run_gemm4_splitk(int ptype, const Gemm4Plan& pl, GemvParams p, float* scratch, hipStream_t st, bool reduce, bool init) {
   if (init && !reduce) throw std::runtime_error("gemm4 split-K: the init form reduces at once");
-  if (p.bias && !init) return false;
-  const Gemm4Plan pl = plan_gemm4(ptype, EPI_ATOMIC, p.M, p.ntiles, p.nsb, true, true);
+  if (p.bias && !init) throw std::runtime_error("gemm4 split-K: a bias takes the init form");
   const int ldp = p.ntiles * 16;
-  if (!pl.ok || (size_t)pl.nsplit * p.M * ldp > scratch_n) return false;
   GemvParams q = p;
   q.Y = scratch; q.ldy = ldp; q.split_stride = (int64_t)p.M * ldp;
   q.bias = nullptr;   // (init: added by the reduction)
   run(ptype, pl, EPI_STORE, q, nullptr, st);
-  if (nsplit_out) *nsplit_out = pl.nsplit;
   if (reduce) launch_splitk_reduce(scratch, pl.nsplit, q.split_stride, ldp, p.M, p.n_valid, p.Y, p.ldy, st, init, p.bias);
+}
+
+// plans itself; false (nothing launched) when the shape does not split or the partials do not fit
+// scratch_n floats
+bool launch_gemm4_splitk(int ptype, GemvParams p, float* scratch, size_t scratch_n, hipStream_t st, bool reduce,
+                         int* nsplit_out, bool init) {
+  if (p.bias && !init) return false;
+  const Gemm4Plan pl = plan_gemm4(ptype, EPI_ATOMIC, p.M, p.ntiles, p.nsb, true, true);
+  if (!pl.ok || (size_t)pl.nsplit * p.M * p.ntiles * 16 > scratch_n) return false;
+  run_gemm4_splitk(ptype, pl, p, scratch, st, reduce, init);
+  if (nsplit_out) *nsplit_out = pl.nsplit;
   return true;
 }
 

@@ -172,9 +172,7 @@ const char* mp_model_config_json(const char* gguf_path) {
 int mp_op_gemm(int ptype, int epi, const void* W, int ntiles, int nsb, const void* X, int ldx, int M, void* Y,
                int ldy, void* H, int ldh, int n_valid, void* stream) {
   API_TRY
-  GemvParams p{};
-  p.W = (const uint8_t*)W; p.X = (const f16*)X; p.ldx = ldx; p.M = M; p.Y = (float*)Y; p.ldy = ldy;
-  p.H = (f16*)H; p.ldh = ldh; p.ntiles = ntiles; p.nsb = nsb; p.n_valid = n_valid;
+  GemvParams p = gemv_params(W, ntiles, nsb, X, ldx, M, Y, ldy, H, ldh, n_valid);
   launch_gemm(ptype, epi, p, (hipStream_t)stream);
   return 0;
   API_CATCH(-1)
@@ -183,9 +181,7 @@ int mp_op_gemm(int ptype, int epi, const void* W, int ntiles, int nsb, const voi
 int mp_op_gemm3(int ptype, int epi, const void* W, int ntiles, int nsb, const void* X, int ldx, int M, void* Y,
                 int ldy, void* H, int ldh, int n_valid, int allow_split, void* stream) {
   API_TRY
-  GemvParams p{};
-  p.W = (const uint8_t*)W; p.X = (const f16*)X; p.ldx = ldx; p.M = M; p.Y = (float*)Y; p.ldy = ldy;
-  p.H = (f16*)H; p.ldh = ldh; p.ntiles = ntiles; p.nsb = nsb; p.n_valid = n_valid;
+  GemvParams p = gemv_params(W, ntiles, nsb, X, ldx, M, Y, ldy, H, ldh, n_valid);
   launch_gemm3(ptype, epi, p, (hipStream_t)stream, allow_split != 0);
   HIP_OK(hipGetLastError());
   return 0;
@@ -195,9 +191,7 @@ int mp_op_gemm3(int ptype, int epi, const void* W, int ntiles, int nsb, const vo
 int mp_op_gemm4(int ptype, int epi, const void* W, int ntiles, int nsb, const void* X, int ldx, int M, void* Y,
                 int ldy, void* H, int ldh, int n_valid, int allow_split, void* stream) {
   API_TRY
-  GemvParams p{};
-  p.W = (const uint8_t*)W; p.X = (const f16*)X; p.ldx = ldx; p.M = M; p.Y = (float*)Y; p.ldy = ldy;
-  p.H = (f16*)H; p.ldh = ldh; p.ntiles = ntiles; p.nsb = nsb; p.n_valid = n_valid;
+  GemvParams p = gemv_params(W, ntiles, nsb, X, ldx, M, Y, ldy, H, ldh, n_valid);
   if (!launch_gemm4(ptype, epi, p, (hipStream_t)stream, allow_split != 0)) throw std::runtime_error("gemm4: unsupported type");
   HIP_OK(hipGetLastError());
   return 0;
@@ -279,9 +273,7 @@ int mp_op_moe_router(const void* X, int ldx, const void* R, int K, int E, int M,
 int mp_op_gemm4_splitk(int ptype, const void* W, int ntiles, int nsb, const void* X, int ldx, int M, void* Y, int ldy,
                        int n_valid, void* scratch, int64_t scratch_n, void* stream) {
   API_TRY
-  GemvParams p{};
-  p.W = (const uint8_t*)W; p.X = (const f16*)X; p.ldx = ldx; p.M = M; p.Y = (float*)Y; p.ldy = ldy;
-  p.ntiles = ntiles; p.nsb = nsb; p.n_valid = n_valid;
+  GemvParams p = gemv_params(W, ntiles, nsb, X, ldx, M, Y, ldy, nullptr, 0, n_valid);
   int ns = 0;
   if (!launch_gemm4_splitk(ptype, p, (float*)scratch, (size_t)scratch_n, (hipStream_t)stream, true, &ns)) return 0;
   HIP_OK(hipGetLastError());
@@ -316,9 +308,7 @@ int mp_op_quant_i8(const void* X, int ldx, int M, int K, void* Q, int ldq, void*
 int mp_op_gemm3_i8(int epi, const void* W, int ntiles, int nsb, const void* Q, int ldq, int M, void* Y, int ldy,
                    void* H, int ldh, int n_valid, const void* xs, const void* ws, int allow_split, void* stream) {
   API_TRY
-  GemvParams p{};
-  p.W = (const uint8_t*)W; p.X = (const f16*)Q; p.ldx = ldq; p.M = M; p.Y = (float*)Y; p.ldy = ldy;
-  p.H = (f16*)H; p.ldh = ldh; p.ntiles = ntiles; p.nsb = nsb; p.n_valid = n_valid;
+  GemvParams p = gemv_params(W, ntiles, nsb, Q, ldq, M, Y, ldy, H, ldh, n_valid);
   p.xscale = (const float*)xs; p.wscale = (const float*)ws;
   launch_gemm3(P_I8, epi, p, (hipStream_t)stream, allow_split != 0);
   HIP_OK(hipGetLastError());
@@ -344,9 +334,7 @@ int mp_reset_knob(const char* name) {
 int mp_op_gemv(int ptype, int epi, const void* W, int ntiles, int nsb, const void* X, int ldx, int M, void* Y,
                int ldy, void* H, int ldh, int n_valid, int nsplit, void* stream) {
   API_TRY
-  GemvParams p{};
-  p.W = (const uint8_t*)W; p.X = (const f16*)X; p.ldx = ldx; p.M = M; p.Y = (float*)Y; p.ldy = ldy;
-  p.H = (f16*)H; p.ldh = ldh; p.ntiles = ntiles; p.nsb = nsb; p.n_valid = n_valid;
+  GemvParams p = gemv_params(W, ntiles, nsb, X, ldx, M, Y, ldy, H, ldh, n_valid);
   if (M > 64) {
     for (int r0 = 0; r0 < M; r0 += 64) {
       GemvParams q = p;
@@ -389,9 +377,7 @@ int mp_op_gemv_fused(int ptype, int epi, const void* W, int ntiles, int nsb, con
                      int ldy, void* H, int ldh, int n_valid, int nsplit, const void* Xf, int ldxf, const void* gamma,
                      float eps, int d_norm, void* ssq, const void* bias, void* zero, int64_t zero_n, void* stream) {
   API_TRY
-  GemvParams p{};
-  p.W = (const uint8_t*)W; p.X = (const f16*)X; p.ldx = ldx; p.M = M; p.Y = (float*)Y; p.ldy = ldy;
-  p.H = (f16*)H; p.ldh = ldh; p.ntiles = ntiles; p.nsb = nsb; p.n_valid = n_valid;
+  GemvParams p = gemv_params(W, ntiles, nsb, X, ldx, M, Y, ldy, H, ldh, n_valid);
   p.Xf = (const float*)Xf; p.ldxf = ldxf; p.gamma = (const float*)gamma; p.eps = eps; p.d_norm = d_norm;
   p.ssq = (float*)ssq; p.bias = (const float*)bias; p.zero = (float*)zero; p.zero_n = zero_n;
   launch_gemv(ptype, epi, p, nsplit, (hipStream_t)stream);
@@ -406,9 +392,7 @@ int mp_op_gemvs(int ptype, int epi, const void* W, int ntiles, int nsb, const vo
                 int ldy, void* H, int ldh, int n_valid, const void* Xf, int ldxf, const void* gamma, float eps,
                 int d_norm, const void* bias, int G, int nsplit, int deterministic, void* stream) {
   API_TRY
-  GemvParams p{};
-  p.W = (const uint8_t*)W; p.X = (const f16*)X; p.ldx = ldx; p.M = M; p.Y = (float*)Y; p.ldy = ldy;
-  p.H = (f16*)H; p.ldh = ldh; p.ntiles = ntiles; p.nsb = nsb; p.n_valid = n_valid;
+  GemvParams p = gemv_params(W, ntiles, nsb, X, ldx, M, Y, ldy, H, ldh, n_valid);
   p.Xf = (const float*)Xf; p.ldxf = ldxf; p.gamma = (const float*)gamma; p.eps = eps; p.d_norm = d_norm;
   p.bias = (const float*)bias;
   launch_gemvs(ptype, epi, p, deterministic != 0, (hipStream_t)stream, G, nsplit);

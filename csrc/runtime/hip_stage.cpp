@@ -534,34 +534,18 @@ void HipStage::alloc_runtime() {
     pf_opart_ = (float*)zalloc((size_t)kPrefillMaxSplit * opt_.prefill_chunk * Hq * Dp_ * 4);
     pf_ml_ = (float*)zalloc((size_t)kPrefillMaxSplit * opt_.prefill_chunk * Hq * 2 * 4);
   }
-  if (opt_.gemm_splitk_store && opt_.prefill_gemm) {
-    // split-K partials of the M > 64 GEMMs (decode micro-batches and prompt chunks wider than 64 rows)
-    size_t need = 0;
-    auto acc = [&](const PackedMat& m) {
-      if (!m.d || is16(m.ptype)) return;
-      for (int M : {opt_.mb_size, opt_.prefill_chunk}) {
-        if (M <= 64) continue;
-        // the plan launch_gemm4_splitk will run (ok: it splits)
-        const Gemm4Plan pl = plan_gemm4(m.ptype, EPI_ATOMIC, M, (int)m.dims.ntiles, (int)m.dims.nsb, true, true);
-        if (pl.ok) need = std::max(need, (size_t)pl.nsplit * M * m.dims.ntiles * 16);
-      }
-    };
-    for (const LayerW& L : layers_) {
-      for (const MatSeg& sg : L.qkv) acc(sg.m);
-      acc(L.wo);
-      acc(L.down);
-    }
-    if (need) sk_part_ = (float*)dmalloc(need * 4);
-    sk_part_n_ = need;
-  }
-  if (opt_.deterministic) {
-    // fixed-order split-K: the largest nsplit x rows x N of any ATOMIC GEMV call (<= 64 rows each)
-    size_t need = 0;
+  {
+    // stored split-K partials, the largest any ATOMIC projection's route asks for (mat_route): sk_part_
+    // for the M > 64 GEMMs (decode micro-batches and prompt chunks wider than 64 rows; a chunk of
+    // another width that needs more runs split-K with atomics), det_part_ for the fixed-order GEMV
+    // splits of the deterministic mode (<= 64 rows per call)
     auto acc = [&](const PackedMat& m) {
       if (!m.d) return;
-      for (int M : {1, 2, 3, 4, 8, 16, 32, 64}) {
-        const int ns = det_splits((int)m.dims.ntiles, (int)m.dims.nsb, M, EPI_ATOMIC);
-        if (ns > 1) need = std::max(need, (size_t)ns * M * m.dims.ntiles * 16);
+      for (int M = 1; M <= std::max(opt_.mb_size, opt_.prefill_chunk); ++M) {
+        if (M > 64 && M != opt_.mb_size && M != opt_.prefill_chunk) continue;
+        const MatRoute r = mat_route(MatCall(m, EPI_ATOMIC, M).in(xn_, Kd_).split(), SIZE_MAX);
+        size_t& need = r.family == GemmRoute::GEMM4 ? sk_part_n_ : det_part_n_;
+        need = std::max(need, r.part_n);
       }
     };
     for (const LayerW& L : layers_) {
@@ -570,8 +554,8 @@ void HipStage::alloc_runtime() {
       acc(L.down);
       if (L.moe) acc(L.ex.router);
     }
-    if (need) det_part_ = (float*)zalloc(need * 4);
-    det_part_n_ = need;
+    if (sk_part_n_) sk_part_ = (float*)dmalloc(sk_part_n_ * 4);
+    if (det_part_n_) det_part_ = (float*)zalloc(det_part_n_ * 4);
   }
   // KV cache: a pool of kv_pages 64-token pages per layer + one TRASH page (id kv_pages) that
   // unmapped block-table entries point at (idle rows of a micro-batch still append K/V); the engine's
@@ -812,101 +796,121 @@ void HipStage::set_history(int mb, const std::vector<std::vector<int32_t>>& seqs
   HIP_OK(hipMemcpy(hist_cnt_ + (size_t)mb * B, cnt.data(), cnt.size() * 4, hipMemcpyHostToDevice));
 }
 
-// the GemvParams fields every launch on a packed matrix shares
-static GemvParams mat_params(const PackedMat& m, const f16* X, int ldx, int M, float* Y, int ldy, f16* H, int ldh,
-                             int n_valid) {
-  GemvParams p{};
-  p.W = m.d; p.X = X; p.ldx = ldx; p.M = M; p.Y = Y; p.ldy = ldy; p.H = H; p.ldh = ldh;
-  p.ntiles = (int)m.dims.ntiles; p.nsb = (int)m.dims.nsb; p.n_valid = n_valid;
-  return p;
-}
-
+// The kernel family of a projection call.  c.small (M <= 4): gemvs, unless its LDS plan overflows:
+// deterministic mode cannot split K over grid.y, so a wide K (70B down: 28672) with M >= 3 rows
+// overflows LDS and takes the v2 GEMV with its fixed-order split-K reduction instead.
 // Up to 64 rows (decode micro-batches, short prompt chunks): the dequant GEMV.  Above: gemm4 for the
 // types it takes, gemm3 for 16-bit weights, the 64 x 64 GEMM for the rest (Q4_0) -- except its wide
 // gate/up (>= 192 workgroups of 16 tiles), which the two-tile GEMV beats per 64 rows
 // (profiles/r1g_prefill_gemm_vs_gemv.txt).  How the selection got here: docs/PERFORMANCE.md, 3.1.
-HipStage::GemmRoute HipStage::gemm_route(const PackedMat& m, int epi, int M, bool have_x) const {
-  if (M <= 64 || !opt_.prefill_gemm) return GemmRoute::GEMV;
-  if (m.i8 && xq_ && have_x) return GemmRoute::I8;
+HipStage::GemmRoute HipStage::gemm_route(const MatCall& c) const {
+  const PackedMat& m = *c.m;
+  if (c.small) {
+    const GemvsPlan pl = plan_gemvs((int)m.dims.ntiles, (int)m.dims.nsb, c.M, c.epi, false, opt_.deterministic);
+    if (c.Xf || pl.lds + (size_t)pl.sb_per_split * 64 <= 150 * 1024) return GemmRoute::GEMVS;   // (+ the single-row form's table)
+  }
+  if (c.M <= 64 || !opt_.prefill_gemm) return GemmRoute::GEMV;
+  if (m.i8 && xq_ && c.X) return GemmRoute::I8;
   const int gv = opt_.prefill_gemm_v == 2 ? 4 : opt_.prefill_gemm_v != 0 ? opt_.prefill_gemm_v : is16(m.ptype) ? 3 : 4;
   if (gv == 4 && gemm4_supported(m.ptype)) return GemmRoute::GEMM4;
   if (gv == 3) return GemmRoute::GEMM3;
-  const bool wide_swiglu = epi == EPI_SWIGLU && m.dims.ntiles / 16 >= 192;
+  const bool wide_swiglu = c.epi == EPI_SWIGLU && m.dims.ntiles / 16 >= 192;
   return wide_swiglu ? GemmRoute::GEMV : GemmRoute::GEMM1;
 }
 
-void HipStage::gemv(const PackedMat& m, int epi, const f16* X, int ldx, int M, float* Y, int ldy, f16* H, int ldh,
-                    int n_valid, bool allow_split, hipStream_t st, const GemvParams* extras) {
-  switch (gemm_route(m, epi, M, X != nullptr)) {
-    case GemmRoute::I8: {
-      // int8_gemm: x rows quantized per row, int8 MFMA against the re-quantized copy (gemm3<P_I8>)
-      const int K = (int)m.dims.nsb * 256;
-      if (X != xq_src_ || M != xq_rows_) {   // not already quantized by norm_x / the previous GEMM on X
-        launch_quant_rows_i8(X, ldx, M, K, xq_, xq_ld_, xqs_, st);
-        xq_src_ = X;
-        xq_rows_ = M;
-      }
-      GemvParams p = mat_params(m, reinterpret_cast<const f16*>(xq_), xq_ld_, M, Y, ldy, H, ldh, n_valid);
-      p.W = m.i8; p.xscale = xqs_; p.wscale = m.i8_ws;
-      launch_gemm3(P_I8, epi, p, st, allow_split && !opt_.deterministic);
-      return;
+HipStage::MatRoute HipStage::mat_route(const MatCall& c, size_t sk_cap) const {
+  const int nt = (int)c.m->dims.ntiles, nsb = (int)c.m->dims.nsb;
+  MatRoute r;
+  r.family = gemm_route(c);
+  if (r.family == GemmRoute::GEMM4) {
+    // split-K shapes store per-split partials while they fit sk_cap floats; the rest run whole-K or,
+    // outside the deterministic mode, split with atomics
+    const bool want = opt_.gemm_splitk_store && c.epi == EPI_ATOMIC && c.allow_split;
+    auto plan = [&](bool store) {
+      return plan_gemm4(c.m->ptype, c.epi, c.M, nt, nsb, store || (c.allow_split && !opt_.deterministic), store);
+    };
+    r.g4 = plan(want);
+    r.part_n = want && r.g4.ok ? (size_t)r.g4.nsplit * c.M * nt * 16 : 0;
+    r.store = r.part_n && r.part_n <= sk_cap;
+    if (!r.store) r.part_n = 0;
+    if (want && !r.store) r.g4 = plan(false);
+  } else if (r.family == GemmRoute::GEMV && c.M <= 64) {   // (wider calls run as 64-row slices, each routed)
+    r.ns = c.allow_split ? gemv_auto_split(nt, nsb, c.M, c.epi) : 1;
+    if (opt_.deterministic && c.epi == EPI_ATOMIC && c.allow_split) {
+      // fixed order: the split count launch_gemv will actually use (its rounding reproduced)
+      const int per = (nsb + std::max(1, r.ns) - 1) / std::max(1, r.ns), ns = (nsb + per - 1) / per;
+      r.det = ns > 1;
+      if (r.det) { r.ns = ns; r.part_n = (size_t)ns * c.M * nt * 16; }
     }
-    case GemmRoute::GEMM4: {
-      // split-K shapes store per-split partials (into the residual x: absorbed by the next RMSNorm),
-      // the rest run whole-K
-      GemvParams p = mat_params(m, X, ldx, M, Y, ldy, H, ldh, n_valid);
-      const bool sk = opt_.gemm_splitk_store && sk_part_ && epi == EPI_ATOMIC && allow_split;
-      const bool defer = sk && Y == sk_defer_;
-      if (sk) flush_sk(st);
-      int ns = 0;
-      if (sk_init_) p.bias = sk_init_bias_;
-      if (sk && launch_gemm4_splitk(m.ptype, p, sk_part_, sk_part_n_, st, !defer, &ns, sk_init_)) {
-        if (defer) sk_pend_ = SkPending{Y, M, n_valid, ldy, ns, p.ntiles * 16, (int64_t)M * p.ntiles * 16};
-      } else if (sk_init_) {   // Y holds no fill to accumulate onto
-        throw std::runtime_error("gemv: the split-K plan took the partial-store route, the launch did not");
-      } else {
-        launch_gemm4(m.ptype, epi, p, st, allow_split && !opt_.deterministic);
-      }
-      return;
-    }
-    case GemmRoute::GEMM3:
-      launch_gemm3(m.ptype, epi, mat_params(m, X, ldx, M, Y, ldy, H, ldh, n_valid), st, allow_split && !opt_.deterministic);
-      return;
-    case GemmRoute::GEMM1:
-      launch_gemm(m.ptype, epi, mat_params(m, X, ldx, M, Y, ldy, H, ldh, n_valid), st);
-      return;
-    case GemmRoute::GEMV: break;
   }
-  for (int r0 = 0; r0 < M; r0 += 64) {
-    GemvParams p = mat_params(m, X + (size_t)r0 * ldx, ldx, std::min(64, M - r0), Y ? Y + (size_t)r0 * ldy : nullptr, ldy,
-                              H ? H + (size_t)r0 * ldh : nullptr, ldh, n_valid);
-    if (extras) {   // fused norm / bias / zero-fill: small M only (one pass of this loop)
-      p.Xf = extras->Xf; p.ldxf = extras->ldxf; p.gamma = extras->gamma; p.eps = extras->eps;
-      p.d_norm = extras->d_norm; p.bias = extras->bias; p.zero = extras->zero; p.zero_n = extras->zero_n;
-      p.ssq = extras->ssq;
-    }
-    const int nsplit = allow_split ? gemv_auto_split(p.ntiles, p.nsb, p.M, epi) : 1;
-    const int ns = det_splits(p.ntiles, p.nsb, p.M, epi, allow_split);
-    if (opt_.deterministic && epi == EPI_ATOMIC && ns > 1) {
-      // split s stores its partial to det_part_[s]; then one fixed-order reduction adds them into Y
-      const int ldp = p.ntiles * 16;
-      if ((size_t)ns * p.M * ldp > det_part_n_) throw std::runtime_error("deterministic split-K scratch too small");
-      GemvParams q = p;
-      q.Y = det_part_; q.ldy = ldp; q.split_stride = (int64_t)p.M * ldp;
-      launch_gemv(m.ptype, EPI_STORE, q, ns, st);
-      launch_splitk_reduce(det_part_, ns, (int64_t)p.M * ldp, ldp, p.M, n_valid, p.Y, ldy, st);
-      continue;
-    }
-    launch_gemv(m.ptype, epi, p, nsplit, st);
-  }
+  return r;
 }
 
-// Whether gemv(m, EPI_ATOMIC, M rows, allow_split) will store split-K partials and reduce them: the
-// launcher's own plan call and scratch bound (launch_gemm4_splitk)
-bool HipStage::splitk_store_route(const PackedMat& m, int M) const {
-  if (!opt_.gemm_splitk_store || !sk_part_ || gemm_route(m, EPI_ATOMIC, M, true) != GemmRoute::GEMM4) return false;
-  const Gemm4Plan pl = plan_gemm4(m.ptype, EPI_ATOMIC, M, (int)m.dims.ntiles, (int)m.dims.nsb, true, true);
-  return pl.ok && (size_t)pl.nsplit * M * m.dims.ntiles * 16 <= sk_part_n_;
+GemvParams HipStage::params(const MatCall& c) const {
+  const PackedMat& m = *c.m;
+  GemvParams p = gemv_params(m.d, (int)m.dims.ntiles, (int)m.dims.nsb, c.X, c.ldx, c.M, c.Y, c.ldy, c.H, c.ldh, c.n_valid);
+  if (c.Xf) { p.Xf = c.Xf; p.ldxf = cfg_.d_model; p.gamma = c.gamma; p.eps = cfg_.eps; p.d_norm = cfg_.d_model; }
+  p.bias = c.bias; p.zero = c.zero; p.zero_n = c.zero_n; p.ssq = c.ssq; p.qa = c.qa;
+  return p;
+}
+
+void HipStage::gemv(const MatCall& c, hipStream_t st) {
+  const PackedMat& m = *c.m;
+  const MatRoute r = mat_route(c, sk_part_n_);
+  const bool init = c.deliver == SplitK::INIT, defer = c.deliver == SplitK::DEFER;
+  const bool vec = r.family == GemmRoute::GEMV || r.family == GemmRoute::GEMVS;   // the families with fusions
+  // a field the route's kernels do not take is an error, never dropped
+  if ((!vec && (c.Xf || c.zero || c.ssq || (c.bias && !(init && r.store)))) || (init && !r.store) ||
+      (c.qa.pos && r.family != GemmRoute::GEMVS) || (r.family == GemmRoute::GEMVS && (c.zero || c.ssq)) ||
+      (r.family == GemmRoute::GEMV && c.M > 64 && (c.Xf || c.zero)))
+    throw std::runtime_error("gemv: the call sets a field its route cannot honour");
+  GemvParams p = params(c);
+  const bool atomics = c.allow_split && !opt_.deterministic;
+  switch (r.family) {
+    case GemmRoute::I8: {
+      // int8_gemm: x rows quantized per row, int8 MFMA against the re-quantized copy (gemm3<P_I8>)
+      if (c.X != xq_src_ || c.M != xq_rows_) {   // not already quantized by norm_x / the previous GEMM on X
+        launch_quant_rows_i8(c.X, c.ldx, c.M, p.nsb * 256, xq_, xq_ld_, xqs_, st);
+        xq_src_ = c.X;
+        xq_rows_ = c.M;
+      }
+      p.X = reinterpret_cast<const f16*>(xq_); p.ldx = xq_ld_;
+      p.W = m.i8; p.xscale = xqs_; p.wscale = m.i8_ws;
+      launch_gemm3(P_I8, c.epi, p, st, atomics);
+      return;
+    }
+    case GemmRoute::GEMM4:
+      if (!r.g4.ok) throw std::runtime_error("gemv: no gemm4 launch plan for this projection");
+      if (!r.store) return run_gemm4(m.ptype, r.g4, c.epi, p, st);
+      flush_sk(st);   // sk_part_ is about to be rewritten
+      run_gemm4_splitk(m.ptype, r.g4, p, sk_part_, st, !defer, init);
+      // (into the residual x: absorbed by the next RMSNorm)
+      if (defer) sk_pend_ = SkPending{c.Y, c.M, c.n_valid, c.ldy, r.g4.nsplit, p.ntiles * 16, (int64_t)c.M * p.ntiles * 16};
+      return;
+    case GemmRoute::GEMM3: return launch_gemm3(m.ptype, c.epi, p, st, atomics);
+    case GemmRoute::GEMM1: return launch_gemm(m.ptype, c.epi, p, st);
+    case GemmRoute::GEMVS: return launch_gemvs(m.ptype, c.epi, p, opt_.deterministic, st);
+    case GemmRoute::GEMV: break;
+  }
+  if (c.M > 64) {
+    for (int r0 = 0; r0 < c.M; r0 += 64) {
+      MatCall s = c;
+      s.M = std::min(64, c.M - r0);
+      s.X = c.X + (size_t)r0 * c.ldx;
+      if (c.Y) s.Y = c.Y + (size_t)r0 * c.ldy;
+      if (c.H) s.H = c.H + (size_t)r0 * c.ldh;
+      gemv(s, st);
+    }
+    return;
+  }
+  if (!r.det) return launch_gemv(m.ptype, c.epi, p, r.ns, st);
+  // split s stores its partial to det_part_[s]; then one fixed-order reduction adds them into Y
+  const int ldp = p.ntiles * 16;
+  if (r.part_n > det_part_n_) throw std::runtime_error("deterministic split-K scratch too small");
+  GemvParams q = p;
+  q.Y = det_part_; q.ldy = ldp; q.split_stride = (int64_t)c.M * ldp;
+  launch_gemv(m.ptype, EPI_STORE, q, r.ns, st);
+  launch_splitk_reduce(det_part_, r.ns, q.split_stride, ldp, c.M, c.n_valid, c.Y, c.ldy, st);
 }
 
 void HipStage::flush_sk(hipStream_t st) {
@@ -968,7 +972,7 @@ void HipStage::moe_ffn_rows(const LayerW& L, int r0, int M, hipStream_t st, floa
     if (L.ex.router_dense && Kd_ >= Kr)
       launch_router_logits(xn, Kd_, L.ex.router_dense, Kr, E, M, logits, moe_ld_, st);
     else
-      gemv(L.ex.router, EPI_ATOMIC, xn, Kd_, M, logits, moe_ld_, nullptr, 0, E, true, st);
+      gemv(MatCall(L.ex.router, EPI_ATOMIC, M).in(xn, Kd_).out(logits, moe_ld_, E).split(), st);
     launch_moe_route(rp, st);
   }
   MoeGemvParams gp{};
@@ -999,18 +1003,33 @@ void HipStage::moe_ffn_rows(const LayerW& L, int r0, int M, hipStream_t st, floa
   if (opt_.deterministic) launch_moe_combine(moe_yslot_, d, k, M, d, x + (size_t)r0 * d, d, st);
 }
 
-// split count launch_gemv will actually use (deterministic mode reproduces its rounding)
-int HipStage::det_splits(int ntiles, int nsb, int M, int epi, bool allow_split) const {
-  if (!allow_split) return 1;
-  int ns = std::max(1, gemv_auto_split(ntiles, nsb, M, epi));
-  const int per = (nsb + ns - 1) / ns;
-  return (nsb + per - 1) / per;
+void HipStage::ffn_tail(const LayerW& L, int M, float* x, bool small, bool fused, hipStream_t st) {
+  const int d = cfg_.d_model, F = cfg_.d_ff;
+  auto up = [&](const PackedMat& m, int epi) {
+    MatCall c = MatCall(m, epi, M).gemvs(small);
+    return fused ? c.in_norm(x, L.ffn_norm) : c.in(xn_, Kd_);
+  };
+  if (L.fused_gateup) {
+    gemv(up(L.gateup, EPI_SWIGLU).out_h(h_, Kff_, F), st);
+  } else {
+    gemv(up(L.gate, EPI_STORE).out(gu_, 2 * F, F), st);
+    gemv(up(L.up, EPI_STORE).out(gu_ + F, 2 * F, F), st);
+    launch_swiglu(gu_, 2 * F, F, M, h_, Kff_, st);
+  }
+  // stored partials: absorbed by the next layer's attention norm (or flushed after the last layer)
+  gemv(MatCall(L.down, EPI_ATOMIC, M).in(h_, Kff_).out(x, d, d).split(SplitK::DEFER).gemvs(small), st);
 }
 
-void HipStage::layer_forward(int li, int M, float* x, const int32_t* pos, const int32_t* kvlen,
-                             const int32_t* slot, bool decode, hipStream_t st) {
+void HipStage::layer_forward(int li, float* x, const Fwd& f) {
   const LayerW& L = layers_[li];
-  const int d = cfg_.d_model;
+  const int d = cfg_.d_model, M = f.M;
+  hipStream_t st = f.st;
+  // q|k|v segment s from the f16 rows xn_, or (norm) from the residual with the attention norm fused
+  auto qkv_seg = [&](const MatSeg& s, int epi, bool norm) {
+    MatCall c = MatCall(s.m, epi, M).out(qkv_ + s.y_off, qkv_n_, (int)s.m.dims.N);
+    return norm ? c.in_norm(x, L.attn_norm) : c.in(xn_, Kd_);
+  };
+  const MatCall wo = MatCall(L.wo, EPI_ATOMIC, M).in(attn_, Ko_).out(x, d, d);
   if (small_path(M)) {
     // gemvs: RMSNorms fused into the qkv / gate-up GEMVs, complete outputs per workgroup (q|k|v
     // stored with its bias, o / down added into the residual by their single owner)
@@ -1018,57 +1037,39 @@ void HipStage::layer_forward(int li, int M, float* x, const int32_t* pos, const 
     // decode: RoPE and the KV append in the qkv GEMV's epilogue (QkvAppend), so the attention starts
     // from rotated q and a complete cache (no dependent position -> page -> append chain of its own)
     // (a q/k-normed layer needs the complete projection before the rotation: no QkvAppend)
-    const bool pre = decode && opt_.fused_attn && knob(KNOB_ATTN_PRE) && !opt_.deterministic && !L.q_norm &&
-                     attn_decode_pre_ok(decode_attn_params(li, M, pos, slot, false));
-    QkvAppend qa{};
-    if (pre) {
-      qa.pos = pos; qa.slot0 = dec_slot0_; qa.block_table = block_table_; qa.max_pages = max_pages_;
-      qa.rope_cs = rope_cs_; qa.k_cache = kc_[li]; qa.v_cache = vc_[li];
-      qa.Hq = cfg_.n_head; qa.Hkv = cfg_.n_head_kv; qa.hd = cfg_.head_dim; qa.Dp = Dp_; qa.kv_fp8 = opt_.kv_fp8;
-    }
+    const bool pre = f.decode && opt_.fused_attn && knob(KNOB_ATTN_PRE) && !opt_.deterministic && !L.q_norm &&
+                     attn_decode_pre_ok(decode_attn_params(li, f, false));
+    auto seg = [&](const MatSeg& s) {
+      MatCall c = qkv_seg(s, EPI_STORE, true).gemvs(true);
+      c.bias = L.qkv_bias ? L.qkv_bias + s.y_off : nullptr;
+      if (pre) {
+        c.qa.pos = f.pos; c.qa.slot0 = f.slot0; c.qa.block_table = block_table_; c.qa.max_pages = max_pages_;
+        c.qa.rope_cs = rope_cs_; c.qa.k_cache = kc_[li]; c.qa.v_cache = vc_[li]; c.qa.col0 = (int)s.y_off;
+        c.qa.Hq = cfg_.n_head; c.qa.Hkv = cfg_.n_head_kv; c.qa.hd = cfg_.head_dim; c.qa.Dp = Dp_; c.qa.kv_fp8 = opt_.kv_fp8;
+      }
+      return c;
+    };
     const int first = L.qkv.size() == 2 && gemvs2_supported(L.qkv[1].m.ptype, L.qkv[0].m.ptype) ? 1 : 0;
     if (two && L.qkv.size() == 2 && gemvs2_supported(L.qkv[first].m.ptype, L.qkv[1 - first].m.ptype) &&
         L.qkv[0].m.dims.nsb == L.qkv[1].m.dims.nsb) {
       // mixed-type q+k | v (Q4_K_M's Q6_K attn_v): both segments in one launch
-      GemvParams ps[2];
-      for (int i = 0; i < 2; ++i) {
-        const MatSeg& sg = L.qkv[i == 0 ? first : 1 - first];
-        GemvParams& q = ps[i];
-        q.W = sg.m.d; q.M = M; q.Y = qkv_ + sg.y_off; q.ldy = qkv_n_;
-        q.ntiles = (int)sg.m.dims.ntiles; q.nsb = (int)sg.m.dims.nsb; q.n_valid = (int)sg.m.dims.N;
-        q.bias = L.qkv_bias ? L.qkv_bias + sg.y_off : nullptr;
-        q.Xf = x; q.ldxf = d; q.gamma = L.attn_norm; q.eps = cfg_.eps; q.d_norm = d;
-        if (pre) { q.qa = qa; q.qa.col0 = (int)sg.y_off; }
-      }
-      launch_gemvs2(L.qkv[first].m.ptype, L.qkv[1 - first].m.ptype, ps[0], ps[1], st);
+      launch_gemvs2(L.qkv[first].m.ptype, L.qkv[1 - first].m.ptype, params(seg(L.qkv[first])),
+                    params(seg(L.qkv[1 - first])), st);
     } else {
-      for (const MatSeg& s : L.qkv) {
-        QkvAppend q = qa;
-        q.col0 = (int)s.y_off;
-        gemv_small(s.m, EPI_STORE, nullptr, 0, x, L.attn_norm, M, qkv_ + s.y_off, qkv_n_, nullptr, 0, (int)s.m.dims.N,
-                   L.qkv_bias ? L.qkv_bias + s.y_off : nullptr, st, pre ? &q : nullptr);
-      }
+      for (const MatSeg& s : L.qkv) gemv(seg(s), st);
     }
     qk_norm(L, M, st);
-    if (!(decode && attention_o(li, M, pos, slot, x, st, pre))) {
-      attention(li, M, pos, kvlen, slot, decode, st, false, pre);
-      gemv_small(L.wo, EPI_ATOMIC, attn_, Ko_, nullptr, nullptr, M, x, d, nullptr, 0, d, nullptr, st);
+    if (!(f.decode && attention_o(li, f, x, pre))) {
+      attention(li, f, false, pre);
+      gemv(MatCall(wo).split().gemvs(true), st);
     }
     if (L.moe) {
       launch_rmsnorm(x, d, L.ffn_norm, d, cfg_.eps, xn_, Kd_, M, moe_logits_, (int64_t)M * moe_ld_, st);
       xq_src_ = nullptr;
       moe_ffn(L, M, st, x);
-      return;
-    }
-    if (L.fused_gateup) {
-      gemv_small(L.gateup, EPI_SWIGLU, nullptr, 0, x, L.ffn_norm, M, nullptr, 0, h_, Kff_, cfg_.d_ff, nullptr, st);
     } else {
-      const int F = cfg_.d_ff;
-      gemv_small(L.gate, EPI_STORE, nullptr, 0, x, L.ffn_norm, M, gu_, 2 * F, nullptr, 0, F, nullptr, st);
-      gemv_small(L.up, EPI_STORE, nullptr, 0, x, L.ffn_norm, M, gu_ + F, 2 * F, nullptr, 0, F, nullptr, st);
-      launch_swiglu(gu_, 2 * F, F, M, h_, Kff_, st);
+      ffn_tail(L, M, x, true, true, st);
     }
-    gemv_small(L.down, EPI_ATOMIC, h_, Kff_, nullptr, nullptr, M, x, d, nullptr, 0, d, nullptr, st);
     return;
   }
   // M <= 4 (fuse_norm): the RMSNorms are folded into the consuming GEMVs (gemv2.hip deferred
@@ -1079,15 +1080,12 @@ void HipStage::layer_forward(int li, int M, float* x, const int32_t* pos, const 
   const bool small = fuse_norm(M);
   // (a q/k-normed layer normalises final q|k|v values: it takes the standalone attn_norm; the o-proj's
   // zero side job below still clears the range, so the invariant holds for the next layer)
-  const bool qkv_deferred = small && decode && opt_.fused_attn && !L.q_norm;
-  GemvParams nx{};
-  nx.Xf = x; nx.ldxf = d; nx.eps = cfg_.eps; nx.d_norm = d;
+  const bool qkv_deferred = small && f.decode && opt_.fused_attn && !L.q_norm;
   if (qkv_deferred) {
     for (const MatSeg& s : L.qkv) {
-      GemvParams e = nx;
-      e.gamma = L.attn_norm;
-      e.ssq = &s == &L.qkv[0] ? ssq_ : nullptr;   // the sums of squares once per row
-      gemv(s.m, EPI_ATOMIC, nullptr, 0, M, qkv_ + s.y_off, qkv_n_, nullptr, 0, (int)s.m.dims.N, true, st, &e);
+      MatCall c = qkv_seg(s, EPI_ATOMIC, true).split();
+      c.ssq = &s == &L.qkv[0] ? ssq_ : nullptr;   // the sums of squares once per row
+      gemv(c, st);
     }
   } else {
     // When every qkv segment stores split-K partials, their reductions write q|k|v = bias + partials
@@ -1095,55 +1093,34 @@ void HipStage::layer_forward(int li, int M, float* x, const int32_t* pos, const 
     int covered = 0;
     bool init = !L.qkv.empty();
     for (const MatSeg& s : L.qkv) {
-      init = init && s.y_off == covered && splitk_store_route(s.m, M);
+      init = init && s.y_off == covered && mat_route(qkv_seg(s, EPI_ATOMIC, false).split(), sk_part_n_).store;
       covered += (int)s.m.dims.N;
     }
     init = init && covered == qkv_n_;
     if (init) norm_x(x, L.attn_norm, M, nullptr, 0, st);
     else norm_x(x, L.attn_norm, M, qkv_, (int64_t)M * qkv_n_, st, L.qkv_bias, qkv_n_);
     for (const MatSeg& s : L.qkv) {
-      sk_init_ = init;
-      sk_init_bias_ = init && L.qkv_bias ? L.qkv_bias + s.y_off : nullptr;
-      gemv(s.m, EPI_ATOMIC, xn_, Kd_, M, qkv_ + s.y_off, qkv_n_, nullptr, 0, (int)s.m.dims.N, true, st);
-      sk_init_ = false;
-      sk_init_bias_ = nullptr;
+      MatCall c = qkv_seg(s, EPI_ATOMIC, false).split(init ? SplitK::INIT : SplitK::ADD);
+      if (init && L.qkv_bias) c.bias = L.qkv_bias + s.y_off;
+      gemv(c, st);
     }
   }
   qk_norm(L, M, st);
-  attention(li, M, pos, kvlen, slot, decode, st, qkv_deferred);
+  attention(li, f, qkv_deferred);
   if (small) {
-    GemvParams z{};
-    z.zero = ssq_; z.zero_n = 64 + (int64_t)M * qkv_n_;
-    gemv(L.wo, EPI_ATOMIC, attn_, Ko_, M, x, d, nullptr, 0, d, true, st, &z);
+    MatCall c = MatCall(wo).split();
+    c.zero = ssq_; c.zero_n = 64 + (int64_t)M * qkv_n_;
+    gemv(c, st);
   } else {
-    sk_defer_ = x;
-    gemv(L.wo, EPI_ATOMIC, attn_, Ko_, M, x, d, nullptr, 0, d, true, st);
-    sk_defer_ = nullptr;
+    gemv(MatCall(wo).split(SplitK::DEFER), st);
     if (opt_.fused_norm && li + 1 == (int)layers_.size())
       HIP_OK(hipMemsetAsync(ssq_, 0, (64 + (size_t)M * qkv_n_) * 4, st));
   }
   const bool ffn_fused = small && !L.moe;
   // MoE: the same launch clears the router logits, which the router GEMV then accumulates split-K
   if (!ffn_fused) norm_x(x, L.ffn_norm, M, L.moe ? moe_logits_ : nullptr, L.moe ? (int64_t)M * moe_ld_ : 0, st);
-  if (L.moe) {
-    moe_ffn(L, M, st, x);
-    return;
-  }
-  GemvParams fx = nx;
-  fx.gamma = L.ffn_norm;
-  const GemvParams* fe = ffn_fused ? &fx : nullptr;
-  const f16* xin = ffn_fused ? nullptr : xn_;
-  if (L.fused_gateup) {
-    gemv(L.gateup, EPI_SWIGLU, xin, Kd_, M, nullptr, 0, h_, Kff_, cfg_.d_ff, false, st, fe);
-  } else {
-    const int F = cfg_.d_ff;
-    gemv(L.gate, EPI_STORE, xin, Kd_, M, gu_, 2 * F, nullptr, 0, F, false, st, fe);
-    gemv(L.up, EPI_STORE, xin, Kd_, M, gu_ + F, 2 * F, nullptr, 0, F, false, st, fe);
-    launch_swiglu(gu_, 2 * F, F, M, h_, Kff_, st);
-  }
-  sk_defer_ = x;   // absorbed by the next layer's attention norm (or flushed after the last layer)
-  gemv(L.down, EPI_ATOMIC, h_, Kff_, M, x, d, nullptr, 0, d, true, st);
-  sk_defer_ = nullptr;
+  if (L.moe) moe_ffn(L, M, st, x);
+  else ffn_tail(L, M, x, false, ffn_fused, st);
 }
 
 void HipStage::qk_norm(const LayerW& L, int M, hipStream_t st) {
@@ -1157,31 +1134,30 @@ void HipStage::qk_norm(const LayerW& L, int M, hipStream_t st) {
 // single-stream decode: attention + o-projection in one launch (attention.hip attn_o_kernel) while
 // the context is short enough for every workgroup of a kv head to compute that head's attention
 // itself; false: the caller runs the two-kernel path
-bool HipStage::attention_o(int li, int M, const int32_t* pos, const int32_t* slot, float* x, hipStream_t st, bool pre) {
+bool HipStage::attention_o(int li, const Fwd& f, float* x, bool pre) {
   const LayerW& L = layers_[li];
   if (!opt_.fused_attn || opt_.deterministic || opt_.attn_o_max_ctx <= 0 || opt_.max_ctx > opt_.attn_o_max_ctx)
     return false;
   // one split over the whole context (every workgroup of a kv head runs that head's attention)
-  DecodeAttnParams dp = decode_attn_params(li, M, pos, slot, false);
+  DecodeAttnParams dp = decode_attn_params(li, f, false);
   dp.split_len = (int)round_up(opt_.max_ctx, 128); dp.n_split = 1;
   dp.pre = pre;   // q rotated and K / V appended by the qkv GEMV
   AttnOParams op{};
   op.W = L.wo.d; op.ptype = L.wo.ptype; op.ntiles = (int)L.wo.dims.ntiles; op.nsb = (int)L.wo.dims.nsb;
   op.Y = x; op.ldy = cfg_.d_model; op.n_valid = cfg_.d_model;
   if (!attn_o_supported(dp, op)) return false;
-  launch_attn_o(dp, op, st);
+  launch_attn_o(dp, op, f.st);
   return true;
 }
 
-// the fused decode attention's parameters for layer li (decode rows: slots dec_slot0_ + t)
-DecodeAttnParams HipStage::decode_attn_params(int li, int M, const int32_t* pos, const int32_t* slot,
-                                              bool qkv_deferred) const {
+// the fused decode attention's parameters for layer li (decode rows: slots f.slot0 + t)
+DecodeAttnParams HipStage::decode_attn_params(int li, const Fwd& f, bool qkv_deferred) const {
   const LayerW& L = layers_[li];
   DecodeAttnParams dp{};
-  dp.qkv = qkv_; dp.ldqkv = qkv_n_; dp.pos = pos; dp.slot = slot; dp.block_table = block_table_;
-  dp.slot0 = dec_slot0_;
+  dp.qkv = qkv_; dp.ldqkv = qkv_n_; dp.pos = f.pos; dp.slot = f.slot; dp.block_table = block_table_;
+  dp.slot0 = f.slot0;
   dp.max_pages = max_pages_; dp.rope_cs = rope_cs_; dp.q_scale = 1.0f / std::sqrt((float)cfg_.head_dim);
-  dp.k_cache = kc_[li]; dp.v_cache = vc_[li]; dp.M = M; dp.Hq = cfg_.n_head; dp.Hkv = cfg_.n_head_kv;
+  dp.k_cache = kc_[li]; dp.v_cache = vc_[li]; dp.M = f.M; dp.Hq = cfg_.n_head; dp.Hkv = cfg_.n_head_kv;
   dp.kv_fp8 = opt_.kv_fp8;
   dp.hd = cfg_.head_dim; dp.Dp = Dp_; dp.split_len = opt_.attn_split_len; dp.n_split = n_split_;
   dp.o_part = o_part_; dp.ml_part = ml_part_; dp.counters = attn_cnt_; dp.out = attn_; dp.ldo = Ko_;
@@ -1189,10 +1165,14 @@ DecodeAttnParams HipStage::decode_attn_params(int li, int M, const int32_t* pos,
   return dp;
 }
 
-void HipStage::attention(int li, int M, const int32_t* pos, const int32_t* kvlen, const int32_t* slot, bool decode,
-                         hipStream_t st, bool qkv_deferred, bool pre) {
+void HipStage::attention(int li, const Fwd& f, bool qkv_deferred, bool pre) {
+  const int M = f.M;
+  const int32_t *pos = f.pos, *kvlen = f.kvlen, *slot = f.slot;
+  const bool decode = f.decode;
+  const std::vector<PrefillSeg>* segs = f.segs;
+  hipStream_t st = f.st;
   if (decode && opt_.fused_attn) {
-    DecodeAttnParams dp = decode_attn_params(li, M, pos, slot, qkv_deferred);
+    DecodeAttnParams dp = decode_attn_params(li, f, qkv_deferred);
     dp.pre = pre;
 #ifdef MIPIPE_TIMING_PROBES
     dp.probe = knob(KNOB_ATTN_PROBE);
@@ -1219,8 +1199,8 @@ void HipStage::attention(int li, int M, const int32_t* pos, const int32_t* kvlen
         }
       };
       int pages_needed = 0, n_tiles = 0;
-      if (segs_ && !segs_->empty()) {
-        for (const PrefillSeg& sg : *segs_) {
+      if (segs && !segs->empty()) {
+        for (const PrefillSeg& sg : *segs) {
           pages_needed = std::max(pages_needed, (sg.p0 + sg.T - 1) / 64 + 1);
           n_tiles += (sg.T + bt - 1) / bt;
         }
@@ -1232,9 +1212,9 @@ void HipStage::attention(int li, int M, const int32_t* pos, const int32_t* kvlen
         pa.n_split = prefill_attn_splits(n_tiles, cfg_.n_head_kv, pages_needed, kPrefillMaxSplit, &pa.split_pages);
         pa.o_part = pf_opart_; pa.ml_part = pf_ml_;
       }
-      if (segs_ && !segs_->empty()) {
+      if (segs && !segs->empty()) {
         int row = 0;
-        for (const PrefillSeg& sg : *segs_) { add_rows(row, sg.T); row += sg.T; }
+        for (const PrefillSeg& sg : *segs) { add_rows(row, sg.T); row += sg.T; }
       } else {
         add_rows(0, M);
       }
@@ -1256,10 +1236,10 @@ void HipStage::attention(int li, int M, const int32_t* pos, const int32_t* kvlen
       ap.split_len = (int)round_up(opt_.max_ctx, 128);
       ap.n_split = 1;
     }
-    if (!decode && segs_ && segs_->size() > 1) {
+    if (!decode && segs && segs->size() > 1) {
       // packed prefill: a row group of the attention kernel must belong to one sequence
       int row = 0;
-      for (const PrefillSeg& s : *segs_) {
+      for (const PrefillSeg& s : *segs) {
         AttnParams a = ap;
         a.q = q_ + (size_t)row * cfg_.n_head * Dp_;
         a.kvlen = kvlen + row; a.slot = slot + row; a.M = s.T;
@@ -1274,36 +1254,21 @@ void HipStage::attention(int li, int M, const int32_t* pos, const int32_t* kvlen
   }
 }
 
-void HipStage::gemv_small(const PackedMat& m, int epi, const f16* X, int ldx, const float* Xf, const float* gamma,
-                          int M, float* Y, int ldy, f16* H, int ldh, int n_valid, const float* bias, hipStream_t st,
-                          const QkvAppend* qa) {
-  GemvParams p = mat_params(m, X, ldx, M, Y, ldy, H, ldh, n_valid);
-  if (qa) p.qa = *qa;
-  p.bias = bias;
-  if (Xf) { p.Xf = Xf; p.ldxf = cfg_.d_model; p.gamma = gamma; p.eps = cfg_.eps; p.d_norm = cfg_.d_model; }
-  const GemvsPlan pl = plan_gemvs(p.ntiles, p.nsb, M, epi, false, opt_.deterministic);
-  if (!Xf && pl.lds + (size_t)pl.sb_per_split * 64 > 150 * 1024) {   // (+ the single-row form's table)
-    // deterministic mode cannot split K over grid.y, so a wide K (70B down: 28672) with M >= 3
-    // rows overflows LDS: take the v2 GEMV with its fixed-order split-K reduction instead
-    gemv(m, epi, X, ldx, M, Y, ldy, H, ldh, n_valid, epi == EPI_ATOMIC, st);
-    return;
-  }
-  launch_gemvs(m.ptype, epi, p, opt_.deterministic, st);
-}
-
 bool HipStage::fuse_norm(int M) const { return opt_.fused_norm && M <= 4; }
 
-void HipStage::head(int mb, int M, const float* x, int32_t* tok_out, uint64_t salt, hipStream_t st) {
+void HipStage::lm_head(const float* x, int M, float* logits, bool small, hipStream_t st) {
   const int d = cfg_.d_model;
+  const MatCall c = MatCall(out_, EPI_STORE, M).out(logits, logits_ld_, cfg_.vocab);
+  if (small) return gemv(MatCall(c).in_norm(x, out_norm_).gemvs(true), st);
   // (the LM head keeps the standalone norm: the deferred-norm GEMV variant needs ~50 more VGPRs,
   // which halves the head's occupancy: 90.5 vs 72.7 + 4.6 us at 8B, profiles/r2h_prof_8b_mb1.txt)
-  if (small_path(M)) {
-    gemv_small(out_, EPI_STORE, nullptr, 0, x, out_norm_, M, logits_, logits_ld_, nullptr, 0, cfg_.vocab, nullptr, st);
-  } else {
-    launch_rmsnorm(x, d, out_norm_, d, cfg_.eps, xn_, Kd_, M, nullptr, 0, st);
-    xq_src_ = nullptr;
-    gemv(out_, EPI_STORE, xn_, Kd_, M, logits_, logits_ld_, nullptr, 0, cfg_.vocab, false, st);
-  }
+  launch_rmsnorm(x, d, out_norm_, d, cfg_.eps, xn_, Kd_, M, nullptr, 0, st);
+  xq_src_ = nullptr;
+  gemv(MatCall(c).in(xn_, Kd_), st);
+}
+
+void HipStage::head(int mb, int M, const float* x, int32_t* tok_out, uint64_t salt, hipStream_t st) {
+  lm_head(x, M, logits_, small_path(M), st);
   const bool pen = penalties_on() && hist_;
   int32_t* hist = pen ? hist_ + (size_t)mb * opt_.mb_size * hist_n_ : nullptr;
   // token logprobs are those of the RAW logits: the statistics (and the raw logits of the ids the
@@ -1358,24 +1323,18 @@ void HipStage::prefill(int mb, const std::vector<PrefillSeg>& segs, hipStream_t 
     T += s.T;
   }
   if (T > opt_.prefill_chunk) throw std::runtime_error("prefill chunk too large");
-  segs_ = &segs;
-  for (size_t li = 0; li < layers_.size(); ++li)
-    layer_forward((int)li, T, x, pf_pos_, pf_kvlen_, pf_slot_, false, st);
+  const Fwd f{T, pf_pos_, pf_kvlen_, pf_slot_, false, -1, &segs, st};
+  for (size_t li = 0; li < layers_.size(); ++li) layer_forward((int)li, x, f);
   flush_sk(st);
-  segs_ = nullptr;
   if (spec_.last() && !segs.empty() && segs[0].verify) {
     // speculative verification: LM head over every row of the chunk, greedy next token per row
     ensure_chunk_head();
-    launch_rmsnorm(x, d, out_norm_, d, cfg_.eps, xn_, Kd_, T, nullptr, 0, st);
-    xq_src_ = nullptr;
-    gemv(out_, EPI_STORE, xn_, Kd_, T, vlogits_, logits_ld_, nullptr, 0, cfg_.vocab, false, st);
+    lm_head(x, T, vlogits_, false, st);
     launch_argmax(vlogits_, logits_ld_, cfg_.vocab, T, vtok_ + (size_t)mb * opt_.prefill_chunk, st, &am_);
   } else if (spec_.last() && !segs.empty() && segs[0].score) {
     // prompt scoring: LM head over every row of the chunk, then each row's target logprob
     if (!sc_tgt_ || !vlogits_) throw std::runtime_error("score chunk without targets");
-    launch_rmsnorm(x, d, out_norm_, d, cfg_.eps, xn_, Kd_, T, nullptr, 0, st);
-    xq_src_ = nullptr;
-    gemv(out_, EPI_STORE, xn_, Kd_, T, vlogits_, logits_ld_, nullptr, 0, cfg_.vocab, false, st);
+    lm_head(x, T, vlogits_, false, st);
     const size_t off = (size_t)mb * opt_.prefill_chunk;
     LogprobParams q{};
     q.logits = vlogits_; q.ld = logits_ld_; q.n = cfg_.vocab; q.M = T;
@@ -1416,9 +1375,8 @@ void HipStage::decode_eager(int mb, hipStream_t st) {
   float* x = act_[mb];
   if (spec_.first())
     launch_embed(embd_type_, embd_raw_, (int64_t)embd_row_bytes_, cfg_.d_model, tok_[mb], B, x, cfg_.d_model, st);
-  dec_slot0_ = slot_of(mb, 0);   // slot_[mb] holds slot_of(mb, b) = dec_slot0_ + b
-  for (size_t li = 0; li < layers_.size(); ++li)
-    layer_forward((int)li, B, x, pos_[mb], kvlen_[mb], slot_[mb], true, st);
+  const Fwd f{B, pos_[mb], kvlen_[mb], slot_[mb], true, slot_of(mb, 0), nullptr, st};   // slot_[mb][b] = slot0 + b
+  for (size_t li = 0; li < layers_.size(); ++li) layer_forward((int)li, x, f);
   flush_sk(st);
   if (spec_.last()) head(mb, B, x, tok_[mb], (uint64_t)mb + 1, st);
   launch_advance(pos_[mb], kvlen_[mb], B, mb == 0 ? step_ : nullptr, st);

@@ -74,6 +74,49 @@ struct LayerW {
   ExpertW ex;
 };
 
+// the GemvParams fields every launch on a packed matrix shares
+inline GemvParams gemv_params(const void* W, int ntiles, int nsb, const void* X, int ldx, int M, void* Y, int ldy,
+                              void* H, int ldh, int n_valid) {
+  GemvParams p{};
+  p.W = (const uint8_t*)W; p.X = (const f16*)X; p.ldx = ldx; p.M = M; p.Y = (float*)Y; p.ldy = ldy;
+  p.H = (f16*)H; p.ldh = ldh; p.ntiles = ntiles; p.nsb = nsb; p.n_valid = n_valid;
+  return p;
+}
+
+// how a split-K projection delivers its sum
+enum class SplitK {
+  ADD,     // into Y within the call
+  DEFER,   // Y is the residual: stored partials stay pending for its next RMSNorm (sk_pend_); else as ADD
+  INIT     // Y = bias + partials, Y holds no fill: only where the route stores partials (MatRoute::store)
+};
+
+// one dense projection call (HipStage::gemv): Y / H [M][n_valid] = epilogue(x W^T)
+struct MatCall {
+  const PackedMat* m; int epi; int M;
+  const f16* X = nullptr; int ldx = 0;                    // input rows as f16, or
+  const float* Xf = nullptr; const float* gamma = nullptr;   // the f32 residual rows + gamma: fused RMSNorm
+  float* Y = nullptr; int ldy = 0; f16* H = nullptr; int ldh = 0; int n_valid = 0;
+  const float* bias = nullptr;                     // [n_valid] added once
+  float* zero = nullptr; int64_t zero_n = 0;       // side job: floats cleared after the GEMV
+  float* ssq = nullptr;                            // ATOMIC + Xf: per-row sums of squares published here
+  QkvAppend qa{};                                  // gemvs STORE + Xf: RoPE + KV append epilogue (qa.pos set)
+  bool allow_split = false; SplitK deliver = SplitK::ADD;
+  bool small = false;                              // the gemvs family (M <= 4) where its LDS plan fits
+  MatCall(const PackedMat& mat, int e, int rows) : m(&mat), epi(e), M(rows) {}
+  MatCall& in(const f16* x, int ld) { X = x; ldx = ld; return *this; }
+  MatCall& in_norm(const float* x, const float* g) { Xf = x; gamma = g; return *this; }
+  MatCall& out(float* y, int ld, int n) { Y = y; ldy = ld; n_valid = n; return *this; }
+  MatCall& out_h(f16* h, int ld, int n) { H = h; ldh = ld; n_valid = n; return *this; }
+  MatCall& split(SplitK d = SplitK::ADD) { allow_split = true; deliver = d; return *this; }
+  MatCall& gemvs(bool on) { small = on; return *this; }
+};
+
+// one forward pass over M rows: decode of a micro-batch (row t in slot slot0 + t) or a packed prefill chunk
+struct Fwd {
+  int M; const int32_t* pos; const int32_t* kvlen; const int32_t* slot; bool decode;
+  int slot0; const std::vector<PrefillSeg>* segs; hipStream_t st;
+};
+
 class HipStage : public Stage {
  public:
   HipStage(const ModelConfig& cfg, const StageSpec& spec, const StageOptions& opt);
@@ -94,7 +137,6 @@ class HipStage : public Stage {
   int32_t* prompt_buf() override { return prompt_dev_; }
   int act_rows() const { return act_rows_; }
   int slot_of(int mb, int b) const { return mb * opt_.mb_size + b; }
-  int dec_slot0_ = -1;   // decode: slot of row 0 of the micro-batch being recorded (decode attention)
 
   // positions of micro-batch mb (host values) before decode; kvlen = pos + 1
   void set_positions(int mb, const std::vector<int32_t>& pos) override;
@@ -133,37 +175,46 @@ class HipStage : public Stage {
   void decode_eager(int mb, hipStream_t st);
 
  private:
-  void layer_forward(int li, int M, float* x, const int32_t* pos, const int32_t* kvlen, const int32_t* slot,
-                     bool decode, hipStream_t st);
+  void layer_forward(int li, float* x, const Fwd& f);
   void moe_ffn(const LayerW& L, int M, hipStream_t st, float* x);
   void moe_ffn_rows(const LayerW& L, int r0, int M, hipStream_t st, float* x, bool grouped = false);
-  bool fuse_norm(int M) const;
+  // the dense FFN: gate/up (+ SwiGLU) into h_, down into the residual x.  small: the gemvs family;
+  // fused: gate/up norm the f32 residual themselves (otherwise they read xn_)
+  void ffn_tail(const LayerW& L, int M, float* x, bool small, bool fused, hipStream_t st);
+  bool fuse_norm(int M) const;   // RMSNorm folded into the consuming GEMVs at this row count
   // Qwen3: per-head RMSNorm of the q and k heads of the complete q|k|v rows in qkv_ (no-op without weights)
   void qk_norm(const LayerW& L, int M, hipStream_t st);
   void build_i8_copies();
   int8_t* xq_ = nullptr; float* xqs_ = nullptr; int xq_ld_ = 0;   // int8_gemm: quantized activation rows
   const void* xq_src_ = nullptr; int xq_rows_ = 0;   // the f16 rows xq_ currently holds (set by norm_x / the quant)
-  bool attention_o(int li, int M, const int32_t* pos, const int32_t* slot, float* x, hipStream_t st, bool pre = false);
-  void attention(int li, int M, const int32_t* pos, const int32_t* kvlen, const int32_t* slot, bool decode,
-                 hipStream_t st, bool qkv_deferred, bool pre = false);
-  DecodeAttnParams decode_attn_params(int li, int M, const int32_t* pos, const int32_t* slot, bool qkv_deferred) const;
+  bool attention_o(int li, const Fwd& f, float* x, bool pre = false);
+  void attention(int li, const Fwd& f, bool qkv_deferred, bool pre = false);
+  DecodeAttnParams decode_attn_params(int li, const Fwd& f, bool qkv_deferred) const;
   bool small_path(int M) const { return opt_.small_gemv && M <= 4; }
-  // gemvs (M <= 4): Xf != nullptr fuses the RMSNorm of the f32 rows Xf with gamma
-  void gemv_small(const PackedMat& m, int epi, const f16* X, int ldx, const float* Xf, const float* gamma, int M,
-                  float* Y, int ldy, f16* H, int ldh, int n_valid, const float* bias, hipStream_t st,
-                  const QkvAppend* qa = nullptr);
   size_t kv_eb() const { return opt_.kv_fp8 ? 1 : 2; }   // bytes per cached K/V element
-  int det_splits(int ntiles, int nsb, int M, int epi, bool allow_split = true) const;   // RMSNorm folded into the consuming GEMVs at this row count
   void flush_sk(hipStream_t st);
   // RMSNorm of the residual x into xn_ (absorbing pending split-K partials of x first)
   void norm_x(float* x, const float* w, int M, float* zero, int64_t zero_n, hipStream_t st, const float* bias = nullptr,
               int bias_n = 0);
-  // the kernel family gemv() launches for a matrix, an epilogue and a row count
-  enum class GemmRoute { I8, GEMM4, GEMM3, GEMM1, GEMV };
-  GemmRoute gemm_route(const PackedMat& m, int epi, int M, bool have_x) const;
-  void gemv(const PackedMat& m, int epi, const f16* X, int ldx, int M, float* Y, int ldy, f16* H, int ldh,
-            int n_valid, bool allow_split, hipStream_t st,
-            const GemvParams* extras = nullptr);
+  // Everything gemv() acts on for one call: the kernel family.  GEMM4: its launch plan, and whether it
+  // stores split-K partials to sk_part_.  GEMV: the split count handed to launch_gemv, and whether the
+  // splits store to det_part_ for the fixed-order reduction (deterministic mode).  part_n: floats of
+  // stored partials, either way
+  enum class GemmRoute { I8, GEMM4, GEMM3, GEMM1, GEMV, GEMVS };
+  struct MatRoute {
+    GemmRoute family = GemmRoute::GEMV;
+    Gemm4Plan g4{}; bool store = false;
+    int ns = 1; bool det = false;
+    size_t part_n = 0;
+  };
+  GemmRoute gemm_route(const MatCall& c) const;
+  // pure; sk_cap: the floats the GEMM4 partials may take (alloc_runtime sizes sk_part_ with "unbounded")
+  MatRoute mat_route(const MatCall& c, size_t sk_cap) const;
+  GemvParams params(const MatCall& c) const;
+  void gemv(const MatCall& c, hipStream_t st);
+  // final RMSNorm + LM head of M rows of x into logits [M][logits_ld_].  small: the gemvs form with
+  // the norm fused (the decode head at M <= 4; the chunk heads of prefill keep the standalone norm)
+  void lm_head(const float* x, int M, float* logits, bool small, hipStream_t st);
   void head(int mb, int M, const float* x, int32_t* tok_out, uint64_t salt, hipStream_t st);
   void ensure_hist();
   void ensure_logprob();
@@ -222,12 +273,6 @@ class HipStage : public Stage {
   // of x absorbs them (norm_x), anything else reading x first calls flush_sk
   struct SkPending { float* x = nullptr; int M = 0, n = 0, ldy = 0, ns = 0, ldp = 0; int64_t ss = 0; };
   SkPending sk_pend_;
-  float* sk_defer_ = nullptr;   // gemv(): ATOMIC GEMMs into this buffer defer their reduction
-  // gemv(): the split-K GEMM must take the partial-store route and its reduction writes Y = bias +
-  // partials (the caller left Y unfilled); sk_init_bias_: the bias of the GEMM's columns, or nullptr
-  bool sk_init_ = false;
-  const float* sk_init_bias_ = nullptr;
-  bool splitk_store_route(const PackedMat& m, int M) const;
   float* o_part_ = nullptr; float* ml_part_ = nullptr; int n_split_ = 1;
   int32_t* attn_cnt_ = nullptr;   // fused decode attention: split arrival counters
   // MoE scratch
@@ -266,7 +311,6 @@ class HipStage : public Stage {
   int32_t* sc_tgt_ = nullptr; float* sc_lp_ = nullptr; float* sc_lse_ = nullptr;   // [n_mb][chunk]
   int32_t* sc_top_id_ = nullptr; float* sc_top_lp_ = nullptr;                      // [n_mb][chunk][kMaxProbs]
   int sc_top_n_ = 0;
-  const std::vector<PrefillSeg>* segs_ = nullptr;    // segments of the prefill in progress
   // graphs
   std::vector<hipGraphExec_t> graphs_;
 };

@@ -106,6 +106,10 @@ bool gemm4_has_geometry(int ptype, int bm, int nwv, int tw, bool moe);
 bool launch_gemm4(int ptype, int epi, GemvParams p, hipStream_t st, bool allow_split = true);
 bool launch_gemm4_splitk(int ptype, GemvParams p, float* scratch, size_t scratch_n, hipStream_t st,
                          bool reduce = true, int* nsplit_out = nullptr, bool init = false);
+// the same launches for a plan the caller already made (pl.ok; _splitk: a partial-store plan whose
+// pl.nsplit * M * ntiles * 16 floats fit scratch)
+void run_gemm4(int ptype, const Gemm4Plan& pl, int epi, const GemvParams& p, hipStream_t st);
+void run_gemm4_splitk(int ptype, const Gemm4Plan& pl, GemvParams p, float* scratch, hipStream_t st, bool reduce, bool init);
 
 // Y[m][n] += sum_{s < nsplit} part[s][m][n], s ascending: the fixed-order split-K reduction of the
 // deterministic mode (part rows of ldp floats, splits split_stride floats apart)
