@@ -766,6 +766,32 @@ int mp_op_hist_push(void* hist, void* cnt, int last_n, const void* tokens, int M
   API_CATCH(-1)
 }
 
+// per-request sampling kernels (sample_rows.hip): rows = device table of M RowSampling records
+int mp_row_sampling_bytes() { return (int)sizeof(RowSampling); }
+int mp_row_adjust(void* logits, int ld, int n, int M, const void* rows, const void* hist, int hist_ld, int last_n,
+                  void* stream) {
+  API_TRY
+  RowAdjustParams p{};
+  p.logits = (float*)logits; p.ld = ld; p.n = n; p.M = M; p.rows = (const RowSampling*)rows;
+  p.hist = (const int32_t*)hist; p.hist_ld = hist_ld; p.last_n = last_n;
+  launch_row_adjust(p, (hipStream_t)stream);
+  HIP_OK(hipGetLastError());
+  return 0;
+  API_CATCH(-1)
+}
+int mp_sample_rows(const void* logits, int ld, int n, int M, const void* rows, void* draw, int advance, void* tokens,
+                   void* stream) {
+  API_TRY
+  if (ld < n || n < 1 || !rows || !draw || !tokens) throw std::runtime_error("sample_rows: bad arguments");
+  SampleRowsParams p{};
+  p.logits = (const float*)logits; p.ld = ld; p.n = n; p.M = M; p.rows = (const RowSampling*)rows;
+  p.draw = (int32_t*)draw; p.advance = advance; p.tokens = (int32_t*)tokens;
+  launch_sample_rows(p, (hipStream_t)stream);
+  HIP_OK(hipGetLastError());
+  return 0;
+  API_CATCH(-1)
+}
+
 // ------------------------------------------------------------------ tokenizer
 void* mp_tok_open(const char* gguf_path) {
   API_TRY
@@ -936,6 +962,25 @@ int mp_engine_admit(void* h, const int32_t* slots, const int32_t* prompt_tokens,
   static_cast<Engine*>(h)->admit(sl, prompts);
   return 0;
   API_CATCH(-1)
+}
+// per-request sampling (engine key "row_sampling"): the record of an idle slot as a JSON object of
+// fields (Engine::sampling_from_json; absent fields = the engine's values, no "seed" = a default one),
+// and the record a slot has (the seed in use as a decimal string).  for_start: the record is for the
+// next mp_engine_start, which resets every slot (a busy slot takes it)
+int mp_engine_set_slot_sampling(void* h, int slot, const char* json, int for_start) {
+  API_TRY
+  Engine* e = static_cast<Engine*>(h);
+  bool has_seed = false;
+  const RowSampling r = e->sampling_from_json(Json::parse(json ? json : "{}"), &has_seed);
+  e->set_slot_sampling(slot, r, has_seed, for_start != 0);
+  return 0;
+  API_CATCH(-1)
+}
+const char* mp_engine_slot_sampling(void* h, int slot) {
+  API_TRY
+  g_str = Engine::sampling_to_json(static_cast<Engine*>(h)->slot_sampling(slot)).dump();
+  return g_str.c_str();
+  API_CATCH(nullptr)
 }
 int mp_engine_release(void* h, int slot) {
   API_TRY

@@ -461,8 +461,14 @@ void CpuStage::ffn(const Layer& L, int M, const float* xn, float* x) {
 // llama.cpp sampler-chain semantics (same as the HIP sampler, csrc/kernels/sample.hip): top-k,
 // top-p and min-p cut the T = 1 distribution, the draw uses temperature T
 int CpuStage::sample_row(const float* lg, uint64_t salt, int row) {
+  if (temp_ <= 0.f) return (int)(std::max_element(lg, lg + cfg_.vocab) - lg);
+  const uint64_t r = mix64((seed_ ^ (salt * 0x9E3779B97F4A7C15ULL)) ^ mix64((step_ << 20) ^ (uint64_t)row));
+  return sample_chain(lg, temp_, top_k_, top_p_, min_p_, (double)(r >> 11) * (1.0 / 9007199254740992.0));
+}
+
+// the chain for one row with the uniform variate u01 in [0, 1) given (temp_ > 0)
+int CpuStage::sample_chain(const float* lg, float temp_, int top_k_, float top_p_, float min_p_, double u01) const {
   const int n = cfg_.vocab;
-  if (temp_ <= 0.f) return (int)(std::max_element(lg, lg + n) - lg);
   std::vector<std::pair<float, int>> v(n);
   for (int i = 0; i < n; ++i) v[i] = {lg[i], i};
   std::sort(v.begin(), v.end(), [](auto& a, auto& b) { return a.first > b.first || (a.first == b.first && a.second < b.second); });
@@ -485,8 +491,7 @@ int CpuStage::sample_row(const float* lg, uint64_t salt, int row) {
   std::vector<double> p(keep);
   double sum = 0;
   for (int i = 0; i < keep; ++i) { p[i] = std::exp(((double)v[i].first - mx) / temp_); sum += p[i]; }
-  const uint64_t r = mix64((seed_ ^ (salt * 0x9E3779B97F4A7C15ULL)) ^ mix64((step_ << 20) ^ (uint64_t)row));
-  const double u = (double)(r >> 11) * (1.0 / 9007199254740992.0) * sum;
+  const double u = u01 * sum;
   double c = 0;
   for (int i = 0; i < keep; ++i) {
     c += p[i];
@@ -596,9 +601,89 @@ void CpuStage::copy_scores(int mb, int n, float* target_lp, int32_t* top_id, flo
   }
 }
 
-void CpuStage::head(int mb, int M, const float* x, int32_t* tok_out, uint64_t salt) {
+void CpuStage::set_row_sampling(int mb, int row, const RowSampling& r) {
+  if (!spec_.last()) return;
+  if (!opt_.row_sampling) throw std::runtime_error("set_row_sampling: the stage was built without row_sampling");
+  if (mb < 0 || mb >= opt_.n_mb || row < 0 || row >= opt_.mb_size) throw std::runtime_error("set_row_sampling: bad row");
+  check_row_sampling(r, cfg_.vocab);
+  if (rows_.empty()) { rows_.assign((size_t)opt_.n_mb * opt_.mb_size, RowSampling{}); draws_.assign(rows_.size(), 0); }
+  rows_[(size_t)mb * opt_.mb_size + row] = r;
+  draws_[(size_t)mb * opt_.mb_size + row] = r.draw0;
+}
+
+void CpuStage::set_row_draws(int mb, const std::vector<int32_t>& draws) {
+  if (!spec_.last() || !opt_.row_sampling) return;
+  if (mb < 0 || mb >= opt_.n_mb || (int)draws.size() != opt_.mb_size) throw std::runtime_error("set_row_draws: bad size");
+  if (rows_.empty()) { rows_.assign((size_t)opt_.n_mb * opt_.mb_size, RowSampling{}); draws_.assign(rows_.size(), 0); }
+  std::copy(draws.begin(), draws.end(), draws_.begin() + (size_t)mb * opt_.mb_size);
+}
+
+// Host counterpart of HipStage::head_rows: bias and penalties in f32 as the kernels apply them, the
+// chain in double, the variate of the request's own stream (kernels_api.h, RowSampling)
+void CpuStage::head_rows(int mb, int M, int32_t* tok_out, bool advance) {
+  const int B = opt_.mb_size, V = cfg_.vocab, top_n = std::max(n_probs_, 0);
+  if (rows_.empty()) { rows_.assign((size_t)opt_.n_mb * B, RowSampling{}); draws_.assign(rows_.size(), 0); }
+  if (hist_.empty()) hist_.resize((size_t)opt_.n_mb * B);
+  const bool lp = n_probs_ != 0;
+  if (lp && lp_rec_.size() < (size_t)opt_.n_mb) lp_rec_.assign(opt_.n_mb, std::vector<uint32_t>(logprob_rec_words(B), 0xFFFFFFFFu));
+  std::unordered_map<int32_t, float> raw;   // raw logits of the ids the bias and the penalty rewrite
+  for (int m = 0; m < M; ++m) {
+    const size_t s = (size_t)mb * B + m;
+    const RowSampling& rs = rows_[s];
+    float* lg = logits_.data() + (size_t)m * V;
+    double lse = 0;
+    raw.clear();
+    if (lp) {
+      uint32_t* rec = lp_rec_[mb].data();
+      lse = row_logprob(lg, V, top_n, reinterpret_cast<int32_t*>(rec + B) + (size_t)m * kMaxProbs,
+                        reinterpret_cast<float*>(rec + B + (size_t)B * kMaxProbs) + (size_t)m * kMaxProbs);
+    }
+    for (int i = 0; i < rs.n_bias; ++i) {
+      const int32_t t = rs.bias_id[i];
+      if (t < 0 || t >= V) continue;
+      raw.emplace(t, lg[t]);
+      lg[t] += rs.bias_val[i];
+    }
+    std::vector<int32_t>& h = hist_[s];
+    if (pen_last_n_ > 0 && (rs.repeat != 1.f || rs.freq != 0.f || rs.presence != 0.f)) {
+      std::unordered_map<int32_t, int> cnt;
+      for (int32_t t : h) ++cnt[t];
+      for (const auto& [t, c] : cnt) {
+        if (t < 0 || t >= V) continue;
+        float l = lg[t];
+        raw.emplace(t, l);
+        l = l > 0.f ? l / rs.repeat : l * rs.repeat;
+        lg[t] = std::fmaf(-(float)c, rs.freq, l) - rs.presence;
+      }
+    }
+    if (rs.temp <= 0.f) {
+      tok_out[m] = (int32_t)(std::max_element(lg, lg + V) - lg);
+    } else {
+      const uint64_t r = mix64(rs.seed ^ mix64((uint64_t)(uint32_t)draws_[s] << 20));
+      tok_out[m] = sample_chain(lg, rs.temp, rs.top_k, rs.top_p, rs.min_p, (double)(r >> 40) * (1.0 / 16777216.0));
+    }
+    if (advance) ++draws_[s];
+    if (lp) {
+      const int32_t t = tok_out[m];
+      float v = -INFINITY;
+      if (t >= 0 && t < V && std::isfinite(lse)) {
+        const auto it = raw.find(t);
+        const float r = it != raw.end() ? it->second : lg[t];
+        if (r == r) v = (float)((double)r - lse);
+      }
+      reinterpret_cast<float*>(lp_rec_[mb].data())[m] = v;
+    }
+    if (pen_last_n_ > 0) {
+      h.push_back(tok_out[m]);
+      if ((int)h.size() > pen_last_n_) h.erase(h.begin());
+    }
+  }
+}
+
+void CpuStage::head(int mb, int M, const float* x, int32_t* tok_out, uint64_t salt, bool advance) {
   rmsnorm(x, out_norm_, xn_.data(), M);
   matmul(out_, xn_.data(), cfg_.d_model, M, logits_.data(), cfg_.vocab, false);
+  if (opt_.row_sampling) return head_rows(mb, M, tok_out, advance);
   const bool pen = penalties_on();
   if (pen && hist_.empty()) hist_.resize((size_t)opt_.n_mb * opt_.mb_size);
   // token logprobs: log-softmax of the RAW logits (before the in-place penalty), Stage::logprob_rec layout
@@ -731,7 +816,7 @@ void CpuStage::decode(int mb, hipStream_t) {
   std::vector<int32_t> slot(B);
   for (int b = 0; b < B; ++b) slot[b] = mb * B + b;
   for (size_t li = 0; li < layers_.size(); ++li) layer_forward((int)li, B, x, pos_[mb].data(), slot.data());
-  if (spec_.last()) head(mb, B, x, tok_[mb].data(), (uint64_t)mb + 1);
+  if (spec_.last()) head(mb, B, x, tok_[mb].data(), (uint64_t)mb + 1, true);
   for (int b = 0; b < B; ++b) pos_[mb][b] = std::min(pos_[mb][b] + 1, opt_.max_ctx - 1);
   if (mb == 0) ++step_;
 }

@@ -70,7 +70,10 @@ class CpuStage : public Stage {
   void rmsnorm(const float* x, const std::vector<float>& w, float* y, int M);
   void layer_forward(int li, int M, float* x, const int32_t* pos, const int32_t* slot);
   void ffn(const Layer& L, int M, const float* xn, float* x);
-  void head(int mb, int M, const float* x, int32_t* tok_out, uint64_t salt);
+  void head(int mb, int M, const float* x, int32_t* tok_out, uint64_t salt, bool advance = false);
+  void head_rows(int mb, int M, int32_t* tok_out, bool advance);
+  void set_row_sampling(int mb, int row, const RowSampling& r) override;
+  void set_row_draws(int mb, const std::vector<int32_t>& draws) override;
   void set_history(int mb, const std::vector<std::vector<int32_t>>& seqs) override;
   void kv_export(int slot, int n_tok, std::vector<uint8_t>& out) override;
   void set_block_table(const std::vector<int32_t>& table) override;
@@ -80,6 +83,7 @@ class CpuStage : public Stage {
   void set_sample_step(uint64_t s) override { step_ = s; }
   const char* backend_name() const override { return "cpu"; }
   int sample_row(const float* logits, uint64_t salt, int row);
+  int sample_chain(const float* logits, float temp, int top_k, float top_p, float min_p, double u01) const;
   CpuMat own_random(int type, int64_t N, int64_t K, uint64_t seed);
 
   ModelConfig cfg_;
@@ -114,6 +118,8 @@ class CpuStage : public Stage {
   Q8Buf xq_;   // matmul: the activation rows as int8 blocks (cpu_q8)
   uint64_t step_ = 0;
   std::vector<std::vector<int32_t>> hist_;   // per slot: accepted tokens, most recent last
+  std::vector<RowSampling> rows_;            // row_sampling: per slot record and draw index
+  std::vector<int32_t> draws_;
 };
 
 }  // namespace mp

@@ -2,6 +2,7 @@
 #include "probe.h"
 
 #include <algorithm>
+#include <cerrno>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -403,6 +404,8 @@ Engine::Engine(const Json& j) : jcfg_(j) {
   so.kv_fp8 = j.get_str("kv_dtype", "f16") == "fp8";
   so.fused_norm = j.get_bool("fused_norm", false) && !so.deterministic;   // its sums of squares are atomics
   so.small_gemv = j.get_bool("small_gemv", true);
+  row_sampling_ = j.get_bool("row_sampling", false);
+  so.row_sampling = row_sampling_;
   so.moe_gemm = j.get_bool("moe_gemm", true);
   packed_prefill_ = j.get_bool("packed_prefill", true);
   prefix_cache_ = j.get_bool("prefix_cache", true);
@@ -410,6 +413,17 @@ Engine::Engine(const Json& j) : jcfg_(j) {
   if (n_probs_ < -1 || n_probs_ > Stage::kMaxProbs)
     throw std::runtime_error("n_probs must be -1 (chosen token only) or 0.." + std::to_string(Stage::kMaxProbs));
 
+  if (row_sampling_) {
+    row_default_.temp = (float)j.get_num("temp", 0.0); row_default_.top_k = j.get_int("top_k", 0);
+    row_default_.top_p = (float)j.get_num("top_p", 1.0); row_default_.min_p = (float)j.get_num("min_p", 0.0);
+    row_default_.repeat = (float)j.get_num("repeat_penalty", 1.0);
+    row_default_.freq = (float)j.get_num("frequency_penalty", 0.0);
+    row_default_.presence = (float)j.get_num("presence_penalty", 0.0);
+    row_default_.seed = seed;
+    check_row_sampling(row_default_, cfg_.vocab);
+    slot_rec_.assign((size_t)M_ * B_, row_default_);
+    slot_seed_given_.assign((size_t)M_ * B_, 0);
+  }
   // ---- stages this process owns
   for (int s = 0; s < S_; ++s) {
     if (mode_ == "mp" && s != rank_) continue;
@@ -430,6 +444,8 @@ Engine::Engine(const Json& j) : jcfg_(j) {
     w->stage->set_penalties(j.get_int("repeat_last_n", 64), (float)j.get_num("repeat_penalty", 1.0),
                             (float)j.get_num("frequency_penalty", 0.0), (float)j.get_num("presence_penalty", 0.0));
     if (n_probs_ != 0) w->stage->set_n_probs(n_probs_);
+    if (row_sampling_ && w->stage->spec().last())   // every slot starts at the engine's values
+      for (int i = 0; i < M_ * B_; ++i) w->stage->set_row_sampling(i / B_, i % B_, row_default_);
     if (w->cpu) {
       w->ring_pending.assign(M_, false);
       workers_.push_back(std::move(w));
@@ -1008,6 +1024,7 @@ Json Engine::health() const {
     o["backend"] = w->stage->backend_name();
     o["device"] = w->device;
     o["items_done"] = (int64_t)w->progress.load();
+    o["graph_captures"] = (int64_t)w->stage->graph_captures();
     if (w->out) {
       o["bytes_sent"] = (int64_t)w->out->bytes_sent;
       o["msgs_sent"] = (int64_t)w->out->msgs_sent;
@@ -1140,6 +1157,11 @@ void Engine::start(const std::vector<std::vector<int32_t>>& prompts) {
   for (size_t i = 0; i < prompts.size(); ++i)
     if (!prompts[i].empty() && (int)prompts[i].size() < max_ctx_) kv_grant(i, (int)prompts[i].size() + 1);
   kv_sync();
+  {
+    std::vector<size_t> all(prompts.size());
+    std::iota(all.begin(), all.end(), (size_t)0);
+    apply_slot_sampling(all);
+  }
   std::vector<Item> items;
   for (auto& w : workers_) {
     Stage& st = *w->stage;
@@ -1181,7 +1203,157 @@ void Engine::start(const std::vector<std::vector<int32_t>>& prompts) {
       gen_[i].push_back(out_host_[i]);
       take_logprobs(i, 0);
     }
+  for (int mb = 0; mb < M_; ++mb) push_row_draws(mb);
   slot_toks_ = prompts;
+}
+
+// ---------------------------------------------------------------- per-request sampling
+static uint64_t seed_mix64(uint64_t x) {
+  x ^= x >> 30; x *= 0xbf58476d1ce4e5b9ULL; x ^= x >> 27; x *= 0x94d049bb133111ebULL; x ^= x >> 31;
+  return x;
+}
+
+void Engine::set_slot_sampling(int slot, const RowSampling& r, bool has_seed, bool for_start) {
+  if (!row_sampling_) throw std::runtime_error("set_slot_sampling: the engine was built without row_sampling");
+  if (mode_ == "mp") throw std::runtime_error("set_slot_sampling: mode \"mp\" is not supported");
+  if (slot < 0 || slot >= M_ * B_) throw std::runtime_error("set_slot_sampling: bad slot");
+  if (!for_start && started_ && slot_active(slot)) throw std::runtime_error("set_slot_sampling: slot " + std::to_string(slot) + " is busy");
+  check_row_sampling(r, cfg_.vocab);
+  slot_rec_[slot] = r;
+  slot_seed_given_[slot] = has_seed ? 1 : 0;
+}
+
+RowSampling Engine::slot_sampling(int slot) const {
+  if (!row_sampling_) throw std::runtime_error("slot_sampling: the engine was built without row_sampling");
+  if (slot < 0 || slot >= M_ * B_) throw std::runtime_error("slot_sampling: bad slot");
+  return slot_rec_[slot];
+}
+
+// the records of the slots about to be prefilled -> the last stage (draw index = draw0); a slot
+// without a seed of its own gets the next default one
+void Engine::apply_slot_sampling(const std::vector<size_t>& seqs) {
+  if (!row_sampling_) return;
+  for (size_t i : seqs) {
+    RowSampling& r = slot_rec_[i];
+    if (!slot_seed_given_[i]) r.seed = seed_mix64(row_default_.seed ^ (0x9E3779B97F4A7C15ULL * (admissions_ + 1)));
+    slot_seed_given_[i] = 1;   // the seed in use: a re-admission without release() keeps it
+    ++admissions_;
+    for (auto& w : workers_)
+      if (w->stage->spec().last()) {
+        if (!w->cpu) HIP_OK(hipSetDevice(w->device));
+        w->stage->set_row_sampling((int)(i / B_), (int)(i % B_), r);
+      }
+  }
+}
+
+// the head of an admission sampled every row of the micro-batch without moving a draw index: every
+// token a slot has generated consumed one draw
+void Engine::push_row_draws(int mb) {
+  if (!row_sampling_) return;
+  std::vector<int32_t> d(B_, 0);
+  for (int b = 0; b < B_; ++b) {
+    const size_t i = (size_t)mb * B_ + b;
+    d[b] = slot_rec_[i].draw0 + (i < gen_.size() ? (int32_t)gen_[i].size() : 0);
+  }
+  for (auto& w : workers_)
+    if (w->stage->spec().last()) {
+      if (!w->cpu) HIP_OK(hipSetDevice(w->device));
+      w->stage->set_row_draws(mb, d);
+    }
+}
+
+RowSampling Engine::sampling_from_json(const Json& j, bool* has_seed) const {
+  if (!row_sampling_) throw std::runtime_error("per-request sampling needs an engine built with row_sampling");
+  if (!j.is_obj()) throw std::runtime_error("sampling: an object of fields is expected");
+  RowSampling r = row_default_;
+  auto num = [&](const char* k, double d) {
+    if (!j.has(k)) return d;
+    if (!j[k].is_num()) throw std::runtime_error(std::string("sampling: ") + k + " must be a number");
+    return j[k].num();
+  };
+  auto integer = [&](const char* k, double d, double lo, double hi) {
+    const double v = num(k, d);
+    if (!(v >= lo && v <= hi) || v != std::floor(v)) throw std::runtime_error(std::string("sampling: bad value for ") + k);
+    return v;
+  };
+  for (const auto& kv : j.obj()) {
+    static const char* known[] = {"temp", "top_k", "top_p", "min_p", "repeat", "freq", "presence", "seed", "draw0", "logit_bias"};
+    bool ok = false;
+    for (const char* k : known) ok |= kv.first == k;
+    if (!ok) throw std::runtime_error("sampling: unknown field " + kv.first);
+  }
+  r.temp = (float)num("temp", r.temp);
+  r.top_k = (int32_t)integer("top_k", r.top_k, 0, 2147483647.0);
+  r.top_p = (float)num("top_p", r.top_p);
+  r.min_p = (float)num("min_p", r.min_p);
+  r.repeat = (float)num("repeat", r.repeat);
+  r.freq = (float)num("freq", r.freq);
+  r.presence = (float)num("presence", r.presence);
+  r.draw0 = (int32_t)integer("draw0", 0, 0, 2147483647.0);
+  bool seeded = false;
+  if (j.has("seed") && !j["seed"].is_null()) {
+    const Json& s = j["seed"];
+    if (s.is_str()) {
+      const std::string& t = s.str();
+      if (t.empty() || t.size() > 20 || t.find_first_not_of("0123456789") != std::string::npos)
+        throw std::runtime_error("sampling: bad value for seed");
+      errno = 0;
+      r.seed = std::strtoull(t.c_str(), nullptr, 10);
+      if (errno) throw std::runtime_error("sampling: bad value for seed");
+    } else {
+      r.seed = (uint64_t)integer("seed", 0, 0, 9007199254740992.0);
+    }
+    seeded = true;
+  }
+  if (has_seed) *has_seed = seeded;
+  r.n_bias = 0;
+  if (j.has("logit_bias") && !j["logit_bias"].is_null()) {
+    const Json& lb = j["logit_bias"];
+    std::vector<std::pair<double, const Json*>> ent;
+    if (lb.is_arr()) {
+      for (const Json& e : lb.arr()) {
+        if (!e.is_arr() || e.arr().size() != 2 || !e.arr()[0].is_num()) throw std::runtime_error("sampling: logit_bias takes [[id, bias], ..]");
+        ent.emplace_back(e.arr()[0].num(), &e.arr()[1]);
+      }
+    } else if (lb.is_obj()) {
+      for (const auto& kv : lb.obj()) {
+        if (kv.first.empty() || kv.first.size() > 9 || kv.first.find_first_not_of("0123456789") != std::string::npos)
+          throw std::runtime_error("sampling: logit_bias id " + kv.first);
+        ent.emplace_back((double)std::atol(kv.first.c_str()), &kv.second);
+      }
+    } else {
+      throw std::runtime_error("sampling: logit_bias takes [[id, bias], ..] or {\"id\": bias}");
+    }
+    if (ent.size() > (size_t)kMaxLogitBias) throw std::runtime_error("sampling: n_bias > " + std::to_string(kMaxLogitBias));
+    for (const auto& [id, v] : ent) {
+      if (!(id >= 0 && id < cfg_.vocab) || id != std::floor(id)) throw std::runtime_error("sampling: logit_bias id outside the vocabulary");
+      float b;
+      if (v->is_bool() && !v->boolean()) b = -INFINITY;   // false bans the token
+      else if (v->is_num()) b = (float)v->num();
+      else throw std::runtime_error("sampling: logit_bias value must be a number or false");
+      r.bias_id[r.n_bias] = (int32_t)id;
+      r.bias_val[r.n_bias++] = b;
+    }
+  }
+  check_row_sampling(r, cfg_.vocab);
+  return r;
+}
+
+Json Engine::sampling_to_json(const RowSampling& r) {
+  Json o = Json::object();
+  o["temp"] = (double)r.temp; o["top_k"] = (int)r.top_k; o["top_p"] = (double)r.top_p; o["min_p"] = (double)r.min_p;
+  o["repeat"] = (double)r.repeat; o["freq"] = (double)r.freq; o["presence"] = (double)r.presence;
+  o["seed"] = std::to_string(r.seed);   // decimal string: a JSON number cannot hold 64 bits
+  o["draw0"] = (int)r.draw0;
+  Json lb = Json::array();
+  for (int i = 0; i < r.n_bias; ++i) {
+    Json e = Json::array();
+    e.push((int)r.bias_id[i]);
+    if (std::isinf(r.bias_val[i])) e.push(Json(false)); else e.push((double)r.bias_val[i]);
+    lb.push(e);
+  }
+  o["logit_bias"] = lb;
+  return o;
 }
 
 // tokens whose KV a slot holds after the last decode round: prompt + every generated token that went
@@ -1278,6 +1450,16 @@ Json Engine::save_state(const std::string& dir) {
     }
     sj["base_round"] = br;
     sj["active"] = ac;
+    if (row_sampling_) {   // the slots' records and the draws each has consumed (draw0 + one per generated token)
+      Json rs = Json::array(), ds = Json::array();
+      for (size_t i = 0; i < prompts_.size(); ++i) {
+        rs.push(sampling_to_json(slot_rec_[i]));
+        ds.push((int)(slot_rec_[i].draw0 + (int32_t)gen_[i].size()));
+      }
+      sj["sampling"] = rs;
+      sj["draws"] = ds;
+      sj["admissions"] = std::to_string(admissions_);
+    }
     std::ofstream f(dir + "/session.json", std::ios::trunc);
     f << sj.dump() << "\n";
     if (!f) throw std::runtime_error("save_state: cannot write session.json");
@@ -1417,6 +1599,27 @@ Json Engine::load_state(const std::string& dir) {
       }
     }
   }
+  if (row_sampling_) {   // the slots' records; the draw indices follow from the generated tokens
+    if (!sj.has("sampling") || sj["sampling"].arr().size() != prompts_.size())
+      throw std::runtime_error("load_state: the session was saved without row_sampling");
+    for (size_t i = 0; i < prompts_.size(); ++i) {
+      bool seeded = false;
+      slot_rec_[i] = sampling_from_json(sj["sampling"].arr()[i], &seeded);
+      slot_seed_given_[i] = 1;
+      if (sj.has("draws") && (int)sj["draws"].arr()[i].num() != slot_rec_[i].draw0 + (int)gen_[i].size())
+        throw std::runtime_error("load_state: bad session (draws)");
+      for (auto& w : workers_)
+        if (w->stage->spec().last()) {
+          if (!w->cpu) HIP_OK(hipSetDevice(w->device));
+          w->stage->set_row_sampling((int)(i / B_), (int)(i % B_), slot_rec_[i]);
+        }
+    }
+    for (size_t i = prompts_.size(); i < (size_t)M_ * B_; ++i) { slot_rec_[i] = row_default_; slot_seed_given_[i] = 0; }
+    admissions_ = std::strtoull(sj.get_str("admissions", "0").c_str(), nullptr, 10);
+    for (int mb = 0; mb < M_; ++mb) push_row_draws(mb);
+  } else if (sj.has("sampling")) {
+    throw std::runtime_error("load_state: the session was saved with row_sampling");
+  }
   started_ = true;
   resumable_ = true;
   refresh_slot_cache();
@@ -1489,6 +1692,16 @@ void Engine::push_positions(int mb) {
 void Engine::release(int slot) {
   if (slot >= 0 && slot < (int)active_.size()) active_[slot] = 0;
   if (slot >= 0 && slot < M_ * B_) pager_.release(slot);   // table pushed before the next engine call
+  if (row_sampling_ && !failed_ && slot >= 0 && slot < M_ * B_) {
+    // the stage too: an idle row at the engine's values stops running a finished request's chain
+    slot_rec_[slot] = row_default_;
+    slot_seed_given_[slot] = 0;
+    for (auto& w : workers_)
+      if (w->stage->spec().last()) {
+        if (!w->cpu) HIP_OK(hipSetDevice(w->device));
+        w->stage->set_row_sampling(slot / B_, slot % B_, row_default_);
+      }
+  }
 }
 
 void Engine::kv_grant(size_t slot, int n_tokens) {
@@ -1534,6 +1747,7 @@ void Engine::admit(const std::vector<int>& slots, const std::vector<std::vector<
     mbs[i / B_] = 1;
   }
   kv_sync();
+  apply_slot_sampling(seqs);
   for (auto& w : workers_) {
     Stage& st = *w->stage;
     if (!w->cpu) HIP_OK(hipSetDevice(w->device));
@@ -1569,6 +1783,8 @@ void Engine::admit(const std::vector<int>& slots, const std::vector<std::vector<
           }
           w->stage->set_history(mb, hs);
         }
+  for (int mb = 0; mb < M_; ++mb)
+    if (mbs[mb]) push_row_draws(mb);
   refresh_slot_cache();
 }
 
@@ -1822,6 +2038,7 @@ Json Engine::spec_generate(const std::vector<std::vector<int32_t>>& prompts, int
   // drafts, grants KV and builds the identical next verify chunk
   const bool mp = mode_ == "mp" && S_ > 1;
   if (!mp && (int)workers_.size() != S_) throw std::runtime_error("speculative decoding needs every stage in this process");
+  if (row_sampling_) throw std::runtime_error("speculative decoding is greedy: not on a row_sampling engine");
   if (jcfg_.get_num("temp", 0.0) > 0.0) throw std::runtime_error("speculative decoding is greedy (temp 0)");
   if (jcfg_.get_num("repeat_penalty", 1.0) != 1.0 || jcfg_.get_num("frequency_penalty", 0.0) != 0.0 ||
       jcfg_.get_num("presence_penalty", 0.0) != 0.0)

@@ -98,6 +98,21 @@ class Engine {
   // KV pages).  Every process of a multi-process pipeline must make the same calls.
   void admit(const std::vector<int>& slots, const std::vector<std::vector<int32_t>>& prompts);
   void release(int slot);
+  // Per-request sampling (config "row_sampling": true; local mode): the record the next start() /
+  // admit() of `slot` uses (kernels_api.h, RowSampling).  Legal before start() and for an idle slot;
+  // release() puts the slot back to the engine's values.  Without has_seed the slot gets
+  // mix64(engine seed ^ 0x9E3779B97F4A7C15 * (n + 1)), n = admissions since the engine was built;
+  // slot_sampling() reports the record with the seed in use.  Throws naming the field on a value
+  // out of range.  JSON form (C API, sessions, HTTP): {"temp", "top_k", "top_p", "min_p", "repeat",
+  // "freq", "presence", "seed" (number or decimal string), "draw0", "logit_bias": [[id, bias | false], ..]},
+  // absent fields = the engine's values.
+  bool row_sampling() const { return row_sampling_; }
+  // for_start: the record is for a start(), which resets every slot, so a busy slot takes it too
+  void set_slot_sampling(int slot, const RowSampling& r, bool has_seed = true, bool for_start = false);
+  RowSampling slot_sampling(int slot) const;
+  const RowSampling& sampling_defaults() const { return row_default_; }
+  RowSampling sampling_from_json(const Json& j, bool* has_seed) const;
+  static Json sampling_to_json(const RowSampling& r);
   int32_t last_token(int slot) const { return slot < (int)gen_.size() && !gen_[slot].empty() ? gen_[slot].back() : -1; }
   int slot_position(int slot) const { return slot_pos((size_t)slot); }
   bool started() const { return started_; }
@@ -226,6 +241,13 @@ class Engine {
     return (i < prompts_.size() ? (int)prompts_[i].size() : 0) + rounds_done_ - (i < base_round_.size() ? base_round_[i] : 0);
   }
   void push_positions(int mb);
+  bool row_sampling_ = false;
+  RowSampling row_default_;                 // the engine keys as a record (seed: the engine's)
+  std::vector<RowSampling> slot_rec_;       // per slot: set for the next admission / in use
+  std::vector<char> slot_seed_given_;
+  uint64_t admissions_ = 0;
+  void apply_slot_sampling(const std::vector<size_t>& seqs);   // before an admission's prefill
+  void push_row_draws(int mb);                                 // after it: draw0 + tokens generated
   std::vector<Item> prefill_items(const std::vector<size_t>& seqs, bool admission);
   double load_ms_ = 0;
   // persistent stage-worker threads of run_all (declared last: joined before anything they use

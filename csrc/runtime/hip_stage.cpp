@@ -604,6 +604,12 @@ void HipStage::alloc_runtime() {
   prompt_dev_ = (int32_t*)zalloc((size_t)n_slots * opt_.max_ctx * 4);
   if (spec_.last())
     for (int mb = 0; mb < NM; ++mb) last_h_.push_back((float*)zalloc((size_t)B * d * 4));
+  if (spec_.last() && opt_.row_sampling) {   // every slot starts greedy and neutral, draw index 0
+    row_host_.assign((size_t)n_slots, RowSampling{});
+    row_tab_ = (RowSampling*)dmalloc(row_host_.size() * sizeof(RowSampling));
+    HIP_OK(hipMemcpy(row_tab_, row_host_.data(), row_host_.size() * sizeof(RowSampling), hipMemcpyHostToDevice));
+    row_draw_ = (int32_t*)zalloc((size_t)n_slots * 4);
+  }
   HIP_OK(hipDeviceSynchronize());
   MP_LOGI("stage %d: layers %d-%d offloaded to GPU %d (%s), weights %.2f GiB, KV %.2f GiB (%d pages of 64 tokens; "
           "%d slots x <= %d ctx)",
@@ -702,13 +708,47 @@ void HipStage::set_penalties(int last_n, float repeat, float freq, float presenc
 }
 
 void HipStage::ensure_hist() {
-  if (!penalties_on() || (hist_ && hist_n_ == pen_last_n_)) return;
+  // (row_sampling: the windows exist whatever the engine's penalties are, a request may bring its own)
+  if (!(penalties_on() || rows_on()) || (hist_ && hist_n_ == pen_last_n_)) return;
   const size_t rows = (size_t)opt_.n_mb * opt_.mb_size;
-  hist_ = (int32_t*)dmalloc(rows * pen_last_n_ * 4);
-  HIP_OK(hipMemset(hist_, 0xFF, rows * pen_last_n_ * 4));   // -1: empty
+  hist_ld_ = pen_last_n_ + (rows_on() ? kMaxLogitBias : 0);
+  hist_ = (int32_t*)dmalloc(rows * hist_ld_ * 4);
+  HIP_OK(hipMemset(hist_, 0xFF, rows * hist_ld_ * 4));   // -1: empty
   if (!hist_cnt_) hist_cnt_ = (int32_t*)dmalloc(rows * 4);
   HIP_OK(hipMemset(hist_cnt_, 0, rows * 4));
   hist_n_ = pen_last_n_;
+  if (rows_on())   // the bias ids the slots already have
+    for (size_t r = 0; r < rows; ++r) {
+      int32_t ids[kMaxLogitBias];
+      for (int i = 0; i < kMaxLogitBias; ++i) ids[i] = i < row_host_[r].n_bias ? row_host_[r].bias_id[i] : -1;
+      HIP_OK(hipMemcpy(hist_ + r * hist_ld_ + hist_n_, ids, sizeof(ids), hipMemcpyHostToDevice));
+    }
+}
+
+void HipStage::set_row_sampling(int mb, int row, const RowSampling& r) {
+  if (!spec_.last()) return;
+  if (!rows_on()) throw std::runtime_error("set_row_sampling: the stage was built without row_sampling");
+  if (mb < 0 || mb >= opt_.n_mb || row < 0 || row >= opt_.mb_size) throw std::runtime_error("set_row_sampling: bad row");
+  check_row_sampling(r, cfg_.vocab);
+  ensure_hist();
+  ensure_logprob();
+  const size_t s = (size_t)slot_of(mb, row);
+  row_host_[s] = r;
+  int32_t ids[kMaxLogitBias];
+  for (int i = 0; i < kMaxLogitBias; ++i) ids[i] = i < r.n_bias ? r.bias_id[i] : -1;
+  HIP_OK(hipSetDevice(spec_.device));
+  HIP_OK(hipStreamSynchronize(stream_));   // no launch may still read the old record
+  HIP_OK(hipMemcpy(row_tab_ + s, &r, sizeof(RowSampling), hipMemcpyHostToDevice));
+  HIP_OK(hipMemcpy(row_draw_ + s, &r.draw0, 4, hipMemcpyHostToDevice));
+  HIP_OK(hipMemcpy(hist_ + s * hist_ld_ + hist_n_, ids, sizeof(ids), hipMemcpyHostToDevice));
+}
+
+void HipStage::set_row_draws(int mb, const std::vector<int32_t>& draws) {
+  if (!spec_.last() || !rows_on()) return;
+  if (mb < 0 || mb >= opt_.n_mb || (int)draws.size() != opt_.mb_size) throw std::runtime_error("set_row_draws: bad size");
+  HIP_OK(hipSetDevice(spec_.device));
+  HIP_OK(hipStreamSynchronize(stream_));
+  HIP_OK(hipMemcpy(row_draw_ + (size_t)slot_of(mb, 0), draws.data(), draws.size() * 4, hipMemcpyHostToDevice));
 }
 
 // token logprob buffers (last stage, n_probs != 0): allocated when recording is switched on and when
@@ -724,9 +764,9 @@ void HipStage::ensure_logprob() {
     }
     lp_lse_ = (float*)dmalloc((size_t)B * 4);
   }
-  if (hist_ && lp_hist_n_ != hist_n_) {
-    lp_hist_raw_ = (float*)dmalloc((size_t)B * hist_n_ * 4);
-    lp_hist_n_ = hist_n_;
+  if (hist_ && lp_hist_n_ != hist_ld_) {
+    lp_hist_raw_ = (float*)dmalloc((size_t)B * hist_ld_ * 4);
+    lp_hist_n_ = hist_ld_;
   }
 }
 
@@ -780,19 +820,25 @@ void HipStage::copy_scores(int mb, int n, float* target_lp, int32_t* top_id, flo
 }
 
 void HipStage::set_history(int mb, const std::vector<std::vector<int32_t>>& seqs) {
-  if (!spec_.last() || !penalties_on()) return;
+  if (!spec_.last() || !(penalties_on() || rows_on())) return;
   ensure_hist();
   ensure_logprob();
-  const int B = opt_.mb_size, n = hist_n_;
-  std::vector<int32_t> h((size_t)B * n, -1), cnt(B, 0);
-  for (int b = 0; b < B && b < (int)seqs.size(); ++b) {
-    const auto& q = seqs[b];
-    const int take = std::min<int>(n, (int)q.size());
-    for (int i = 0; i < take; ++i) h[(size_t)b * n + i] = q[q.size() - take + i];
-    cnt[b] = take;
+  const int B = opt_.mb_size, n = hist_n_, ld = hist_ld_;
+  std::vector<int32_t> h((size_t)B * ld, -1), cnt(B, 0);
+  for (int b = 0; b < B; ++b) {
+    if (b < (int)seqs.size()) {
+      const auto& q = seqs[b];
+      const int take = std::min<int>(n, (int)q.size());
+      for (int i = 0; i < take; ++i) h[(size_t)b * ld + i] = q[q.size() - take + i];
+      cnt[b] = take;
+    }
+    if (rows_on()) {   // the row's bias ids stay behind its window
+      const RowSampling& r = row_host_[(size_t)slot_of(mb, b)];
+      for (int i = 0; i < r.n_bias; ++i) h[(size_t)b * ld + n + i] = r.bias_id[i];
+    }
   }
   HIP_OK(hipSetDevice(spec_.device));
-  HIP_OK(hipMemcpy(hist_ + (size_t)mb * B * n, h.data(), h.size() * 4, hipMemcpyHostToDevice));
+  HIP_OK(hipMemcpy(hist_ + (size_t)mb * B * ld, h.data(), h.size() * 4, hipMemcpyHostToDevice));
   HIP_OK(hipMemcpy(hist_cnt_ + (size_t)mb * B, cnt.data(), cnt.size() * 4, hipMemcpyHostToDevice));
 }
 
@@ -1267,8 +1313,47 @@ void HipStage::lm_head(const float* x, int M, float* logits, bool small, hipStre
   gemv(MatCall(c).in(xn_, Kd_), st);
 }
 
-void HipStage::head(int mb, int M, const float* x, int32_t* tok_out, uint64_t salt, hipStream_t st) {
+// head() with row_sampling: every launch has fixed arguments and reads the rows' records, draw
+// indices and windows from device memory, so the decode graphs are captured once.  Raw-logit
+// statistics (n_probs) -> bias + penalties per row -> arg-max of every row -> the sampled rows' draws
+// over it -> the chosen tokens' logprobs -> the windows.
+void HipStage::head_rows(int mb, int M, int32_t* tok_out, bool advance, hipStream_t st) {
+  const int B = opt_.mb_size;
+  const size_t r0 = (size_t)mb * B;
+  if (!hist_) throw std::runtime_error("row_sampling: the windows were not allocated (set_penalties)");
+  int32_t* hist = hist_ + r0 * hist_ld_;
+  const bool lp = n_probs_ != 0 && !lp_rec_.empty();
+  float* rec = lp ? lp_rec_[mb] : nullptr;
+  if (lp) {   // the ids whose raw logits are saved: the window, then the bias ids
+    LogprobParams q{};
+    q.logits = logits_; q.ld = logits_ld_; q.n = cfg_.vocab; q.M = M;
+    q.top_n = std::max(n_probs_, 0); q.lse = lp_lse_;
+    q.top_id = (int32_t*)(rec + B); q.top_lp = rec + B + (size_t)B * kMaxProbs; q.ld_top = kMaxProbs;
+    q.hist = hist; q.last_n = hist_ld_; q.hist_raw = lp_hist_raw_;
+    launch_logprob(q, st);
+  }
+  RowAdjustParams ra{};
+  ra.logits = logits_; ra.ld = logits_ld_; ra.n = cfg_.vocab; ra.M = M;
+  ra.rows = row_tab_ + r0; ra.hist = hist; ra.hist_ld = hist_ld_; ra.last_n = hist_n_;
+  launch_row_adjust(ra, st);
+  launch_argmax(logits_, logits_ld_, cfg_.vocab, M, tok_out, st, &am_);
+  SampleRowsParams sp{};
+  sp.logits = logits_; sp.ld = logits_ld_; sp.n = cfg_.vocab; sp.M = M;
+  sp.rows = row_tab_ + r0; sp.draw = row_draw_ + r0; sp.advance = advance ? 1 : 0; sp.tokens = tok_out;
+  launch_sample_rows(sp, st);
+  if (lp) {
+    LogprobChosenParams c{};
+    c.logits = logits_; c.ld = logits_ld_; c.n = cfg_.vocab; c.M = M; c.tokens = tok_out; c.lse = lp_lse_;
+    c.hist = hist; c.last_n = hist_ld_; c.hist_raw = lp_hist_raw_;
+    c.chosen_lp = rec;
+    launch_logprob_chosen(c, st);
+  }
+  launch_hist_push_ld(hist, hist_ld_, hist_cnt_ + r0, hist_n_, tok_out, M, st);
+}
+
+void HipStage::head(int mb, int M, const float* x, int32_t* tok_out, uint64_t salt, hipStream_t st, bool advance) {
   lm_head(x, M, logits_, small_path(M), st);
+  if (rows_on()) return head_rows(mb, M, tok_out, advance, st);
   const bool pen = penalties_on() && hist_;
   int32_t* hist = pen ? hist_ + (size_t)mb * opt_.mb_size * hist_n_ : nullptr;
   // token logprobs are those of the RAW logits: the statistics (and the raw logits of the ids the
@@ -1378,13 +1463,14 @@ void HipStage::decode_eager(int mb, hipStream_t st) {
   const Fwd f{B, pos_[mb], kvlen_[mb], slot_[mb], true, slot_of(mb, 0), nullptr, st};   // slot_[mb][b] = slot0 + b
   for (size_t li = 0; li < layers_.size(); ++li) layer_forward((int)li, x, f);
   flush_sk(st);
-  if (spec_.last()) head(mb, B, x, tok_[mb], (uint64_t)mb + 1, st);
+  if (spec_.last()) head(mb, B, x, tok_[mb], (uint64_t)mb + 1, st, true);
   launch_advance(pos_[mb], kvlen_[mb], B, mb == 0 ? step_ : nullptr, st);
 }
 
 void HipStage::capture_graphs() {
   HIP_OK(hipSetDevice(spec_.device));
   destroy_graphs();
+  ++graph_captures_;
   if (!opt_.use_graphs) return;
   for (int mb = 0; mb < opt_.n_mb; ++mb) {
     hipGraph_t g;

@@ -158,6 +158,9 @@ class HipStage : public Stage {
   void set_sampling(float temp, int top_k, float top_p, float min_p, uint64_t seed) override;
   void set_penalties(int last_n, float repeat, float freq, float presence) override;
   void set_history(int mb, const std::vector<std::vector<int32_t>>& seqs) override;
+  void set_row_sampling(int mb, int row, const RowSampling& r) override;
+  void set_row_draws(int mb, const std::vector<int32_t>& draws) override;
+  long graph_captures() const override { return graph_captures_; }
 
   size_t weight_bytes() const override { return weight_bytes_; }
   size_t kv_bytes() const override { return kv_bytes_; }
@@ -215,7 +218,8 @@ class HipStage : public Stage {
   // final RMSNorm + LM head of M rows of x into logits [M][logits_ld_].  small: the gemvs form with
   // the norm fused (the decode head at M <= 4; the chunk heads of prefill keep the standalone norm)
   void lm_head(const float* x, int M, float* logits, bool small, hipStream_t st);
-  void head(int mb, int M, const float* x, int32_t* tok_out, uint64_t salt, hipStream_t st);
+  // advance: a decode step (row_sampling: the rows' draw indices move on)
+  void head(int mb, int M, const float* x, int32_t* tok_out, uint64_t salt, hipStream_t st, bool advance = false);
   void ensure_hist();
   void ensure_logprob();
   void ensure_chunk_head();
@@ -296,6 +300,16 @@ class HipStage : public Stage {
   int32_t* hist_ = nullptr;
   int32_t* hist_cnt_ = nullptr;
   int hist_n_ = 0;
+  int hist_ld_ = 0;   // row stride of hist_: hist_n_, plus kMaxLogitBias with row_sampling (the row's bias ids
+                      // follow its window, so launch_logprob saves their raw logits with the window's)
+  // per-request sampling (opt_.row_sampling, last stage): the slots' records [n_mb][mb_size] on the
+  // device and their host copy, and each slot's draw index
+  RowSampling* row_tab_ = nullptr;
+  std::vector<RowSampling> row_host_;
+  int32_t* row_draw_ = nullptr;
+  bool rows_on() const { return row_tab_ != nullptr; }
+  void head_rows(int mb, int M, int32_t* tok_out, bool advance, hipStream_t st);
+  long graph_captures_ = 0;
   // prefill metadata
   int32_t* pf_pos_ = nullptr; int32_t* pf_kvlen_ = nullptr; int32_t* pf_slot_ = nullptr;
   int32_t* prompt_dev_ = nullptr;

@@ -317,6 +317,50 @@ void launch_penalize(const PenaltyParams& p, hipStream_t st);
 // append tokens[m] to row m's ring: hist[m][cnt[m] % last_n] = tokens[m]; ++cnt[m]
 void launch_hist_push(int32_t* hist, int32_t* cnt, int last_n, const int32_t* tokens, int M, hipStream_t st);
 
+// Per-request sampling (sample_rows.hip; engine key "row_sampling"): one record per sequence slot in a
+// device table the captured decode graphs read, so an admit copies records and never re-captures.
+// Chain of a row: raw logits -> logit bias -> penalties -> cuts at T = 1 (top-k, top-p, min-p) ->
+// draw at temperature T.  The d-th token a request generates (d = draw0, draw0 + 1, ..) uses
+//   u = (mix64(seed ^ mix64(d << 20)) >> 40) / 2^24
+// whatever its slot, row, micro-batch or round of admission.
+constexpr int kMaxLogitBias = 32;
+struct RowSampling {
+  float temp = 0.f; int32_t top_k = 0; float top_p = 1.f; float min_p = 0.f;   // temp <= 0: greedy
+  float repeat = 1.f, freq = 0.f, presence = 0.f;
+  int32_t n_bias = 0;
+  uint64_t seed = 0;
+  int32_t draw0 = 0;      // draws the request consumed before this admission (failover, resume)
+  int32_t pad_ = 0;
+  int32_t bias_id[kMaxLogitBias] = {};
+  float bias_val[kMaxLogitBias] = {};   // -inf bans the token
+};
+static_assert(sizeof(RowSampling) == 304, "RowSampling is a device record");
+// bias, then penalties, in place; one workgroup per row; a row without bias and with neutral
+// penalties (repeat 1, freq 0, presence 0) returns before touching its logits.  The window of row m
+// is hist[m * hist_ld .. + last_n) (-1 = empty); penalty maths as launch_penalize.  An id listed
+// several times in bias_id gets its values added in list order.
+struct RowAdjustParams {
+  float* logits; int ld; int n; int M;
+  const RowSampling* rows;               // [M]
+  const int32_t* hist; int hist_ld; int last_n;
+};
+void launch_row_adjust(const RowAdjustParams& p, hipStream_t st);
+// sampled rows (temp > 0) get tokens[m] from the chain of sample_kernel with the row's own
+// parameters and the variate above at d = draw[m]; greedy rows return without writing tokens[m]
+// (the caller ran launch_argmax into tokens first).  advance: draw[m] += 1 for every row.
+struct SampleRowsParams {
+  const float* logits; int ld; int n; int M;
+  const RowSampling* rows;               // [M]
+  int32_t* draw;                         // [M] draw index of each row's next token
+  int advance;
+  int32_t* tokens;
+};
+void launch_sample_rows(const SampleRowsParams& p, hipStream_t st);
+// launch_hist_push for windows stored with a row stride (the same kernel; launch_hist_push passes
+// hist_ld = last_n): hist[m * hist_ld + cnt[m] % last_n] = tokens[m]
+void launch_hist_push_ld(int32_t* hist, int hist_ld, int32_t* cnt, int last_n, const int32_t* tokens, int M,
+                         hipStream_t st);
+
 // pos[i] += 1, kvlen[i] = pos[i] + 1 for i < M (graph-resident decode step advance)
 void launch_advance(int32_t* pos, int32_t* kvlen, int M, int32_t* step, hipStream_t st);
 

@@ -153,7 +153,10 @@ std::vector<GenResult> Session::run(std::vector<GenRequest>& reqs) {
     }
     return res;
   }
+  for (size_t i = 0; i < reqs.size(); ++i) set_slot_record((int)i, reqs[i], res[i]);
   eng_->start(prompts);
+  if (eng_->row_sampling())
+    for (size_t i = 0; i < reqs.size(); ++i) { res[i].seed = eng_->slot_sampling((int)i).seed; res[i].has_seed = true; }
   const double t1 = now_ms();
   // a middle rank of a multi-process pipeline sees no tokens (they travel the ring from the last
   // stage to the first): nothing to consume there
@@ -183,6 +186,18 @@ std::vector<GenResult> Session::run(std::vector<GenRequest>& reqs) {
     res[i].decode_ms = t2 - t1;
   }
   return res;
+}
+
+void Session::set_slot_record(int slot, const GenRequest& req, const GenResult& res) {
+  if (!eng_->row_sampling()) {
+    if (req.has_sampling) throw std::runtime_error("per-request sampling needs an engine built with row_sampling");
+    return;
+  }
+  RowSampling r = req.has_sampling ? req.sampling : eng_->sampling_defaults();
+  bool seeded = req.has_sampling && req.has_seed;
+  if (res.has_seed) { r.seed = res.seed; seeded = true; }
+  r.draw0 += (int32_t)res.tokens.size();
+  eng_->set_slot_sampling(slot, r, seeded, /*for_start=*/true);
 }
 
 void Session::serve(const std::function<std::vector<Served>(int free)>& next) {
@@ -342,7 +357,11 @@ void Session::serve(const std::function<std::vector<Served>(int free)>& next) {
     }
     for (auto it = requeue.rbegin(); it != requeue.rend(); ++it) waiting.push_front(std::move(*it));
     if (prompts.empty()) return false;
+    // each request goes on in its own random stream: its seed, draw0 = the tokens it has produced
+    for (size_t i = 0; i < prompts.size(); ++i) set_slot_record((int)i, live[i]->s.req, live[i]->res);
     eng_->start(prompts);   // a replacement fault propagates (the handler already had its turn)
+    for (size_t i = 0; i < prompts.size(); ++i)
+      if (eng_->row_sampling()) { live[i]->res.seed = eng_->slot_sampling((int)i).seed; live[i]->res.has_seed = true; }
     for (size_t i = 0; i < prompts.size(); ++i)
       if (!consume((int)i, eng_->last_token((int)i))) finish((int)i);
     return false;
@@ -385,6 +404,7 @@ void Session::serve(const std::function<std::vector<Served>(int free)>& next) {
     if (!slots.empty()) {
       // nothing running: a plain start() of slots 0..n-1 (resets the engine's rounds)
       const bool ok = guarded([&] {
+        for (int sl : slots) set_slot_record(sl, live[sl]->s.req, live[sl]->res);
         if (idle && slots.back() == (int)slots.size() - 1) eng_->start(prompts);
         else eng_->admit(slots, prompts);
       });
@@ -392,6 +412,7 @@ void Session::serve(const std::function<std::vector<Served>(int free)>& next) {
       const double t = now_ms();
       for (int sl : slots) {
         Live& L = *live[sl];
+        if (eng_->row_sampling()) { L.res.seed = eng_->slot_sampling(sl).seed; L.res.has_seed = true; }
         if (!L.resumed) {
           L.t1 = t;
           L.res.prefill_ms = t - L.t0;

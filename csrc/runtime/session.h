@@ -23,6 +23,10 @@ double session_now_ms();
 struct GenRequest {
   std::string prompt;
   int n_predict = 200;
+  // per-request sampling (engines built with row_sampling): the slot record of this request; without
+  // has_seed it gets the engine's next default seed (GenResult::seed reports the one used)
+  bool has_sampling = false, has_seed = false;
+  RowSampling sampling;
   // receives text pieces (complete UTF-8); return false to cancel this sequence
   std::function<bool(const std::string& piece)> on_piece;
 };
@@ -44,6 +48,8 @@ struct GenResult {
   std::string stop;   // "eog" | "length" | "cancelled" | "context"
   std::vector<int32_t> tokens;
   std::vector<TokenProb> probs;   // one per token of `tokens` when the engine records logprobs
+  bool has_seed = false;          // row_sampling engines: the seed of the request's random stream
+  uint64_t seed = 0;
 };
 
 class Session {
@@ -86,6 +92,10 @@ class Session {
 
  private:
   void push_prob(GenResult& r, int slot, int32_t t) const;
+  // row_sampling engines: the record of `slot` for the admission of req (the engine's values without
+  // one).  A request that has already produced res.tokens (failover, resume) keeps its seed and goes on
+  // at draw0 + tokens produced, so it continues its own stream.
+  void set_slot_record(int slot, const GenRequest& req, const GenResult& res);
   Engine* eng_;
   std::function<Engine*(const std::string&)> on_fault_;
   int max_failovers_ = 0, failovers_ = 0;

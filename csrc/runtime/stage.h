@@ -5,10 +5,13 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdint>
+#include <stdexcept>
 #include <string>
 #include <vector>
 
+#include "kernels_api.h"
 #include "model.h"
 
 namespace mp {
@@ -43,6 +46,8 @@ struct StageOptions {
   bool fused_norm = false;  // M <= 4 rows: deferred RMSNorm folded into the qkv / gate-up GEMVs (gemv2.hip);
                             // off by default: 8B mb1 470.7 vs 473.7 tok/s, 70B mb1 92.5 vs 104.8 (r2i)
   bool moe_gemm = true;     // M > 64 MoE FFN on the grouped expert GEMM (gemm4.hip) instead of 64-row GEMV slices
+  bool row_sampling = false;   // per-request sampling: the last stage keeps a RowSampling record and a draw
+                               // index per sequence slot, and head() reads them (set_row_sampling)
   bool small_gemv = true;   // M <= 4 rows: the gemvs kernels (gemvs.hip: x staged once per workgroup,
                             // RMSNorm fused into the qkv / gate-up / LM-head GEMVs, in-workgroup split-K)
 };
@@ -57,6 +62,24 @@ struct PrefillSeg {
   bool verify = false;  // speculative verification chunk: the last stage scores EVERY row (greedy
                         // argmax after each row -> verify_tokens), nothing is kept for prefill_finish
 };
+
+// throws naming the field a record is out of range in
+inline void check_row_sampling(const RowSampling& r, int vocab) {
+  auto bad = [](const char* f) { throw std::runtime_error(std::string("row sampling: bad value for ") + f); };
+  if (!(r.temp == r.temp)) bad("temp");
+  if (r.top_k < 0) bad("top_k");
+  if (!(r.top_p > 0.f && r.top_p <= 1.f)) bad("top_p");
+  if (!(r.min_p >= 0.f && r.min_p <= 1.f)) bad("min_p");
+  if (!(r.repeat > 0.f) || std::isinf(r.repeat)) bad("repeat");
+  if (!std::isfinite(r.freq)) bad("freq");
+  if (!std::isfinite(r.presence)) bad("presence");
+  if (r.draw0 < 0) bad("draw0");
+  if (r.n_bias < 0 || r.n_bias > kMaxLogitBias) bad("n_bias");
+  for (int i = 0; i < r.n_bias; ++i) {
+    if (r.bias_id[i] < 0 || r.bias_id[i] >= vocab) bad("logit_bias id");
+    if (r.bias_val[i] != r.bias_val[i] || r.bias_val[i] == INFINITY) bad("logit_bias value");
+  }
+}
 
 class Stage {
  public:
@@ -121,6 +144,15 @@ class Stage {
   }
   // last stage: seed the penalty window of micro-batch mb (row b <- seqs[b], its last tokens)
   virtual void set_history(int mb, const std::vector<std::vector<int32_t>>& seqs) { (void)mb; (void)seqs; }
+
+  // Per-request sampling (StageOptions::row_sampling), last stage, between engine calls: the record of
+  // row `row` of micro-batch mb; its draw index becomes r.draw0.  head() then samples every row by its
+  // own record; a decode step advances every row's draw index, prefill_finish() none (the engine
+  // sets the indices of a micro-batch after an admission: set_row_draws).  Other stages ignore both.
+  virtual void set_row_sampling(int mb, int row, const RowSampling& r) { (void)mb; (void)row; (void)r; }
+  virtual void set_row_draws(int mb, const std::vector<int32_t>& draws) { (void)mb; (void)draws; }
+  // how often capture_graphs() ran (health(): an admit on a row_sampling engine must not grow it)
+  virtual long graph_captures() const { return 0; }
 
   // Checkpoint / resume (the reference has none beyond re-reading the GGUF):
   // the KV of sequence slot `slot` (= mb * mb_size + row) for positions [0, n_tok) of every layer

@@ -95,6 +95,8 @@ inline void print_common_usage(FILE* f) {
           "  --sampling greedy         force greedy\n"
           "  --n-probs N               record token log-probabilities (raw log-softmax): -1 the chosen token's\n"
           "                            only, 1..20 plus that many alternatives (default 0: off)\n"
+          "  --row-sampling            sample every sequence slot by its own record in a device table (engine key\n"
+          "                            row_sampling; the slots start at the values above)\n"
           "  --perplexity -f FILE      perplexity of a text file, llama.cpp's procedure: windows of -c tokens,\n"
           "                            the second half of each window counts\n"
           "  --draft-max K             speculative decoding by prompt lookup: up to K drafted tokens per\n"
@@ -193,6 +195,7 @@ inline CliOptions parse_cli(int argc, char** argv,
     else if (a == "--bench") o.bench = true;
     else if (a == "--perplexity") o.perplexity = true;
     else if (a == "--n-probs") e["n_probs"] = std::atoi(val().c_str());
+    else if (a == "--row-sampling") e["row_sampling"] = true;
     else if (a == "--bench-prompt") o.bench_prompt = std::atoi(val().c_str());
     else if (a == "--bench-warmup") o.bench_warmup = std::atoi(val().c_str());
     else if (a == "--bench-steps") o.bench_steps = std::atoi(val().c_str());

@@ -74,6 +74,9 @@ struct Job {
   std::string prompt;
   std::string model;   // "" = the default model
   int n_predict = 200;
+  // per-request sampling (--row-sampling): the record built from the request's fields
+  bool has_sampling = false, has_seed = false;
+  RowSampling sampling;
   double enqueued_ms = 0;   // fairness between models (serve_model)
   std::mutex mu;
   std::condition_variable cv;
@@ -303,6 +306,7 @@ void serve_model(Server& S, ModelSlot* slot, const std::string& model) {
       Session::Served sv;
       sv.req.prompt = j->prompt;
       sv.req.n_predict = j->n_predict;
+      sv.req.has_sampling = j->has_sampling; sv.req.has_seed = j->has_seed; sv.req.sampling = j->sampling;
       Job* jp = j.get();
       sv.req.on_piece = [jp](const std::string& p) {
         if (jp->cancelled) return false;
@@ -444,6 +448,8 @@ void generation_loop(Server& S) {
         for (size_t i = 0; i < batch.size(); ++i) {
           reqs[i].prompt = batch[i]->prompt;
           reqs[i].n_predict = batch[i]->n_predict;
+          reqs[i].has_sampling = batch[i]->has_sampling; reqs[i].has_seed = batch[i]->has_seed;
+          reqs[i].sampling = batch[i]->sampling;
           Job* jp = batch[i].get();
           reqs[i].on_piece = [jp](const std::string& p) {
             if (jp->cancelled) return false;
@@ -751,8 +757,64 @@ void spawn_job(Server& S, std::shared_ptr<Job> job) {
   job->finish();
 }
 
-std::shared_ptr<Job> submit(Server& S, const std::string& prompt, int n, const std::string& model = "") {
+// The sampling fields every llama.cpp-server client sends: temperature, top_k, top_p, min_p, seed,
+// repeat_penalty, frequency_penalty, presence_penalty, logit_bias ([[id, bias | false], ..] or {"id": bias})
+// -> the request's slot record (Engine::sampling_from_json).  They need a server started with
+// --row-sampling; repeat_last_n is the server's (a request may only repeat it).  false: a 400 was sent.
+struct ReqSampling {
+  bool has = false, has_seed = false;
+  RowSampling rec;
+};
+bool parse_sampling(Server& S, int fd, const Json& body, const std::string& model, ReqSampling* out) {
+  static const char* const kFields[][2] = {{"temperature", "temp"}, {"top_k", "top_k"}, {"top_p", "top_p"},
+                                           {"min_p", "min_p"}, {"seed", "seed"}, {"repeat_penalty", "repeat"},
+                                           {"frequency_penalty", "freq"}, {"presence_penalty", "presence"},
+                                           {"logit_bias", "logit_bias"}};
+  Json j = Json::object();
+  bool any = body.has("repeat_last_n");
+  for (auto& f : kFields)
+    if (body.has(f[0]) && !body[f[0]].is_null()) {
+      any = true;
+      // llama.cpp clients send seed -1 (or 2^32 - 1) for "pick one": the same as no seed
+      if (std::string(f[0]) == "seed" && body[f[0]].is_num() && (body[f[0]].num() < 0 || body[f[0]].num() == 4294967295.0))
+        continue;
+      j[f[1]] = body[f[0]];
+    }
+  if (!any) return true;
+  if (!S.spawn_cli.empty()) {
+    respond_text(fd, 400, "per-request sampling fields are not supported in --spawn-cli mode");
+    return false;
+  }
+  std::lock_guard<std::mutex> l(S.eng_mu);
+  Engine* e = S.eng;
+  if (!model.empty())
+    if (ModelSlot* m = find_model(S, model)) e = m->eng.get();
+  if (!e || !e->row_sampling()) {
+    respond_text(fd, 400, "per-request sampling fields (temperature, top_k, top_p, min_p, seed, repeat_penalty, "
+                          "frequency_penalty, presence_penalty, logit_bias) need a server started with --row-sampling");
+    return false;
+  }
+  if (body.has("repeat_last_n")) {
+    const int have = e->config().get_int("repeat_last_n", 64);
+    if (!body["repeat_last_n"].is_num() || body["repeat_last_n"].num() != (double)have) {
+      respond_text(fd, 400, "repeat_last_n is the server's (" + std::to_string(have) + "), not a per-request value");
+      return false;
+    }
+  }
+  try {
+    out->rec = e->sampling_from_json(j, &out->has_seed);
+    out->has = true;
+  } catch (const std::exception& ex) {
+    respond_text(fd, 400, ex.what());
+    return false;
+  }
+  return true;
+}
+
+std::shared_ptr<Job> submit(Server& S, const std::string& prompt, int n, const std::string& model = "",
+                            const ReqSampling* rs = nullptr) {
   auto job = std::make_shared<Job>();
+  if (rs && rs->has) { job->has_sampling = true; job->has_seed = rs->has_seed; job->sampling = rs->rec; }
   job->prompt = prompt;
   job->n_predict = n;
   job->model = model;
@@ -792,8 +854,11 @@ void handle_chat(Server& S, int fd, const Request& r) {
   std::string prompt;
   int n = S.default_n;
   std::string model;
-  if (!parse_prompt_body(fd, r, &prompt, &n, S.default_n, &model) || !known_model(S, fd, &model)) return;
-  auto job = submit(S, prompt, n, model);
+  Json body;
+  if (!parse_prompt_body(fd, r, &prompt, &n, S.default_n, &model, &body) || !known_model(S, fd, &model)) return;
+  ReqSampling rs;
+  if (!parse_sampling(S, fd, body, model, &rs)) return;
+  auto job = submit(S, prompt, n, model, &rs);
   std::string h = "HTTP/1.1 200 OK\r\nContent-Type: text/event-stream\r\nCache-Control: no-cache\r\n";
   h += kCors;
   h += "Transfer-Encoding: chunked\r\nConnection: close\r\n\r\n";
@@ -848,7 +913,9 @@ void handle_completion(Server& S, int fd, const Request& r) {
                               std::to_string(have) + ")");
     return;
   }
-  auto job = submit(S, prompt, n, model);
+  ReqSampling rs;
+  if (!parse_sampling(S, fd, body, model, &rs)) return;
+  auto job = submit(S, prompt, n, model, &rs);
   {
     std::unique_lock<std::mutex> l(job->mu);
     job->cv.wait(l, [&] { return job->done; });
@@ -858,6 +925,10 @@ void handle_completion(Server& S, int fd, const Request& r) {
   o["content"] = g.text;
   o["response"] = g.text;
   o["tokens_predicted"] = g.n_gen;
+  if (g.has_seed) {   // --row-sampling: the seed of this request's stream (a string above 2^53, which a number cannot hold)
+    if (g.seed <= (1ULL << 53)) o["seed"] = (double)g.seed;
+    else o["seed"] = std::to_string(g.seed);
+  }
   if (n_probs > 0) {   // llama.cpp's field: one entry per generated token, n_probs alternatives each
     Json cp = Json::array();
     for (const TokenProb& tp : g.probs) {

@@ -141,6 +141,11 @@ _SIGS = {
     "mp_engine_start": ([c_void_p, c_void_p, c_void_p, c_int], c_int),
     "mp_engine_admit": ([c_void_p, c_void_p, c_void_p, c_void_p, c_int], c_int),
     "mp_engine_release": ([c_void_p, c_int], c_int),
+    "mp_engine_set_slot_sampling": ([c_void_p, c_int, c_char_p, c_int], c_int),
+    "mp_engine_slot_sampling": ([c_void_p, c_int], c_char_p),
+    "mp_row_sampling_bytes": ([], c_int),
+    "mp_row_adjust": ([c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p], c_int),
+    "mp_sample_rows": ([c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p], c_int),
     "mp_engine_decode": ([c_void_p, c_int], c_char_p),
     "mp_engine_tokens": ([c_void_p, c_void_p, c_int, c_int], c_int),
     "mp_engine_logprobs": ([c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int], c_int),

@@ -13,7 +13,8 @@ threads (CPU backend), trace, watchdog_s, link_timeout_s, fault (fault injection
 kv_dtype ("f16" | "fp8"), kv_pool_tokens (paged KV pool), prefill_gemm_v (0 auto | 1 | 2 | 3 | 4), prefill_flash,
 deterministic, fused_norm, small_gemv, act_dtype (stage-boundary wire: "auto" | "f32" | "bf16" | "f16"),
 device_speed ("probe" or a list; Halda-style partition weights), n_probs (token logprobs: 0 off, -1 the
-chosen token's only, 1..20 plus that many alternatives; read with logprobs()).
+chosen token's only, 1..20 plus that many alternatives; read with logprobs()), row_sampling (per-request
+sampling: every sequence slot has its own record, see set_slot_sampling).
 """
 from __future__ import annotations
 
@@ -76,15 +77,54 @@ class Engine:
                         n_predict, draft_max, ngram, out.ctypes.data, what="spec_generate")
         return out.tolist(), stats
 
-    def start(self, prompts):
+    def set_slot_sampling(self, slot: int, _for_start: bool = False, **fields):
+        """Per-request sampling (Engine(row_sampling=True)): the record the next start() / admit() of the
+        idle slot `slot` uses.  Fields: temp, top_k, top_p, min_p, repeat, freq, presence (absent = the
+        engine's values; temp <= 0 = greedy), seed (the request's own random stream; absent = a default
+        one, reported by slot_sampling), draw0 (draws already consumed: the request continues its
+        stream there), logit_bias ([[id, bias], ..], bias False or -inf bans the token; at most 32).
+        The d-th token a request generates is drawn with u = (mix64(seed ^ mix64(d << 20)) >> 40) / 2^24
+        whatever slot, micro-batch or round it runs in.  release() puts the slot back to the defaults."""
+        f = dict(fields)
+        for k, v in f.items():   # JSON carries no NaN / inf: refuse them here, by name, as the engine would
+            if isinstance(v, float) and not np.isfinite(v):
+                raise RuntimeError(f"set_slot_sampling: bad value for {k}")
+        if f.get("seed") is not None:
+            f["seed"] = str(int(f["seed"]))
+        if f.get("logit_bias") is not None:
+            lb = f["logit_bias"]
+            lb = list(lb.items()) if isinstance(lb, dict) else list(lb)
+            f["logit_bias"] = [[int(i), False if (b is False or b == float("-inf")) else float(b)] for i, b in lb]
+        N.check(N.lib().mp_engine_set_slot_sampling(self._h, int(slot), N.cstr(json.dumps(f)), int(_for_start)),
+                "set_slot_sampling")
+
+    def slot_sampling(self, slot: int) -> dict:
+        """The record of a slot, with the seed in use (int)."""
+        j = N.jcall(N.lib().mp_engine_slot_sampling, self._h, int(slot), what="slot_sampling")
+        j["seed"] = int(j["seed"])
+        return j
+
+    def _set_sampling(self, slots, sampling, for_start=False):
+        if sampling is None:
+            return
+        if len(sampling) != len(slots):
+            raise ValueError("sampling: one dict or None per prompt")
+        for sl, f in zip(slots, sampling):
+            if f is not None:
+                self.set_slot_sampling(sl, _for_start=for_start, **f)
+
+    def start(self, prompts, sampling=None):
+        """sampling (row_sampling engines): one dict of set_slot_sampling fields or None per prompt."""
         flat, lens = self._flat(prompts)
         self._n_seq = len(prompts)
+        self._set_sampling(range(len(prompts)), sampling, for_start=True)   # start() resets every slot
         N.check(N.lib().mp_engine_start(self._h, flat.ctypes.data, lens.ctypes.data, len(prompts)), "start")
 
-    def admit(self, slots, prompts):
+    def admit(self, slots, prompts, sampling=None):
         """Continuous batching: between decode rounds, prefill `prompts` into the idle sequence slots
-        `slots` (slot = micro-batch * mb_size + row); the other slots keep generating."""
+        `slots` (slot = micro-batch * mb_size + row); the other slots keep generating.  sampling: as start()."""
         flat, lens = self._flat(prompts)
+        self._set_sampling(list(slots), sampling)
         sl = np.asarray(slots, np.int32)
         N.check(N.lib().mp_engine_admit(self._h, sl.ctypes.data, flat.ctypes.data, lens.ctypes.data, len(prompts)),
                 "admit")

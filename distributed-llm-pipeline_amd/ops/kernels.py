@@ -456,6 +456,61 @@ def penalize(logits: torch.Tensor, hist: torch.Tensor, repeat: float = 1.0, freq
     return logits
 
 
+MAX_LOGIT_BIAS = 32
+# the device record of one row (RowSampling, csrc/runtime/kernels_api.h)
+ROW_SAMPLING_DTYPE = np.dtype([("temp", "<f4"), ("top_k", "<i4"), ("top_p", "<f4"), ("min_p", "<f4"), ("repeat", "<f4"),
+                               ("freq", "<f4"), ("presence", "<f4"), ("n_bias", "<i4"), ("seed", "<u8"), ("draw0", "<i4"),
+                               ("pad", "<i4"), ("bias_id", "<i4", (MAX_LOGIT_BIAS,)), ("bias_val", "<f4", (MAX_LOGIT_BIAS,))])
+
+
+def row_records(rows, device) -> torch.Tensor:
+    """Device table (uint8 [M][304]) of per-row sampling records from dicts with the keys temp, top_k,
+    top_p, min_p, repeat, freq, presence, seed, draw0 and bias (a list of (id, value) pairs, <= 32)."""
+    assert ROW_SAMPLING_DTYPE.itemsize == N.lib().mp_row_sampling_bytes()
+    a = np.zeros(len(rows), ROW_SAMPLING_DTYPE)
+    a["top_p"], a["repeat"] = 1.0, 1.0
+    for i, r in enumerate(rows):
+        r = dict(r)
+        bias = list(r.pop("bias", ()))
+        assert len(bias) <= MAX_LOGIT_BIAS
+        for k, v in r.items():
+            a[k][i] = v
+        a["n_bias"][i] = len(bias)
+        for j, (t, v) in enumerate(bias):
+            a["bias_id"][i, j], a["bias_val"][i, j] = t, v
+    return torch.from_numpy(a.view(np.uint8).reshape(len(rows), -1).copy()).to(device)
+
+
+def row_adjust(logits: torch.Tensor, records: torch.Tensor, hist: torch.Tensor | None = None,
+               last_n: int | None = None) -> torch.Tensor:
+    """In place, per row: logit bias, then the repetition penalties of the row's record over its window
+    hist[m][:last_n] (int32 [M][hist_ld], -1 = empty; last_n defaults to the width).  logits f32 [M][n]."""
+    M, n = logits.shape
+    assert logits.dtype == torch.float32 and logits.stride(1) == 1 and records.shape[0] == M
+    hist_ld = 0
+    if hist is not None:
+        assert hist.dtype == torch.int32 and hist.shape[0] == M and hist.is_contiguous()
+        hist_ld = hist.shape[1]
+    last_n = hist_ld if last_n is None else last_n
+    N.check(N.lib().mp_row_adjust(_ptr(logits), logits.stride(0), n, M, _ptr(records), _ptr(hist), hist_ld, last_n,
+                                  _stream()), "row_adjust")
+    return logits
+
+
+def sample_rows(logits: torch.Tensor, records: torch.Tensor, draw: torch.Tensor, tokens: torch.Tensor | None = None,
+                advance: bool = False) -> torch.Tensor:
+    """Per-row sampler: row m with temp > 0 draws tokens[m] by its own record at draw index draw[m]
+    (int32 [M]); a greedy row leaves tokens[m] as given (-1 when tokens is None).  advance: draw += 1."""
+    M, n = logits.shape
+    assert logits.dtype == torch.float32 and logits.stride(1) == 1 and records.shape[0] == M
+    assert draw.dtype == torch.int32 and draw.numel() == M and draw.is_contiguous()
+    out = torch.full((M,), -1, dtype=torch.int32, device=logits.device) if tokens is None else tokens
+    assert out.dtype == torch.int32 and out.numel() == M and out.is_contiguous()
+    N.check(N.lib().mp_sample_rows(_ptr(logits), logits.stride(0), n, M, _ptr(records), _ptr(draw), int(advance),
+                                   _ptr(out), _stream()), "sample_rows")
+    return out
+
+
 LOGPROB_MAX_TOP = 20
 
 
