@@ -378,6 +378,128 @@ template <> struct Deq<P_Q2_K> {
   }
 };
 
+// ------------------------------------------------------------------ 5-bit affine blocks (Q5_0, Q5_1)
+// Q4_K's nibble order and Q5_K's high-bit byte hb (bit 4 (j & 1) + (j >> 1)) OR-ed in at +16;
+// w = S q + M in one fma: Q5_1 has S = d, M = m; Q5_0 has M = -16 d (exact), so the fma rounds
+// d (q - 16) once.
+__device__ __forceinline__ half8_t q5_frag(uint32_t w, uint32_t hb, half2_t S, half2_t M, const Consts& k) {
+  const uint32_t t = w >> 8, x = hb | (hb << 12);   // (x >> i): hi(2i) at bit 0, hi(2i+1) at bit 16
+  const uint32_t h0 = ((x << 4) & 0x00100010u) | k.mag_hi, h1 = ((x << 7) & 0x01000100u) | k.mag_lo;
+  const uint32_t h2 = ((x << 2) & 0x00100010u) | k.mag_hi, h3 = ((x << 5) & 0x01000100u) | k.mag_lo;
+  return pack8(as_u32(__builtin_elementwise_fma(as_h2(and_or(w, k.mlo, h0)) - h2c(1024.f), S, M)),
+               as_u32(__builtin_elementwise_fma(as_h2(and_or(w, k.mhi, h1)) - h2c(64.f), S, M)),
+               as_u32(__builtin_elementwise_fma(as_h2(and_or(t, k.mlo, h2)) - h2c(1024.f), S, M)),
+               as_u32(__builtin_elementwise_fma(as_h2(and_or(t, k.mhi, h3)) - h2c(64.f), S, M)));
+}
+__device__ __forceinline__ half2_t q5_0_min(half2_t S) { return S * h2c(-16.f); }
+
+// chunk: quants [h][lane] 16 B | high bits [h][lane] 4 B | d [r] 16 B (dword g = blocks 2g, 2g + 1)
+// | Q5_1: m [r] 16 B   (csrc/runtime/qtypes.h)
+template <int PT> struct Deq5 {
+  static constexpr int CB = chunk_bytes(PT);
+  struct Raw { u32x4 q0, q1; uint32_t qh0, qh1, dd, mm; };
+  __device__ static __forceinline__ void load(Raw& r, const uint8_t* c, int lane) { load(r, PtrSrc{c}, lane); }
+  template <class S>
+  __device__ static __forceinline__ void load(Raw& r, const S& c, int lane) {
+    r.q0 = c.q16nt(lane * 16);
+    r.q1 = c.q16nt(1024 + lane * 16);
+    r.qh0 = c.q4nt(2048 + lane * 4);
+    r.qh1 = c.q4nt(2048 + 256 + lane * 4);
+    r.dd = c.q4(2560 + (lane & 15) * 16 + 4 * (lane >> 4));
+    r.mm = 0;
+    if constexpr (PT == P_Q5_1) r.mm = c.q4(2816 + (lane & 15) * 16 + 4 * (lane >> 4));
+  }
+  template <int H>
+  __device__ static __forceinline__ void dequant(const Raw& r, half8_t b[4], int lane) { dequant<H>(r, b, lane, make_consts()); }
+  template <int H>
+  __device__ static __forceinline__ void dequant(const Raw& r, half8_t b[4], int, const Consts& k) {
+    const half2_t S = H ? h2hi(as_h2(r.dd)) : h2lo(as_h2(r.dd));   // block 2g + H
+    const half2_t M = PT == P_Q5_1 ? (H ? h2hi(as_h2(r.mm)) : h2lo(as_h2(r.mm))) : q5_0_min(S);
+    const u32x4 q = H == 0 ? r.q0 : r.q1;
+    const uint32_t qh = H == 0 ? r.qh0 : r.qh1;
+#pragma unroll
+    for (int s = 0; s < 4; ++s) b[s] = q5_frag(q[s], (qh >> (8 * s)) & 0xFFu, S, M, k);
+  }
+};
+template <> struct Deq<P_Q5_0> : Deq5<P_Q5_0> {};
+template <> struct Deq<P_Q5_1> : Deq5<P_Q5_1> {};
+
+// ------------------------------------------------------------------ codebook blocks (IQ4_NL, IQ4_XS)
+// A nibble indexes kvalues[16] (non-uniform int8), so the exponent magic does not apply.  The table
+// lives in registers as kvalues + 128 in four dwords; four indices (one per byte) are looked up by
+// two v_perm (table bytes 0-7 and 8-15, selector = index & 7) merged on bit 3 of each index.  The
+// result is four bytes q + 128, the input of the Q8_0 path (v_perm to 1024 + byte pairs, minus
+// 1152, times the block scale: one rounding).  A dword's even nibbles are elements j = 0..3 and
+// its odd nibbles j = 4..7 (qtypes.h), so both lookups come out in fragment order.
+__device__ __forceinline__ uint32_t iq4_lut4(uint32_t idx) {
+  const uint32_t sel = idx & 0x07070707u, m = idx & 0x08080808u;
+  const uint32_t lo = __builtin_amdgcn_perm(0x766A5D4Fu, 0x3F2D1801u, sel);   // kvalues[0..7] + 128
+  const uint32_t hi = __builtin_amdgcn_perm(0xF1D9C5B5u, 0xA6998D81u, sel);   // kvalues[8..15] + 128
+  const uint32_t mask = (m << 5) - (m >> 3);   // 0xFF in every byte whose index has bit 3
+  return (hi & mask) | (lo & ~mask);
+}
+__device__ __forceinline__ half8_t iq4_frag(uint32_t w, half2_t S) {
+  const uint32_t a = iq4_lut4(w & 0x0F0F0F0Fu), b = iq4_lut4((w >> 4) & 0x0F0F0F0Fu);
+  const half2_t off = h2c(1152.f);   // 1024 magic + 128
+  return pack8(as_u32((as_h2(__builtin_amdgcn_perm(0x64646464u, a, 0x04010400u)) - off) * S),
+               as_u32((as_h2(__builtin_amdgcn_perm(0x64646464u, a, 0x04030402u)) - off) * S),
+               as_u32((as_h2(__builtin_amdgcn_perm(0x64646464u, b, 0x04010400u)) - off) * S),
+               as_u32((as_h2(__builtin_amdgcn_perm(0x64646464u, b, 0x04030402u)) - off) * S));
+}
+// IQ4_XS header (h0 = d | scales_h << 16, h1 = scales_l) -> f16(d (ls - 32)) of sub-blocks 2q, 2q + 1:
+// the product is exact in f32, so the f16 multiply rounds it once
+__device__ __forceinline__ half2_t iq4xs_scales(uint32_t h0, uint32_t h1, uint32_t q) {
+  const f16 d = __builtin_bit_cast(f16, (uint16_t)h0);
+  const uint32_t sl = h1 >> (8 * q), sh = h0 >> (16 + 4 * q);
+  return half2_t{k3_scale((sl & 15u) | ((sh & 3u) << 4), d), k3_scale(((sl >> 4) & 15u) | ((sh & 12u) << 2), d)};
+}
+
+// chunk: quants [h][lane] 16 B | d [r] 16 B (dword g = blocks 2g, 2g + 1)
+template <> struct Deq<P_IQ4_NL> {
+  static constexpr int CB = chunk_bytes(P_IQ4_NL);
+  struct Raw { u32x4 q0, q1; uint32_t dd; };
+  __device__ static __forceinline__ void load(Raw& r, const uint8_t* c, int lane) { load(r, PtrSrc{c}, lane); }
+  template <class S>
+  __device__ static __forceinline__ void load(Raw& r, const S& c, int lane) {
+    r.q0 = c.q16nt(lane * 16);
+    r.q1 = c.q16nt(1024 + lane * 16);
+    r.dd = c.q4(2048 + (lane & 15) * 16 + 4 * (lane >> 4));
+  }
+  template <int H>
+  __device__ static __forceinline__ void dequant(const Raw& r, half8_t b[4], int lane, const Consts&) { dequant<H>(r, b, lane); }
+  template <int H>
+  __device__ static __forceinline__ void dequant(const Raw& r, half8_t b[4], int) {
+    const u32x4 q = H == 0 ? r.q0 : r.q1;
+    const half2_t S = H ? h2hi(as_h2(r.dd)) : h2lo(as_h2(r.dd));
+#pragma unroll
+    for (int s = 0; s < 4; ++s) b[s] = iq4_frag(q[s], S);
+  }
+};
+
+// chunk: quants [h][lane] 16 B | header [r] 8 B (d, scales_h, scales_l as in GGUF)
+template <> struct Deq<P_IQ4_XS> {
+  static constexpr int CB = chunk_bytes(P_IQ4_XS);
+  struct Raw { u32x4 q0, q1; uint32_t h0, h1; };
+  __device__ static __forceinline__ void load(Raw& r, const uint8_t* c, int lane) { load(r, PtrSrc{c}, lane); }
+  template <class S>
+  __device__ static __forceinline__ void load(Raw& r, const S& c, int lane) {
+    r.q0 = c.q16nt(lane * 16);
+    r.q1 = c.q16nt(1024 + lane * 16);
+    r.h0 = c.q4(2048 + (lane & 15) * 8);
+    r.h1 = c.q4(2048 + (lane & 15) * 8 + 4);
+  }
+  template <int H>
+  __device__ static __forceinline__ void dequant(const Raw& r, half8_t b[4], int lane, const Consts&) { dequant<H>(r, b, lane); }
+  template <int H>
+  __device__ static __forceinline__ void dequant(const Raw& r, half8_t b[4], int lane) {
+    const half2_t S2 = iq4xs_scales(r.h0, r.h1, (uint32_t)lane >> 4);   // shared by H = 0 / 1 (CSE)
+    const half2_t S = H ? h2hi(S2) : h2lo(S2);
+    const u32x4 q = H == 0 ? r.q0 : r.q1;
+#pragma unroll
+    for (int s = 0; s < 4; ++s) b[s] = iq4_frag(q[s], S);
+  }
+};
+
 // bf16 pair (low, high halves of w) -> f16 pair (dense unpack only: the GEMV/GEMM kernels keep bf16):
 // exact inside f16's normal range; v_cvt_pkrtz rounds toward zero, so a bf16 beyond 65504 becomes
 // +-65504 (saturation) instead of an infinity

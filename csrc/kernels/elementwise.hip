@@ -142,6 +142,30 @@ __device__ float deq_elem(int t, const uint8_t* row, int e) {
       const int q = l < 16 ? (b[2 + l] & 15) : (b[2 + l - 16] >> 4);
       return h2f(*reinterpret_cast<const uint16_t*>(b)) * (float)(q - 8);
     }
+    case T_Q5_0: case T_Q5_1: {   // fifth bit of element l: bit l of the 32-bit word qh
+      const int ho = t == T_Q5_0 ? 2 : 4;
+      const uint8_t* b = row + (e / 32) * (ho + 20);
+      const int l = e % 32;
+      const int q = (l < 16 ? (b[ho + 4 + l] & 15) : (b[ho + 4 + l - 16] >> 4)) | (((b[ho + l / 8] >> (l % 8)) & 1) << 4);
+      const float d = h2f(*reinterpret_cast<const uint16_t*>(b));
+      return t == T_Q5_0 ? d * (float)(q - 16) : d * (float)q + h2f(*reinterpret_cast<const uint16_t*>(b + 2));
+    }
+    case T_IQ4_NL: case T_IQ4_XS: {   // codebook nibbles; IQ4_XS: 6-bit sub-block scale ls - 32
+      const int8_t kv[16] = {-127, -104, -83, -65, -49, -35, -22, -10, 1, 13, 25, 38, 53, 69, 89, 113};
+      const int l = e % 32;
+      if (t == T_IQ4_NL) {
+        const uint8_t* b = row + (e / 32) * 18;
+        const int i = l < 16 ? (b[2 + l] & 15) : (b[2 + l - 16] >> 4);
+        return h2f(*reinterpret_cast<const uint16_t*>(b)) * (float)kv[i];
+      }
+      const uint8_t* b = row + (e / 256) * 136;
+      const int ib = (e % 256) / 32;
+      const uint8_t* qs = b + 8 + 16 * ib;
+      const int i = l < 16 ? (qs[l] & 15) : (qs[l - 16] >> 4);
+      const int sh = *reinterpret_cast<const uint16_t*>(b + 2);
+      const int ls = ((b[4 + ib / 2] >> (4 * (ib % 2))) & 15) | (((sh >> (2 * ib)) & 3) << 4);
+      return h2f(*reinterpret_cast<const uint16_t*>(b)) * (float)(ls - 32) * (float)kv[i];
+    }
     case T_Q4_K: case T_Q5_K: {
       const int bb = t == T_Q4_K ? 144 : 176;
       const uint8_t* b = row + (e / 256) * bb;

@@ -132,6 +132,10 @@ void launch_gemm(int ptype, int epi, GemvParams p, hipStream_t st) {
     case P_Q4_0: gemm_pt<P_Q4_0>(epi, p, st); break;
     case P_Q3_K: gemm_pt<P_Q3_K>(epi, p, st); break;
     case P_Q2_K: gemm_pt<P_Q2_K>(epi, p, st); break;
+    case P_Q5_0: gemm_pt<P_Q5_0>(epi, p, st); break;
+    case P_Q5_1: gemm_pt<P_Q5_1>(epi, p, st); break;
+    case P_IQ4_NL: gemm_pt<P_IQ4_NL>(epi, p, st); break;
+    case P_IQ4_XS: gemm_pt<P_IQ4_XS>(epi, p, st); break;
     case P_F16: gemm_pt<P_F16>(epi, p, st); break;
     case P_BF16: gemm_pt<P_BF16>(epi, p, st); break;
   }

@@ -373,6 +373,10 @@ void launch_gemm3(int ptype, int epi, GemvParams p, hipStream_t st, bool allow_s
     case P_Q4_0: gemm3_pt<P_Q4_0>(epi, p, allow_split, st); break;
     case P_Q3_K: gemm3_pt<P_Q3_K>(epi, p, allow_split, st); break;
     case P_Q2_K: gemm3_pt<P_Q2_K>(epi, p, allow_split, st); break;
+    case P_Q5_0: gemm3_pt<P_Q5_0>(epi, p, allow_split, st); break;
+    case P_Q5_1: gemm3_pt<P_Q5_1>(epi, p, allow_split, st); break;
+    case P_IQ4_NL: gemm3_pt<P_IQ4_NL>(epi, p, allow_split, st); break;
+    case P_IQ4_XS: gemm3_pt<P_IQ4_XS>(epi, p, allow_split, st); break;
     case P_F16: gemm3_pt<P_F16>(epi, p, allow_split, st); break;
     case P_BF16: gemm3_pt<P_BF16>(epi, p, allow_split, st); break;
     case P_I8: gemm3_pt<P_I8>(epi, p, allow_split, st); break;

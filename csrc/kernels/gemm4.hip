@@ -6,7 +6,8 @@ namespace mp {
 
 bool gemm4_supported(int ptype) {
   return ptype == P_Q4_K || ptype == P_Q5_K || ptype == P_Q6_K || ptype == P_Q8_0 || ptype == P_F16 || ptype == P_BF16 ||
-         ptype == P_Q3_K || ptype == P_Q2_K;
+         ptype == P_Q3_K || ptype == P_Q2_K || ptype == P_Q5_0 || ptype == P_Q5_1 || ptype == P_IQ4_NL ||
+         ptype == P_IQ4_XS;
 }
 
 bool gemm4_has_geometry(int ptype, int bm, int nwv, int tw, bool moe) {
@@ -30,6 +31,10 @@ static void run(int ptype, const Gemm4Plan& pl, int epi, const GemvParams& p, co
     case P_Q8_0: return gemm4_run<P_Q8_0>(pl, epi, p, mo, st);
     case P_Q3_K: return gemm4_run<P_Q3_K>(pl, epi, p, mo, st);
     case P_Q2_K: return gemm4_run<P_Q2_K>(pl, epi, p, mo, st);
+    case P_Q5_0: return gemm4_run<P_Q5_0>(pl, epi, p, mo, st);
+    case P_Q5_1: return gemm4_run<P_Q5_1>(pl, epi, p, mo, st);
+    case P_IQ4_NL: return gemm4_run<P_IQ4_NL>(pl, epi, p, mo, st);
+    case P_IQ4_XS: return gemm4_run<P_IQ4_XS>(pl, epi, p, mo, st);
     case P_F16: return gemm4_run<P_F16>(pl, epi, p, mo, st);
     case P_BF16: return gemm4_run<P_BF16>(pl, epi, p, mo, st);
     default: throw std::runtime_error("gemm4: weight type " + std::to_string(ptype));

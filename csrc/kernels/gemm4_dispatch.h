@@ -1,5 +1,6 @@
 // gemm4: from a launch plan (csrc/runtime/gemm4_plan.h) to the kernel instantiation it names.
-// gemm4_<type>.hip instantiate gemm4_run per weight type (Q3_K beside Q5_K, Q2_K beside Q6_K);
+// gemm4_<type>.hip instantiate gemm4_run per weight type (Q3_K beside Q5_K, Q2_K beside Q6_K, IQ4_NL
+// and IQ4_XS beside F16, Q5_0 and Q5_1 beside Q8_0);
 // gemm4.hip switches on the type.
 #pragma once
 #include "gemm4_kernel.h"
@@ -119,6 +120,10 @@ extern template void gemm4_run<P_Q6_K>(const Gemm4Plan&, int, const GemvParams&,
 extern template void gemm4_run<P_Q8_0>(const Gemm4Plan&, int, const GemvParams&, const mpk::G4Moe*, hipStream_t);
 extern template void gemm4_run<P_Q3_K>(const Gemm4Plan&, int, const GemvParams&, const mpk::G4Moe*, hipStream_t);
 extern template void gemm4_run<P_Q2_K>(const Gemm4Plan&, int, const GemvParams&, const mpk::G4Moe*, hipStream_t);
+extern template void gemm4_run<P_Q5_0>(const Gemm4Plan&, int, const GemvParams&, const mpk::G4Moe*, hipStream_t);
+extern template void gemm4_run<P_Q5_1>(const Gemm4Plan&, int, const GemvParams&, const mpk::G4Moe*, hipStream_t);
+extern template void gemm4_run<P_IQ4_NL>(const Gemm4Plan&, int, const GemvParams&, const mpk::G4Moe*, hipStream_t);
+extern template void gemm4_run<P_IQ4_XS>(const Gemm4Plan&, int, const GemvParams&, const mpk::G4Moe*, hipStream_t);
 extern template void gemm4_run<P_F16>(const Gemm4Plan&, int, const GemvParams&, const mpk::G4Moe*, hipStream_t);
 extern template void gemm4_run<P_BF16>(const Gemm4Plan&, int, const GemvParams&, const mpk::G4Moe*, hipStream_t);
 

@@ -240,6 +240,71 @@ template <> struct W4<P_Q2_K> {
   }
 };
 
+// Q5_0 / Q5_1: quants and the high-bit dword as Q5_K, block scales (and mins) [u][r] of the quarter
+template <int PT> struct W4_Q5 {
+  using Q3 = W3<PT>;
+  static constexpr int NR = Q3::kM ? 6 : 5;
+  static constexpr bool kParts = false;
+  template <int P, class RW, class PR>   // (unused: kParts false) the whole fragment's dword P
+  __device__ static __forceinline__ uint32_t fragp(const RW& w, const PR& p, int t, int h, const Consts& k) {
+    return __builtin_bit_cast(u32x4, frag(w, p, t, h, k))[P];
+  }
+  struct Raw { uint32_t dd, mm; u32x2 q[2]; uint32_t qh[2]; };
+  using Prep = typename Q3::Prep;
+  template <int TW>
+  __device__ static __forceinline__ void load(const char* R, int lane, int pair, Raw& w) {
+    const int c = lane & 31, u = 2 * pair + (c >> 4), r = c & 15, h = lane >> 5;
+    ds_b32(w.dd, R + TW * 640 + (u * 16 + r) * 4);
+    if constexpr (Q3::kM) ds_b32(w.mm, R + TW * Q3::MO + (u * 16 + r) * 4);
+    else w.mm = 0;
+#pragma unroll
+    for (int kk = 0; kk < 2; ++kk) {
+      ds_b64(w.q[kk], R + ((u * 2 + kk) * 16 + r) * 16 + 8 * h);
+      ds_b32(w.qh[kk], R + TW * 512 + ((u * 2 + kk) * 16 + r) * 4);
+    }
+  }
+  __device__ static __forceinline__ Prep prep(const Raw& w, int) { return Q3::mk(w.dd, w.mm); }
+  __device__ static __forceinline__ half8_t frag(const Raw& w, const Prep& p, int t, int h, const Consts& k) {
+    const int kk = t >> 1, e = t & 1, g = 2 * h + e;
+    return q5_frag(w.q[kk][e], (w.qh[kk] >> (8 * g)) & 0xFFu, kk ? h2hi(p.S2) : h2lo(p.S2),
+                   kk ? h2hi(p.M2) : h2lo(p.M2), k);
+  }
+};
+template <> struct W4<P_Q5_0> : W4_Q5<P_Q5_0> {};
+template <> struct W4<P_Q5_1> : W4_Q5<P_Q5_1> {};
+
+// IQ4_NL / IQ4_XS: quants as Q4_K (dwords 2h, 2h + 1 of the row's piece: one b64 per kk), the block
+// scale pair [u][r] of the quarter, or the row's 8-B header it is computed from
+template <int PT> struct W4_IQ4 {
+  static constexpr bool kXS = PT == P_IQ4_XS;
+  static constexpr int NR = 3;
+  static constexpr bool kParts = false;
+  template <int P, class RW, class PR>   // (unused: kParts false) the whole fragment's dword P
+  __device__ static __forceinline__ uint32_t fragp(const RW& w, const PR& p, int t, int h, const Consts& k) {
+    return __builtin_bit_cast(u32x4, frag(w, p, t, h, k))[P];
+  }
+  struct Raw { u32x2 hdr; uint32_t dd; u32x2 q[2]; };   // IQ4_XS: the header; IQ4_NL: dd = (d(2q), d(2q+1))
+  using Prep = W3<P_IQ4_NL>::Prep;
+  template <int TW>
+  __device__ static __forceinline__ void load(const char* R, int lane, int pair, Raw& w) {
+    const int c = lane & 31, u = 2 * pair + (c >> 4), r = c & 15, h = lane >> 5;
+    if constexpr (kXS) { ds_b64(w.hdr, R + TW * 512 + (u * 16 + r) * 8); w.dd = 0; }
+    else { ds_b32(w.dd, R + TW * 512 + (u * 16 + r) * 4); w.hdr = u32x2{0u, 0u}; }
+#pragma unroll
+    for (int kk = 0; kk < 2; ++kk) ds_b64(w.q[kk], R + ((u * 2 + kk) * 16 + r) * 16 + 8 * h);
+  }
+  __device__ static __forceinline__ Prep prep(const Raw& w, int q) {
+    if constexpr (kXS) return Prep{iq4xs_scales(w.hdr.x, w.hdr.y, (uint32_t)q)};
+    else return Prep{as_h2(w.dd)};
+  }
+  __device__ static __forceinline__ half8_t frag(const Raw& w, const Prep& p, int t, int, const Consts&) {
+    const int kk = t >> 1, e = t & 1;
+    return iq4_frag(w.q[kk][e], kk ? h2hi(p.S2) : h2lo(p.S2));
+  }
+};
+template <> struct W4<P_IQ4_NL> : W4_IQ4<P_IQ4_NL> {};
+template <> struct W4<P_IQ4_XS> : W4_IQ4<P_IQ4_XS> {};
+
 // Q8_0: piece (u, kk, r) = 32 int8 (+128) at R + ((u*2 + kk)*16 + r)*32; bytes 16h .. 16h+15 hold
 // dwords g = 2h, 2h+1 of the 16x16 map (one b128 per kk); block scales [u][r] = (d(2q), d(2q+1))
 template <> struct W4<P_Q8_0> {
@@ -302,7 +367,7 @@ template <> struct W4<P_BF16> : W4_16<P_BF16> {};
 
 template <int PT> constexpr bool g4_supported() {
   return PT == P_Q4_K || PT == P_Q5_K || PT == P_Q6_K || PT == P_Q8_0 || PT == P_F16 || PT == P_BF16 ||
-         PT == P_Q3_K || PT == P_Q2_K;
+         PT == P_Q3_K || PT == P_Q2_K || PT == P_Q5_0 || PT == P_Q5_1 || PT == P_IQ4_NL || PT == P_IQ4_XS;
 }
 
 // MoE mode (grouped GEMM over the routed experts): blockIdx.z = expert e, whose rows are

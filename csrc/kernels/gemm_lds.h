@@ -547,6 +547,127 @@ template <> struct W3<P_Q4_0> {
   }
 };
 
+// Q5_0 / Q5_1: quants and high bits as Q5_K, block scales [u][r] 4 B = (d(2q), d(2q+1)), Q5_1: the
+// mins [u][r] 4 B likewise
+template <int PT> struct W3_Q5 {
+  static constexpr bool kM = PT == P_Q5_1;
+  static constexpr int CB = chunk_bytes(PT);
+  static constexpr int MO = 704;   // the mins' offset per tile
+  static constexpr int RAW(int TW) { return TW * (kM ? 768 : 704); }
+  static constexpr int NI(int TW) { return wi(32 * TW) + wi(8 * TW) + (kM ? 2 : 1) * wi(16 * TW); }
+  static constexpr int NR(int TW) { return (kM ? 6 : 5) * TW; }
+  template <int TW> struct Raw { uint32_t dd[TW], mm[TW], q[TW][2], qh[TW][2]; };
+  struct Prep { half2_t S2, M2; };
+  template <int TW, class E>
+  __device__ static __forceinline__ void issue(char* R, const W3Src& c, E&& em) {
+    em.template go<16>(R, 32 * TW, [&](int e) {
+      return c.chunk(e >> 5, CB) + ((e >> 4) & 1) * 1024 + (16 * c.q + (e & 15)) * 16;
+    });
+    em.template go<16>(R + TW * 512, 8 * TW, [&](int f) {
+      return c.chunk(f >> 3, CB) + 2048 + ((f >> 2) & 1) * 256 + (16 * c.q + 4 * (f & 3)) * 4;
+    });
+    em.template go<4>(R + TW * 640, 16 * TW, [&](int e) { return c.chunk(e >> 4, CB) + 2560 + (e & 15) * 16 + 4 * c.q; });
+    if constexpr (kM)
+      em.template go<4>(R + TW * MO, 16 * TW, [&](int e) { return c.chunk(e >> 4, CB) + 2816 + (e & 15) * 16 + 4 * c.q; });
+  }
+  template <int TW>
+  __device__ static __forceinline__ void load(const char* R, int lane, Raw<TW>& w) {
+    const int r = lane & 15, g = lane >> 4;
+#pragma unroll
+    for (int u = 0; u < TW; ++u) {
+      ds_b32(w.dd[u], R + TW * 640 + (u * 16 + r) * 4);
+      if constexpr (kM) ds_b32(w.mm[u], R + TW * MO + (u * 16 + r) * 4);
+      else w.mm[u] = 0;
+#pragma unroll
+      for (int kk = 0; kk < 2; ++kk) {
+        ds_b32(w.q[u][kk], R + ((u * 2 + kk) * 16 + r) * 16 + 4 * g);
+        ds_b32(w.qh[u][kk], R + TW * 512 + ((u * 2 + kk) * 16 + r) * 4);
+      }
+    }
+  }
+  __device__ static __forceinline__ Prep mk(uint32_t dd, uint32_t mm) {
+    return Prep{as_h2(dd), kM ? as_h2(mm) : q5_0_min(as_h2(dd))};
+  }
+  template <int TW>
+  __device__ static __forceinline__ Prep prep(const Raw<TW>& w, int u, int, int) { return mk(w.dd[u], w.mm[u]); }
+  template <int TW>
+  __device__ static __forceinline__ half8_t frag(const Raw<TW>& w, const Prep& p, int u, int kk, int lane, const Consts& k) {
+    const int g = lane >> 4;
+    return q5_frag(w.q[u][kk], (w.qh[u][kk] >> (8 * g)) & 0xFFu, kk ? h2hi(p.S2) : h2lo(p.S2),
+                   kk ? h2hi(p.M2) : h2lo(p.M2), k);
+  }
+};
+template <> struct W3<P_Q5_0> : W3_Q5<P_Q5_0> {};
+template <> struct W3<P_Q5_1> : W3_Q5<P_Q5_1> {};
+
+// IQ4_NL: quants [u][h][r] 16 B, block scales [u][r] 4 B = (d(2q), d(2q+1)) (the Q4_0 image)
+template <> struct W3<P_IQ4_NL> {
+  static constexpr int CB = chunk_bytes(P_IQ4_NL);
+  static constexpr int RAW(int TW) { return TW * 576; }
+  static constexpr int NI(int TW) { return wi(32 * TW) + wi(16 * TW); }
+  static constexpr int NR(int TW) { return 3 * TW; }
+  template <int TW> struct Raw { uint32_t dd[TW], q[TW][2]; };
+  struct Prep { half2_t S2; };
+  template <int TW, class E>
+  __device__ static __forceinline__ void issue(char* R, const W3Src& c, E&& em) {
+    em.template go<16>(R, 32 * TW, [&](int e) {
+      return c.chunk(e >> 5, CB) + ((e >> 4) & 1) * 1024 + (16 * c.q + (e & 15)) * 16;
+    });
+    em.template go<4>(R + TW * 512, 16 * TW, [&](int e) { return c.chunk(e >> 4, CB) + 2048 + (e & 15) * 16 + 4 * c.q; });
+  }
+  template <int TW>
+  __device__ static __forceinline__ void load(const char* R, int lane, Raw<TW>& w) {
+    const int r = lane & 15, g = lane >> 4;
+#pragma unroll
+    for (int u = 0; u < TW; ++u) {
+      ds_b32(w.dd[u], R + TW * 512 + (u * 16 + r) * 4);
+#pragma unroll
+      for (int kk = 0; kk < 2; ++kk) ds_b32(w.q[u][kk], R + ((u * 2 + kk) * 16 + r) * 16 + 4 * g);
+    }
+  }
+  template <int TW>
+  __device__ static __forceinline__ Prep prep(const Raw<TW>& w, int u, int, int) { return Prep{as_h2(w.dd[u])}; }
+  template <int TW>
+  __device__ static __forceinline__ half8_t frag(const Raw<TW>& w, const Prep& p, int u, int kk, int, const Consts&) {
+    return iq4_frag(w.q[u][kk], kk ? h2hi(p.S2) : h2lo(p.S2));
+  }
+};
+
+// IQ4_XS: quants [u][h][r] 16 B, header [u][r] 8 B (d, scales_h, scales_l: the tile's 128 contiguous bytes)
+template <> struct W3<P_IQ4_XS> {
+  static constexpr int CB = chunk_bytes(P_IQ4_XS);
+  static constexpr int RAW(int TW) { return TW * 640; }
+  static constexpr int NI(int TW) { return wi(32 * TW) + wi(8 * TW); }
+  static constexpr int NR(int TW) { return 3 * TW; }
+  template <int TW> struct Raw { u32x2 hdr[TW]; uint32_t q[TW][2]; };
+  using Prep = W3<P_IQ4_NL>::Prep;
+  template <int TW, class E>
+  __device__ static __forceinline__ void issue(char* R, const W3Src& c, E&& em) {
+    em.template go<16>(R, 32 * TW, [&](int e) {
+      return c.chunk(e >> 5, CB) + ((e >> 4) & 1) * 1024 + (16 * c.q + (e & 15)) * 16;
+    });
+    em.template go<16>(R + TW * 512, 8 * TW, [&](int f) { return c.chunk(f >> 3, CB) + 2048 + (f & 7) * 16; });
+  }
+  template <int TW>
+  __device__ static __forceinline__ void load(const char* R, int lane, Raw<TW>& w) {
+    const int r = lane & 15, g = lane >> 4;
+#pragma unroll
+    for (int u = 0; u < TW; ++u) {
+      ds_b64(w.hdr[u], R + TW * 512 + (u * 16 + r) * 8);
+#pragma unroll
+      for (int kk = 0; kk < 2; ++kk) ds_b32(w.q[u][kk], R + ((u * 2 + kk) * 16 + r) * 16 + 4 * g);
+    }
+  }
+  template <int TW>
+  __device__ static __forceinline__ Prep prep(const Raw<TW>& w, int u, int q, int) {
+    return Prep{iq4xs_scales(w.hdr[u].x, w.hdr[u].y, (uint32_t)q)};
+  }
+  template <int TW>
+  __device__ static __forceinline__ half8_t frag(const Raw<TW>& w, const Prep& p, int u, int kk, int, const Consts&) {
+    return iq4_frag(w.q[u][kk], kk ? h2hi(p.S2) : h2lo(p.S2));
+  }
+};
+
 // 16-bit weights (F16, or BF16 for the bf16 MFMA: the A fragments go to bf16): the fragment bytes themselves,
 // [u][kk][lane] 16 B = element 4 kk + g of lane (q, r) of the T16 chunk
 template <int PT> struct W3_16 {

@@ -105,6 +105,10 @@ void launch_unpack(int ptype, const uint8_t* W, int ntiles, int nsb, f16* out, i
     case P_Q4_0: hipLaunchKernelGGL(mpk::unpack_kernel<P_Q4_0>, grid, dim3(64), 0, st, W, nsb, out, ldo); break;
     case P_Q3_K: hipLaunchKernelGGL(mpk::unpack_kernel<P_Q3_K>, grid, dim3(64), 0, st, W, nsb, out, ldo); break;
     case P_Q2_K: hipLaunchKernelGGL(mpk::unpack_kernel<P_Q2_K>, grid, dim3(64), 0, st, W, nsb, out, ldo); break;
+    case P_Q5_0: hipLaunchKernelGGL(mpk::unpack_kernel<P_Q5_0>, grid, dim3(64), 0, st, W, nsb, out, ldo); break;
+    case P_Q5_1: hipLaunchKernelGGL(mpk::unpack_kernel<P_Q5_1>, grid, dim3(64), 0, st, W, nsb, out, ldo); break;
+    case P_IQ4_NL: hipLaunchKernelGGL(mpk::unpack_kernel<P_IQ4_NL>, grid, dim3(64), 0, st, W, nsb, out, ldo); break;
+    case P_IQ4_XS: hipLaunchKernelGGL(mpk::unpack_kernel<P_IQ4_XS>, grid, dim3(64), 0, st, W, nsb, out, ldo); break;
     case P_F16: hipLaunchKernelGGL(mpk::unpack_kernel<P_F16>, grid, dim3(64), 0, st, W, nsb, out, ldo); break;
     case P_BF16: hipLaunchKernelGGL(mpk::unpack_kernel<P_BF16>, grid, dim3(64), 0, st, W, nsb, out, ldo); break;
   }

@@ -304,6 +304,10 @@ void launch_gemv2(int ptype, int epi, const GemvParams& p, int nsplit, int nw, i
     case P_Q4_0: gemv2_pt<P_Q4_0>(epi, p, nsplit, nw, tw, st); break;
     case P_Q3_K: gemv2_pt<P_Q3_K>(epi, p, nsplit, nw, tw, st); break;
     case P_Q2_K: gemv2_pt<P_Q2_K>(epi, p, nsplit, nw, tw, st); break;
+    case P_Q5_0: gemv2_pt<P_Q5_0>(epi, p, nsplit, nw, tw, st); break;
+    case P_Q5_1: gemv2_pt<P_Q5_1>(epi, p, nsplit, nw, tw, st); break;
+    case P_IQ4_NL: gemv2_pt<P_IQ4_NL>(epi, p, nsplit, nw, tw, st); break;
+    case P_IQ4_XS: gemv2_pt<P_IQ4_XS>(epi, p, nsplit, nw, tw, st); break;
     case P_F16: gemv2_pt<P_F16>(epi, p, nsplit, nw, tw, st); break;
     case P_BF16: gemv2_pt<P_BF16>(epi, p, nsplit, nw, tw, st); break;
   }

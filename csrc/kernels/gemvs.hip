@@ -613,6 +613,10 @@ void launch_gemvs(int ptype, int epi, GemvParams p, bool deterministic, hipStrea
     case P_Q4_0: gemvs_pt<P_Q4_0>(epi, p, pl, st); break;
     case P_Q3_K: gemvs_pt<P_Q3_K>(epi, p, pl, st); break;
     case P_Q2_K: gemvs_pt<P_Q2_K>(epi, p, pl, st); break;
+    case P_Q5_0: gemvs_pt<P_Q5_0>(epi, p, pl, st); break;
+    case P_Q5_1: gemvs_pt<P_Q5_1>(epi, p, pl, st); break;
+    case P_IQ4_NL: gemvs_pt<P_IQ4_NL>(epi, p, pl, st); break;
+    case P_IQ4_XS: gemvs_pt<P_IQ4_XS>(epi, p, pl, st); break;
     case P_F16: gemvs_pt<P_F16>(epi, p, pl, st); break;
     case P_BF16: gemvs_pt<P_BF16>(epi, p, pl, st); break;
     default: throw std::runtime_error("launch_gemvs: unknown packed type");

@@ -85,6 +85,26 @@ __global__ void init_packed_kernel(uint8_t* W, size_t nbytes, int pt, float scal
 #pragma unroll
       for (int k = 0; k < 4; ++k) v[k] = (uint32_t)f2h(scale / 13.5f) | ((uint32_t)f2h(scale / 9.f) << 16);
     }
+  } else if (pt == P_Q5_0 || pt == P_Q5_1) {
+    // random quants and high bits; q - 16 (Q5_1: q with m = -15.5 d) has deviation ~9.2
+    if (in_chunk >= 2560) {
+      const uint16_t h = f2h((pt == P_Q5_1 && in_chunk >= 2816 ? -15.5f : 1.f) * scale / 9.2f);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) v[k] = (uint32_t)h | ((uint32_t)h << 16);
+    }
+  } else if (pt == P_IQ4_NL) {
+    if (in_chunk >= 2048) {   // a uniformly drawn codebook entry has rms ~67
+      const uint16_t h = f2h(scale / 67.f);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) v[k] = (uint32_t)h | ((uint32_t)h << 16);
+    }
+  } else if (pt == P_IQ4_XS) {
+    // two rows' headers per 16 B: d, then random scales_h / scales_l (ls - 32 has rms ~18.5)
+    if (in_chunk >= 2048) {
+      const uint32_t h = f2h(scale / (18.5f * 67.f));
+      v[0] = (v[0] & 0xFFFF0000u) | h;
+      v[2] = (v[2] & 0xFFFF0000u) | h;
+    }
   } else if (pt == P_Q4_0) {
     if (in_chunk >= 2048) {
 #pragma unroll
@@ -117,6 +137,10 @@ __global__ void init_raw_kernel(uint8_t* W, int64_t nblocks, int t, float scale,
       break;
     }
     case T_Q3_K: *reinterpret_cast<uint16_t*>(p + 108) = f2h(scale / 43.f); break;
+    case T_Q5_0: h[0] = f2h(scale / 9.2f); break;
+    case T_Q5_1: h[0] = f2h(scale / 9.2f); h[1] = f2h(-15.5f * scale / 9.2f); break;
+    case T_IQ4_NL: h[0] = f2h(scale / 67.f); break;
+    case T_IQ4_XS: h[0] = f2h(scale / (18.5f * 67.f)); break;
     case T_Q2_K:
       *reinterpret_cast<uint16_t*>(p + 80) = f2h(scale / 13.5f);
       *reinterpret_cast<uint16_t*>(p + 82) = f2h(scale / 9.f);

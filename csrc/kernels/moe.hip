@@ -516,6 +516,10 @@ void launch_moe_gemv(int ptype, int epi, MoeGemvParams p, int nsplit, hipStream_
     case P_Q4_0: moe_launch_pt<P_Q4_0>(epi, p, nsplit, st); break;
     case P_Q3_K: moe_launch_pt<P_Q3_K>(epi, p, nsplit, st); break;
     case P_Q2_K: moe_launch_pt<P_Q2_K>(epi, p, nsplit, st); break;
+    case P_Q5_0: moe_launch_pt<P_Q5_0>(epi, p, nsplit, st); break;
+    case P_Q5_1: moe_launch_pt<P_Q5_1>(epi, p, nsplit, st); break;
+    case P_IQ4_NL: moe_launch_pt<P_IQ4_NL>(epi, p, nsplit, st); break;
+    case P_IQ4_XS: moe_launch_pt<P_IQ4_XS>(epi, p, nsplit, st); break;
     case P_F16: moe_launch_pt<P_F16>(epi, p, nsplit, st); break;
     case P_BF16: moe_launch_pt<P_BF16>(epi, p, nsplit, st); break;
   }

@@ -79,6 +79,13 @@ void fill_random(int type, int64_t nblocks, float scale, uint64_t seed, uint8_t*
         put_f16(p + 80, scale / 24.f);
         put_f16(p + 82, scale / 16.f);
         break;
+      case T_Q5_0: put_f16(p, scale / 10.f); break;   // q - 16 in [-16, 15]
+      case T_Q5_1:   // m = -15.5 d centres the weights
+        put_f16(p, scale / 10.f);
+        put_f16(p + 2, -15.5f * scale / 10.f);
+        break;
+      case T_IQ4_NL: put_f16(p, scale / 72.f); break;            // a random codebook entry has rms ~67
+      case T_IQ4_XS: put_f16(p, scale / (20.f * 72.f)); break;   // random 6-bit scales: rms(ls - 32) ~ 18.5
       default: throw std::runtime_error("cpu synthetic: unsupported type");
     }
   }

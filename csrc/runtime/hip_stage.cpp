@@ -50,6 +50,14 @@ SyntheticTypes SyntheticTypes::from_ftype(const std::string& ftype_in, int layer
     all(T_Q2_K);
     t.out = T_Q6_K;
     t.v = t.o = t.down = T_Q3_K;
+  } else if (f == "Q5_0") all(T_Q5_0);
+  else if (f == "Q5_1") all(T_Q5_1);
+  else if (f == "IQ4_NL") all(T_IQ4_NL);
+  else if (f == "IQ4_XS") {   // the mix of models/config.py tensor_type
+    all(T_IQ4_XS);
+    t.out = T_Q6_K;
+    t.v = T_Q5_K;
+    if (layer < n_layer / 8) t.down = T_Q5_K;
   } else throw std::runtime_error("unknown synthetic ftype " + ftype_in);
   if (f == "Q5_K_M" && more_bits(layer, n_layer)) { t.v = T_Q6_K; t.down = T_Q6_K; }
   return t;

@@ -95,7 +95,7 @@ void launch_gemm(int ptype, int epi, GemvParams p, hipStream_t st);
 void launch_gemm3(int ptype, int epi, GemvParams p, hipStream_t st, bool allow_split = true);
 // Prompt / wide-decode GEMM v4 (gemm4*.hip): gemm3's LDS-DMA stream on v_mfma_f32_32x32x16 (BM 128 |
 // 256 rows x 256 columns, each wave owning 32 columns, and the opt-in forms of the geometry table).
-// Q4_K, Q5_K, Q6_K, Q8_0, Q3_K, Q2_K, F16, BF16; false = type not supported (nothing launched).  Every launch
+// Q4_K, Q5_K, Q6_K, Q8_0, Q3_K, Q2_K, Q5_0, Q5_1, IQ4_NL, IQ4_XS, F16, BF16; false = type not supported (nothing launched).  Every launch
 // runs plan_gemm4 / plan_moe_gemm4 (gemm4_plan.h).  _splitk: split-K partial stores, split s into
 // scratch + s * M * ntiles * 16 (false: the shape does not split or scratch_n floats are too few),
 // then (reduce) added into p.Y in split order.

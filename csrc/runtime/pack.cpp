@@ -110,6 +110,20 @@ static inline void put_nib(uint8_t* chunk, const Pos& p, int v) {
   byte |= (uint8_t)((v & 15) << ((pos & 1) * 4));
 }
 
+// codebook types: element j at bit 8 (j & 3) + 4 (j >> 2) of the dword (nibble 2 (j & 3) + (j >> 2))
+static inline void put_nib_cb(uint8_t* chunk, const Pos& p, int v) {
+  chunk[p.h * 1024 + p.lane * 16 + p.s * 4 + (p.j & 3)] |= (uint8_t)((v & 15) << (4 * (p.j >> 2)));
+}
+// the fifth bit of a Q5_0 / Q5_1 weight into the Q5_K high-bit plane at 2048
+static inline void put_hi5(uint8_t* chunk, const Pos& p, int v) {
+  uint8_t* qh = chunk + 2048 + p.h * 256 + p.lane * 4;
+  const int bit = 8 * p.s + (p.j & 1) * 4 + (p.j >> 1);
+  qh[bit / 8] |= (uint8_t)((v & 1) << (bit % 8));
+}
+// element l of a 32-weight block's 16 nibble bytes
+static inline int nib32(const uint8_t* qs, int l) { return l < 16 ? (qs[l] & 15) : (qs[l - 16] >> 4); }
+static const int8_t kIq4Values[16] = {-127, -104, -83, -65, -49, -35, -22, -10, 1, 13, 25, 38, 53, 69, 89, 113};
+
 // 2-bit field of (h, s, j) inside the lane's ONE 16-B piece: dword 2 (s >> 1) + h, bit
 // 16 (j & 1) + 8 (s & 1) + 2 (j >> 1)
 static inline void put_2bit(uint8_t* chunk, const Pos& p, int v) {
@@ -198,6 +212,35 @@ static void pack_chunk(int t, int pt, const uint8_t* src, int64_t K, int64_t k0,
           put_nib(chunk, pos_of(32 * b + l, r), v);
         }
       }
+      break;
+    }
+    case P_Q5_0: case P_Q5_1: {
+      const int bb = pt == P_Q5_0 ? 22 : 24, ho = bb - 20;   // qh offset in the block
+      for (int b = 0; b < 8; ++b) {
+        if (k0 + 32 * b >= K) break;
+        const uint8_t* blk = src + bb * b;
+        std::memcpy(chunk + 2560 + 16 * r + 2 * b, blk, 2);
+        if (pt == P_Q5_1) std::memcpy(chunk + 2816 + 16 * r + 2 * b, blk + 2, 2);
+        for (int l = 0; l < 32; ++l) {
+          const Pos p = pos_of(32 * b + l, r);
+          put_nib(chunk, p, nib32(blk + ho + 4, l));
+          put_hi5(chunk, p, (blk[ho + l / 8] >> (l % 8)) & 1);
+        }
+      }
+      break;
+    }
+    case P_IQ4_NL: {
+      for (int b = 0; b < 8; ++b) {
+        if (k0 + 32 * b >= K) break;
+        const uint8_t* blk = src + 18 * b;
+        std::memcpy(chunk + 2048 + 16 * r + 2 * b, blk, 2);
+        for (int l = 0; l < 32; ++l) put_nib_cb(chunk, pos_of(32 * b + l, r), nib32(blk + 2, l));
+      }
+      break;
+    }
+    case P_IQ4_XS: {
+      for (int w = 0; w < 256; ++w) put_nib_cb(chunk, pos_of(w, r), nib32(src + 8 + 16 * (w / 32), w % 32));
+      std::memcpy(chunk + 2048 + 8 * r, src, 8);
       break;
     }
     case P_BF16: {   // bits as stored in the GGUF (T_BF16 only)
@@ -293,6 +336,36 @@ MP_HOST_AVX2_CLONES void dequant_row(int t, const uint8_t* src, float* dst, int6
         for (int l = 0; l < 16; ++l) {
           dst[32 * b + l] = d * (float)((blk[2 + l] & 15) - 8);
           dst[32 * b + l + 16] = d * (float)((blk[2 + l] >> 4) - 8);
+        }
+      }
+      return;
+    case T_Q5_0: case T_Q5_1:
+      for (int64_t b = 0; b < K / 32; ++b) {
+        const int bb = t == T_Q5_0 ? 22 : 24, ho = bb - 20;
+        const uint8_t* blk = src + bb * b;
+        const float d = f16_to_f32(rd16(blk)), m = t == T_Q5_1 ? f16_to_f32(rd16(blk + 2)) : 0.f;
+        for (int l = 0; l < 32; ++l) {
+          const int q = nib32(blk + ho + 4, l) | (((blk[ho + l / 8] >> (l % 8)) & 1) << 4);
+          dst[32 * b + l] = t == T_Q5_0 ? d * (float)(q - 16) : d * (float)q + m;
+        }
+      }
+      return;
+    case T_IQ4_NL:
+      for (int64_t b = 0; b < K / 32; ++b) {
+        const uint8_t* blk = src + 18 * b;
+        const float d = f16_to_f32(rd16(blk));
+        for (int l = 0; l < 32; ++l) dst[32 * b + l] = d * (float)kIq4Values[nib32(blk + 2, l)];
+      }
+      return;
+    case T_IQ4_XS:
+      for (int64_t b = 0; b < K / 256; ++b) {
+        const uint8_t* blk = src + 136 * b;
+        const float d = f16_to_f32(rd16(blk));
+        const int sh = rd16(blk + 2);
+        for (int ib = 0; ib < 8; ++ib) {
+          const int ls = ((blk[4 + ib / 2] >> (4 * (ib % 2))) & 15) | (((sh >> (2 * ib)) & 3) << 4);
+          const float dl = d * (float)(ls - 32);
+          for (int l = 0; l < 32; ++l) dst[256 * b + 32 * ib + l] = dl * (float)kIq4Values[nib32(blk + 8 + 16 * ib, l)];
         }
       }
       return;

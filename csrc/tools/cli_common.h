@@ -82,7 +82,8 @@ inline void print_common_usage(FILE* f) {
           "  -m, --model FILE          GGUF model (llama/mistral/mixtral/qwen2/qwen3/qwen3moe architectures)\n"
           "  --synthetic NAME          random-init model instead of -m (llama3-70b, llama3-8b, tinyllama,\n"
           "                            mixtral-8x7b, stories15m, qwen3-8b, qwen3-30b-a3b);\n"
-          "                            --ftype Q4_K_M|Q4_K|Q5_K_M|Q6_K|Q8_0|F16|Q3_K_S|Q3_K_M|Q3_K_L|Q2_K\n"
+          "                            --ftype Q4_K_M|Q4_K|Q5_K_M|Q6_K|Q8_0|F16|Q3_K_S|Q3_K_M|Q3_K_L|Q2_K|\n"
+          "                                    Q5_0|Q5_1|IQ4_NL|IQ4_XS\n"
           "  --no-qk-norm              synthetic Qwen3 shapes without the per-head Q/K RMSNorm (A/B of its cost)\n"
           "generation:\n"
           "  -p, --prompt TEXT         prompt (default \"Once upon a time\")\n"

@@ -81,6 +81,9 @@ CONFIGS = {
     "tiny-qwen3moe": LlamaConfig("tiny-qwen3moe", 2, 256, 4, 2, 256, 4096, 1e6, 1e-6, 1024, head_dim=128,
                                  n_expert=128, n_expert_used=8, tokenizer="gpt2", arch="qwen3moe", qk_norm=True,
                                  tied_output=True, router_std=1.0 / 16.0),
+    # d_model = one full super-block and a half one: every projection but ffn_down has K = 384, so
+    # the K-quant file types fall to the 32-weight-block types there
+    "tiny-k384": LlamaConfig("tiny-k384", 3, 384, 6, 2, 1024, 2048, 10000.0, 1e-5, 1024, head_dim=64),
     "tiny-l3": LlamaConfig("tiny-l3", 4, 1024, 8, 2, 2048, 4096, 500000.0, 1e-5, 1024,
                            tokenizer="gpt2", rope_freq_factors=True),
 }
@@ -95,7 +98,7 @@ def tensor_type(ftype: str, name: str, layer: int, n_layer: int, k_dim: int) -> 
     """ggml type of a 2-D weight under a named file type (mix)."""
     ftype = ftype.upper()
     plain = {"F32": Q.F32, "F16": Q.F16, "BF16": Q.BF16, "Q8_0": Q.Q8_0, "Q6_K": Q.Q6_K,
-             "Q5_K": Q.Q5_K, "Q4_0": Q.Q4_0}
+             "Q5_K": Q.Q5_K, "Q4_0": Q.Q4_0, "Q5_0": Q.Q5_0, "Q5_1": Q.Q5_1, "IQ4_NL": Q.IQ4_NL}
     kq = k_dim % 256 == 0
     if ftype in plain:
         t = plain[ftype]
@@ -142,5 +145,17 @@ def tensor_type(ftype: str, name: str, layer: int, n_layer: int, k_dim: int) -> 
                 t = Q.Q3_K
         if not kq:   # upstream's rule for the two low-bit types; the others as above
             return Q.Q4_0 if t in (Q.Q2_K, Q.Q3_K) else Q.Q8_0
+        return t
+    if ftype == "IQ4_XS":
+        # (as recalled from upstream) the base type beside a Q6_K output, Q5_K attn_v and early ffn_down;
+        # rows that are no multiple of 256 fall to the 32-weight-block type of the same width
+        if name == "output":
+            t = Q.Q6_K
+        elif name == "attn_v" or (name == "ffn_down" and layer < n_layer // 8):
+            t = Q.Q5_K
+        else:
+            t = Q.IQ4_XS
+        if not kq:
+            return {Q.IQ4_XS: Q.IQ4_NL, Q.Q5_K: Q.Q5_1, Q.Q6_K: Q.Q8_0}[t]
         return t
     raise ValueError(ftype)

@@ -16,6 +16,7 @@ from ..utils import quants as Q
 EPI_STORE, EPI_ATOMIC, EPI_SWIGLU = 0, 1, 2
 P_F16, P_Q8_0, P_Q4_K, P_Q5_K, P_Q6_K, P_Q4_0, P_BF16, P_I8 = 0, 1, 2, 3, 4, 5, 6, 7
 P_Q3_K, P_Q2_K = 8, 9
+P_Q5_0, P_Q5_1, P_IQ4_NL, P_IQ4_XS = 10, 11, 12, 13
 
 
 def _ptr(t: torch.Tensor | None):

@@ -5,7 +5,7 @@ synthetic-GGUF generator.  The block layouts follow the GGUF/ggml spec recorded 
 SURVEY.md §2.8 (the reference delegates these formats to its llama.cpp submodule,
 `.gitmodules:1-3`, which is not in the mount; the spec is reconstructed there).
 
-Formats: F32, F16, BF16, Q8_0, Q4_0, Q2_K, Q3_K, Q4_K, Q5_K, Q6_K.  Quantizers are simple
+Formats: F32, F16, BF16, Q8_0, Q4_0, Q5_0, Q5_1, IQ4_NL, IQ4_XS, Q2_K, Q3_K, Q4_K, Q5_K, Q6_K.  Quantizers are simple
 (min/max based) but produce valid blocks; dequantizers are exact implementations of
 the block math, so `dequant(bytes)` is the ground truth a kernel must reproduce.
 """
@@ -16,18 +16,21 @@ import numpy as np
 # ggml type ids
 F32, F16, Q4_0, Q4_1, Q5_0, Q5_1, Q8_0, Q8_1 = 0, 1, 2, 3, 6, 7, 8, 9
 Q2_K, Q3_K, Q4_K, Q5_K, Q6_K, Q8_K = 10, 11, 12, 13, 14, 15
+IQ4_NL, IQ4_XS = 20, 23
 BF16 = 30
 
 QK_K = 256
 
 TYPE_NAMES = {F32: "F32", F16: "F16", BF16: "BF16", Q8_0: "Q8_0", Q4_0: "Q4_0",
-              Q2_K: "Q2_K", Q3_K: "Q3_K", Q4_K: "Q4_K", Q5_K: "Q5_K", Q6_K: "Q6_K"}
+              Q2_K: "Q2_K", Q3_K: "Q3_K", Q4_K: "Q4_K", Q5_K: "Q5_K", Q6_K: "Q6_K",
+              Q5_0: "Q5_0", Q5_1: "Q5_1", IQ4_NL: "IQ4_NL", IQ4_XS: "IQ4_XS"}
 NAME_TO_TYPE = {v: k for k, v in TYPE_NAMES.items()}
 
 # (block_elems, block_bytes)
 BLOCK = {
     F32: (1, 4), F16: (1, 2), BF16: (1, 2),
     Q8_0: (32, 34), Q4_0: (32, 18),
+    Q5_0: (32, 22), Q5_1: (32, 24), IQ4_NL: (32, 18), IQ4_XS: (256, 136),
     Q2_K: (256, 84), Q3_K: (256, 110),
     Q4_K: (256, 144), Q5_K: (256, 176), Q6_K: (256, 210),
 }
@@ -406,6 +409,143 @@ def dequantize_q3_k(b: np.ndarray) -> np.ndarray:
     return (d * s * q).reshape(-1)
 
 
+# ----------------------------------------------------------------------------- Q5_0 / Q5_1
+# (block layouts recalled from upstream ggml; the scalar decoders of tests/test_iq4_q5_quants_cpu.py
+# pin them.)  In every 32-weight block element l < 16 is the low nibble of qs[l], element l + 16 the
+# high nibble of qs[l] (as Q4_0); the fifth bit of element e is bit e of the 32-bit word qh.
+def _signed_max(x: np.ndarray) -> np.ndarray:
+    """the signed element of largest magnitude of each row"""
+    return x[np.arange(x.shape[0]), np.abs(x).argmax(axis=1)]
+
+
+def _f16r(v: np.ndarray) -> np.ndarray:
+    """v rounded to f16 (a zero block's 0 / -16 becomes +0)"""
+    return np.asarray(v, np.float32).astype(np.float16).astype(np.float32) + np.float32(0)
+
+
+def _inv(d: np.ndarray) -> np.ndarray:
+    return np.where(d != 0, 1.0 / np.where(d != 0, d, 1), 0.0).astype(np.float32)
+
+
+def _pack5(q: np.ndarray):
+    """q [n, 32] in 0..31 -> (qh [n, 4], qs [n, 16])"""
+    hi = (q >> 4).astype(np.uint32)
+    word = (hi << np.arange(32, dtype=np.uint32)).sum(axis=1).astype(np.uint32)
+    qh = word.reshape(-1, 1).view(np.uint8)
+    lo = q & 15
+    return qh, (lo[:, :16] | (lo[:, 16:] << 4)).astype(np.uint8)
+
+
+def _unpack5(qh: np.ndarray, qs: np.ndarray) -> np.ndarray:
+    word = np.ascontiguousarray(qh).view(np.uint32).reshape(-1, 1)
+    hi = (word >> np.arange(32, dtype=np.uint32)) & 1
+    lo = np.concatenate([qs & 15, qs >> 4], axis=1).astype(np.uint32)
+    return (lo | (hi << 4)).astype(np.float32)
+
+
+def quantize_q5_0(x: np.ndarray) -> np.ndarray:
+    """Q5_0, 22 bytes / 32 weights: f16 d, qh[4], qs[16]; w = d (q - 16)."""
+    x = np.asarray(x, np.float32).reshape(-1, 32)
+    d = _f16r(_signed_max(x) / -16.0)
+    q = np.clip(np.floor(x * _inv(d)[:, None] + 16.5), 0, 31).astype(np.uint8)
+    out = np.zeros((x.shape[0], 22), np.uint8)
+    out[:, 0:2] = d.astype(np.float16).reshape(-1, 1).view(np.uint8)
+    out[:, 2:6], out[:, 6:] = _pack5(q)
+    return out.reshape(-1)
+
+
+def dequantize_q5_0(b: np.ndarray) -> np.ndarray:
+    b = np.asarray(b, np.uint8).reshape(-1, 22)
+    d = b[:, 0:2].copy().view(np.float16).astype(np.float32)
+    return (d * (_unpack5(b[:, 2:6], b[:, 6:]) - 16)).reshape(-1)
+
+
+def quantize_q5_1(x: np.ndarray) -> np.ndarray:
+    """Q5_1, 24 bytes / 32 weights: f16 d, f16 m, qh[4], qs[16]; w = d q + m."""
+    x = np.asarray(x, np.float32).reshape(-1, 32)
+    m = _f16r(x.min(axis=1))
+    d = _f16r((x.max(axis=1) - x.min(axis=1)) / 31.0)
+    q = np.clip(np.rint((x - m[:, None]) * _inv(d)[:, None]), 0, 31).astype(np.uint8)
+    out = np.zeros((x.shape[0], 24), np.uint8)
+    out[:, 0:2] = d.astype(np.float16).reshape(-1, 1).view(np.uint8)
+    out[:, 2:4] = m.astype(np.float16).reshape(-1, 1).view(np.uint8)
+    out[:, 4:8], out[:, 8:] = _pack5(q)
+    return out.reshape(-1)
+
+
+def dequantize_q5_1(b: np.ndarray) -> np.ndarray:
+    b = np.asarray(b, np.uint8).reshape(-1, 24)
+    d = b[:, 0:2].copy().view(np.float16).astype(np.float32)
+    m = b[:, 2:4].copy().view(np.float16).astype(np.float32)
+    return (d * _unpack5(b[:, 4:8], b[:, 8:]) + m).reshape(-1)
+
+
+# ----------------------------------------------------------------------------- IQ4_NL / IQ4_XS
+# Codebook quants: a nibble indexes 16 non-uniform int8 values.
+KVALUES_IQ4 = np.array([-127, -104, -83, -65, -49, -35, -22, -10, 1, 13, 25, 38, 53, 69, 89, 113], np.float32)
+
+
+def _nearest_kvalue(y: np.ndarray) -> np.ndarray:
+    return np.abs(y[..., None] - KVALUES_IQ4).argmin(axis=-1).astype(np.uint8)
+
+
+def _nibbles32(qs: np.ndarray) -> np.ndarray:
+    """qs [..., 16] -> indices [..., 32] (low nibbles, then high nibbles)"""
+    return np.concatenate([qs & 15, qs >> 4], axis=-1)
+
+
+def quantize_iq4_nl(x: np.ndarray) -> np.ndarray:
+    """IQ4_NL, 18 bytes / 32 weights: f16 d, qs[16]; w = d kvalues[nibble]."""
+    x = np.asarray(x, np.float32).reshape(-1, 32)
+    d = _f16r(_signed_max(x) / -127.0)
+    idx = _nearest_kvalue(x * _inv(d)[:, None])
+    out = np.zeros((x.shape[0], 18), np.uint8)
+    out[:, 0:2] = d.astype(np.float16).reshape(-1, 1).view(np.uint8)
+    out[:, 2:] = idx[:, :16] | (idx[:, 16:] << 4)
+    return out.reshape(-1)
+
+
+def dequantize_iq4_nl(b: np.ndarray) -> np.ndarray:
+    b = np.asarray(b, np.uint8).reshape(-1, 18)
+    d = b[:, 0:2].copy().view(np.float16).astype(np.float32)
+    return (d * KVALUES_IQ4[_nibbles32(b[:, 2:])]).reshape(-1)
+
+
+def quantize_iq4_xs(x: np.ndarray) -> np.ndarray:
+    """IQ4_XS, 136 bytes / 256 weights: f16 d, u16 scales_h, scales_l[4], qs[128]; sub-block ib of 32
+    weights has the 6-bit scale ls = low nibble ib of scales_l | 2 bits of scales_h << 4 and
+    w = d (ls - 32) kvalues[nibble]."""
+    x = np.asarray(x, np.float32).reshape(-1, 8, 32)
+    nb = x.shape[0]
+    dib = (_signed_max(x.reshape(-1, 32)) / -127.0).reshape(nb, 8)
+    D = dib[np.arange(nb), np.abs(dib).argmax(axis=1)]
+    d = _f16r(D / -32.0)
+    l = np.clip(np.rint(dib * _inv(d)[:, None]), -32, 31).astype(np.int32)
+    sub = d[:, None] * l.astype(np.float32)
+    idx = _nearest_kvalue(x * _inv(sub)[:, :, None])
+    ls = (l + 32).astype(np.uint32)
+    out = np.zeros((nb, 136), np.uint8)
+    out[:, 0:2] = d.astype(np.float16).reshape(-1, 1).view(np.uint8)
+    sh = ((ls >> 4) << (2 * np.arange(8, dtype=np.uint32))).sum(axis=1).astype(np.uint16)
+    out[:, 2:4] = sh.reshape(-1, 1).view(np.uint8)
+    lo = (ls & 15).astype(np.uint8)
+    out[:, 4:8] = lo[:, 0::2] | (lo[:, 1::2] << 4)
+    out[:, 8:] = (idx[:, :, :16] | (idx[:, :, 16:] << 4)).reshape(nb, 128)
+    return out.reshape(-1)
+
+
+def dequantize_iq4_xs(b: np.ndarray) -> np.ndarray:
+    b = np.asarray(b, np.uint8).reshape(-1, 136)
+    d = b[:, 0:2].copy().view(np.float16).astype(np.float32)
+    sh = b[:, 2:4].copy().view(np.uint16).astype(np.uint32)
+    ib = np.arange(8, dtype=np.uint32)
+    lo = (b[:, 4:8][:, ib // 2] >> (4 * (ib % 2)).astype(np.uint8)) & 15
+    ls = lo.astype(np.int32) | (((sh >> (2 * ib)) & 3).astype(np.int32) << 4)
+    dl = d * (ls - 32).astype(np.float32)
+    kv = KVALUES_IQ4[_nibbles32(b[:, 8:].reshape(-1, 8, 16))]
+    return (dl[:, :, None] * kv).reshape(-1)
+
+
 # ----------------------------------------------------------------------------- dispatch
 def quantize(x: np.ndarray, qtype: int) -> np.ndarray:
     x = np.ascontiguousarray(x, np.float32)
@@ -416,7 +556,8 @@ def quantize(x: np.ndarray, qtype: int) -> np.ndarray:
     if qtype == BF16:
         return f32_to_bf16_bits(x.reshape(-1)).view(np.uint8).copy()
     return {Q8_0: quantize_q8_0, Q4_0: quantize_q4_0, Q2_K: quantize_q2_k, Q3_K: quantize_q3_k, Q4_K: quantize_q4_k,
-            Q5_K: quantize_q5_k, Q6_K: quantize_q6_k}[qtype](x)
+            Q5_K: quantize_q5_k, Q6_K: quantize_q6_k, Q5_0: quantize_q5_0, Q5_1: quantize_q5_1,
+            IQ4_NL: quantize_iq4_nl, IQ4_XS: quantize_iq4_xs}[qtype](x)
 
 
 def dequantize(b: np.ndarray, qtype: int, shape=None) -> np.ndarray:
@@ -430,7 +571,8 @@ def dequantize(b: np.ndarray, qtype: int, shape=None) -> np.ndarray:
     else:
         y = {Q8_0: dequantize_q8_0, Q4_0: dequantize_q4_0, Q2_K: dequantize_q2_k, Q3_K: dequantize_q3_k,
              Q4_K: dequantize_q4_k,
-             Q5_K: dequantize_q5_k, Q6_K: dequantize_q6_k}[qtype](b)
+             Q5_K: dequantize_q5_k, Q6_K: dequantize_q6_k, Q5_0: dequantize_q5_0, Q5_1: dequantize_q5_1,
+             IQ4_NL: dequantize_iq4_nl, IQ4_XS: dequantize_iq4_xs}[qtype](b)
     return y.reshape(shape) if shape is not None else y
 
 
@@ -466,4 +608,17 @@ def random_blocks(rng: np.random.Generator, qtype: int, n_rows: int, n_cols: int
     elif qtype == Q3_K:
         # every hmask / quant / 6-bit scale bit random: |s_k| averages 16, q deviation ~2.3
         raw[:, 108:110] = np.full((nblk, 1), scale / 42.0, np.float16).view(np.uint8)
+    elif qtype == Q5_0:
+        # q - 16 uniform in [-16, 15]: deviation ~9.2
+        raw[:, 0:2] = np.full((nblk, 1), scale / 9.2, np.float16).view(np.uint8)
+    elif qtype == Q5_1:
+        # q uniform in [0, 31], m = -15.5 d centres the weights
+        raw[:, 0:2] = np.full((nblk, 1), scale / 9.2, np.float16).view(np.uint8)
+        raw[:, 2:4] = np.full((nblk, 1), -15.5 * scale / 9.2, np.float16).view(np.uint8)
+    elif qtype == IQ4_NL:
+        # a uniformly drawn codebook entry has rms ~67
+        raw[:, 0:2] = np.full((nblk, 1), scale / 67.0, np.float16).view(np.uint8)
+    elif qtype == IQ4_XS:
+        # ls - 32 uniform in [-32, 31] (rms ~18.5) times a codebook entry (rms ~67)
+        raw[:, 0:2] = np.full((nblk, 1), scale / (18.5 * 67.0), np.float16).view(np.uint8)
     return raw.reshape(-1)

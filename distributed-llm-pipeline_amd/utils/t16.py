@@ -12,10 +12,12 @@ from . import quants as Q
 
 P_F16, P_Q8_0, P_Q4_K, P_Q5_K, P_Q6_K, P_Q4_0, P_BF16 = 0, 1, 2, 3, 4, 5, 6
 P_Q3_K, P_Q2_K = 8, 9   # (7 is P_I8, which has no GGUF type)
+P_Q5_0, P_Q5_1, P_IQ4_NL, P_IQ4_XS = 10, 11, 12, 13
 CHUNK = {P_F16: 8192, P_Q8_0: 4352, P_Q4_K: 2304, P_Q5_K: 2816, P_Q6_K: 3360, P_Q4_0: 2304, P_BF16: 8192,
-         P_Q3_K: 1760, P_Q2_K: 1344}
+         P_Q3_K: 1760, P_Q2_K: 1344, P_Q5_0: 2816, P_Q5_1: 3072, P_IQ4_NL: 2304, P_IQ4_XS: 2176}
 PACK_OF = {Q.F32: P_F16, Q.F16: P_F16, Q.BF16: P_BF16, Q.Q8_0: P_Q8_0, Q.Q4_0: P_Q4_0,
-           Q.Q4_K: P_Q4_K, Q.Q5_K: P_Q5_K, Q.Q6_K: P_Q6_K, Q.Q3_K: P_Q3_K, Q.Q2_K: P_Q2_K}
+           Q.Q4_K: P_Q4_K, Q.Q5_K: P_Q5_K, Q.Q6_K: P_Q6_K, Q.Q3_K: P_Q3_K, Q.Q2_K: P_Q2_K,
+           Q.Q5_0: P_Q5_0, Q.Q5_1: P_Q5_1, Q.IQ4_NL: P_IQ4_NL, Q.IQ4_XS: P_IQ4_XS}
 
 
 def _f16(b2):
@@ -45,7 +47,7 @@ def unpack_t16(packed: np.ndarray, ptype: int, n: int, k: int) -> np.ndarray:
                         kk = sb * 256 + 64 * g + 32 * h + 8 * s + j           # [64]
                         row = 16 * t + r
                         pos = (j & 1) * 4 + (j >> 1)                          # nibble position
-                        if ptype in (P_Q4_K, P_Q5_K, P_Q6_K, P_Q4_0):
+                        if ptype in (P_Q4_K, P_Q5_K, P_Q6_K, P_Q4_0, P_Q5_0, P_Q5_1):
                             dw = c[h * 1024 + lane * 16 + s * 4 + pos // 2]
                             q = (dw >> ((pos & 1) * 4)) & 15
                         if ptype in (P_Q4_K, P_Q5_K):
@@ -83,6 +85,30 @@ def unpack_t16(packed: np.ndarray, ptype: int, n: int, k: int) -> np.ndarray:
                                 sk = ((vg >> (6 * sub)) & 63).astype(np.float32) - 32
                                 d = _f16(np.stack([c[1728 + 2 * rr: 1728 + 2 * rr + 2] for rr in r]))
                                 v = d * sk * (q + 4 * hi - 4)
+                        elif ptype in (P_Q5_0, P_Q5_1):
+                            # Q4_K nibbles, the Q5_K high-bit plane, d [r] 16 B (block 2g + h), Q5_1: m [r] 16 B
+                            qh = c[2048 + h * 256 + lane * 4 + (8 * s + pos) // 8]
+                            q = (q + (((qh >> ((8 * s + pos) % 8)) & 1) << 4)).astype(np.float32)
+                            blk = 2 * g + h
+                            d = _f16(np.stack([c[2560 + 16 * rr + 2 * bb: 2560 + 16 * rr + 2 * bb + 2] for rr, bb in zip(r, blk)]))
+                            if ptype == P_Q5_0:
+                                v = d * (q - 16)
+                            else:
+                                m = _f16(np.stack([c[2816 + 16 * rr + 2 * bb: 2816 + 16 * rr + 2 * bb + 2] for rr, bb in zip(r, blk)]))
+                                v = d * q + m
+                        elif ptype in (P_IQ4_NL, P_IQ4_XS):
+                            # codebook nibbles: element j at bit 8 (j & 3) + 4 (j >> 2) of dword s
+                            idx = (c[h * 1024 + lane * 16 + s * 4 + (j & 3)] >> (4 * (j >> 2))) & 15
+                            blk = 2 * g + h
+                            if ptype == P_IQ4_NL:
+                                d = _f16(np.stack([c[2048 + 16 * rr + 2 * bb: 2048 + 16 * rr + 2 * bb + 2] for rr, bb in zip(r, blk)]))
+                            else:
+                                # header [r] 8 B as in GGUF: d, scales_h, scales_l[4]
+                                hdr = np.stack([c[2048 + 8 * rr: 2048 + 8 * rr + 8] for rr in r])
+                                sh = hdr[:, 2].astype(np.int64) | (hdr[:, 3].astype(np.int64) << 8)
+                                ls = ((hdr[lane, 4 + blk // 2] >> (4 * (blk % 2))) & 15) | (((sh >> (2 * blk)) & 3) << 4)
+                                d = _f16(hdr[:, 0:2]) * (ls.astype(np.float32) - 32)
+                            v = d * Q.KVALUES_IQ4[idx]
                         elif ptype == P_Q6_K:
                             i = j >> 1
                             bit = 16 * s + ((8 + 2 * i) if (j & 1) else 2 * i)
