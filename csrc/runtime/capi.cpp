@@ -163,6 +163,7 @@ const char* mp_model_config_json(const char* gguf_path) {
   j["arch"] = c.arch; j["rope_neox"] = c.rope_neox; j["qkv_bias"] = c.qkv_bias;
   j["qk_norm"] = c.qk_norm;
   j["expert_ff"] = c.expert_ff;
+  j["pooling_type"] = c.pooling_type;
   g_str = j.dump();
   return g_str.c_str();
   API_CATCH(nullptr)
@@ -404,6 +405,25 @@ int mp_op_gemvs(int ptype, int epi, const void* W, int ntiles, int nsb, const vo
 int mp_op_rmsnorm(const void* x, int ldx, const void* w, int d, float eps, void* out, int ldo, int M, void* stream) {
   API_TRY
   launch_rmsnorm((const float*)x, ldx, (const float*)w, d, eps, (f16*)out, ldo, M, nullptr, 0, (hipStream_t)stream);
+  HIP_OK(hipGetLastError());
+  return 0;
+  API_CATCH(-1)
+}
+
+// launch_pool_embed (pool.hip) with the caller's buffers: segs = HOST int32 [n_seg][6] rows of
+// {row0, T, slot, p0, prompt_len, ends_prompt}; seg_tab = device scratch of the same size; h / part /
+// pool_acc / emb device f32 as in PoolParams (the ones the pooling does not use may be null)
+int mp_op_pool_embed(const void* x, int ldx, const void* w, int d, float eps, const int32_t* segs, int n_seg, void* seg_tab,
+                     int T, int pooling, int normalize, int n_slots, void* h, void* part, int part_cap, void* pool_acc,
+                     void* emb, void* stream) {
+  API_TRY
+  static_assert(sizeof(PoolSeg) == 6 * sizeof(int32_t), "PoolSeg is six int32");
+  PoolParams p{};
+  p.x = (const float*)x; p.ldx = ldx; p.w = (const float*)w; p.d = d; p.eps = eps;
+  p.segs = reinterpret_cast<const PoolSeg*>(segs); p.n_seg = n_seg; p.seg_tab = (PoolSeg*)seg_tab; p.seg_cap = n_seg;
+  p.T = T; p.pooling = pooling; p.normalize = normalize; p.n_slots = n_slots;
+  p.h = (float*)h; p.part = (float*)part; p.part_cap = part_cap; p.pool_acc = (float*)pool_acc; p.emb = (float*)emb;
+  launch_pool_embed(p, (hipStream_t)stream);
   HIP_OK(hipGetLastError());
   return 0;
   API_CATCH(-1)
@@ -838,6 +858,13 @@ int mp_tok_add_bos(void* h) {
   return static_cast<Tokenizer*>(h)->add_bos_default() ? 1 : 0;
   API_CATCH(-1)
 }
+// 1 when the embedding text paths append EOS (tokenizer.ggml.add_eos_token)
+int mp_tok_add_eos(void* h) {
+  API_TRY
+  if (!h) throw std::runtime_error("tokenizer handle is null");
+  return static_cast<Tokenizer*>(h)->add_eos_default() ? 1 : 0;
+  API_CATCH(-1)
+}
 // pre-tokenizer split (tests): returns pieces joined by '\x1f'
 const char* mp_tok_pretokenize(const char* text, int max_digits) {
   API_TRY
@@ -1061,6 +1088,52 @@ int mp_engine_score(void* h, const int32_t* prompt_tokens, const int32_t* lens, 
     o += s.lp.size();
   }
   return 0;
+  API_CATCH(-1)
+}
+// Embeddings (Engine::embed).  json_request: {"prompts": [[token id, ..], ..], "slots": [slot, ..]
+// (optional: the first idle slots), "pooling": "none" | "mean" | "cls" | "last" | id | null (the
+// model's default), "normalize": bool (default true)}.  The vectors are written back to back in
+// prompt order ([d] each, or [len][d] with "none"); returns the floats written, -1 on error (also
+// when they exceed cap).
+long mp_engine_embed(void* h, const char* json_request, float* out, long cap) {
+  API_TRY
+  Engine* e = static_cast<Engine*>(h);
+  const Json rq = Json::parse(json_request ? json_request : "{}");
+  if (!rq.has("prompts") || !rq["prompts"].is_arr()) throw std::runtime_error("embed: \"prompts\" must be a list of token lists");
+  std::vector<std::vector<int32_t>> prompts;
+  for (const Json& p : rq["prompts"].arr()) {
+    if (!p.is_arr()) throw std::runtime_error("embed: \"prompts\" must be a list of token lists");
+    std::vector<int32_t> t;
+    for (const Json& x : p.arr()) t.push_back((int32_t)x.num());
+    prompts.push_back(std::move(t));
+  }
+  std::vector<int> slots;
+  if (rq.has("slots") && rq["slots"].is_arr()) {
+    for (const Json& s : rq["slots"].arr()) slots.push_back((int)s.num());
+  } else {
+    slots = e->idle_slots();
+    if (slots.size() < prompts.size())
+      throw std::runtime_error("embed: " + std::to_string(prompts.size()) + " prompts but " + std::to_string(slots.size()) +
+                               " idle slots");
+    slots.resize(prompts.size());
+  }
+  int pooling = -1;
+  if (rq.has("pooling") && rq["pooling"].is_str()) pooling = Engine::pooling_from_name(rq["pooling"].str());
+  else if (rq.has("pooling") && rq["pooling"].is_num()) {
+    pooling = (int)rq["pooling"].num();
+    if (pooling < 0) throw std::runtime_error("embed: bad pooling " + std::to_string(pooling));
+  }
+  std::vector<Engine::EmbedResult> res;
+  e->embed(slots, prompts, pooling, rq.get_bool("normalize", true), &res);
+  long n = 0;
+  for (const auto& r : res) n += (long)r.v.size();
+  if (n > cap || (n > 0 && !out)) throw std::runtime_error("embed: output buffer too small");
+  long o = 0;
+  for (const auto& r : res) {
+    std::copy(r.v.begin(), r.v.end(), out + o);
+    o += (long)r.v.size();
+  }
+  return n;
   API_CATCH(-1)
 }
 // the --perplexity procedure's helpers (perplexity.h) for tests and Python callers.

@@ -787,6 +787,44 @@ void CpuStage::prefill(int mb, const std::vector<PrefillSeg>& segs, hipStream_t)
       const int32_t t = sc_tgt_[mb][m];
       if (t >= 0 && t < cfg_.vocab && std::isfinite(lse) && r[t] == r[t]) sc_lp_[mb][m] = (float)((double)r[t] - lse);
     }
+  } else if (spec_.last() && !segs.empty() && segs[0].embed) {
+    // embeddings: output norm + pooling of the rows in f32 (the arithmetic of pool.hip); no LM head
+    const size_t ns = (size_t)opt_.n_mb * opt_.mb_size;
+    if (pool_emb_.empty()) { pool_emb_.assign(ns * d, 0.f); pool_acc_.assign(ns * d, 0.f); }
+    if (pool_h_.size() < (size_t)opt_.n_mb) pool_h_.resize(opt_.n_mb);
+    std::vector<float>& h = pool_h_[mb];
+    h.resize((size_t)T * d);
+    rmsnorm(x, out_norm_, h.data(), T);
+    auto finish = [&](const float* v, float* o) {
+      float s = 0.f;
+      for (int i = 0; i < d; ++i) s += v[i] * v[i];
+      const float l2 = !embed_norm_ ? 1.f : s > 0.f ? 1.f / std::sqrt(s) : 0.f;
+      for (int i = 0; i < d; ++i) o[i] = v[i] * l2;
+    };
+    int row = 0;
+    for (const PrefillSeg& s : segs) {
+      const size_t sl = (size_t)mb * opt_.mb_size + s.b;
+      float* acc = pool_acc_.data() + sl * d;
+      float* emb = pool_emb_.data() + sl * d;
+      if (embed_pool_ == POOL_NONE) {
+        for (int t = 0; t < s.T; ++t) finish(h.data() + (size_t)(row + t) * d, h.data() + (size_t)(row + t) * d);
+      } else if (embed_pool_ == POOL_MEAN) {
+        if (s.p0 == 0) std::fill(acc, acc + d, 0.f);
+        for (int t = 0; t < s.T; ++t)
+          for (int i = 0; i < d; ++i) acc[i] += h[(size_t)(row + t) * d + i];
+        if (s.last) {
+          const float inv = 1.f / (float)(s.p0 + s.T);
+          std::vector<float> v(acc, acc + d);
+          for (float& e : v) e *= inv;
+          finish(v.data(), emb);
+        }
+      } else if (embed_pool_ == POOL_CLS) {
+        if (s.p0 == 0) finish(h.data() + (size_t)row * d, emb);
+      } else if (s.last) {
+        finish(h.data() + (size_t)(row + s.T - 1) * d, emb);
+      }
+      row += s.T;
+    }
   } else if (spec_.last()) {
     int row = 0;
     for (const PrefillSeg& s : segs) {
@@ -799,6 +837,20 @@ void CpuStage::prefill(int mb, const std::vector<PrefillSeg>& segs, hipStream_t)
 void CpuStage::copy_verify_tokens(int mb, int32_t* host, int n) {
   if ((size_t)mb >= vtok_.size() || (int)vtok_[mb].size() < n) throw std::runtime_error("no verify tokens");
   std::memcpy(host, vtok_[mb].data(), (size_t)n * 4);
+}
+
+void CpuStage::copy_embeddings(const std::vector<int>& slots, float* host) {
+  const size_t d = (size_t)cfg_.d_model;
+  for (size_t k = 0; k < slots.size(); ++k) {
+    if (slots[k] < 0 || ((size_t)slots[k] + 1) * d > pool_emb_.size()) throw std::runtime_error("no embeddings");
+    std::memcpy(host + k * d, pool_emb_.data() + (size_t)slots[k] * d, d * 4);
+  }
+}
+
+void CpuStage::copy_token_embeddings(int mb, int n_rows, float* host) {
+  if ((size_t)mb >= pool_h_.size() || pool_h_[mb].size() < (size_t)n_rows * cfg_.d_model)
+    throw std::runtime_error("no token embeddings");
+  std::memcpy(host, pool_h_[mb].data(), (size_t)n_rows * cfg_.d_model * 4);
 }
 
 void CpuStage::prefill_finish(int mb, hipStream_t, const std::vector<int>* rows) {

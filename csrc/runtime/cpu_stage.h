@@ -49,6 +49,8 @@ class CpuStage : public Stage {
   }
   void set_score_targets(int mb, const int32_t* host, int n, int top_n) override;
   void copy_scores(int mb, int n, float* target_lp, int32_t* top_id, float* top_lp) override;
+  void copy_embeddings(const std::vector<int>& slots, float* host) override;
+  void copy_token_embeddings(int mb, int n_rows, float* host) override;
   void decode(int mb, hipStream_t st) override;
   const float* logits_ptr() const override { return logits_.data(); }
   int logits_ld() const override { return cfg_.vocab; }
@@ -113,6 +115,10 @@ class CpuStage : public Stage {
   int sc_top_n_ = 0;
   std::vector<std::vector<int32_t>> vtok_;   // last stage: [mb][rows] greedy tokens of a verify chunk
   std::vector<float> logits_;
+  // embeddings (last stage): per slot running sum and result [n_slots][d]; per micro-batch the
+  // last embed chunk's per-token vectors (pooling none)
+  std::vector<float> pool_acc_, pool_emb_;
+  std::vector<std::vector<float>> pool_h_;
   // scratch
   std::vector<float> xn_, qkv_, att_, h_, gu_;
   Q8Buf xq_;   // matmul: the activation rows as int8 blocks (cpu_q8)

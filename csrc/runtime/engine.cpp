@@ -1985,6 +1985,143 @@ void Engine::score(const std::vector<std::vector<int32_t>>& prompts, int n_top, 
   }
 }
 
+std::vector<int> Engine::idle_slots() const {
+  std::vector<int> s;
+  for (int i = 0; i < M_ * B_; ++i)
+    if (!((size_t)i < active_.size() && active_[i])) s.push_back(i);
+  return s;
+}
+
+// Embeddings.  The prompts run through the packed-prefill path as `embed` segments (several prompts
+// per chunk, prompts spanning chunks) with no PREFILL_END: the last stage norms and pools the rows
+// of each chunk (its per-slot accumulator carries a mean across chunks) and never runs the LM head
+// or the sampler.  Pooled modes send every chunk in one pass and read the slots' vectors after it;
+// "none" sends one chunk per micro-batch per pass and reads that chunk's rows (the stage keeps one
+// chunk of per-token vectors per micro-batch).
+void Engine::embed(const std::vector<int>& slots, const std::vector<std::vector<int32_t>>& prompts, int pooling,
+                   bool normalize, std::vector<EmbedResult>* out) {
+  if (mode_ == "mp" && S_ > 1)
+    throw std::runtime_error("embed: needs every stage in this process (mode \"mp\" is not supported)");
+  if ((int)workers_.size() != S_) throw std::runtime_error("embed: needs every stage in this process");
+  if (failed_) throw std::runtime_error("embed: the pipeline has failed");
+  if (pooling < 0) pooling = default_pooling();
+  if (pooling == POOL_RANK) throw std::runtime_error("embed: pooling \"rank\" (reranking) is not supported");
+  if (pooling > POOL_LAST)
+    throw std::runtime_error("embed: bad pooling " + std::to_string(pooling) + " (0 none, 1 mean, 2 cls, 3 last)");
+  if (slots.size() != prompts.size()) throw std::runtime_error("embed: one prompt per slot");
+  const size_t NS = (size_t)M_ * B_, n = prompts.size(), d = (size_t)cfg_.d_model;
+  std::vector<int> k_of(NS, -1);
+  for (size_t k = 0; k < n; ++k) {
+    const int i = slots[k];
+    if (i < 0 || (size_t)i >= NS) throw std::runtime_error("embed: bad slot " + std::to_string(i));
+    if (k_of[i] >= 0) throw std::runtime_error("embed: slot " + std::to_string(i) + " given twice");
+    if ((size_t)i < active_.size() && active_[i]) throw std::runtime_error("embed: slot " + std::to_string(i) + " is busy");
+    if (prompts[k].empty()) throw std::runtime_error("embed: prompt " + std::to_string(k) + " is empty");
+    if ((int)prompts[k].size() > max_ctx_)
+      throw std::runtime_error("embed: prompt " + std::to_string(k) + " has " + std::to_string(prompts[k].size()) +
+                               " tokens, more than max_ctx = " + std::to_string(max_ctx_));
+    for (int32_t t : prompts[k])
+      if (t < 0 || t >= cfg_.vocab)
+        throw std::runtime_error("embed: token id " + std::to_string(t) + " out of range (vocab " + std::to_string(cfg_.vocab) + ")");
+    k_of[i] = (int)k;
+  }
+  out->assign(n, {});
+  if (n == 0) return;
+  Worker* wf = nullptr;
+  Worker* wl = nullptr;
+  for (auto& w : workers_) {
+    if (w->stage->spec().first()) wf = w.get();
+    if (w->stage->spec().last()) wl = w.get();
+  }
+  // KV pages for the prompts (all or none: a pool too small for this call leaves the slots as they were)
+  try {
+    for (size_t k = 0; k < n; ++k) kv_grant((size_t)slots[k], (int)prompts[k].size());
+  } catch (...) {
+    for (size_t k = 0; k < n; ++k) pager_.release(slots[k]);
+    throw;
+  }
+  kv_sync();
+  for (size_t k = 0; k < n; ++k) {
+    const size_t i = (size_t)slots[k];
+    if (i < slot_toks_.size()) slot_toks_[i].clear();   // the slot's KV is overwritten: no prefix to reuse
+    if (wf->cpu) std::memcpy(wf->stage->prompt_buf() + i * max_ctx_, prompts[k].data(), prompts[k].size() * 4);
+    else {
+      HIP_OK(hipSetDevice(wf->device));
+      HIP_OK(hipMemcpy(wf->stage->prompt_buf() + i * max_ctx_, prompts[k].data(), prompts[k].size() * 4, hipMemcpyHostToDevice));
+    }
+  }
+  if (!wl->cpu) HIP_OK(hipSetDevice(wl->device));
+  wl->stage->set_embed(pooling, normalize);
+  // the chunks of each micro-batch, in order (prefill_items without prefix reuse or a head item)
+  std::vector<std::vector<Item>> chunks(M_);
+  for (int mb = 0; mb < M_; ++mb) {
+    Item it{Item::PREFILL};
+    it.mb = mb;
+    auto flush = [&] {
+      if (it.T > 0) chunks[mb].push_back(it);
+      it.segs.clear();
+      it.T = 0;
+    };
+    for (int b = 0; b < B_; ++b) {
+      const int k = k_of[(size_t)mb * B_ + b];
+      if (k < 0) continue;
+      const int len = (int)prompts[k].size();
+      for (int p0 = 0; p0 < len;) {
+        PrefillSeg sg;
+        sg.b = b; sg.p0 = p0; sg.T = std::min(chunk_ - it.T, len - p0); sg.last = p0 + sg.T >= len; sg.embed = true;
+        it.segs.push_back(sg);
+        it.T += sg.T;
+        p0 += sg.T;
+        if (it.T == chunk_ || !packed_prefill_) flush();
+      }
+    }
+    flush();
+  }
+  for (size_t k = 0; k < n; ++k) {
+    (*out)[k].n_rows = pooling == POOL_NONE ? (int)prompts[k].size() : 1;
+    (*out)[k].v.assign((size_t)(*out)[k].n_rows * d, 0.f);
+  }
+  auto give_back = [&] {
+    for (size_t k = 0; k < n; ++k) pager_.release(slots[k]);
+    if (!failed_) kv_sync();
+  };
+  try {
+    if (pooling != POOL_NONE) {
+      std::vector<Item> items;
+      for (int mb = 0; mb < M_; ++mb) items.insert(items.end(), chunks[mb].begin(), chunks[mb].end());
+      run_all(items);
+      std::vector<float> v(n * d);
+      if (!wl->cpu) HIP_OK(hipSetDevice(wl->device));
+      wl->stage->copy_embeddings(slots, v.data());
+      for (size_t k = 0; k < n; ++k) std::copy(v.begin() + k * d, v.begin() + (k + 1) * d, (*out)[k].v.begin());
+    } else {
+      std::vector<float> rows((size_t)chunk_ * d);
+      for (size_t pass = 0;; ++pass) {
+        std::vector<Item> items;
+        for (int mb = 0; mb < M_; ++mb)
+          if (pass < chunks[mb].size()) items.push_back(chunks[mb][pass]);
+        if (items.empty()) break;
+        run_all(items);
+        for (const Item& it : items) {
+          if (!wl->cpu) HIP_OK(hipSetDevice(wl->device));
+          wl->stage->copy_token_embeddings(it.mb, it.T, rows.data());
+          int row = 0;
+          for (const PrefillSeg& sg : it.segs) {
+            const int k = k_of[(size_t)it.mb * B_ + sg.b];
+            std::copy(rows.begin() + (size_t)row * d, rows.begin() + (size_t)(row + sg.T) * d,
+                      (*out)[k].v.begin() + (size_t)sg.p0 * d);
+            row += sg.T;
+          }
+        }
+      }
+    }
+  } catch (...) {
+    give_back();
+    throw;
+  }
+  give_back();
+}
+
 Json Engine::generate(const std::vector<std::vector<int32_t>>& prompts, int n_predict,
                       std::vector<std::vector<int32_t>>* out) {
   const double t0 = now_ms();
@@ -2227,6 +2364,11 @@ Json Engine::info() const {
     j["device_speed"] = ds;
   }
   j["kv_free_pages"] = pager_.free_pages();
+  {
+    Json is = Json::array();
+    for (int s : idle_slots()) is.push(s);
+    j["idle_slots"] = is;
+  }
   j["mode"] = mode_;
   j["backend"] = cpu_ ? "cpu" : hybrid_ ? "hybrid" : "hip";
   j["load_ms"] = load_ms_;
@@ -2248,6 +2390,8 @@ Json Engine::info() const {
   // d_ff is the width of one expert where the file gives it separately (qwen3moe)
   m["d_ff_kind"] = cfg_.expert_ff ? "expert" : "dense";
   if (cfg_.expert_ff) m["expert_d_ff"] = cfg_.d_ff;
+  m["pooling_type"] = cfg_.pooling_type;   // the file's (-1: none); embed() pools by "pooling" unless told otherwise
+  j["pooling"] = std::string(pooling_name(default_pooling()));
   m["describe"] = cfg_.describe();
   j["model"] = m;
   size_t wb = 0, kb = 0;

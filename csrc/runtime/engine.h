@@ -91,6 +91,33 @@ class Engine {
   // this process.  Ends any running generation (the slots' KV is overwritten).
   void score(const std::vector<std::vector<int32_t>>& prompts, int n_top, std::vector<SeqLogprobs>* out);
 
+  // Embeddings: prompts[k] runs through the packed-prefill path in the idle slot slots[k]; the last
+  // stage norms the rows (output_norm), pools them per prompt and, with `normalize`, scales each
+  // vector to unit L2 length (the zero vector stays zero).  pooling: POOL_NONE (one vector per
+  // token, n_rows = prompt length), POOL_MEAN, POOL_CLS, POOL_LAST, or -1 for default_pooling().
+  // No LM head, no sampler step.  Like admit(), legal before start() and between decode_steps
+  // calls, for idle slots only; the other slots keep their state and the used slots are idle again
+  // (their KV pages returned, their prefix-cache entry dropped) when the call returns.  Every stage
+  // in this process.  Throws naming the cause: a busy slot, an empty prompt, a prompt over max_ctx,
+  // a token id out of range, a pooling that is not supported.
+  struct EmbedResult { std::vector<float> v; int n_rows = 1; };
+  void embed(const std::vector<int>& slots, const std::vector<std::vector<int32_t>>& prompts, int pooling,
+             bool normalize, std::vector<EmbedResult>* out);
+  // the file's pooling_type when it is mean, cls or last; otherwise last (in a causal model the last
+  // row is the only one that has seen the whole prompt)
+  int default_pooling() const {
+    return cfg_.pooling_type >= POOL_MEAN && cfg_.pooling_type <= POOL_LAST ? cfg_.pooling_type : POOL_LAST;
+  }
+  // "none" | "mean" | "cls" | "last" | "rank" -> its id, "" -> -1 (the default); throws on any other name
+  static int pooling_from_name(const std::string& s) {
+    if (s.empty()) return -1;
+    for (int p = POOL_NONE; p <= POOL_RANK; ++p)
+      if (s == pooling_name(p)) return p;
+    throw std::runtime_error("unknown pooling \"" + s + "\" (none, mean, cls, last)");
+  }
+  // slots embed() may use now, ascending
+  std::vector<int> idle_slots() const;
+
   // Continuous batching: between decode rounds, prefill new sequences into the
   // given sequence slots (slot = mb * mb_size + row) while the other slots keep their state; each
   // admitted slot gets its first token like start().  release() marks a slot idle (its row keeps

@@ -827,6 +827,63 @@ void HipStage::copy_scores(int mb, int n, float* target_lp, int32_t* top_id, flo
   }
 }
 
+void HipStage::ensure_pool(int mb) {
+  const size_t d = (size_t)cfg_.d_model, ns = (size_t)opt_.n_mb * opt_.mb_size;
+  if (!pool_tab_) {
+    pool_tab_cap_ = opt_.mb_size;   // a chunk holds at most one segment per sequence of its micro-batch
+    pool_tab_ = (PoolSeg*)dmalloc((size_t)pool_tab_cap_ * sizeof(PoolSeg));
+    pool_emb_ = (float*)dmalloc(ns * d * 4);
+  }
+  if (embed_pool_ == POOL_MEAN && !pool_acc_) {
+    pool_acc_ = (float*)dmalloc(ns * d * 4);
+    // every segment's last block may be short: ceil(T / rows) summed is at most chunk / rows + segments
+    pool_part_cap_ = opt_.prefill_chunk / kPoolBlockRows + opt_.mb_size + 1;
+    pool_part_ = (float*)dmalloc((size_t)pool_part_cap_ * d * 4);
+  }
+  if (embed_pool_ == POOL_MEAN || embed_pool_ == POOL_NONE) {
+    if (pool_h_.empty()) pool_h_.assign(opt_.n_mb, nullptr);
+    if (!pool_h_[mb]) pool_h_[mb] = (float*)dmalloc((size_t)opt_.prefill_chunk * d * 4);
+  }
+}
+
+// last stage, embed chunk: x [T][d] -> the slots' vectors (pool.hip)
+void HipStage::pool_chunk(int mb, const std::vector<PrefillSeg>& segs, const float* x, int T, hipStream_t st) {
+  ensure_pool(mb);
+  std::vector<PoolSeg> tab;
+  int row = 0;
+  for (const PrefillSeg& s : segs) {
+    if (!s.embed) throw std::runtime_error("embed chunk: a segment of another kind");
+    // an embed prompt is prefilled whole (no prefix reuse), so the segment that ends it tells its length
+    tab.push_back(PoolSeg{row, s.T, slot_of(mb, s.b), s.p0, s.p0 + s.T, s.last ? 1 : 0});
+    row += s.T;
+  }
+  PoolParams p{};
+  p.x = x; p.ldx = cfg_.d_model; p.w = out_norm_; p.d = cfg_.d_model; p.eps = cfg_.eps;
+  p.segs = tab.data(); p.n_seg = (int)tab.size(); p.seg_tab = pool_tab_; p.seg_cap = pool_tab_cap_;
+  p.T = T; p.pooling = embed_pool_; p.normalize = embed_norm_ ? 1 : 0; p.n_slots = opt_.n_mb * opt_.mb_size;
+  p.h = pool_h_.empty() ? nullptr : pool_h_[mb];
+  p.part = pool_part_; p.part_cap = pool_part_cap_; p.pool_acc = pool_acc_; p.emb = pool_emb_;
+  launch_pool_embed(p, st);
+}
+
+void HipStage::copy_embeddings(const std::vector<int>& slots, float* host) {
+  if (!pool_emb_) throw std::runtime_error("no embeddings");
+  HIP_OK(hipSetDevice(spec_.device));
+  HIP_OK(hipStreamSynchronize(stream_));
+  const size_t d = (size_t)cfg_.d_model;
+  for (size_t k = 0; k < slots.size(); ++k) {
+    if (slots[k] < 0 || slots[k] >= opt_.n_mb * opt_.mb_size) throw std::runtime_error("copy_embeddings: bad slot");
+    HIP_OK(hipMemcpy(host + k * d, pool_emb_ + (size_t)slots[k] * d, d * 4, hipMemcpyDeviceToHost));
+  }
+}
+
+void HipStage::copy_token_embeddings(int mb, int n_rows, float* host) {
+  if ((size_t)mb >= pool_h_.size() || !pool_h_[mb] || n_rows > opt_.prefill_chunk) throw std::runtime_error("no token embeddings");
+  HIP_OK(hipSetDevice(spec_.device));
+  HIP_OK(hipStreamSynchronize(stream_));
+  HIP_OK(hipMemcpy(host, pool_h_[mb], (size_t)n_rows * cfg_.d_model * 4, hipMemcpyDeviceToHost));
+}
+
 void HipStage::set_history(int mb, const std::vector<std::vector<int32_t>>& seqs) {
   if (!spec_.last() || !(penalties_on() || rows_on())) return;
   ensure_hist();
@@ -1435,6 +1492,9 @@ void HipStage::prefill(int mb, const std::vector<PrefillSeg>& segs, hipStream_t 
     if (sc_top_n_ > 0) { q.top_id = sc_top_id_ + off * kMaxProbs; q.top_lp = sc_top_lp_ + off * kMaxProbs; }
     q.ld_top = kMaxProbs;
     launch_logprob(q, st);
+  } else if (spec_.last() && !segs.empty() && segs[0].embed) {
+    // embeddings: output norm + pooling of the rows; no LM head, nothing kept for prefill_finish
+    pool_chunk(mb, segs, x, T, st);
   } else if (spec_.last()) {
     int row = 0;
     for (const PrefillSeg& s : segs) {

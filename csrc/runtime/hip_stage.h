@@ -149,6 +149,8 @@ class HipStage : public Stage {
   const void* logprob_rec(int mb) const override { return lp_rec_.empty() ? nullptr : lp_rec_[mb]; }
   void set_score_targets(int mb, const int32_t* host, int n, int top_n) override;
   void copy_scores(int mb, int n, float* target_lp, int32_t* top_id, float* top_lp) override;
+  void copy_embeddings(const std::vector<int>& slots, float* host) override;
+  void copy_token_embeddings(int mb, int n_rows, float* host) override;
 
   // One decode step for micro-batch mb (graph replay if captured).
   void decode(int mb, hipStream_t st) override;
@@ -325,6 +327,15 @@ class HipStage : public Stage {
   int32_t* sc_tgt_ = nullptr; float* sc_lp_ = nullptr; float* sc_lse_ = nullptr;   // [n_mb][chunk]
   int32_t* sc_top_id_ = nullptr; float* sc_top_lp_ = nullptr;                      // [n_mb][chunk][kMaxProbs]
   int sc_top_n_ = 0;
+  // embeddings (last stage; allocated by the first embed chunk): the chunk's segment table, the
+  // slots' running sums and results [n_slots][d], the mean's block sums, and per micro-batch the
+  // chunk's normed rows [chunk][d] (none: the result; mean: the rows the block sums are taken over)
+  void ensure_pool(int mb);
+  void pool_chunk(int mb, const std::vector<PrefillSeg>& segs, const float* x, int T, hipStream_t st);
+  PoolSeg* pool_tab_ = nullptr; int pool_tab_cap_ = 0;
+  float* pool_acc_ = nullptr; float* pool_emb_ = nullptr;
+  float* pool_part_ = nullptr; int pool_part_cap_ = 0;
+  std::vector<float*> pool_h_;
   // graphs
   std::vector<hipGraphExec_t> graphs_;
 };

@@ -131,6 +131,36 @@ void launch_rmsnorm_acc(float* x, int ldx, const float* w, int d, float eps, f16
                         const float* bias = nullptr, int bias_n = 0, int8_t* q8 = nullptr, int ldq8 = 0,
                         float* q8s = nullptr);
 
+// Embedding pooling (pool.hip): the output RMSNorm of a prefill chunk's residual rows, pooled per
+// prompt.  Pooling ids are llama.cpp's (<arch>.pooling_type); rank is not implemented.
+enum { POOL_NONE = 0, POOL_MEAN = 1, POOL_CLS = 2, POOL_LAST = 3, POOL_RANK = 4 };
+constexpr int kPoolMaxD = 8192;      // widest row (a multiple of 64)
+constexpr int kPoolBlockRows = 32;   // mean: rows per partial sum, counted from the segment's first row
+constexpr int kPoolSegBatch = 32;    // segments per table upload launch
+struct PoolSeg {                     // one prompt's rows in the chunk
+  int32_t row0, T;                   // rows [row0, row0 + T) of x
+  int32_t slot;                      // sequence slot: row of pool_acc / emb
+  int32_t p0;                        // position of the segment's first row in its prompt
+  int32_t prompt_len;                // tokens of the whole prompt
+  int32_t ends_prompt;               // p0 + T == prompt_len: the segment finishes the vector
+};
+struct PoolParams {
+  const float* x; int ldx;           // [T][ldx] f32 residual
+  const float* w; int d; float eps;  // output_norm: h = x * rsqrt(mean(x^2) + eps) * w
+  const PoolSeg* segs; int n_seg;    // HOST table: checked, then written to seg_tab on the stream
+  PoolSeg* seg_tab; int seg_cap;     // device table
+  int T;                             // rows of the chunk = sum of the segments' T
+  int pooling; int normalize;        // POOL_NONE..POOL_LAST; normalize: v * (s > 0 ? 1 / sqrt(s) : 0), s = sum v^2
+  int n_slots;
+  float* h;                          // none, mean: [T][d] normed rows (none: the result, each row normalised alone)
+  float* part; int part_cap;         // mean: [part_cap][d] block sums, part_cap >= pool_blocks(segs, n_seg)
+  float* pool_acc;                   // mean: [n_slots][d] running sums: stored by a p0 == 0 segment, added to by later ones
+  float* emb;                        // mean, cls, last: [n_slots][d] results
+};
+int pool_blocks(const PoolSeg* segs, int n_seg);
+// throws on a shape or table the kernels cannot take; every sum has a fixed order (no float atomics)
+void launch_pool_embed(const PoolParams& p, hipStream_t st);
+
 // embedding gather + dequant of raw GGUF rows -> x f32 [M][ldx]
 void launch_embed(int ggml_type, const uint8_t* table, int64_t row_bytes, int d, const int32_t* tokens,
                   int M, float* x, int ldx, hipStream_t st);

@@ -32,6 +32,7 @@ ModelConfig ModelConfig::from_gguf(const GgufFile& f) {
   c.n_ctx_train = (int)f.get_int(a + "context_length", 2048);
   c.rope_base = (float)f.get_float(a + "rope.freq_base", 10000.0);
   c.eps = (float)f.get_float(a + "attention.layer_norm_rms_epsilon", 1e-5);
+  c.pooling_type = (int)f.get_int(a + "pooling_type", -1);
   c.n_expert = (int)f.get_int(a + "expert_count", 0);
   c.n_expert_used = (int)f.get_int(a + "expert_used_count", 0);
   if (c.n_expert > 128)
@@ -89,6 +90,7 @@ std::string ModelConfig::describe() const {
   if (rope_neox) o << " rope=neox";
   if (qkv_bias) o << " qkv_bias";
   if (qk_norm) o << " qk_norm";
+  if (pooling_type >= 0) o << " pooling_type=" << pooling_type;
   return o.str();
 }
 

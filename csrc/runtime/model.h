@@ -40,6 +40,9 @@ struct ModelConfig {
   // the PER-EXPERT width, read from expert_feed_forward_length (else the shape of ffn_gate_exps);
   // expert_ff records that, for describe() and Engine::info().
   bool expert_ff = false;
+  // <arch>.pooling_type of an embedding model (llama.cpp's ids: 0 none, 1 mean, 2 cls, 3 last, 4 rank);
+  // -1: the file has none.  Engine::embed pools by it when it is 1..3 and by `last` otherwise.
+  int pooling_type = -1;
 
   int q_dim() const { return n_head * head_dim; }
   int kv_dim() const { return n_head_kv * head_dim; }

@@ -50,6 +50,11 @@ std::vector<int32_t> Session::encode(const std::string& text) const {
   return o;
 }
 
+std::vector<int32_t> Session::encode_embedding(const std::string& text) const {
+  if (tok_) return tok_->encode_for_embedding(text);
+  return encode(text);
+}
+
 std::vector<int32_t> Session::encode_raw(const std::string& text) const {
   if (tok_) return tok_->encode(text, false, false);
   std::vector<int32_t> o;
@@ -228,6 +233,53 @@ void Session::serve(const std::function<std::vector<Served>(int free)>& next) {
   int reserved = 0;
   std::deque<Pending> waiting;
   std::vector<std::unique_ptr<Live>> live(cap);
+  // embedding jobs in arrival order: `at` prompts done, their vectors in `out`
+  struct EmbedRun {
+    std::shared_ptr<EmbedJob> job;
+    size_t at = 0;
+    std::vector<Engine::EmbedResult> out;
+  };
+  std::deque<EmbedRun> emb_wait;
+  // One engine call for the front job: as many of its remaining prompts as there are slots no
+  // request holds and pages beyond what the running requests have reserved.  The slots are idle
+  // again when the call returns, so nothing is reserved for it.
+  auto embed_round = [&] {
+    if (emb_wait.empty()) return;
+    EmbedRun& er = emb_wait.front();
+    EmbedJob& job = *er.job;
+    std::string err;
+    std::vector<int> sl;
+    std::vector<std::vector<int32_t>> pr;
+    int pages = 0;
+    for (int s = 0; s < cap && er.at + pr.size() < job.prompts.size(); ++s) {
+      if (live[s]) continue;
+      const std::vector<int32_t>& p = job.prompts[er.at + pr.size()];
+      const int need = ((int)p.size() + 63) / 64;
+      if ((int)p.size() > max_ctx || need > pool) {
+        err = "embedding input of " + std::to_string(p.size()) + " tokens exceeds the context (" + std::to_string(max_ctx) +
+              ") or the KV pool";
+        break;
+      }
+      if (reserved + pages + need > pool) break;   // wait for pages to come back
+      pages += need;
+      sl.push_back(s);
+      pr.push_back(p);
+    }
+    if (err.empty() && !pr.empty()) {
+      try {
+        std::vector<Engine::EmbedResult> r;
+        eng_->embed(sl, pr, job.pooling, job.normalize, &r);
+        for (auto& v : r) er.out.push_back(std::move(v));
+        er.at += pr.size();
+      } catch (const std::exception& e) {
+        err = e.what();
+      }
+    }
+    if (!err.empty() || er.at == job.prompts.size()) {
+      if (job.done) job.done(er.out, err);
+      emb_wait.pop_front();
+    }
+  };
   // pages a request can ever need (its context is capped at max_ctx), and that clamped to the pool
   auto pages_need = [&](long prompt_len, int n_predict) {
     const long want = prompt_len + std::max(0, n_predict) + 1;
@@ -370,8 +422,12 @@ void Session::serve(const std::function<std::vector<Served>(int free)>& next) {
     int free = 0;
     for (auto& l : live) free += l ? 0 : 1;
     // new requests only when nobody is waiting for pages (FIFO)
-    if (free > (int)waiting.size() && waiting.empty())
+    if (free > (int)waiting.size() && waiting.empty() && emb_wait.empty())
       for (auto& f : next(free)) {
+        if (f.embed) {
+          emb_wait.push_back(EmbedRun{f.embed, 0, {}});
+          continue;
+        }
         Pending pd;
         pd.prompt = encode(f.req.prompt);
         if ((int)pd.prompt.size() >= max_ctx) pd.prompt.erase(pd.prompt.begin(), pd.prompt.end() - (max_ctx / 2));
@@ -420,10 +476,12 @@ void Session::serve(const std::function<std::vector<Served>(int free)>& next) {
         if (L.s.req.n_predict <= 0 || !consume(sl, eng_->last_token(sl))) finish(sl);
       }
     }
+    const bool had_embed = !emb_wait.empty();
+    embed_round();
     bool any = false;
     for (auto& l : live) any = any || (bool)l;
     if (!any) {
-      if (waiting.empty() && slots.empty()) return;
+      if (waiting.empty() && slots.empty() && !had_embed) return;
       continue;
     }
     if (!guarded([&] { eng_->decode_steps(1); })) continue;

@@ -71,6 +71,8 @@ class Session {
   std::vector<int32_t> encode(const std::string& text) const;
   // text as a bare token stream (no BOS), and the BOS id the vocabulary puts in front (-1: none)
   std::vector<int32_t> encode_raw(const std::string& text) const;
+  // text of an embedding request: encode(), plus EOS when the file sets tokenizer.ggml.add_eos_token
+  std::vector<int32_t> encode_embedding(const std::string& text) const;
   int bos() const;
   std::string piece(int32_t id) const;
   bool is_eog(int32_t id) const;
@@ -82,9 +84,20 @@ class Session {
   // for up to `free` new requests (non-blocking), which are admitted into idle sequence slots while
   // the running ones keep decoding; `done(request, result)` fires as each request finishes (EOG,
   // n_predict, cancellation, context).  Returns when nothing runs and next() has nothing.
+  // An embedding job (Served::embed set; req / done unused): its prompts are embedded between decode
+  // rounds in slots no request holds, as many per round as slots and KV pages are free (it waits
+  // while there are none), the running requests untouched.  done fires once, with one result per
+  // prompt or with the error that ended the job.
+  struct EmbedJob {
+    std::vector<std::vector<int32_t>> prompts;
+    int pooling = -1;        // POOL_NONE .. POOL_LAST, -1: the model's default (Engine::default_pooling)
+    bool normalize = true;
+    std::function<void(std::vector<Engine::EmbedResult>& out, const std::string& error)> done;
+  };
   struct Served {
     GenRequest req;
     std::function<void(GenResult&)> done;
+    std::shared_ptr<EmbedJob> embed;
   };
   void serve(const std::function<std::vector<Served>(int free)>& next);
   // llama.cpp-style summary lines (prompt eval / eval / total)

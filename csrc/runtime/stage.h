@@ -61,7 +61,15 @@ struct PrefillSeg {
                         // log-probability of each row's target token (set_score_targets -> copy_scores)
   bool verify = false;  // speculative verification chunk: the last stage scores EVERY row (greedy
                         // argmax after each row -> verify_tokens), nothing is kept for prefill_finish
+  bool embed = false;   // embedding chunk (every segment from position 0 of its prompt on, no prefix reuse): the
+                        // last stage norms and pools the rows by set_embed (-> copy_embeddings /
+                        // copy_token_embeddings); no LM head, nothing kept for prefill_finish, no sampler state
 };
+
+inline const char* pooling_name(int p) {
+  static const char* n[] = {"none", "mean", "cls", "last", "rank"};
+  return p >= 0 && p <= 4 ? n[p] : "?";
+}
 
 // throws naming the field a record is out of range in
 inline void check_row_sampling(const RowSampling& r, int vocab) {
@@ -125,6 +133,18 @@ class Stage {
   // target logprobs (and top_n ids / logprobs, [n][top_n]) -> host
   virtual void set_score_targets(int mb, const int32_t* host, int n, int top_n) = 0;
   virtual void copy_scores(int mb, int n, float* target_lp, int32_t* top_id, float* top_lp) = 0;
+  // Embeddings, last stage.  set_embed: how the following embed chunks pool (POOL_NONE .. POOL_LAST of
+  // kernels_api.h; throws on anything else, naming it) and whether vectors are L2-normalised.  After
+  // the chunks that end the prompts of `slots`: their vectors, [slots.size()][d] -> host.  POOL_NONE:
+  // after each chunk of micro-batch mb, its n_rows rows' vectors [n_rows][d] -> host.
+  virtual void set_embed(int pooling, bool normalize) {
+    if (pooling < POOL_NONE || pooling > POOL_LAST)
+      throw std::runtime_error(std::string("embed: pooling \"") + pooling_name(pooling) + "\" (" + std::to_string(pooling) +
+                               ") is not supported (none, mean, cls, last)");
+    embed_pool_ = pooling; embed_norm_ = normalize;
+  }
+  virtual void copy_embeddings(const std::vector<int>& slots, float* host) = 0;
+  virtual void copy_token_embeddings(int mb, int n_rows, float* host) = 0;
   virtual const float* logits_ptr() const = 0;   // last computed logits (device/host)
   virtual int logits_ld() const = 0;
   virtual size_t weight_bytes() const = 0;
@@ -177,6 +197,8 @@ class Stage {
   int pen_last_n_ = 64;
   int n_probs_ = 0;
   float pen_repeat_ = 1.f, pen_freq_ = 0.f, pen_presence_ = 0.f;
+  int embed_pool_ = POOL_LAST;
+  bool embed_norm_ = true;
 };
 
 }  // namespace mp

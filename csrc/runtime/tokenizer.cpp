@@ -193,6 +193,7 @@ Tokenizer Tokenizer::from_gguf(const GgufFile& f) {
   const std::string pre = f.get_str("tokenizer.ggml.pre", "llama-bpe");
   t.max_digits_ = pre == "qwen2" ? 1 : 3;   // qwen2 splits numbers into single digits
   t.add_bos_default_ = f.get_bool("tokenizer.ggml.add_bos_token", pre != "qwen2");
+  t.add_eos_default_ = f.get_bool("tokenizer.ggml.add_eos_token", false);
   for (size_t i = 0; i < V; ++i)
     if ((t.types_[i] == 3 || t.types_[i] == 4) && !t.tokens_[i].empty()) t.specials_.push_back({t.tokens_[i], (int32_t)i});
   std::sort(t.specials_.begin(), t.specials_.end(),

@@ -28,6 +28,15 @@ class Tokenizer {
   int n_vocab() const { return (int)tokens_.size(); }
   int bos() const { return bos_; }
   bool add_bos_default() const { return add_bos_default_; }
+  // tokenizer.ggml.add_eos_token (default false): the embedding text paths append eos() when it is set
+  // (Qwen3-Embedding files pool the EOS row); encode() and the generation paths never do
+  bool add_eos_default() const { return add_eos_default_; }
+  // encode() for an embedding request: BOS by the file's default, EOS appended when the file asks
+  std::vector<int32_t> encode_for_embedding(const std::string& text) const {
+    std::vector<int32_t> t = encode(text, add_bos_default_);
+    if (add_eos_default_ && eos_ >= 0) t.push_back(eos_);
+    return t;
+  }
   int eos() const { return eos_; }
   int eot() const { return eot_; }
   Kind kind() const { return kind_; }
@@ -51,6 +60,7 @@ class Tokenizer {
   int32_t bos_ = -1, eos_ = -1, eot_ = -1, unk_ = 0;
   bool add_space_prefix_ = true;
   bool add_bos_default_ = true;
+  bool add_eos_default_ = false;
   int32_t byte_tok_[256];
 };
 

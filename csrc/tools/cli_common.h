@@ -26,6 +26,9 @@ struct CliOptions {
   bool echo_prompt = true;
   bool bench = false;
   bool perplexity = false;    // --perplexity: llama.cpp's perplexity procedure over the -f file
+  bool embedding = false;     // --embedding: print one embedding per prompt (-p TEXT, or -f FILE: one per line)
+  std::string pooling;        // --pooling none|mean|cls|last ("" = the model's pooling_type, else last)
+  int embd_normalize = 2;     // --embd-normalize: 2 = L2 (default), -1 = none
   int bench_prompt = 128, bench_warmup = 3, bench_steps = 20;
   std::string trace;
   std::string rpc;            // --rpc host:port,... (without --world): stage workers to attach to (rpc.h)
@@ -100,6 +103,13 @@ inline void print_common_usage(FILE* f) {
           "                            row_sampling; the slots start at the values above)\n"
           "  --perplexity -f FILE      perplexity of a text file, llama.cpp's procedure: windows of -c tokens,\n"
           "                            the second half of each window counts\n"
+          "  --embedding               print embeddings instead of generating: one per prompt (-p TEXT, or -f FILE\n"
+          "                            with one prompt per line), as `embedding N: v0 v1 ...`; EOS is appended\n"
+          "                            when the model sets tokenizer.ggml.add_eos_token\n"
+          "  --pooling none|mean|cls|last   how a prompt's rows become its vector (default: the model's\n"
+          "                            pooling_type, else last: in a causal model only the last row has seen the\n"
+          "                            whole prompt); none prints one vector per token\n"
+          "  --embd-normalize N        2: scale each vector to unit L2 length (default); -1: leave it as it is\n"
           "  --draft-max K             speculative decoding by prompt lookup: up to K drafted tokens per\n"
           "                            verify round (greedy; --lookup-ngram N, default 3)\n"
           "placement / pipeline:\n"
@@ -195,6 +205,17 @@ inline CliOptions parse_cli(int argc, char** argv,
     else if (a == "--no-display-prompt") o.echo_prompt = false;
     else if (a == "--bench") o.bench = true;
     else if (a == "--perplexity") o.perplexity = true;
+    else if (a == "--embedding" || a == "--embeddings") o.embedding = true;
+    else if (a == "--pooling") {
+      o.pooling = val();
+      if (o.pooling != "none" && o.pooling != "mean" && o.pooling != "cls" && o.pooling != "last")
+        throw std::runtime_error("--pooling " + o.pooling + ": must be none, mean, cls or last" +
+                                 (o.pooling == "rank" ? " (rank pooling is not supported)" : ""));
+    }
+    else if (a == "--embd-normalize") {
+      o.embd_normalize = std::atoi(val().c_str());
+      if (o.embd_normalize != 2 && o.embd_normalize != -1) throw std::runtime_error("--embd-normalize must be 2 (L2) or -1 (none)");
+    }
     else if (a == "--n-probs") e["n_probs"] = std::atoi(val().c_str());
     else if (a == "--row-sampling") e["row_sampling"] = true;
     else if (a == "--bench-prompt") o.bench_prompt = std::atoi(val().c_str());

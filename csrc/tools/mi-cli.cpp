@@ -5,6 +5,7 @@
 //   mi-cli -m model.gguf -p "Once upon a time" -n 200 -c 2048 -ngl 99 --stages 2 --verbose
 //   mi-cli --synthetic llama3-70b --ftype Q4_K --bench --mb-size 16
 //   mi-cli -m m.gguf --world 2 --rank 0 --next 10.0.0.2      (one process per stage, TCP ring)
+//   mi-cli -m embed.gguf --embedding -p "a query" --pooling last     (`embedding 0: v0 v1 ...`)
 //   mi-cli -m m.gguf --daemon      (JSON-lines server on stdin/stdout for the orchestrator)
 //   mi-cli --rpc-server 50052      (long-lived stage worker; a client attaches with --rpc host:port,..)
 #include <cstdio>
@@ -66,6 +67,45 @@ static int run_perplexity(Engine& eng, Session& s, const std::string& text) {
   MP_LOGI("perplexity: %.1f ms, %ld positions counted", session_now_ms() - t0, est.count);
   printf("Final estimate: PPL = %.4lf +/- %.5lf\n", est.ppl(), est.err());
   fflush(stdout);
+  return 0;
+}
+
+// --embedding: one prompt per line of the -p / -f text; `embedding N: v0 v1 ...` per vector (with
+// --pooling none one per token, numbered through), values as %.9g so that they read back exactly
+static int run_embedding(Engine& eng, Session& s, const CliOptions& o) {
+  std::vector<std::vector<int32_t>> prompts;
+  std::stringstream ss(o.prompt);
+  for (std::string line; std::getline(ss, line);) {
+    if (!line.empty() && line.back() == '\r') line.pop_back();
+    if (!line.empty()) prompts.push_back(s.encode_embedding(line));
+  }
+  if (prompts.empty()) throw std::runtime_error("--embedding: no prompt (-p TEXT, or -f FILE with one prompt per line)");
+  const int pooling = Engine::pooling_from_name(o.pooling);
+  const size_t d = (size_t)eng.model().d_model;
+  const double t0 = session_now_ms();
+  size_t n_tok = 0;
+  int n = 0;
+  for (size_t g = 0; g < prompts.size();) {
+    const std::vector<int> idle = eng.idle_slots();
+    const size_t take = std::min(idle.size(), prompts.size() - g);
+    if (take == 0) throw std::runtime_error("--embedding: no idle slot");
+    std::vector<Engine::EmbedResult> res;
+    eng.embed(std::vector<int>(idle.begin(), idle.begin() + take),
+              std::vector<std::vector<int32_t>>(prompts.begin() + g, prompts.begin() + g + take), pooling, o.embd_normalize == 2,
+              &res);
+    if (eng.owns_last())
+      for (const auto& r : res)
+        for (int row = 0; row < r.n_rows; ++row) {
+          printf("embedding %d:", n++);
+          for (size_t i = 0; i < d; ++i) printf(" %.9g", (double)r.v[(size_t)row * d + i]);
+          printf("\n");
+        }
+    for (size_t k = g; k < g + take; ++k) n_tok += prompts[k].size();
+    g += take;
+  }
+  fflush(stdout);
+  MP_LOGI("embedding: %zu prompts, %zu tokens, pooling %s, %.1f ms", prompts.size(), n_tok,
+          pooling_name(pooling < 0 ? eng.default_pooling() : pooling), session_now_ms() - t0);
   return 0;
 }
 
@@ -176,6 +216,7 @@ int main(int argc, char** argv) {
     Session s(eng, o.eng.get_str("gguf", ""));
     if (daemon) return run_daemon(s);
     if (o.perplexity) return run_perplexity(eng, s, o.prompt);
+    if (o.embedding) return run_embedding(eng, s, o);
     if (!state_load.empty()) {
       // resume: continue sequence 0 of the checkpoint token by token
       eng.load_state(state_load);

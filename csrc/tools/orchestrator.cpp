@@ -9,6 +9,11 @@
 //                     client disconnects (the reference lets the child run on, main.rs:77,91)
 //   POST /completion  {"prompt", "n_predict"} -> {"content", "response", "tokens_predicted", ...}
 //                     (the PDF's proxy design, p.9-10, llama-server style)
+//   POST /embedding   {"content": str | [str], "pooling"?, "embd_normalize"?: 2 | -1} -> [{"index", "embedding"}]
+//   POST /v1/embeddings  {"input": str | [str] | [int] | [[int]], "encoding_format"?: "float"} ->
+//                     {"object": "list", "data": [{"object": "embedding", "index", "embedding"}], "model",
+//                     "usage": {"prompt_tokens", "total_tokens"}}; queued like a completion and run between
+//                     decode rounds in idle slots (Engine::embed: output norm + pooling, no LM head)
 //   GET  /metrics     Prometheus text (requests, tokens, tok/s, p50/p90/p99 per token, stage
 //                     heartbeats, link bytes)
 //   GET  /health      engine health JSON
@@ -84,6 +89,16 @@ struct Job {
   bool done = false;
   std::atomic<bool> cancelled{false};
   GenResult result;
+  // an embedding request (/embedding, /v1/embeddings): its inputs as texts or token lists, queued like
+  // a completion; the vectors (or the error that ended it) when done
+  bool is_embed = false;
+  std::vector<std::string> embed_texts;
+  std::vector<std::vector<int32_t>> embed_tokens;
+  int embed_pooling = -1;
+  bool embed_normalize = true;
+  std::vector<Engine::EmbedResult> embed_out;
+  int embed_n_tokens = 0;
+  std::string embed_err;
   void push(Event e) {
     {
       std::lock_guard<std::mutex> l(mu);
@@ -103,6 +118,7 @@ struct Job {
 struct Metrics {
   std::mutex mu;
   uint64_t requests = 0, completed = 0, cancelled = 0, errors = 0, prompt_tokens = 0, gen_tokens = 0;
+  uint64_t embed_requests = 0, embed_tokens = 0;
   double last_decode_tok_s = 0, last_prefill_tok_s = 0;
   std::vector<double> token_ms;   // recent per-token latencies
   void add_latency(double ms) {
@@ -272,6 +288,27 @@ void restart_if_failed(Server& S, ModelSlot* slot) {
   }
 }
 
+// the token lists of an embedding job: given as ids, or its texts through the model's tokenizer
+// (EOS appended when the file sets tokenizer.ggml.add_eos_token)
+std::vector<std::vector<int32_t>> embed_prompts(const Job& j, const Session& sess) {
+  std::vector<std::vector<int32_t>> p = j.embed_tokens;
+  for (const std::string& t : j.embed_texts) p.push_back(sess.encode_embedding(t));
+  return p;
+}
+
+void record_embedding(Server& S, Job& j, std::vector<Engine::EmbedResult>& out, const std::string& err, int n_tokens) {
+  j.embed_out = std::move(out);
+  j.embed_err = err;
+  j.embed_n_tokens = n_tokens;
+  std::lock_guard<std::mutex> l(S.metrics.mu);
+  if (err.empty()) {
+    S.metrics.completed++;
+    S.metrics.embed_tokens += (uint64_t)n_tokens;
+  } else {
+    S.metrics.errors++;
+  }
+}
+
 // Continuous batching (default): requests for `model` are admitted into free sequence slots between
 // decode rounds while the running ones keep generating; each finishes (and frees its slot) on its own.
 void serve_model(Server& S, ModelSlot* slot, const std::string& model) {
@@ -304,6 +341,25 @@ void serve_model(Server& S, ModelSlot* slot, const std::string& model) {
       j->push({"log", "orchestrator: request accepted (continuous batching, " + std::to_string(free) + " free slots)\n"});
       for (auto& sl : S.startup_logs) j->push({"log", sl});
       Session::Served sv;
+      if (j->is_embed) {
+        std::shared_ptr<Job> keep = j;
+        sv.embed = std::make_shared<Session::EmbedJob>();
+        sv.embed->prompts = embed_prompts(*j, *slot->sess);
+        sv.embed->pooling = j->embed_pooling;
+        sv.embed->normalize = j->embed_normalize;
+        int n_tok = 0;
+        for (auto& pr : sv.embed->prompts) n_tok += (int)pr.size();
+        sv.embed->done = [&S, keep, n_tok](std::vector<Engine::EmbedResult>& out, const std::string& err) {
+          record_embedding(S, *keep, out, err, n_tok);
+          {
+            std::lock_guard<std::mutex> l(S.active_mu);
+            S.active.erase(std::remove(S.active.begin(), S.active.end(), keep), S.active.end());
+          }
+          keep->finish();
+        };
+        out.push_back(std::move(sv));
+        continue;
+      }
       sv.req.prompt = j->prompt;
       sv.req.n_predict = j->n_predict;
       sv.req.has_sampling = j->has_sampling; sv.req.has_seed = j->has_seed; sv.req.sampling = j->sampling;
@@ -365,6 +421,7 @@ void serve_model(Server& S, ModelSlot* slot, const std::string& model) {
       S.metrics.errors += left.size();
     }
     for (auto& j : left) {
+      j->embed_err = e.what();   // (read by an embedding request; a completion reads the log line)
       j->push({"log", std::string("error: ") + e.what() + "\n"});
       j->finish();
     }
@@ -409,6 +466,7 @@ void generation_loop(Server& S) {
           j = S.pending.front();
           S.pending.pop_front();
         }
+        j->embed_err = e.what();   // (read by an embedding request; a completion reads the log line)
         j->push({"log", std::string("error: ") + e.what() + "\n"});
         j->finish();
         continue;
@@ -429,6 +487,36 @@ void generation_loop(Server& S) {
           ++it;
         }
       }
+    }
+    // embedding requests of the batch run first, on the idle engine (one batch per engine run: nothing
+    // is generating between batches)
+    for (auto it = batch.begin(); it != batch.end();) {
+      if (!(*it)->is_embed) { ++it; continue; }
+      Job& j = **it;
+      std::vector<Engine::EmbedResult> out;
+      std::string err;
+      int n_tok = 0;
+      try {
+        if (S.mock) throw std::runtime_error("the mock engine has no embeddings");
+        Engine& e = *slot->eng;
+        for (int sl = 0; sl < cap; ++sl) e.release(sl);
+        const auto prompts = embed_prompts(j, *slot->sess);
+        for (size_t g = 0; g < prompts.size(); g += (size_t)cap) {
+          const size_t take = std::min((size_t)cap, prompts.size() - g);
+          std::vector<int> sl(take);
+          for (size_t k = 0; k < take; ++k) sl[k] = (int)k;
+          std::vector<Engine::EmbedResult> r;
+          e.embed(sl, std::vector<std::vector<int32_t>>(prompts.begin() + g, prompts.begin() + g + take), j.embed_pooling,
+                  j.embed_normalize, &r);
+          for (auto& v : r) out.push_back(std::move(v));
+        }
+        for (auto& pr : prompts) n_tok += (int)pr.size();
+      } catch (const std::exception& ex) {
+        err = ex.what();
+      }
+      record_embedding(S, j, out, err, n_tok);
+      j.finish();
+      it = batch.erase(it);
     }
     if (batch.empty()) continue;
     {
@@ -955,6 +1043,129 @@ void handle_completion(Server& S, int fd, const Request& r) {
   respond(fd, 200, "application/json", o.dump());
 }
 
+// POST /embedding (llama.cpp server: {"content": str | [str]} -> [{"index", "embedding"}]) and
+// POST /v1/embeddings (OpenAI: {"input": str | [str] | [int] | [[int]], "encoding_format": "float"} ->
+// {"object": "list", "data": [{"object": "embedding", "index", "embedding"}], "model", "usage"}).
+// Both take "pooling" (none | mean | cls | last; default: the model's pooling_type, else last) and
+// "embd_normalize" (2: unit L2 length, the default; -1: as computed).  The request waits in the same
+// queue as completions and runs between decode rounds (Session::serve).
+void handle_embedding(Server& S, int fd, const Request& r, bool openai) {
+  if (lower(r.header("content-type")).find("application/json") == std::string::npos)
+    return respond_text(fd, 415, "Expected request with `Content-Type: application/json`");
+  Json body;
+  try {
+    body = Json::parse(r.body);
+  } catch (const std::exception& e) {
+    return respond_text(fd, 400, std::string("Failed to parse the request body as JSON: ") + e.what());
+  }
+  const char* key = openai ? "input" : (body.is_obj() && body.has("content") ? "content" : "input");
+  if (!body.is_obj() || !body.has(key))
+    return respond_text(fd, 422, std::string("Failed to deserialize the JSON body into the target type: missing field `") +
+                                     (openai ? "input" : "content") + "`");
+  if (S.mock || !S.spawn_cli.empty()) return respond_text(fd, 501, "embeddings need a model in this process (not --mock / --spawn-cli)");
+  auto job = std::make_shared<Job>();
+  job->is_embed = true;
+  // str | [str] | [int] | [[int]]
+  const Json& in = body[key];
+  auto ints = [](const Json& a, std::vector<int32_t>* t) {
+    for (const Json& x : a.arr()) {
+      if (!x.is_num() || x.num() != (double)(int32_t)x.num()) return false;
+      t->push_back((int32_t)x.num());
+    }
+    return true;
+  };
+  bool ok = true;
+  if (in.is_str()) job->embed_texts.push_back(in.str());
+  else if (in.is_arr() && !in.arr().empty() && in.arr()[0].is_num()) {
+    job->embed_tokens.emplace_back();
+    ok = ints(in, &job->embed_tokens.back());
+  } else if (in.is_arr() && !in.arr().empty()) {
+    for (const Json& e : in.arr()) {
+      if (e.is_str() && job->embed_tokens.empty()) job->embed_texts.push_back(e.str());
+      else if (e.is_arr() && !e.arr().empty() && job->embed_texts.empty()) {
+        job->embed_tokens.emplace_back();
+        ok = ok && ints(e, &job->embed_tokens.back());
+      } else ok = false;
+    }
+  } else ok = false;
+  for (const std::string& t : job->embed_texts) ok = ok && !t.empty();
+  if (!ok)
+    return respond_text(fd, 400, std::string("`") + key + "` must be a non-empty string, a list of them, a list of token ids or a "
+                                     "list of such lists");
+  if (body.has("embd_normalize") && !body["embd_normalize"].is_null()) {
+    const Json& n = body["embd_normalize"];
+    if (!n.is_num() || (n.num() != 2 && n.num() != -1))
+      return respond_text(fd, 422, "embd_normalize must be 2 (unit L2 length) or -1 (none)");
+    job->embed_normalize = n.num() == 2;
+  }
+  if (body.has("pooling") && !body["pooling"].is_null()) {
+    try {
+      if (!body["pooling"].is_str()) throw std::runtime_error("pooling must be a string (none, mean, cls, last)");
+      job->embed_pooling = Engine::pooling_from_name(body["pooling"].str());
+    } catch (const std::exception& e) {
+      return respond_text(fd, 400, e.what());
+    }
+    if (job->embed_pooling == POOL_RANK) return respond_text(fd, 400, "pooling \"rank\" (reranking) is not supported");
+  }
+  if (openai && job->embed_pooling == POOL_NONE)
+    return respond_text(fd, 400, "pooling \"none\" is not supported on /v1/embeddings (one vector per input); use /embedding");
+  if (openai && body.has("encoding_format") && !body["encoding_format"].is_null() &&
+      (!body["encoding_format"].is_str() || body["encoding_format"].str() != "float"))
+    return respond_text(fd, 400, "encoding_format must be \"float\" (base64 is not supported)");
+  std::string model = body.get_str("model", "");
+  const std::string model_name = model;
+  if (!known_model(S, fd, &model)) return;
+  job->model = model;
+  {
+    std::lock_guard<std::mutex> l(S.metrics.mu);
+    S.metrics.requests++;
+    S.metrics.embed_requests++;
+  }
+  {
+    std::lock_guard<std::mutex> l(S.jobs_mu);
+    job->enqueued_ms = now_ms();
+    S.pending.push_back(job);
+  }
+  S.jobs_cv.notify_all();
+  {
+    std::unique_lock<std::mutex> l(job->mu);
+    job->cv.wait(l, [&] { return job->done; });
+  }
+  if (!job->embed_err.empty()) return respond_text(fd, 400, job->embed_err);
+  size_t d = 0;
+  for (auto& e : job->embed_out) d = e.n_rows > 0 ? e.v.size() / (size_t)e.n_rows : d;
+  Json data = Json::array();
+  for (size_t i = 0; i < job->embed_out.size(); ++i) {
+    const Engine::EmbedResult& e = job->embed_out[i];
+    auto row = [&](int t) {
+      Json v = Json::array();
+      for (size_t c = 0; c < d; ++c) v.push(Json((double)e.v[(size_t)t * d + c]));
+      return v;
+    };
+    Json o = Json::object();
+    if (openai) o["object"] = "embedding";
+    o["index"] = (int)i;
+    if (job->embed_pooling == POOL_NONE) {
+      Json rows = Json::array();
+      for (int t = 0; t < e.n_rows; ++t) rows.push(row(t));
+      o["embedding"] = rows;
+    } else {
+      o["embedding"] = row(0);
+    }
+    data.push(o);
+  }
+  if (!openai) return respond(fd, 200, "application/json", data.dump());
+  Json o = Json::object();
+  o["object"] = "list";
+  o["data"] = data;
+  o["model"] = model_name.empty() && !S.models.empty() ? S.models[0]->name : model_name;
+  Json u = Json::object();
+  u["prompt_tokens"] = job->embed_n_tokens;
+  u["total_tokens"] = job->embed_n_tokens;
+  o["usage"] = u;
+  respond(fd, 200, "application/json", o.dump());
+}
+
 void handle_metrics(Server& S, int fd) {
   std::string m;
   char b[512];
@@ -970,6 +1181,11 @@ void handle_metrics(Server& S, int fd) {
              "# TYPE mipipe_generated_tokens_total counter\nmipipe_generated_tokens_total %llu\n",
              (unsigned long long)M.requests, (unsigned long long)M.completed, (unsigned long long)M.cancelled,
              (unsigned long long)M.errors, (unsigned long long)M.prompt_tokens, (unsigned long long)M.gen_tokens);
+    m += b;
+    snprintf(b, sizeof(b),
+             "# TYPE mipipe_embedding_requests_total counter\nmipipe_embedding_requests_total %llu\n"
+             "# TYPE mipipe_embedding_tokens_total counter\nmipipe_embedding_tokens_total %llu\n",
+             (unsigned long long)M.embed_requests, (unsigned long long)M.embed_tokens);
     m += b;
     snprintf(b, sizeof(b),
              "# TYPE mipipe_decode_tokens_per_second gauge\nmipipe_decode_tokens_per_second %.3f\n"
@@ -1027,6 +1243,9 @@ void handle_conn(Server& S, int fd, std::string peer) {
       } else if (r.path == "/completion") {
         if (r.method != "POST") respond(fd, 405, "text/plain; charset=utf-8", "Method Not Allowed", "Allow: POST\r\n");
         else if (authorized(S, fd, r)) handle_completion(S, fd, r);
+      } else if (r.path == "/embedding" || r.path == "/embeddings" || r.path == "/v1/embeddings") {
+        if (r.method != "POST") respond(fd, 405, "text/plain; charset=utf-8", "Method Not Allowed", "Allow: POST\r\n");
+        else if (authorized(S, fd, r)) handle_embedding(S, fd, r, r.path == "/v1/embeddings");
       } else if (r.path == "/metrics" && r.method == "GET") {
         handle_metrics(S, fd);
       } else if (r.path == "/health" && r.method == "GET") {

@@ -123,6 +123,7 @@ _SIGS = {
     "mp_tok_open": ([c_char_p], c_void_p),
     "mp_tok_close": ([c_void_p], None),
     "mp_tok_add_bos": ([c_void_p], c_int),
+    "mp_tok_add_eos": ([c_void_p], c_int),
     "mp_tok_encode": ([c_void_p, c_char_p, c_int, c_int, c_void_p, c_int], c_int),
     "mp_tok_piece": ([c_void_p, c_int, c_void_p, c_int], c_int),
     "mp_tok_decode": ([c_void_p, c_void_p, c_int, c_void_p, c_int], c_int),
@@ -150,7 +151,10 @@ _SIGS = {
     "mp_engine_tokens": ([c_void_p, c_void_p, c_int, c_int], c_int),
     "mp_engine_logprobs": ([c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int], c_int),
     "mp_engine_score": ([c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p], c_int),
-    "mp_ppl_windows": ([ctypes.c_long, c_int], ctypes.c_long),
+    "mp_engine_embed": ([c_void_p, c_char_p, c_void_p, ctypes.c_long], ctypes.c_long),
+    "mp_op_pool_embed": ([c_void_p, c_int, c_void_p, c_int, c_float, c_void_p, c_int, c_void_p, c_int, c_int, c_int,
+                          c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p], c_int),
+    "mp_ppl_windows":([ctypes.c_long, c_int], ctypes.c_long),
     "mp_ppl_estimate": ([c_void_p, c_int, c_int, c_void_p], c_int),
     "mp_engine_logits": ([c_void_p, c_int, c_void_p, c_int], c_int),
     "mp_rccl_unique_id": ([c_void_p], c_int),

@@ -187,6 +187,43 @@ class Engine:
                 o += n
         return res
 
+    def idle_slots(self):
+        """Sequence slots no running sequence holds (all of them before start())."""
+        j = N.jcall(N.lib().mp_engine_info, self._h, what="engine info")
+        return list(j["idle_slots"])
+
+    def embed(self, prompts, pooling=None, normalize: bool = True, slots=None):
+        """Embeddings of token-id prompts: a list of float32 arrays, [d_model] each, or [len][d_model]
+        with pooling "none" (one vector per token).  pooling: "none" | "mean" | "cls" | "last", or
+        None for the model's own (its GGUF pooling_type when that is mean, cls or last, otherwise
+        "last": in a causal model only the last row has seen the whole prompt).  normalize scales each
+        vector to unit L2 length (the zero vector stays zero).  The output RMSNorm is applied, the LM
+        head is not run.  Legal before start() and between decode() calls: the prompts run in idle
+        slots (`slots`, or as many idle ones as needed, in groups when there are more prompts than
+        idle slots), running sequences are untouched and the slots are idle again afterwards."""
+        d = self.info["model"]["d_model"]
+        prompts = [list(map(int, p)) for p in prompts]
+        res = []
+        group = len(slots) if slots is not None else max(len(self.idle_slots()), 1)
+        for g in range(0, len(prompts), group):
+            grp = prompts[g:g + group]
+            rq = {"prompts": grp, "normalize": bool(normalize)}
+            if pooling is not None:
+                rq["pooling"] = pooling
+            if slots is not None:
+                rq["slots"] = [int(s) for s in slots][:len(grp)]
+            rows = [len(p) if pooling == "none" or pooling == 0 else 1 for p in grp]
+            out = np.zeros(max(sum(rows), 1) * d, np.float32)
+            n = N.check(N.lib().mp_engine_embed(self._h, N.cstr(json.dumps(rq)), out.ctypes.data, out.size), "embed")
+            if n != sum(rows) * d:
+                raise RuntimeError(f"embed: {n} floats returned, {sum(rows) * d} expected")
+            o = 0
+            for r in rows:
+                v = out[o:o + r * d].copy()
+                res.append(v.reshape(r, d) if pooling == "none" or pooling == 0 else v)
+                o += r * d
+        return res
+
     def bench(self, prompt_len: int, warmup: int, steps: int):
         return N.jcall(N.lib().mp_engine_bench, self._h, prompt_len, warmup, steps, what="bench")
 

@@ -38,6 +38,10 @@ class LlamaConfig:
     # experts then puts nearly all weight on one of them, and a wrong 2nd .. k-th expert would barely
     # move the output.  1 / sqrt(d_model) gives logits of about unit standard deviation.
     router_std: float = 0.5
+    # <arch>.pooling_type of an embedding model (llama.cpp's ids: 0 none, 1 mean, 2 cls, 3 last, 4 rank);
+    # -1 = the key is not written.  Engine.embed pools by it when it is 1..3, by `last` otherwise.
+    pooling_type: int = -1
+    add_eos: bool = False       # tokenizer.ggml.add_eos_token (Qwen3-Embedding files set it)
 
     @property
     def hd(self) -> int:

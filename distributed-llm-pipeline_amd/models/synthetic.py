@@ -108,6 +108,8 @@ def write_synthetic_gguf(path: str, cfg: LlamaConfig, ftype: str = "Q4_K_M", see
     if cfg.n_expert:
         w.add(f"{arch}.expert_count", cfg.n_expert, U32)
         w.add(f"{arch}.expert_used_count", cfg.n_expert_used, U32)
+    if cfg.pooling_type >= 0:
+        w.add(f"{arch}.pooling_type", cfg.pooling_type, U32)
     if with_tokenizer:
         tokenizer_data.add_tokenizer_kv(w, cfg)
 

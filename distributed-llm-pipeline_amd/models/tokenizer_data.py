@@ -155,3 +155,5 @@ def add_tokenizer_kv(w, cfg):
         w.add("tokenizer.ggml.unknown_token_id", 0, U32)
         w.add("tokenizer.ggml.add_bos_token", True)
         w.add("tokenizer.ggml.add_space_prefix", True)
+    if getattr(cfg, "add_eos", False):
+        w.add("tokenizer.ggml.add_eos_token", True)

@@ -327,6 +327,25 @@ def rmsnorm_acc(x, ldx, w, d, eps, out, ldo, M, zero=None, zero_n=0, part=None, 
             "rmsnorm_acc")
 
 
+POOL_NONE, POOL_MEAN, POOL_CLS, POOL_LAST = 0, 1, 2, 3
+POOL_BLOCK_ROWS = 32
+
+
+def pool_embed(x, w, eps, segs, pooling, normalize, n_slots, h=None, part=None, pool_acc=None, emb=None) -> None:
+    """launch_pool_embed (pool.hip): output RMSNorm of the chunk's rows x f32 [T][d] with weights w, then
+    pooling per prompt.  segs: one (row0, T, slot, p0, prompt_len, ends_prompt) per segment, tiling the
+    rows in order.  none: h [T][d] gets every row's vector; mean: h [T][d] scratch, part [>= blocks][d]
+    scratch (32-row blocks per segment), pool_acc [n_slots][d] the running sums, emb [n_slots][d] the
+    result of prompt-ending segments; cls / last: emb only.  Raises on a shape the kernel refuses."""
+    T, d = x.shape
+    tab = torch.tensor([list(map(int, s)) for s in segs], dtype=torch.int32).reshape(-1, 6).contiguous()
+    seg_tab = torch.empty(max(tab.shape[0], 1) * 6, dtype=torch.int32, device=x.device)
+    N.check(N.lib().mp_op_pool_embed(_ptr(x), x.stride(0), _ptr(w), d, float(eps), tab.data_ptr(), tab.shape[0],
+                                     _ptr(seg_tab), T, int(pooling), int(bool(normalize)), int(n_slots), _ptr(h), _ptr(part),
+                                     0 if part is None else part.shape[0], _ptr(pool_acc), _ptr(emb), _stream()),
+            "pool_embed")
+
+
 def splitk_reduce(part, nsplit, ss, ldp, M, n, y, ldy, init=False, bias=None) -> None:
     """y[m][j] (+)= sum_s part[s * ss + m * ldp + j] in split order; init: y starts from bias[j] or 0."""
     N.check(N.lib().mp_op_splitk_reduce(_ptr(part), nsplit, ss, ldp, M, n, _ptr(y), ldy, int(init), _ptr(bias),

@@ -22,6 +22,15 @@ class Tokenizer:
         self.n_vocab, self.bos, self.eos, self.eot = (int(v) for v in info)
         self.add_bos = bool(N.check(L.mp_tok_add_bos(self._h), "tokenizer add_bos"))   # BOS in front of a prompt by default
 
+        # tokenizer.ggml.add_eos_token: the embedding text paths (mi-cli --embedding, the server) append EOS
+        self.add_eos = bool(N.check(L.mp_tok_add_eos(self._h), "tokenizer add_eos"))
+
+    def encode_for_embedding(self, text: str) -> list[int]:
+        """The tokens an embedding request of `text` runs on: BOS by the file's default, EOS appended
+        when the file sets tokenizer.ggml.add_eos_token."""
+        t = self.encode(text, add_bos=self.add_bos)
+        return t + [self.eos] if self.add_eos and self.eos >= 0 else t
+
     def close(self):
         if getattr(self, "_h", None):
             N.lib().mp_tok_close(self._h)
