@@ -18,6 +18,7 @@
 #include "probe.h"
 #include "model.h"
 #include "gguf.h"
+#include "grammar.h"
 #include "hip_stage.h"
 #include "json.h"
 #include "kernels_api.h"
@@ -811,6 +812,16 @@ int mp_sample_rows(const void* logits, int ld, int n, int M, const void* rows, v
   return 0;
   API_CATCH(-1)
 }
+int mp_op_row_mask(void* logits, int ld, int n, int M, const void* bits, int ldw, const void* on, void* stream) {
+  API_TRY
+  RowMaskParams p{};
+  p.logits = (float*)logits; p.ld = ld; p.n = n; p.M = M;
+  p.bits = (const uint32_t*)bits; p.ldw = ldw; p.on = (const int32_t*)on;
+  launch_row_mask(p, (hipStream_t)stream);
+  HIP_OK(hipGetLastError());
+  return 0;
+  API_CATCH(-1)
+}
 
 // ------------------------------------------------------------------ tokenizer
 void* mp_tok_open(const char* gguf_path) {
@@ -870,6 +881,82 @@ const char* mp_tok_pretokenize(const char* text, int max_digits) {
   API_TRY
   g_str.clear();
   for (auto& p : Tokenizer::llama3_pretokenize(text, max_digits > 0 ? max_digits : 3)) { g_str += p; g_str += '\x1f'; }
+  return g_str.c_str();
+  API_CATCH(nullptr)
+}
+
+// ------------------------------------------------------------------ grammars
+// A grammar handle is a parsed grammar plus (optionally) the vocabulary of a tokenizer handle; a state
+// handle is one GrammarState.  Calls returning int: < 0 = error (mp_last_error), else the answer.
+namespace {
+struct GrammarHandle {
+  std::shared_ptr<const Grammar> g;
+  std::shared_ptr<const GrammarVocab> v;
+};
+}  // namespace
+void* mp_grammar_parse(const char* gbnf, void* tok) {
+  API_TRY
+  auto h = std::make_unique<GrammarHandle>();
+  h->g = Grammar::parse(gbnf ? gbnf : "");
+  if (tok) h->v = std::make_shared<GrammarVocab>(*static_cast<Tokenizer*>(tok));
+  return h.release();
+  API_CATCH(nullptr)
+}
+void mp_grammar_free(void* h) { delete static_cast<GrammarHandle*>(h); }
+void* mp_grammar_state_new(void* h) {
+  API_TRY
+  auto* gh = static_cast<GrammarHandle*>(h);
+  return new GrammarState(gh->g, gh->v);
+  API_CATCH(nullptr)
+}
+void* mp_grammar_state_clone(void* s) {
+  API_TRY
+  return new GrammarState(*static_cast<GrammarState*>(s));
+  API_CATCH(nullptr)
+}
+void mp_grammar_state_free(void* s) { delete static_cast<GrammarState*>(s); }
+int mp_grammar_accept(void* s, int token) {
+  API_TRY
+  return static_cast<GrammarState*>(s)->accept(token) ? 1 : 0;
+  API_CATCH(-1)
+}
+int mp_grammar_accept_text(void* s, const void* bytes, int n) {
+  API_TRY
+  return static_cast<GrammarState*>(s)->accept_text(std::string((const char*)bytes, (size_t)std::max(n, 0))) ? 1 : 0;
+  API_CATCH(-1)
+}
+int mp_grammar_mask_words(void* s) {
+  API_TRY
+  auto* st = static_cast<GrammarState*>(s);
+  if (!st->vocab()) throw std::runtime_error("grammar state: no vocabulary");
+  return st->vocab()->mask_words();
+  API_CATCH(-1)
+}
+// bits: n_words >= mask_words() uint32 words; the words past mask_words() are cleared
+int mp_grammar_mask(void* s, void* bits, int n_words) {
+  API_TRY
+  auto* st = static_cast<GrammarState*>(s);
+  if (!st->vocab()) throw std::runtime_error("grammar state: no vocabulary");
+  const int nw = st->vocab()->mask_words();
+  if (!bits || n_words < nw) throw std::runtime_error("grammar mask: the buffer is too small");
+  std::memset(bits, 0, (size_t)n_words * 4);
+  st->mask(static_cast<uint32_t*>(bits));
+  return nw;
+  API_CATCH(-1)
+}
+int mp_grammar_can_end(void* s) {
+  API_TRY
+  return static_cast<GrammarState*>(s)->can_end() ? 1 : 0;
+  API_CATCH(-1)
+}
+int mp_grammar_only_end(void* s) {
+  API_TRY
+  return static_cast<GrammarState*>(s)->only_end() ? 1 : 0;
+  API_CATCH(-1)
+}
+const char* mp_json_schema_to_gbnf(const char* schema_json) {
+  API_TRY
+  g_str = json_schema_to_gbnf(Json::parse(schema_json ? schema_json : ""));
   return g_str.c_str();
   API_CATCH(nullptr)
 }
@@ -1009,6 +1096,16 @@ const char* mp_engine_slot_sampling(void* h, int slot) {
   return g_str.c_str();
   API_CATCH(nullptr)
 }
+// masks: n pointers, each ceil(vocab / 32) uint32 words or null (the slot's mask off)
+int mp_engine_set_slot_masks(void* h, const int32_t* slots, int n, const void* const* masks, int for_start) {
+  API_TRY
+  if (n < 0 || (n > 0 && (!slots || !masks))) throw std::runtime_error("set_slot_masks: bad arguments");
+  std::vector<int> s(slots, slots + n);
+  static_cast<Engine*>(h)->set_slot_masks(s, reinterpret_cast<const uint32_t* const*>(masks), for_start != 0);
+  return 0;
+  API_CATCH(-1)
+}
+int mp_engine_row_masks(void* h) { return static_cast<Engine*>(h)->row_masks() ? 1 : 0; }
 int mp_engine_release(void* h, int slot) {
   API_TRY
   static_cast<Engine*>(h)->release(slot);

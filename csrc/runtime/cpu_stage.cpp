@@ -625,6 +625,19 @@ void CpuStage::set_row_draws(int mb, const std::vector<int32_t>& draws) {
   std::copy(draws.begin(), draws.end(), draws_.begin() + (size_t)mb * opt_.mb_size);
 }
 
+void CpuStage::set_row_masks(const std::vector<int>& slots, const uint32_t* const* bits) {
+  if (!spec_.last()) return;
+  if (!opt_.row_masks) throw std::runtime_error("set_row_masks: the stage was built without row_masks");
+  const size_t n_slots = (size_t)opt_.n_mb * opt_.mb_size, ldw = ((size_t)cfg_.vocab + 31) / 32;
+  for (int s : slots)
+    if (s < 0 || (size_t)s >= n_slots) throw std::runtime_error("set_row_masks: bad slot");
+  if (masks_.empty()) masks_.resize(n_slots);
+  for (size_t i = 0; i < slots.size(); ++i) {
+    if (bits[i]) masks_[slots[i]].assign(bits[i], bits[i] + ldw);
+    else masks_[slots[i]].clear();
+  }
+}
+
 // Host counterpart of HipStage::head_rows: bias and penalties in f32 as the kernels apply them, the
 // chain in double, the variate of the request's own stream (kernels_api.h, RowSampling)
 void CpuStage::head_rows(int mb, int M, int32_t* tok_out, bool advance) {
@@ -662,6 +675,11 @@ void CpuStage::head_rows(int mb, int M, int32_t* tok_out, bool advance) {
         l = l > 0.f ? l / rs.repeat : l * rs.repeat;
         lg[t] = std::fmaf(-(float)c, rs.freq, l) - rs.presence;
       }
+    }
+    if (s < masks_.size() && !masks_[s].empty()) {   // the slot's token mask (row_mask_kernel)
+      const uint32_t* mk = masks_[s].data();
+      for (int t = 0; t < V; ++t)
+        if (!((mk[t >> 5] >> (t & 31)) & 1u)) lg[t] = -INFINITY;
     }
     if (rs.temp <= 0.f) {
       tok_out[m] = (int32_t)(std::max_element(lg, lg + V) - lg);

@@ -76,6 +76,7 @@ class CpuStage : public Stage {
   void head_rows(int mb, int M, int32_t* tok_out, bool advance);
   void set_row_sampling(int mb, int row, const RowSampling& r) override;
   void set_row_draws(int mb, const std::vector<int32_t>& draws) override;
+  void set_row_masks(const std::vector<int>& slots, const uint32_t* const* bits) override;
   void set_history(int mb, const std::vector<std::vector<int32_t>>& seqs) override;
   void kv_export(int slot, int n_tok, std::vector<uint8_t>& out) override;
   void set_block_table(const std::vector<int32_t>& table) override;
@@ -126,6 +127,7 @@ class CpuStage : public Stage {
   std::vector<std::vector<int32_t>> hist_;   // per slot: accepted tokens, most recent last
   std::vector<RowSampling> rows_;            // row_sampling: per slot record and draw index
   std::vector<int32_t> draws_;
+  std::vector<std::vector<uint32_t>> masks_;   // row_masks: per slot ceil(vocab / 32) words (empty: off)
 };
 
 }  // namespace mp

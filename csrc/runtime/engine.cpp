@@ -405,7 +405,16 @@ Engine::Engine(const Json& j) : jcfg_(j) {
   so.fused_norm = j.get_bool("fused_norm", false) && !so.deterministic;   // its sums of squares are atomics
   so.small_gemv = j.get_bool("small_gemv", true);
   row_sampling_ = j.get_bool("row_sampling", false);
+  row_masks_ = j.get_bool("row_masks", false);
+  if (row_masks_) {
+    if (j.has("row_sampling") && !row_sampling_)
+      throw std::runtime_error("\"row_masks\": true needs per-request sampling: \"row_sampling\": false contradicts it");
+    if (mode_ == "mp") throw std::runtime_error("\"row_masks\": mode \"mp\" is not supported");
+    row_sampling_ = true;
+    mask_state_.assign((size_t)M_ * B_, 0);
+  }
   so.row_sampling = row_sampling_;
+  so.row_masks = row_masks_;
   so.moe_gemm = j.get_bool("moe_gemm", true);
   packed_prefill_ = j.get_bool("packed_prefill", true);
   prefix_cache_ = j.get_bool("prefix_cache", true);
@@ -1157,6 +1166,7 @@ void Engine::start(const std::vector<std::vector<int32_t>>& prompts) {
   for (size_t i = 0; i < prompts.size(); ++i)
     if (!prompts[i].empty() && (int)prompts[i].size() < max_ctx_) kv_grant(i, (int)prompts[i].size() + 1);
   kv_sync();
+  clear_masks(false);
   {
     std::vector<size_t> all(prompts.size());
     std::iota(all.begin(), all.end(), (size_t)0);
@@ -1221,6 +1231,51 @@ void Engine::set_slot_sampling(int slot, const RowSampling& r, bool has_seed, bo
   check_row_sampling(r, cfg_.vocab);
   slot_rec_[slot] = r;
   slot_seed_given_[slot] = has_seed ? 1 : 0;
+}
+
+void Engine::set_slot_masks(const std::vector<int>& slots, const uint32_t* const* bits, bool for_start) {
+  if (!row_masks_) throw std::runtime_error("set_slot_masks: the engine was built without row_masks");
+  if (slots.empty()) return;
+  if (!bits) throw std::runtime_error("set_slot_masks: no masks given");
+  const int V = cfg_.vocab, nw = mask_words();
+  for (size_t i = 0; i < slots.size(); ++i) {
+    const int s = slots[i];
+    if (s < 0 || s >= M_ * B_) throw std::runtime_error("set_slot_masks: slot " + std::to_string(s) + " is out of range");
+    for (size_t k = 0; k < i; ++k)
+      if (slots[k] == s) throw std::runtime_error("set_slot_masks: slot " + std::to_string(s) + " is listed twice");
+    if (!bits[i]) continue;
+    bool any = false;
+    for (int w = 0; w < nw && !any; ++w) {
+      uint32_t v = bits[i][w];
+      if (w == nw - 1 && (V & 31)) v &= (1u << (V & 31)) - 1u;
+      any = v != 0;
+    }
+    if (!any) throw std::runtime_error("set_slot_masks: the mask of slot " + std::to_string(s) + " allows no token below the vocabulary size");
+  }
+  for (auto& w : workers_)
+    if (w->stage->spec().last()) {
+      if (!w->cpu) HIP_OK(hipSetDevice(w->device));
+      w->stage->set_row_masks(slots, bits);
+    }
+  for (size_t i = 0; i < slots.size(); ++i)
+    mask_state_[slots[i]] = !bits[i] ? 0 : (!for_start && started_ && slot_active(slots[i])) ? 2 : 1;
+}
+
+void Engine::clear_masks(bool all) {
+  if (!row_masks_) return;
+  std::vector<int> slots;
+  for (int s = 0; s < M_ * B_; ++s)
+    if (mask_state_[s] == 2 || (all && mask_state_[s])) slots.push_back(s);
+  for (int s = 0; s < M_ * B_; ++s)
+    if (mask_state_[s] == 1 && !all) mask_state_[s] = 2;   // set for this start(): in use from here on
+  if (slots.empty()) return;
+  std::vector<const uint32_t*> none(slots.size(), nullptr);
+  for (auto& w : workers_)
+    if (w->stage->spec().last()) {
+      if (!w->cpu) HIP_OK(hipSetDevice(w->device));
+      w->stage->set_row_masks(slots, none.data());
+    }
+  for (int s : slots) mask_state_[s] = 0;
 }
 
 RowSampling Engine::slot_sampling(int slot) const {
@@ -1620,6 +1675,7 @@ Json Engine::load_state(const std::string& dir) {
   } else if (sj.has("sampling")) {
     throw std::runtime_error("load_state: the session was saved with row_sampling");
   }
+  clear_masks(true);   // masks are not part of a checkpoint: every slot resumes unconstrained
   started_ = true;
   resumable_ = true;
   refresh_slot_cache();
@@ -1702,6 +1758,16 @@ void Engine::release(int slot) {
         w->stage->set_row_sampling(slot / B_, slot % B_, row_default_);
       }
   }
+  if (row_masks_ && !failed_ && slot >= 0 && slot < M_ * B_ && mask_state_[slot]) {
+    const std::vector<int> one{slot};
+    const uint32_t* none = nullptr;
+    for (auto& w : workers_)
+      if (w->stage->spec().last()) {
+        if (!w->cpu) HIP_OK(hipSetDevice(w->device));
+        w->stage->set_row_masks(one, &none);
+      }
+    mask_state_[slot] = 0;
+  }
 }
 
 void Engine::kv_grant(size_t slot, int n_tokens) {
@@ -1748,6 +1814,9 @@ void Engine::admit(const std::vector<int>& slots, const std::vector<std::vector<
   }
   kv_sync();
   apply_slot_sampling(seqs);
+  if (row_masks_)
+    for (size_t i : seqs)
+      if (mask_state_[i] == 1) mask_state_[i] = 2;   // set for this admission: in use from here on
   for (auto& w : workers_) {
     Stage& st = *w->stage;
     if (!w->cpu) HIP_OK(hipSetDevice(w->device));
@@ -2175,7 +2244,9 @@ Json Engine::spec_generate(const std::vector<std::vector<int32_t>>& prompts, int
   // drafts, grants KV and builds the identical next verify chunk
   const bool mp = mode_ == "mp" && S_ > 1;
   if (!mp && (int)workers_.size() != S_) throw std::runtime_error("speculative decoding needs every stage in this process");
-  if (row_sampling_) throw std::runtime_error("speculative decoding is greedy: not on a row_sampling engine");
+  if (row_sampling_)
+    throw std::runtime_error(std::string("speculative decoding is greedy: not on a row_sampling engine") +
+                             (row_masks_ ? " (row_masks switches row_sampling on)" : ""));
   if (jcfg_.get_num("temp", 0.0) > 0.0) throw std::runtime_error("speculative decoding is greedy (temp 0)");
   if (jcfg_.get_num("repeat_penalty", 1.0) != 1.0 || jcfg_.get_num("frequency_penalty", 0.0) != 0.0 ||
       jcfg_.get_num("presence_penalty", 0.0) != 0.0)

@@ -140,6 +140,20 @@ class Engine {
   const RowSampling& sampling_defaults() const { return row_default_; }
   RowSampling sampling_from_json(const Json& j, bool* has_seed) const;
   static Json sampling_to_json(const RowSampling& r);
+  // Per-slot token masks (config "row_masks": true; needs row_sampling and switches it on when that
+  // key is absent; local mode).  bits[i]: ceil(vocab / 32) words for slot slots[i], token t allowed iff
+  // bits[i][t >> 5] >> (t & 31) & 1; a null entry clears the slot's mask.  From the slot's next token
+  // on, the last stage bans every other token after the bias and the penalties, before the cuts and the
+  // draw (logprobs stay those of the raw logits).  Legal before start(), for idle slots before admit()
+  // and between decode_steps calls for running slots; never re-captures a graph.  A mask set for an
+  // idle slot holds for its next start() / admit(); start() clears the masks of the generation before
+  // it, release() the slot's, load_state() all of them.  Throws naming the cause: an engine without the
+  // key, a slot out of range, a mask that allows no token < vocab.
+  bool row_masks() const { return row_masks_; }
+  // for_start: the masks are for the next start(), which clears every mask of the generation before
+  // it: they survive it even when their slots are still busy with that generation
+  void set_slot_masks(const std::vector<int>& slots, const uint32_t* const* bits, bool for_start = false);
+  int mask_words() const { return (cfg_.vocab + 31) / 32; }
   int32_t last_token(int slot) const { return slot < (int)gen_.size() && !gen_[slot].empty() ? gen_[slot].back() : -1; }
   int slot_position(int slot) const { return slot_pos((size_t)slot); }
   bool started() const { return started_; }
@@ -269,6 +283,9 @@ class Engine {
   }
   void push_positions(int mb);
   bool row_sampling_ = false;
+  bool row_masks_ = false;
+  std::vector<char> mask_state_;            // per slot: 0 off, 1 set for the next admission, 2 in use
+  void clear_masks(bool all);               // start(): those in use; load_state(): all
   RowSampling row_default_;                 // the engine keys as a record (seed: the engine's)
   std::vector<RowSampling> slot_rec_;       // per slot: set for the next admission / in use
   std::vector<char> slot_seed_given_;

@@ -81,6 +81,8 @@ HipStage::~HipStage() {
   (void)hipSetDevice(spec_.device);
   destroy_graphs();
   for (void* p : allocs_) (void)hipFree(p);
+  if (mask_host_) (void)hipHostFree(mask_host_);
+  if (mask_on_host_) (void)hipHostFree(mask_on_host_);
   if (stream_) (void)hipStreamDestroy(stream_);
 }
 
@@ -618,6 +620,17 @@ void HipStage::alloc_runtime() {
     HIP_OK(hipMemcpy(row_tab_, row_host_.data(), row_host_.size() * sizeof(RowSampling), hipMemcpyHostToDevice));
     row_draw_ = (int32_t*)zalloc((size_t)n_slots * 4);
   }
+  if (opt_.row_masks && !opt_.row_sampling) throw std::runtime_error("row_masks needs row_sampling");
+  if (spec_.last() && opt_.row_masks) {   // every slot starts unconstrained
+    mask_ldw_ = (cfg_.vocab + 31) / 32;
+    const size_t words = (size_t)n_slots * mask_ldw_;
+    mask_tab_ = (uint32_t*)zalloc(words * 4);
+    mask_on_ = (int32_t*)zalloc((size_t)n_slots * 4);
+    HIP_OK(hipHostMalloc((void**)&mask_host_, words * 4, hipHostMallocDefault));
+    HIP_OK(hipHostMalloc((void**)&mask_on_host_, (size_t)n_slots * 4, hipHostMallocDefault));
+    std::memset(mask_host_, 0, words * 4);
+    std::memset(mask_on_host_, 0, (size_t)n_slots * 4);
+  }
   HIP_OK(hipDeviceSynchronize());
   MP_LOGI("stage %d: layers %d-%d offloaded to GPU %d (%s), weights %.2f GiB, KV %.2f GiB (%d pages of 64 tokens; "
           "%d slots x <= %d ctx)",
@@ -757,6 +770,32 @@ void HipStage::set_row_draws(int mb, const std::vector<int32_t>& draws) {
   HIP_OK(hipSetDevice(spec_.device));
   HIP_OK(hipStreamSynchronize(stream_));
   HIP_OK(hipMemcpy(row_draw_ + (size_t)slot_of(mb, 0), draws.data(), draws.size() * 4, hipMemcpyHostToDevice));
+}
+
+// The changed rows go to the pinned mirror, then to the device on the stage's stream with the on
+// flags behind them; one synchronisation, after the last copy, so the mirror is free again and no
+// head() can run between a row and its flag.
+void HipStage::set_row_masks(const std::vector<int>& slots, const uint32_t* const* bits) {
+  if (!spec_.last()) return;
+  if (!mask_tab_) throw std::runtime_error("set_row_masks: the stage was built without row_masks");
+  const int n_slots = opt_.n_mb * opt_.mb_size;
+  for (size_t i = 0; i < slots.size(); ++i) {
+    if (slots[i] < 0 || slots[i] >= n_slots) throw std::runtime_error("set_row_masks: bad slot");
+    for (size_t k = 0; k < i; ++k)   // a second copy into the same mirror row would race the first one's stream copy
+      if (slots[k] == slots[i]) throw std::runtime_error("set_row_masks: a slot is listed twice");
+  }
+  if (slots.empty()) return;
+  HIP_OK(hipSetDevice(spec_.device));
+  const size_t row_bytes = (size_t)mask_ldw_ * 4;
+  for (size_t i = 0; i < slots.size(); ++i) {
+    const size_t s = (size_t)slots[i];
+    mask_on_host_[s] = bits[i] ? 1 : 0;
+    if (!bits[i]) continue;
+    std::memcpy(mask_host_ + s * mask_ldw_, bits[i], row_bytes);
+    HIP_OK(hipMemcpyAsync(mask_tab_ + s * mask_ldw_, mask_host_ + s * mask_ldw_, row_bytes, hipMemcpyHostToDevice, stream_));
+  }
+  HIP_OK(hipMemcpyAsync(mask_on_, mask_on_host_, (size_t)n_slots * 4, hipMemcpyHostToDevice, stream_));
+  HIP_OK(hipStreamSynchronize(stream_));
 }
 
 // token logprob buffers (last stage, n_probs != 0): allocated when recording is switched on and when
@@ -1380,7 +1419,7 @@ void HipStage::lm_head(const float* x, int M, float* logits, bool small, hipStre
 
 // head() with row_sampling: every launch has fixed arguments and reads the rows' records, draw
 // indices and windows from device memory, so the decode graphs are captured once.  Raw-logit
-// statistics (n_probs) -> bias + penalties per row -> arg-max of every row -> the sampled rows' draws
+// statistics (n_probs) -> bias + penalties per row -> the slots' token masks (row_masks) -> arg-max of every row -> the sampled rows' draws
 // over it -> the chosen tokens' logprobs -> the windows.
 void HipStage::head_rows(int mb, int M, int32_t* tok_out, bool advance, hipStream_t st) {
   const int B = opt_.mb_size;
@@ -1401,6 +1440,12 @@ void HipStage::head_rows(int mb, int M, int32_t* tok_out, bool advance, hipStrea
   ra.logits = logits_; ra.ld = logits_ld_; ra.n = cfg_.vocab; ra.M = M;
   ra.rows = row_tab_ + r0; ra.hist = hist; ra.hist_ld = hist_ld_; ra.last_n = hist_n_;
   launch_row_adjust(ra, st);
+  if (mask_tab_) {   // the slots' masks, after the bias and the penalties: the cuts and the draw see -inf
+    RowMaskParams rm{};
+    rm.logits = logits_; rm.ld = logits_ld_; rm.n = cfg_.vocab; rm.M = M;
+    rm.bits = mask_tab_ + r0 * mask_ldw_; rm.ldw = mask_ldw_; rm.on = mask_on_ + r0;
+    launch_row_mask(rm, st);
+  }
   launch_argmax(logits_, logits_ld_, cfg_.vocab, M, tok_out, st, &am_);
   SampleRowsParams sp{};
   sp.logits = logits_; sp.ld = logits_ld_; sp.n = cfg_.vocab; sp.M = M;

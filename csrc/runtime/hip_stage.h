@@ -162,6 +162,7 @@ class HipStage : public Stage {
   void set_history(int mb, const std::vector<std::vector<int32_t>>& seqs) override;
   void set_row_sampling(int mb, int row, const RowSampling& r) override;
   void set_row_draws(int mb, const std::vector<int32_t>& draws) override;
+  void set_row_masks(const std::vector<int>& slots, const uint32_t* const* bits) override;
   long graph_captures() const override { return graph_captures_; }
 
   size_t weight_bytes() const override { return weight_bytes_; }
@@ -311,6 +312,11 @@ class HipStage : public Stage {
   int32_t* row_draw_ = nullptr;
   bool rows_on() const { return row_tab_ != nullptr; }
   void head_rows(int mb, int M, int32_t* tok_out, bool advance, hipStream_t st);
+  // per-slot token masks (opt_.row_masks, last stage): the table [n_mb * mb_size][mask_ldw_] and the
+  // slots' on flags on the device, and their pinned host mirrors (the source of the stream copies)
+  uint32_t* mask_tab_ = nullptr; uint32_t* mask_host_ = nullptr;
+  int32_t* mask_on_ = nullptr; int32_t* mask_on_host_ = nullptr;
+  int mask_ldw_ = 0;
   long graph_captures_ = 0;
   // prefill metadata
   int32_t* pf_pos_ = nullptr; int32_t* pf_kvlen_ = nullptr; int32_t* pf_slot_ = nullptr;

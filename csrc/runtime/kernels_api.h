@@ -391,6 +391,17 @@ void launch_sample_rows(const SampleRowsParams& p, hipStream_t st);
 void launch_hist_push_ld(int32_t* hist, int hist_ld, int32_t* cnt, int last_n, const int32_t* tokens, int M,
                          hipStream_t st);
 
+// Per-row token masks (row_mask.hip; engine key "row_masks"): in a row with on[m] != 0 every logit
+// whose bit is clear becomes -inf; allowed logits, columns n..ld-1 and rows that are off are never
+// written, and no logit is read.  Bits at positions >= n of a row's last word are ignored.  Rows
+// need only 4-byte alignment.  Throws when ldw < ceil(n / 32).
+struct RowMaskParams {
+  float* logits; int ld; int n; int M;
+  const uint32_t* bits; int ldw;   // row m: bits + m * ldw, token t allowed iff bits[t >> 5] >> (t & 31) & 1
+  const int32_t* on;               // [M]; 0: the row is not constrained
+};
+void launch_row_mask(const RowMaskParams& p, hipStream_t st);
+
 // pos[i] += 1, kvlen[i] = pos[i] + 1 for i < M (graph-resident decode step advance)
 void launch_advance(int32_t* pos, int32_t* kvlen, int M, int32_t* step, hipStream_t st);
 

@@ -88,6 +88,37 @@ std::string Session::piece(int32_t id) const {
 
 bool Session::is_eog(int32_t id) const { return tok_ && tok_->is_eog(id); }
 
+GrammarState Session::grammar_state(const GenRequest& req) {
+  if (!req.grammar) return GrammarState();
+  if (!eng_->row_masks()) throw std::runtime_error("a grammar needs an engine built with row_masks");
+  if (!tok_) throw std::runtime_error("a grammar needs the model's tokenizer");
+  if (!eng_->owns_first() || !eng_->owns_last()) throw std::runtime_error("a grammar needs every stage in this process");
+  if (!gvocab_) gvocab_ = std::make_shared<GrammarVocab>(*tok_);
+  if (gvocab_->n_vocab() > eng_->model().vocab) throw std::runtime_error("grammar: the tokenizer has more tokens than the model");
+  return GrammarState(req.grammar, gvocab_);
+}
+
+std::vector<std::string> Session::push_masks(const std::vector<int>& slots, const std::vector<const GrammarState*>& states,
+                                             bool for_start) {
+  std::vector<std::string> errors(slots.size());
+  if (slots.empty()) return errors;
+  const size_t nw = (size_t)eng_->mask_words();
+  if (mask_buf_.size() < slots.size()) mask_buf_.resize(slots.size());
+  std::vector<const uint32_t*> ptrs(slots.size(), nullptr);
+  for (size_t i = 0; i < slots.size(); ++i) {
+    if (!states[i]) continue;
+    mask_buf_[i].assign(nw, 0u);   // the model's vocabulary may be padded past the tokenizer's: those ids stay banned
+    try {
+      states[i]->mask(mask_buf_[i].data());
+      ptrs[i] = mask_buf_[i].data();
+    } catch (const std::exception& e) {   // the request's own trouble, not the engine's
+      errors[i] = e.what();
+    }
+  }
+  eng_->set_slot_masks(slots, ptrs.data(), for_start);
+  return errors;
+}
+
 std::vector<GenResult> Session::run(std::vector<GenRequest>& reqs) {
   if ((int)reqs.size() > capacity()) throw std::runtime_error("more requests than sequence slots");
   std::vector<GenResult> res(reqs.size());
@@ -112,17 +143,49 @@ std::vector<GenResult> Session::run(std::vector<GenRequest>& reqs) {
   const bool emit = eng_->owns_last();
   std::vector<Utf8Acc> acc(reqs.size());
   std::vector<bool> active(reqs.size(), true);
+  // grammar requests: one state each; `dirty` = the slot's mask on the engine is behind its state
+  std::vector<GrammarState> gs(reqs.size());
+  std::vector<char> dirty(reqs.size(), 0);
+  bool any_grammar = false;
+  for (size_t i = 0; i < reqs.size(); ++i) {
+    gs[i] = grammar_state(reqs[i]);
+    if (gs[i].valid()) { dirty[i] = 1; any_grammar = true; }
+  }
+  if (any_grammar && eng_->config().get_int("draft_max", 0) > 0)
+    throw std::runtime_error("a grammar cannot be combined with speculative decoding (draft_max)");
+  auto sync_masks = [&](bool for_start) {
+    std::vector<int> sl;
+    std::vector<const GrammarState*> st;
+    for (size_t i = 0; i < reqs.size(); ++i)
+      if (dirty[i]) { sl.push_back((int)i); st.push_back(active[i] ? &gs[i] : nullptr); dirty[i] = 0; }
+    const std::vector<std::string> err = push_masks(sl, st, for_start);
+    for (size_t k = 0; k < sl.size(); ++k)
+      if (!err[k].empty() && active[sl[k]]) { active[sl[k]] = false; res[sl[k]].stop = "error: " + err[k]; }
+  };
+  // false: the token cannot follow (the mask should have banned it) or the grammar's tables are full
+  auto grammar_accept = [&](GrammarState& g, int32_t t, std::string* why) {
+    try {
+      if (g.accept(t)) return true;
+      *why = "error: grammar: the engine produced a token the mask bans";
+    } catch (const std::exception& e) {
+      *why = std::string("error: ") + e.what();
+    }
+    return false;
+  };
   auto consume = [&](size_t i, int32_t t, int step) {
     if (!active[i]) return;
     GenResult& r = res[i];
+    if (gs[i].valid()) dirty[i] = 1;   // the state moves, or the request ends and its mask goes
     if (step >= reqs[i].n_predict) { active[i] = false; r.stop = "length"; return; }
     if (is_eog(t)) { active[i] = false; r.stop = "eog"; return; }
+    if (gs[i].valid() && !grammar_accept(gs[i], t, &r.stop)) { active[i] = false; return; }
     r.tokens.push_back(t);
     r.n_gen++;
     push_prob(r, (int)i, t);
     const std::string p = acc[i].push(piece(t));
     r.text += p;
     if (emit && !p.empty() && reqs[i].on_piece && !reqs[i].on_piece(p)) { active[i] = false; r.stop = "cancelled"; }
+    if (active[i] && gs[i].valid() && gs[i].only_end()) { active[i] = false; r.stop = "eog"; }   // nothing can follow
   };
   const double t0 = now_ms();
   const int draft_max = eng_->config().get_int("draft_max", 0);
@@ -159,6 +222,7 @@ std::vector<GenResult> Session::run(std::vector<GenRequest>& reqs) {
     return res;
   }
   for (size_t i = 0; i < reqs.size(); ++i) set_slot_record((int)i, reqs[i], res[i]);
+  sync_masks(true);
   eng_->start(prompts);
   if (eng_->row_sampling())
     for (size_t i = 0; i < reqs.size(); ++i) { res[i].seed = eng_->slot_sampling((int)i).seed; res[i].has_seed = true; }
@@ -173,6 +237,7 @@ std::vector<GenResult> Session::run(std::vector<GenRequest>& reqs) {
   int step = 1;
   auto any_active = [&] { return std::any_of(active.begin(), active.end(), [](bool b) { return b; }); };
   while (step < n_max && (!early_stop || any_active())) {
+    sync_masks(false);
     eng_->decode_steps(1);
     const auto toks = eng_->tokens();
     for (size_t i = 0; i < reqs.size(); ++i)
@@ -216,6 +281,9 @@ void Session::serve(const std::function<std::vector<Served>(int free)>& next) {
     std::vector<int32_t> prompt;   // for re-admission into a replacement engine after a fault
     double t0 = 0, t1 = 0;
     bool resumed = false;          // requeued by a failover: keeps its timings and produced tokens
+    GrammarState gs;               // grammar requests: where the produced text stands (survives a failover)
+    bool mask_dirty = false;       // the slot's mask on the engine is behind gs
+    std::string gs_error;          // the grammar gave up on this request (its tables are full): it ends at its next token
   };
   struct Pending {
     Served s;
@@ -291,8 +359,18 @@ void Session::serve(const std::function<std::vector<Served>(int free)>& next) {
   auto consume = [&](int slot, int32_t t) -> bool {   // false: the request is finished
     Live& L = *live[slot];
     GenResult& r = L.res;
+    if (!L.gs_error.empty()) { r.stop = "error: " + L.gs_error; return false; }   // this request only
     if (L.step >= L.s.req.n_predict) { r.stop = "length"; return false; }
     if (is_eog(t)) { r.stop = "eog"; return false; }
+    if (L.gs.valid()) {
+      try {
+        if (!L.gs.accept(t)) L.gs_error = "grammar: the engine produced a token the mask bans";
+      } catch (const std::exception& e) {
+        L.gs_error = e.what();
+      }
+      if (!L.gs_error.empty()) { r.stop = "error: " + L.gs_error; return false; }
+      L.mask_dirty = true;
+    }
     r.tokens.push_back(t);
     r.n_gen++;
     push_prob(r, slot, t);
@@ -300,10 +378,26 @@ void Session::serve(const std::function<std::vector<Served>(int free)>& next) {
     r.text += p;
     ++L.step;
     if (!p.empty() && L.s.req.on_piece && !L.s.req.on_piece(p)) { r.stop = "cancelled"; return false; }
+    if (L.gs.valid() && L.gs.only_end()) { r.stop = "eog"; return false; }   // nothing can follow
     if (L.step >= L.s.req.n_predict) { r.stop = "length"; return false; }
     // the context or the request's share of the KV pool is full
     if (eng_->slot_position(slot) + 1 >= std::min(max_ctx, L.pages * 64)) { r.stop = "context"; return false; }
     return true;
+  };
+  // the masks of the given slots' grammar requests, one engine call (made inside guarded(): it copies
+  // to the device); a request whose mask cannot be computed gets gs_error and ends at its next token
+  auto sync_masks = [&](const std::vector<int>& among, bool for_start) {
+    std::vector<int> sl;
+    std::vector<const GrammarState*> st;
+    for (int s : among)
+      if (live[s] && live[s]->gs.valid() && (for_start || live[s]->mask_dirty)) {
+        sl.push_back(s);
+        st.push_back(&live[s]->gs);
+        live[s]->mask_dirty = false;
+      }
+    const std::vector<std::string> err = push_masks(sl, st, for_start);
+    for (size_t k = 0; k < sl.size(); ++k)
+      if (!err[k].empty()) live[sl[k]]->gs_error = err[k];
   };
   auto finish = [&](int slot) {
     Live& L = *live[slot];
@@ -411,6 +505,11 @@ void Session::serve(const std::function<std::vector<Served>(int free)>& next) {
     if (prompts.empty()) return false;
     // each request goes on in its own random stream: its seed, draw0 = the tokens it has produced
     for (size_t i = 0; i < prompts.size(); ++i) set_slot_record((int)i, live[i]->s.req, live[i]->res);
+    {   // each grammar request goes on from its own state: its mask is set before the re-admission
+      std::vector<int> all(prompts.size());
+      for (size_t i = 0; i < all.size(); ++i) all[i] = (int)i;
+      sync_masks(all, true);
+    }
     eng_->start(prompts);   // a replacement fault propagates (the handler already had its turn)
     for (size_t i = 0; i < prompts.size(); ++i)
       if (eng_->row_sampling()) { live[i]->res.seed = eng_->slot_sampling((int)i).seed; live[i]->res.has_seed = true; }
@@ -450,6 +549,13 @@ void Session::serve(const std::function<std::vector<Served>(int free)>& next) {
         L->prompt = pd.prompt;
         L->s = std::move(pd.s);
         L->t0 = now_ms();
+        try {
+          L->gs = grammar_state(L->s.req);
+        } catch (const std::exception& e) {   // not this engine's fault: the request ends with the reason
+          L->res.stop = std::string("error: ") + e.what();
+          if (L->s.done) L->s.done(L->res);
+          continue;
+        }
       }
       L->pages = pd.pages;
       reserved += L->pages;
@@ -461,7 +567,9 @@ void Session::serve(const std::function<std::vector<Served>(int free)>& next) {
       // nothing running: a plain start() of slots 0..n-1 (resets the engine's rounds)
       const bool ok = guarded([&] {
         for (int sl : slots) set_slot_record(sl, live[sl]->s.req, live[sl]->res);
-        if (idle && slots.back() == (int)slots.size() - 1) eng_->start(prompts);
+        const bool as_start = idle && slots.back() == (int)slots.size() - 1;
+        sync_masks(slots, true);   // the first token is constrained too
+        if (as_start) eng_->start(prompts);
         else eng_->admit(slots, prompts);
       });
       if (!ok) continue;   // failed over: every live request (these included) was re-admitted
@@ -484,7 +592,14 @@ void Session::serve(const std::function<std::vector<Served>(int free)>& next) {
       if (waiting.empty() && slots.empty() && !had_embed) return;
       continue;
     }
-    if (!guarded([&] { eng_->decode_steps(1); })) continue;
+    // every constrained slot's next mask (one call per round), then the round
+    if (!guarded([&] {
+          std::vector<int> all(cap);
+          for (int s = 0; s < cap; ++s) all[s] = s;
+          sync_masks(all, false);
+          eng_->decode_steps(1);
+        }))
+      continue;
     for (int sl = 0; sl < cap; ++sl)
       if (live[sl] && !consume(sl, eng_->last_token(sl))) finish(sl);
   }

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "engine.h"
+#include "grammar.h"
 #include "tokenizer.h"
 
 namespace mp {
@@ -27,6 +28,9 @@ struct GenRequest {
   // has_seed it gets the engine's next default seed (GenResult::seed reports the one used)
   bool has_sampling = false, has_seed = false;
   RowSampling sampling;
+  // constrained output (engines built with row_masks): every token the request generates keeps its
+  // text inside the grammar's language; it ends with stop "eog" as soon as nothing can follow
+  std::shared_ptr<const Grammar> grammar;
   // receives text pieces (complete UTF-8); return false to cancel this sequence
   std::function<bool(const std::string& piece)> on_piece;
 };
@@ -109,6 +113,17 @@ class Session {
   // one).  A request that has already produced res.tokens (failover, resume) keeps its seed and goes on
   // at draw0 + tokens produced, so it continues its own stream.
   void set_slot_record(int slot, const GenRequest& req, const GenResult& res);
+  // grammar requests: the state at the start of req's grammar (throws without a tokenizer or on an
+  // engine without row_masks), and the masks of the given slots' states in one engine call (a null
+  // state clears the slot's mask)
+  GrammarState grammar_state(const GenRequest& req);
+  // Returns one string per slot: empty, or why that state's mask could not be computed (the grammar's
+  // tables are full, a state is too ambiguous); such a slot's mask is cleared and its request is the
+  // caller's to end.  An engine error is thrown.
+  std::vector<std::string> push_masks(const std::vector<int>& slots, const std::vector<const GrammarState*>& states,
+                                      bool for_start);
+  std::shared_ptr<const GrammarVocab> gvocab_;
+  std::vector<std::vector<uint32_t>> mask_buf_;
   Engine* eng_;
   std::function<Engine*(const std::string&)> on_fault_;
   int max_failovers_ = 0, failovers_ = 0;

@@ -48,6 +48,9 @@ struct StageOptions {
   bool moe_gemm = true;     // M > 64 MoE FFN on the grouped expert GEMM (gemm4.hip) instead of 64-row GEMV slices
   bool row_sampling = false;   // per-request sampling: the last stage keeps a RowSampling record and a draw
                                // index per sequence slot, and head() reads them (set_row_sampling)
+  bool row_masks = false;      // per-slot token masks (needs row_sampling): the last stage keeps a table of
+                               // ceil(vocab / 32) words per sequence slot, and head() bans the tokens whose
+                               // bit is clear in the rows that are on (set_row_masks)
   bool small_gemv = true;   // M <= 4 rows: the gemvs kernels (gemvs.hip: x staged once per workgroup,
                             // RMSNorm fused into the qkv / gate-up / LM-head GEMVs, in-workgroup split-K)
 };
@@ -171,6 +174,15 @@ class Stage {
   // sets the indices of a micro-batch after an admission: set_row_draws).  Other stages ignore both.
   virtual void set_row_sampling(int mb, int row, const RowSampling& r) { (void)mb; (void)row; (void)r; }
   virtual void set_row_draws(int mb, const std::vector<int32_t>& draws) { (void)mb; (void)draws; }
+  // Per-slot token masks (StageOptions::row_masks), last stage, between engine calls.  bits[i] is the
+  // mask of sequence slot slots[i] (= mb * mb_size + row): ceil(vocab / 32) words, token t allowed iff
+  // bits[i][t >> 5] >> (t & 31) & 1; a null entry switches the slot's mask off.  From the next head()
+  // on, a row that is on gets -inf in every banned logit after the bias and the penalties and before
+  // the arg-max, the cuts and the draw.  The caller guarantees an allowed token < vocab per mask.
+  // Captured graphs are not touched.  Throws on a stage built without the option.
+  virtual void set_row_masks(const std::vector<int>& slots, const uint32_t* const* bits) {
+    (void)slots; (void)bits;
+  }
   // how often capture_graphs() ran (health(): an admit on a row_sampling engine must not grow it)
   virtual long graph_captures() const { return 0; }
 

@@ -12,6 +12,7 @@
 #include <string>
 #include <vector>
 
+#include "grammar.h"
 #include "json.h"
 
 namespace mp {
@@ -29,6 +30,7 @@ struct CliOptions {
   bool embedding = false;     // --embedding: print one embedding per prompt (-p TEXT, or -f FILE: one per line)
   std::string pooling;        // --pooling none|mean|cls|last ("" = the model's pooling_type, else last)
   int embd_normalize = 2;     // --embd-normalize: 2 = L2 (default), -1 = none
+  std::string grammar;        // --grammar / --grammar-file / -j: the GBNF text the output must match ("" = free)
   int bench_prompt = 128, bench_warmup = 3, bench_steps = 20;
   std::string trace;
   std::string rpc;            // --rpc host:port,... (without --world): stage workers to attach to (rpc.h)
@@ -101,6 +103,12 @@ inline void print_common_usage(FILE* f) {
           "                            only, 1..20 plus that many alternatives (default 0: off)\n"
           "  --row-sampling            sample every sequence slot by its own record in a device table (engine key\n"
           "                            row_sampling; the slots start at the values above)\n"
+          "  --grammar GBNF            constrain the output to a GBNF grammar (--grammar-file FILE reads it from a\n"
+          "                            file); switches the engine keys row_masks and row_sampling on\n"
+          "  -j, --json-schema SCHEMA  constrain the output to the JSON documents that fit a JSON schema\n"
+          "                            ({\"type\": \"json_object\"}: any JSON object)\n"
+          "  --row-masks               keep a token mask per sequence slot on the last stage (engine key row_masks;\n"
+          "                            implies --row-sampling): what the server's grammar fields need\n"
           "  --perplexity -f FILE      perplexity of a text file, llama.cpp's procedure: windows of -c tokens,\n"
           "                            the second half of each window counts\n"
           "  --embedding               print embeddings instead of generating: one per prompt (-p TEXT, or -f FILE\n"
@@ -145,6 +153,7 @@ inline CliOptions parse_cli(int argc, char** argv,
   e["max_ctx"] = 2048;
   std::string synthetic, devices, rpc, next, master;
   bool no_qk_norm = false;
+  int n_grammar = 0;
   int stages = 0, world = 0, rank = -1;
   for (int i = 1; i < argc; ++i) {
     const std::string a = argv[i];
@@ -218,6 +227,17 @@ inline CliOptions parse_cli(int argc, char** argv,
     }
     else if (a == "--n-probs") e["n_probs"] = std::atoi(val().c_str());
     else if (a == "--row-sampling") e["row_sampling"] = true;
+    else if (a == "--row-masks") e["row_masks"] = true;
+    else if (a == "--grammar") { o.grammar = val(); ++n_grammar; }
+    else if (a == "--grammar-file") { o.grammar = read_file(val()); ++n_grammar; }
+    else if (a == "-j" || a == "--json-schema") {
+      try {
+        o.grammar = json_schema_to_gbnf(Json::parse(val()));
+      } catch (const std::exception& ex) {
+        throw std::runtime_error(a + ": " + ex.what());
+      }
+      ++n_grammar;
+    }
     else if (a == "--bench-prompt") o.bench_prompt = std::atoi(val().c_str());
     else if (a == "--bench-warmup") o.bench_warmup = std::atoi(val().c_str());
     else if (a == "--bench-steps") o.bench_steps = std::atoi(val().c_str());
@@ -230,6 +250,19 @@ inline CliOptions parse_cli(int argc, char** argv,
     e["synthetic"] = syn;
   }
   if (!e.has("gguf") && !e.has("synthetic")) throw std::runtime_error("need -m FILE or --synthetic NAME");
+  if (n_grammar > 1) throw std::runtime_error("give one of --grammar, --grammar-file and --json-schema");
+  if (n_grammar) {   // the grammar is parsed here, so a bad one ends the run before the model loads
+    if (o.grammar.empty()) throw std::runtime_error("the grammar is empty");
+    (void)Grammar::parse(o.grammar);
+    if (world > 0) throw std::runtime_error("a grammar needs every stage in this process (not with --world)");
+    if (!rpc.empty()) throw std::runtime_error("a grammar cannot be combined with --rpc");
+    if (o.perplexity) throw std::runtime_error("a grammar cannot be combined with --perplexity");
+    if (o.embedding) throw std::runtime_error("a grammar cannot be combined with --embedding");
+    if (o.bench) throw std::runtime_error("a grammar cannot be combined with --bench");
+    if (e.get_int("draft_max", 0) > 0) throw std::runtime_error("a grammar cannot be combined with --draft-max");
+    if (!e.has("gguf")) throw std::runtime_error("a grammar needs a model with a tokenizer (-m FILE)");
+    e["row_masks"] = true;
+  }
   if (o.ngl == 0) e["backend"] = "cpu";
   else if (o.ngl > 0) e["gpu_layers"] = o.ngl;   // explicit -ngl only: >= n_layer puts every layer on the GPUs
   if (stages > 0) e["stages"] = stages;

@@ -196,6 +196,8 @@ int main(int argc, char** argv) {
     return 2;
   }
   try {
+    if (!o.grammar.empty() && (daemon || !state_load.empty()))
+      throw std::runtime_error("a grammar cannot be combined with --daemon or --state-load");
     if (o.bench) {
       if (!o.eng.has("mb_size")) o.eng["mb_size"] = 16;
       const int need = o.bench_prompt + o.bench_warmup + o.bench_steps + 8;
@@ -247,6 +249,7 @@ int main(int argc, char** argv) {
     std::vector<GenRequest> reqs(1);
     reqs[0].prompt = o.prompt;
     reqs[0].n_predict = o.n_predict;
+    if (!o.grammar.empty()) reqs[0].grammar = Grammar::parse(o.grammar);
     reqs[0].on_piece = [](const std::string& p) {
       fwrite(p.data(), 1, p.size(), stdout);
       fflush(stdout);

@@ -82,6 +82,7 @@ struct Job {
   // per-request sampling (--row-sampling): the record built from the request's fields
   bool has_sampling = false, has_seed = false;
   RowSampling sampling;
+  std::shared_ptr<const Grammar> grammar;   // constrained output (--row-masks): grammar | json_schema | response_format
   double enqueued_ms = 0;   // fairness between models (serve_model)
   std::mutex mu;
   std::condition_variable cv;
@@ -363,6 +364,7 @@ void serve_model(Server& S, ModelSlot* slot, const std::string& model) {
       sv.req.prompt = j->prompt;
       sv.req.n_predict = j->n_predict;
       sv.req.has_sampling = j->has_sampling; sv.req.has_seed = j->has_seed; sv.req.sampling = j->sampling;
+      sv.req.grammar = j->grammar;
       Job* jp = j.get();
       sv.req.on_piece = [jp](const std::string& p) {
         if (jp->cancelled) return false;
@@ -538,6 +540,7 @@ void generation_loop(Server& S) {
           reqs[i].n_predict = batch[i]->n_predict;
           reqs[i].has_sampling = batch[i]->has_sampling; reqs[i].has_seed = batch[i]->has_seed;
           reqs[i].sampling = batch[i]->sampling;
+          reqs[i].grammar = batch[i]->grammar;
           Job* jp = batch[i].get();
           reqs[i].on_piece = [jp](const std::string& p) {
             if (jp->cancelled) return false;
@@ -852,6 +855,7 @@ void spawn_job(Server& S, std::shared_ptr<Job> job) {
 struct ReqSampling {
   bool has = false, has_seed = false;
   RowSampling rec;
+  std::shared_ptr<const Grammar> grammar;
 };
 bool parse_sampling(Server& S, int fd, const Json& body, const std::string& model, ReqSampling* out) {
   static const char* const kFields[][2] = {{"temperature", "temp"}, {"top_k", "top_k"}, {"top_p", "top_p"},
@@ -899,9 +903,79 @@ bool parse_sampling(Server& S, int fd, const Json& body, const std::string& mode
   return true;
 }
 
+// Constrained output: "grammar" (GBNF text), "json_schema" (a schema object) or "response_format"
+// ({"type": "json_object"}, or {"type": "json_schema", "json_schema": {"schema": ..}} / {.., "schema": ..}),
+// at most one of them.  They need a server started with --row-masks.  Parsed grammars are kept by
+// their text.  false: a 400 was sent.
+bool parse_grammar(Server& S, int fd, const Json& body, const std::string& model, ReqSampling* out) {
+  int n = 0;
+  for (const char* k : {"grammar", "json_schema", "response_format"}) n += body.has(k) && !body[k].is_null() ? 1 : 0;
+  if (!n) return true;
+  if (n > 1) {
+    respond_text(fd, 400, "send one of grammar, json_schema and response_format, not several");
+    return false;
+  }
+  if (!S.spawn_cli.empty()) {
+    respond_text(fd, 400, "grammar, json_schema and response_format are not supported in --spawn-cli mode");
+    return false;
+  }
+  {
+    std::lock_guard<std::mutex> l(S.eng_mu);
+    Engine* e = S.eng;
+    if (!model.empty())
+      if (ModelSlot* m = find_model(S, model)) e = m->eng.get();
+    if (!e || !e->row_masks()) {
+      respond_text(fd, 400, "grammar, json_schema and response_format need a server started with --row-masks");
+      return false;
+    }
+  }
+  try {
+    std::string text;
+    if (body.has("grammar") && !body["grammar"].is_null()) {
+      if (!body["grammar"].is_str()) throw std::runtime_error("grammar is a string of GBNF text");
+      text = body["grammar"].str();
+      if (text.empty()) throw std::runtime_error("grammar is empty");
+    } else if (body.has("json_schema") && !body["json_schema"].is_null()) {
+      text = json_schema_to_gbnf(body["json_schema"]);
+    } else {
+      const Json& rf = body["response_format"];
+      const std::string type = rf.is_obj() ? rf.get_str("type", "") : "";
+      if (type == "json_object") {
+        Json any = Json::object();
+        any["type"] = "json_object";
+        text = json_schema_to_gbnf(rf.has("schema") ? rf["schema"] : any);
+      } else if (type == "json_schema") {
+        if (rf.has("json_schema") && rf["json_schema"].is_obj() && rf["json_schema"].has("schema")) text = json_schema_to_gbnf(rf["json_schema"]["schema"]);
+        else if (rf.has("schema")) text = json_schema_to_gbnf(rf["schema"]);
+        else throw std::runtime_error("response_format of type json_schema carries no schema");
+      } else {
+        throw std::runtime_error("response_format.type must be json_object or json_schema");
+      }
+    }
+    static std::mutex mu;
+    static std::map<std::string, std::shared_ptr<const Grammar>> cache;
+    std::lock_guard<std::mutex> l(mu);
+    auto it = cache.find(text);
+    if (it != cache.end() && it->second->table_full()) {   // its state tables only grow: start over
+      cache.erase(it);
+      it = cache.end();
+    }
+    if (it == cache.end()) {
+      if (cache.size() >= 64) cache.clear();
+      it = cache.emplace(text, Grammar::parse(text)).first;
+    }
+    out->grammar = it->second;
+  } catch (const std::exception& ex) {
+    respond_text(fd, 400, ex.what());
+    return false;
+  }
+  return true;
+}
+
 std::shared_ptr<Job> submit(Server& S, const std::string& prompt, int n, const std::string& model = "",
                             const ReqSampling* rs = nullptr) {
   auto job = std::make_shared<Job>();
+  if (rs) job->grammar = rs->grammar;
   if (rs && rs->has) { job->has_sampling = true; job->has_seed = rs->has_seed; job->sampling = rs->rec; }
   job->prompt = prompt;
   job->n_predict = n;
@@ -945,7 +1019,7 @@ void handle_chat(Server& S, int fd, const Request& r) {
   Json body;
   if (!parse_prompt_body(fd, r, &prompt, &n, S.default_n, &model, &body) || !known_model(S, fd, &model)) return;
   ReqSampling rs;
-  if (!parse_sampling(S, fd, body, model, &rs)) return;
+  if (!parse_sampling(S, fd, body, model, &rs) || !parse_grammar(S, fd, body, model, &rs)) return;
   auto job = submit(S, prompt, n, model, &rs);
   std::string h = "HTTP/1.1 200 OK\r\nContent-Type: text/event-stream\r\nCache-Control: no-cache\r\n";
   h += kCors;
@@ -1002,7 +1076,7 @@ void handle_completion(Server& S, int fd, const Request& r) {
     return;
   }
   ReqSampling rs;
-  if (!parse_sampling(S, fd, body, model, &rs)) return;
+  if (!parse_sampling(S, fd, body, model, &rs) || !parse_grammar(S, fd, body, model, &rs)) return;
   auto job = submit(S, prompt, n, model, &rs);
   {
     std::unique_lock<std::mutex> l(job->mu);

@@ -147,6 +147,21 @@ _SIGS = {
     "mp_row_sampling_bytes": ([], c_int),
     "mp_row_adjust": ([c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p], c_int),
     "mp_sample_rows": ([c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p], c_int),
+    "mp_op_row_mask": ([c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p], c_int),
+    "mp_engine_set_slot_masks": ([c_void_p, c_void_p, c_int, c_void_p, c_int], c_int),
+    "mp_engine_row_masks": ([c_void_p], c_int),
+    "mp_grammar_parse": ([c_char_p, c_void_p], c_void_p),
+    "mp_grammar_free": ([c_void_p], None),
+    "mp_grammar_state_new": ([c_void_p], c_void_p),
+    "mp_grammar_state_clone": ([c_void_p], c_void_p),
+    "mp_grammar_state_free": ([c_void_p], None),
+    "mp_grammar_accept": ([c_void_p, c_int], c_int),
+    "mp_grammar_accept_text": ([c_void_p, c_void_p, c_int], c_int),
+    "mp_grammar_mask": ([c_void_p, c_void_p, c_int], c_int),
+    "mp_grammar_mask_words": ([c_void_p], c_int),
+    "mp_grammar_can_end": ([c_void_p], c_int),
+    "mp_grammar_only_end": ([c_void_p], c_int),
+    "mp_json_schema_to_gbnf": ([c_char_p], c_char_p),
     "mp_engine_decode": ([c_void_p, c_int], c_char_p),
     "mp_engine_tokens": ([c_void_p, c_void_p, c_int, c_int], c_int),
     "mp_engine_logprobs": ([c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int], c_int),

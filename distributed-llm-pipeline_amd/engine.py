@@ -14,7 +14,8 @@ kv_dtype ("f16" | "fp8"), kv_pool_tokens (paged KV pool), prefill_gemm_v (0 auto
 deterministic, fused_norm, small_gemv, act_dtype (stage-boundary wire: "auto" | "f32" | "bf16" | "f16"),
 device_speed ("probe" or a list; Halda-style partition weights), n_probs (token logprobs: 0 off, -1 the
 chosen token's only, 1..20 plus that many alternatives; read with logprobs()), row_sampling (per-request
-sampling: every sequence slot has its own record, see set_slot_sampling).
+sampling: every sequence slot has its own record, see set_slot_sampling), row_masks (a token mask per
+sequence slot for constrained output, see set_slot_masks and mipipe.grammar; switches row_sampling on).
 """
 from __future__ import annotations
 
@@ -104,6 +105,40 @@ class Engine:
         j["seed"] = int(j["seed"])
         return j
 
+    @property
+    def row_masks(self) -> bool:
+        """Whether the engine was built with row_masks (set_slot_masks raises without it)."""
+        return bool(N.lib().mp_engine_row_masks(self._h))
+
+    def set_slot_masks(self, slots, masks, _for_start: bool = False):
+        """Per-slot token masks (Engine(row_masks=True)): masks[i] is a uint32 array of
+        ceil(vocab / 32) words for slot slots[i] (token t allowed iff masks[i][t >> 5] >> (t & 31) & 1,
+        what mipipe.grammar's State.mask() returns) or None to clear the slot's mask.  From the slot's
+        next token on every other token is banned, after the logit bias and the penalties and before
+        the cuts and the draw.  Legal for idle slots before admit() and between decode() calls for running
+        slots.  The masks of a generation's FIRST tokens go through start(..., masks=) / admit(..., masks=):
+        start() clears every mask the generation before it left, so a mask set here for a slot that is
+        still busy with that generation (it was never released) would not survive it; those arguments
+        mark the masks as meant for the call.  release() clears a slot's mask, load_state() all of them."""
+        slots = [int(s) for s in slots]
+        if len(slots) != len(masks):
+            raise ValueError("set_slot_masks: one mask or None per slot")
+        nw = (self.info["model"]["vocab"] + 31) // 32
+        keep = []
+        ptrs = (ctypes.c_void_p * max(len(slots), 1))()
+        for i, m in enumerate(masks):
+            if m is None:
+                ptrs[i] = None
+                continue
+            a = np.ascontiguousarray(m, dtype=np.uint32)
+            if a.size != nw:
+                raise ValueError(f"set_slot_masks: a mask has {a.size} words, {nw} expected")
+            keep.append(a)
+            ptrs[i] = a.ctypes.data
+        sl = np.asarray(slots, np.int32)
+        N.check(N.lib().mp_engine_set_slot_masks(self._h, sl.ctypes.data, len(slots), ptrs, int(_for_start)),
+                "set_slot_masks")
+
     def _set_sampling(self, slots, sampling, for_start=False):
         if sampling is None:
             return
@@ -113,18 +148,30 @@ class Engine:
             if f is not None:
                 self.set_slot_sampling(sl, _for_start=for_start, **f)
 
-    def start(self, prompts, sampling=None):
-        """sampling (row_sampling engines): one dict of set_slot_sampling fields or None per prompt."""
+    def _set_masks(self, slots, masks):
+        if masks is None:
+            return
+        if len(masks) != len(slots):
+            raise ValueError("masks: one mask or None per prompt")
+        self.set_slot_masks(list(slots), list(masks), _for_start=True)
+
+    def start(self, prompts, sampling=None, masks=None):
+        """sampling (row_sampling engines): one dict of set_slot_sampling fields or None per prompt.
+        masks (row_masks engines): one set_slot_masks mask or None per prompt; they constrain the
+        prompts' first tokens and stay until changed, whatever the slots ran before."""
         flat, lens = self._flat(prompts)
         self._n_seq = len(prompts)
         self._set_sampling(range(len(prompts)), sampling, for_start=True)   # start() resets every slot
+        self._set_masks(range(len(prompts)), masks)
         N.check(N.lib().mp_engine_start(self._h, flat.ctypes.data, lens.ctypes.data, len(prompts)), "start")
 
-    def admit(self, slots, prompts, sampling=None):
+    def admit(self, slots, prompts, sampling=None, masks=None):
         """Continuous batching: between decode rounds, prefill `prompts` into the idle sequence slots
-        `slots` (slot = micro-batch * mb_size + row); the other slots keep generating.  sampling: as start()."""
+        `slots` (slot = micro-batch * mb_size + row); the other slots keep generating.  sampling, masks: as
+        start()."""
         flat, lens = self._flat(prompts)
         self._set_sampling(list(slots), sampling)
+        self._set_masks(list(slots), masks)
         sl = np.asarray(slots, np.int32)
         N.check(N.lib().mp_engine_admit(self._h, sl.ctypes.data, flat.ctypes.data, lens.ctypes.data, len(prompts)),
                 "admit")

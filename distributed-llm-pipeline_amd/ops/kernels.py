@@ -531,6 +531,20 @@ def sample_rows(logits: torch.Tensor, records: torch.Tensor, draw: torch.Tensor,
     return out
 
 
+def row_mask(logits: torch.Tensor, bits: torch.Tensor, on: torch.Tensor, n: int | None = None) -> torch.Tensor:
+    """In place: in every row m with on[m] != 0, logits[m][t] = -inf for each t < n whose bit
+    bits[m][t >> 5] >> (t & 31) & 1 is clear.  logits f32 [M][>= n] (row stride free, 4-byte aligned),
+    bits int32 [M][ldw] holding the uint32 words, on int32 [M].  Nothing else is written."""
+    M = logits.shape[0]
+    n = logits.shape[1] if n is None else n
+    assert logits.dtype == torch.float32 and logits.stride(1) == 1 and n <= logits.shape[1]
+    assert bits.dtype == torch.int32 and bits.shape[0] == M and bits.stride(1) == 1
+    assert on.dtype == torch.int32 and on.numel() == M and on.is_contiguous()
+    N.check(N.lib().mp_op_row_mask(_ptr(logits), logits.stride(0), n, M, _ptr(bits), bits.stride(0), _ptr(on),
+                                   _stream()), "row_mask")
+    return logits
+
+
 LOGPROB_MAX_TOP = 20
 
 
