@@ -52,7 +52,17 @@ $(BUILD)/fuzz_host_asan: $(SAN_SRC) $(HDRS) | $(BUILD)
 	  -Icsrc/runtime $(SAN_SRC) -o $@
 sanitize: $(BUILD)/fuzz_host_asan
 
+# the same for the LoRA adapter reader (lora.cpp parses user-supplied adapter files): a stand-alone
+# program, run as a plain executable over adapter files and corrupted copies of them
+SAN_LORA_SRC := csrc/tools/fuzz_lora.cpp csrc/runtime/lora.cpp csrc/runtime/gguf.cpp csrc/runtime/model.cpp \
+                csrc/runtime/pack.cpp csrc/runtime/log.cpp
+# (ROCm's clang: pack.cpp's f16 conversion uses _Float16, which older g++ lacks; host code only)
+$(BUILD)/fuzz_lora_asan: $(SAN_LORA_SRC) $(HDRS) | $(BUILD)
+	$(ROCM)/llvm/bin/clang++ -std=c++17 -O1 -g -fno-omit-frame-pointer -fsanitize=address,undefined -fno-sanitize-recover=all \
+	  -Icsrc/runtime $(SAN_LORA_SRC) -o $@
+sanitize-lora: $(BUILD)/fuzz_lora_asan
+
 clean:
 	rm -rf $(BUILD) $(LIBDIR)/libmipipe.so $(TOOLS)
 
-.PHONY: all tools clean sanitize
+.PHONY: all tools clean sanitize sanitize-lora

@@ -812,6 +812,37 @@ int mp_sample_rows(const void* logits, int ld, int n, int M, const void* rows, v
   return 0;
   API_CATCH(-1)
 }
+// LoRA (lora.h / lora.hip): the host tile-table builder the stages use, and the two kernels
+int mp_lora_max_tiles(int M, int n_adapters) { return lora_max_tiles(M, n_adapters); }
+int mp_lora_table_words(int max_tiles) { return (int)lora_table_words(max_tiles); }
+int mp_lora_rank_pad(int r) { return lora_rank_pad(r); }
+int mp_lora_target_rec_bytes() { return (int)sizeof(LoraTargetRec); }
+int64_t mp_lora_part_floats(int max_tiles, int K, int n_t, int rcap) { return (int64_t)lora_part_floats(max_tiles, K, n_t, rcap); }
+int mp_lora_build_tiles(const int32_t* ids, const float* scales, int M, int n_adapters, int max_tiles, int32_t* out) {
+  API_TRY
+  if (!ids && M > 0) throw std::runtime_error("lora tiles: no ids");
+  return lora_build_tiles(ids, scales, M, n_adapters, max_tiles, out);
+  API_CATCH(-1)
+}
+// which: 0 shrink, 1 expand; tgt / N / yoff: n_t ints each
+int mp_op_lora(int which, const void* tiles, int max_tiles, const void* targets, int n_adapters, int n_layers, int layer,
+               int n_t, const int32_t* tgt, const int32_t* N, const int32_t* yoff, const void* X, int ldx, int K, void* Y,
+               int ldy, void* part, int64_t part_floats, int rcap, void* stream) {
+  API_TRY
+  if (n_t < 1 || n_t > 3 || !tgt || !N || !yoff) throw std::runtime_error("lora: a group holds 1..3 targets");
+  LoraGroupParams p{};
+  p.tiles = (const int32_t*)tiles; p.max_tiles = max_tiles; p.targets = (const LoraTargetRec*)targets;
+  p.n_adapters = n_adapters; p.n_layers = n_layers; p.layer = layer; p.n_t = n_t;
+  for (int i = 0; i < n_t; ++i) { p.tgt[i] = tgt[i]; p.N[i] = N[i]; p.yoff[i] = yoff[i]; }
+  p.X = (const f16*)X; p.ldx = ldx; p.K = K; p.Y = (float*)Y; p.ldy = ldy;
+  p.part = (float*)part; p.part_floats = (size_t)std::max<int64_t>(part_floats, 0); p.rcap = rcap;
+  if (which == 0) launch_lora_shrink(p, (hipStream_t)stream);
+  else launch_lora_expand(p, (hipStream_t)stream);
+  HIP_OK(hipGetLastError());
+  return 0;
+  API_CATCH(-1)
+}
+
 int mp_op_row_mask(void* logits, int ld, int n, int M, const void* bits, int ldw, const void* on, void* stream) {
   API_TRY
   RowMaskParams p{};
@@ -1106,6 +1137,33 @@ int mp_engine_set_slot_masks(void* h, const int32_t* slots, int n, const void* c
   API_CATCH(-1)
 }
 int mp_engine_row_masks(void* h) { return static_cast<Engine*>(h)->row_masks() ? 1 : 0; }
+// LoRA adapters: load -> the adapter's id; adapters -> JSON list; set_slot_adapters: n slots, ids (-1: none), scales
+int mp_engine_load_adapter(void* h, const char* path) {
+  API_TRY
+  if (!path) throw std::runtime_error("load_adapter: no path");
+  return static_cast<Engine*>(h)->load_adapter(path);
+  API_CATCH(-1)
+}
+int mp_engine_unload_adapter(void* h, int id) {
+  API_TRY
+  static_cast<Engine*>(h)->unload_adapter(id);
+  return 0;
+  API_CATCH(-1)
+}
+const char* mp_engine_adapters(void* h) {
+  API_TRY
+  g_str = static_cast<Engine*>(h)->adapters().dump();
+  return g_str.c_str();
+  API_CATCH(nullptr)
+}
+int mp_engine_set_slot_adapters(void* h, const int32_t* slots, int n, const int32_t* ids, const float* scales, int for_start) {
+  API_TRY
+  if (n < 0 || (n > 0 && (!slots || !ids || !scales))) throw std::runtime_error("set_slot_adapters: bad arguments");
+  static_cast<Engine*>(h)->set_slot_adapters(std::vector<int>(slots, slots + n), std::vector<int>(ids, ids + n),
+                                             std::vector<float>(scales, scales + n), for_start != 0);
+  return 0;
+  API_CATCH(-1)
+}
 int mp_engine_release(void* h, int slot) {
   API_TRY
   static_cast<Engine*>(h)->release(slot);

@@ -122,9 +122,82 @@ CpuStage::CpuStage(const ModelConfig& cfg, const StageSpec& spec, const StageOpt
   int nt = opt_.threads > 0 ? opt_.threads : default_cpu_threads();
   pool_.reset(new ThreadPool(std::max(1, std::min(nt, 64))));
   layers_.resize(spec_.layer_end - spec_.layer_begin);
+  if (opt_.lora_adapters > 0) {
+    lora_.resize(opt_.lora_adapters);
+    row_ad_.assign((size_t)opt_.n_mb * opt_.mb_size, -1);
+    row_sc_.assign((size_t)opt_.n_mb * opt_.mb_size, 0.f);
+  }
 }
 
 CpuStage::~CpuStage() = default;
+
+size_t CpuStage::load_adapter(int id, const GgufFile& f) {
+  if (lora_.empty()) return Stage::load_adapter(id, f);
+  if (id < 0 || id >= (int)lora_.size() || lora_[id].used) throw std::runtime_error("load_adapter: adapter id " + std::to_string(id) + " is not free");
+  LoraFile lf = lora_read(f, cfg_, opt_.lora_max_rank, spec_.layer_begin, spec_.layer_end);
+  Adapter& a = lora_[id];
+  a.pairs = std::move(lf.pairs);
+  a.index.assign(layers_.size() * LORA_N_TARGETS, -1);
+  a.bytes = 0;
+  for (size_t i = 0; i < a.pairs.size(); ++i) {
+    a.index[(size_t)(a.pairs[i].layer - spec_.layer_begin) * LORA_N_TARGETS + a.pairs[i].target] = (int)i;
+    a.bytes += (a.pairs[i].A.size() + a.pairs[i].B.size()) * 4;
+  }
+  a.used = true;
+  weight_bytes_ += a.bytes;
+  return a.bytes;
+}
+
+void CpuStage::unload_adapter(int id) {
+  if (lora_.empty()) return Stage::unload_adapter(id);
+  if (id < 0 || id >= (int)lora_.size() || !lora_[id].used) throw std::runtime_error("unload_adapter: adapter id " + std::to_string(id) + " is not loaded");
+  for (int a : row_ad_)
+    if (a == id) throw std::runtime_error("unload_adapter: adapter " + std::to_string(id) + " is bound to a slot");
+  weight_bytes_ -= lora_[id].bytes;
+  lora_[id] = Adapter{};
+}
+
+void CpuStage::set_row_adapters(const std::vector<int>& slots, const std::vector<int>& ids, const std::vector<float>& scales) {
+  if (lora_.empty()) return Stage::set_row_adapters(slots, ids, scales);
+  if (ids.size() != slots.size() || scales.size() != slots.size()) throw std::runtime_error("set_row_adapters: one id and one scale per slot");
+  for (size_t i = 0; i < slots.size(); ++i) {
+    if (slots[i] < 0 || slots[i] >= (int)row_ad_.size()) throw std::runtime_error("set_row_adapters: bad slot");
+    if (ids[i] < -1 || ids[i] >= (int)lora_.size() || (ids[i] >= 0 && !lora_[ids[i]].used))
+      throw std::runtime_error("set_row_adapters: adapter id " + std::to_string(ids[i]) + " is not loaded");
+  }
+  for (size_t i = 0; i < slots.size(); ++i) {
+    row_ad_[slots[i]] = ids[i];
+    row_sc_[slots[i]] = ids[i] >= 0 ? scales[i] : 0.f;
+  }
+}
+
+void CpuStage::lora_add(int li, int target, const float* X, int ldx, int M, float* Y, int ldy, const int32_t* slot) {
+  if (lora_.empty()) return;
+  std::vector<float> t;
+  for (int m = 0; m < M; ++m) {
+    const int id = row_ad_[slot[m]];
+    if (id < 0) continue;
+    const int pi = lora_[id].index[(size_t)li * LORA_N_TARGETS + target];
+    if (pi < 0) continue;
+    const LoraPair& p = lora_[id].pairs[pi];
+    const float s = row_sc_[slot[m]];
+    const float* x = X + (size_t)m * ldx;
+    t.assign(p.r, 0.f);
+    for (int j = 0; j < p.r; ++j) {
+      const float* a = p.A.data() + (size_t)j * p.K;
+      double acc = 0;
+      for (int k = 0; k < p.K; ++k) acc += (double)a[k] * x[k];
+      t[j] = (float)acc;
+    }
+    float* y = Y + (size_t)m * ldy;
+    for (int n = 0; n < p.N; ++n) {
+      const float* b = p.B.data() + (size_t)n * p.r;
+      float acc = 0;
+      for (int j = 0; j < p.r; ++j) acc += b[j] * t[j];
+      y[n] += s * acc;
+    }
+  }
+}
 
 CpuMat CpuStage::own_random(int type, int64_t N, int64_t K, uint64_t seed) {
   CpuMat m;
@@ -354,6 +427,9 @@ void CpuStage::layer_forward(int li, int M, float* x, const int32_t* pos, const 
   matmul(L.q, xn_.data(), d, M, qkv_.data(), ldq, false);
   matmul(L.k, xn_.data(), d, M, qkv_.data() + qd, ldq, false);
   matmul(L.v, xn_.data(), d, M, qkv_.data() + qd + kvd, ldq, false);
+  lora_add(li, LORA_Q, xn_.data(), d, M, qkv_.data(), ldq, slot);
+  lora_add(li, LORA_K, xn_.data(), d, M, qkv_.data() + qd, ldq, slot);
+  lora_add(li, LORA_V, xn_.data(), d, M, qkv_.data() + qd + kvd, ldq, slot);
   if (!L.bq.empty())
     for (int m = 0; m < M; ++m) {
       float* row = qkv_.data() + (size_t)m * ldq;
@@ -424,15 +500,20 @@ void CpuStage::layer_forward(int li, int M, float* x, const int32_t* pos, const 
     }
   });
   matmul(L.o, att_.data(), qd, M, x, d, true);
+  lora_add(li, LORA_O, att_.data(), qd, M, x, d, slot);
   rmsnorm(x, L.ffn_norm, xn_.data(), M);
-  ffn(L, M, xn_.data(), x);
+  ffn(L, li, M, xn_.data(), x, slot);
 }
 
-void CpuStage::ffn(const Layer& L, int M, const float* xn, float* x) {
+void CpuStage::ffn(const Layer& L, int li, int M, const float* xn, float* x, const int32_t* slot) {
   const int d = cfg_.d_model, F = cfg_.d_ff;
   auto swiglu = [&](const CpuMat& g, const CpuMat& u, const float* xin, int rows) {
     matmul(g, xin, d, rows, gu_.data(), 2 * F, false);
     matmul(u, xin, d, rows, gu_.data() + F, 2 * F, false);
+    if (!L.moe) {
+      lora_add(li, LORA_GATE, xin, d, rows, gu_.data(), 2 * F, slot);
+      lora_add(li, LORA_UP, xin, d, rows, gu_.data() + F, 2 * F, slot);
+    }
     for (int m = 0; m < rows; ++m)
       for (int j = 0; j < F; ++j) {
         const float a = gu_[(size_t)m * 2 * F + j], b = gu_[(size_t)m * 2 * F + F + j];
@@ -442,6 +523,7 @@ void CpuStage::ffn(const Layer& L, int M, const float* xn, float* x) {
   if (!L.moe) {
     swiglu(L.gate, L.up, xn, M);
     matmul(L.down, h_.data(), F, M, x, d, true);
+    lora_add(li, LORA_DOWN, h_.data(), F, M, x, d, slot);
     return;
   }
   const int E = cfg_.n_expert, k = cfg_.n_expert_used;

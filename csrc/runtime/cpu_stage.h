@@ -13,6 +13,7 @@
 
 #include "model.h"
 #include "cpu_qdot.h"
+#include "lora.h"
 #include "stage.h"
 #include "threadpool.h"
 
@@ -71,7 +72,13 @@ class CpuStage : public Stage {
   void matmul(const CpuMat& W, const float* X, int ldx, int M, float* Y, int ldy, bool accumulate);
   void rmsnorm(const float* x, const std::vector<float>& w, float* y, int M);
   void layer_forward(int li, int M, float* x, const int32_t* pos, const int32_t* slot);
-  void ffn(const Layer& L, int M, const float* xn, float* x);
+  void ffn(const Layer& L, int li, int M, const float* xn, float* x, const int32_t* slot);
+  // LoRA (opt_.lora_adapters > 0), plain f32: Y[m] += scale * B (A X[m]) for every row whose slot is bound
+  // to an adapter that has a pair for (layer li of this stage, target)
+  void lora_add(int li, int target, const float* X, int ldx, int M, float* Y, int ldy, const int32_t* slot);
+  size_t load_adapter(int id, const GgufFile& f) override;
+  void unload_adapter(int id) override;
+  void set_row_adapters(const std::vector<int>& slots, const std::vector<int>& ids, const std::vector<float>& scales) override;
   void head(int mb, int M, const float* x, int32_t* tok_out, uint64_t salt, bool advance = false);
   void head_rows(int mb, int M, int32_t* tok_out, bool advance);
   void set_row_sampling(int mb, int row, const RowSampling& r) override;
@@ -128,6 +135,12 @@ class CpuStage : public Stage {
   std::vector<RowSampling> rows_;            // row_sampling: per slot record and draw index
   std::vector<int32_t> draws_;
   std::vector<std::vector<uint32_t>> masks_;   // row_masks: per slot ceil(vocab / 32) words (empty: off)
+  // lora_adapters: per adapter id its pairs and their index by (layer of the stage, target), -1 = none;
+  // per slot the bound adapter (-1: none) and user scale
+  struct Adapter { bool used = false; std::vector<LoraPair> pairs; std::vector<int> index; size_t bytes = 0; };
+  std::vector<Adapter> lora_;
+  std::vector<int> row_ad_;
+  std::vector<float> row_sc_;
 };
 
 }  // namespace mp

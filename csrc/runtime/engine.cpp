@@ -416,6 +416,24 @@ Engine::Engine(const Json& j) : jcfg_(j) {
   so.row_sampling = row_sampling_;
   so.row_masks = row_masks_;
   so.moe_gemm = j.get_bool("moe_gemm", true);
+  lora_cap_ = j.get_int("lora_adapters", 0);
+  lora_max_rank_ = j.get_int("lora_max_rank", 64);
+  if (lora_cap_ < 0 || lora_cap_ > kLoraMaxAdapters)
+    throw std::runtime_error("\"lora_adapters\" must be 0.." + std::to_string(kLoraMaxAdapters));
+  if (lora_cap_ > 0) {
+    if (lora_max_rank_ < 1 || lora_max_rank_ > kLoraMaxRank)
+      throw std::runtime_error("\"lora_max_rank\" must be 1.." + std::to_string(kLoraMaxRank));
+    if (mode_ == "mp") throw std::runtime_error("\"lora_adapters\": mode \"mp\" is not supported");
+    if (j.get_int("world", 1) > 1) throw std::runtime_error("\"lora_adapters\": a multi-process ring (\"world\" > 1) is not supported");
+    if (j.has("rpc")) throw std::runtime_error("\"lora_adapters\": rpc workers (\"rpc\") are not supported");
+    so.lora_adapters = lora_cap_;
+    so.lora_max_rank = lora_max_rank_;
+    adapters_.assign((size_t)lora_cap_, AdapterRec{});
+    bind_id_.assign((size_t)M_ * B_, -1);
+    bind_scale_.assign((size_t)M_ * B_, 0.f);
+    bind_state_.assign((size_t)M_ * B_, 0);
+    kv_tag_.assign((size_t)M_ * B_, KvTag{});
+  }
   packed_prefill_ = j.get_bool("packed_prefill", true);
   prefix_cache_ = j.get_bool("prefix_cache", true);
   n_probs_ = j.get_int("n_probs", 0);
@@ -533,6 +551,23 @@ Engine::Engine(const Json& j) : jcfg_(j) {
     }
     std::memset(lp_host_, 0xff, words * 4);
   }
+  // adapters a rebuilt engine takes over from the one it replaces (failover_config), by id
+  if (lora_cap_ > 0 && j.has("lora_preload") && j["lora_preload"].is_arr())
+    for (const Json& a : j["lora_preload"].arr()) {
+      const int id = a.get_int("id", -1);
+      if (id < 0 || id >= lora_cap_) throw std::runtime_error("\"lora_preload\": adapter id out of range");
+      // ids below that the old engine had free stay free: occupy them for the duration of the load
+      std::vector<int> held;
+      for (int k = 0; k < id; ++k)
+        if (!adapters_[k].used) { adapters_[k].used = true; held.push_back(k); }
+      try {
+        load_adapter(a.get_str("path", ""));
+      } catch (...) {
+        for (int k : held) adapters_[k].used = false;
+        throw;
+      }
+      for (int k : held) adapters_[k].used = false;
+    }
   load_ms_ = now_ms() - t0;
   MP_LOGI("engine ready: %d stage(s), %d micro-batch(es) x %d seq, ctx %d, load %.1f ms", S_, M_, B_, max_ctx_,
           load_ms_);
@@ -1042,6 +1077,7 @@ Json Engine::health() const {
     st.push(o);
   }
   j["stages"] = st;
+  if (lora_cap_ > 0) j["lora_adapters"] = adapters();
   return j;
 }
 
@@ -1055,6 +1091,8 @@ Json Engine::health() const {
 Json Engine::failover_config(const Json& cfg, const Json& health) {
   Json c = cfg;
   c["fault"] = Json::object();   // an injected fault does not follow the engine across a rebuild
+  // the adapters the lost engine had loaded (its own record: ids and paths) go onto the rebuilt stages
+  if (health.has("lora_adapters") && health["lora_adapters"].is_arr()) c["lora_preload"] = health["lora_adapters"];
   const int S = cfg.get_int("stages", 1);   // GPU stages (a hybrid split puts its CPU stage 0 in front)
   if (!health.has("failed_stage") || S <= 1 || cfg.get_str("mode", "local") == "mp") return c;
   int bad = health.get_int("failed_stage", 0);
@@ -1167,6 +1205,7 @@ void Engine::start(const std::vector<std::vector<int32_t>>& prompts) {
     if (!prompts[i].empty() && (int)prompts[i].size() < max_ctx_) kv_grant(i, (int)prompts[i].size() + 1);
   kv_sync();
   clear_masks(false);
+  clear_bindings(false);
   {
     std::vector<size_t> all(prompts.size());
     std::iota(all.begin(), all.end(), (size_t)0);
@@ -1276,6 +1315,127 @@ void Engine::clear_masks(bool all) {
       w->stage->set_row_masks(slots, none.data());
     }
   for (int s : slots) mask_state_[s] = 0;
+}
+
+// ---------------------------------------------------------------- LoRA adapters
+int Engine::load_adapter(const std::string& path) {
+  if (lora_cap_ <= 0) throw std::runtime_error("load_adapter: the engine was built without \"lora_adapters\"");
+  int id = -1;
+  for (int k = 0; k < lora_cap_ && id < 0; ++k)
+    if (!adapters_[k].used) id = k;
+  if (id < 0) throw std::runtime_error("load_adapter: all " + std::to_string(lora_cap_) + " adapter ids (\"lora_adapters\") are in use");
+  GgufFile f(path);
+  // checked once against the whole model before any stage allocates
+  const LoraFile head = lora_read(f, cfg_, lora_max_rank_, 0, 0);
+  sync_all();
+  size_t bytes = 0;
+  std::vector<Worker*> done;
+  try {
+    for (auto& w : workers_) {
+      if (!w->cpu) HIP_OK(hipSetDevice(w->device));
+      bytes += w->stage->load_adapter(id, f);
+      done.push_back(w.get());
+    }
+  } catch (...) {
+    for (Worker* w : done) w->stage->unload_adapter(id);
+    throw;
+  }
+  AdapterRec& a = adapters_[id];
+  a.used = true; a.path = path; a.alpha = head.alpha; a.r_min = head.r_min; a.r_max = head.r_max; a.bytes = bytes;
+  a.serial = ++lora_serial_;
+  MP_LOGI("lora: adapter %d <- %s (alpha %g, ranks %d..%d, %d tensor pairs, %.2f MiB)", id, path.c_str(), a.alpha, a.r_min,
+          a.r_max, head.n_pairs, bytes / 1048576.0);
+  return id;
+}
+
+void Engine::unload_adapter(int id) {
+  if (lora_cap_ <= 0) throw std::runtime_error("unload_adapter: the engine was built without \"lora_adapters\"");
+  if (id < 0 || id >= lora_cap_ || !adapters_[id].used) throw std::runtime_error("unload_adapter: adapter id " + std::to_string(id) + " is not loaded");
+  for (size_t s = 0; s < bind_id_.size(); ++s)
+    if (bind_id_[s] == id) throw std::runtime_error("unload_adapter: adapter " + std::to_string(id) + " is bound to slot " + std::to_string(s));
+  sync_all();
+  for (auto& w : workers_) {
+    if (!w->cpu) HIP_OK(hipSetDevice(w->device));
+    w->stage->unload_adapter(id);
+  }
+  adapters_[id] = AdapterRec{};
+}
+
+Json Engine::adapters() const {
+  Json a = Json::array();
+  for (int k = 0; k < lora_cap_; ++k) {
+    if (!adapters_[k].used) continue;
+    Json o = Json::object();
+    o["id"] = k; o["path"] = adapters_[k].path; o["alpha"] = (double)adapters_[k].alpha;
+    o["rank_min"] = adapters_[k].r_min; o["rank_max"] = adapters_[k].r_max; o["bytes"] = (int64_t)adapters_[k].bytes;
+    a.push(o);
+  }
+  return a;
+}
+
+Engine::KvTag Engine::bind_tag(size_t slot) const {
+  KvTag t;
+  if (slot < bind_id_.size() && bind_id_[slot] >= 0) { t.serial = adapters_[bind_id_[slot]].serial; t.scale = bind_scale_[slot]; }
+  return t;
+}
+
+int Engine::slot_adapter(int slot, float* scale) const {
+  if (lora_cap_ <= 0 || slot < 0 || slot >= M_ * B_) return -1;
+  if (scale) *scale = bind_scale_[slot];
+  return bind_id_[slot];
+}
+
+void Engine::push_bindings(const std::vector<int>& slots, const std::vector<int>& ids, const std::vector<float>& scales) {
+  if (slots.empty()) return;
+  for (auto& w : workers_) {
+    if (!w->cpu) HIP_OK(hipSetDevice(w->device));
+    w->stage->set_row_adapters(slots, ids, scales);
+  }
+  for (size_t i = 0; i < slots.size(); ++i) {
+    const size_t s = (size_t)slots[i];
+    const bool changed = bind_id_[s] != ids[i] || (ids[i] >= 0 && bind_scale_[s] != scales[i]);
+    bind_id_[s] = ids[i];
+    bind_scale_[s] = ids[i] >= 0 ? scales[i] : 0.f;
+    // a running sequence's KV now mixes two bindings: no later prompt may reuse it as a prefix
+    if (changed && started_ && slot_active((int)s)) kv_tag_[s].serial = kMixedTag;
+  }
+}
+
+void Engine::set_slot_adapters(const std::vector<int>& slots, const std::vector<int>& ids, const std::vector<float>& scales,
+                               bool for_start) {
+  if (lora_cap_ <= 0) throw std::runtime_error("set_slot_adapters: the engine was built without \"lora_adapters\"");
+  if (ids.size() != slots.size() || scales.size() != slots.size())
+    throw std::runtime_error("set_slot_adapters: one adapter id and one scale per slot (stacking adapters on a sequence is not supported)");
+  for (size_t i = 0; i < slots.size(); ++i) {
+    const int s = slots[i];
+    if (s < 0 || s >= M_ * B_) throw std::runtime_error("set_slot_adapters: slot " + std::to_string(s) + " is out of range");
+    for (size_t k = 0; k < i; ++k)
+      if (slots[k] == s)
+        throw std::runtime_error("set_slot_adapters: slot " + std::to_string(s) + " is listed twice (one adapter per sequence)");
+    if (ids[i] < -1 || ids[i] >= lora_cap_ || (ids[i] >= 0 && !adapters_[ids[i]].used))
+      throw std::runtime_error("set_slot_adapters: adapter id " + std::to_string(ids[i]) + " is not loaded");
+    if (ids[i] >= 0 && !(scales[i] - scales[i] == 0.f)) throw std::runtime_error("set_slot_adapters: scale is not finite");
+  }
+  if (failed_) throw std::runtime_error("set_slot_adapters after a pipeline fault");
+  sync_all();
+  push_bindings(slots, ids, scales);
+  for (size_t i = 0; i < slots.size(); ++i)
+    bind_state_[slots[i]] = ids[i] < 0 ? 0 : (!for_start && started_ && slot_active(slots[i])) ? 2 : 1;
+}
+
+void Engine::clear_bindings(bool all) {
+  if (lora_cap_ <= 0) return;
+  std::vector<int> slots;
+  for (int s = 0; s < M_ * B_; ++s)
+    if (bind_state_[s] == 2 || (all && bind_state_[s])) slots.push_back(s);
+  for (int s = 0; s < M_ * B_; ++s)
+    if (bind_state_[s] == 1 && !all) bind_state_[s] = 2;   // set for this start(): in use from here on
+  if (slots.empty()) return;
+  const bool was = started_;
+  started_ = false;   // (the generation these bindings belonged to is over: nothing to mark as mixed)
+  push_bindings(slots, std::vector<int>(slots.size(), -1), std::vector<float>(slots.size(), 0.f));
+  started_ = was;
+  for (int s : slots) bind_state_[s] = 0;
 }
 
 RowSampling Engine::slot_sampling(int slot) const {
@@ -1445,6 +1605,10 @@ Json Engine::save_state(const std::string& dir) {
   if (!started_) throw std::runtime_error("save_state before start");
   if (failed_) throw std::runtime_error("save_state after a pipeline fault");
   if (!resumable_) throw std::runtime_error("save_state: not supported after speculative decoding");
+  for (size_t s = 0; s < bind_id_.size(); ++s)
+    if (bind_id_[s] >= 0)
+      throw std::runtime_error("save_state: slot " + std::to_string(s) + " is bound to LoRA adapter " + std::to_string(bind_id_[s]) +
+                               " (a checkpoint does not carry adapters: release or unbind the slots first)");
   ::mkdir(dir.c_str(), 0755);
   sync_all();
   const Json fp = state_fingerprint(cfg_, S_, M_, B_, max_ctx_, cpu_, kv_fp8_);
@@ -1676,6 +1840,8 @@ Json Engine::load_state(const std::string& dir) {
     throw std::runtime_error("load_state: the session was saved with row_sampling");
   }
   clear_masks(true);   // masks are not part of a checkpoint: every slot resumes unconstrained
+  clear_bindings(true);
+  for (KvTag& t : kv_tag_) t = KvTag{};   // a checkpoint is taken unbound: its KV is the base model's
   started_ = true;
   resumable_ = true;
   refresh_slot_cache();
@@ -1710,7 +1876,10 @@ std::vector<Item> Engine::prefill_items(const std::vector<size_t>& seqs, bool ad
       // prefix cache: the slot's KV already holds the tokens of slot_toks_[i]; only the part after
       // the common prefix is prefilled (at least the last prompt token, whose row feeds the head)
       int reuse = 0;
-      if (prefix_cache_ && i < slot_toks_.size()) {
+      // (a lora_adapters engine: only KV computed under the slot's present binding)
+      const bool same_bind = lora_cap_ <= 0 || (kv_tag_[i].serial == bind_tag(i).serial && kv_tag_[i].scale == bind_tag(i).scale);
+      if (lora_cap_ > 0) kv_tag_[i] = bind_tag(i);   // what this prefill computes the slot's KV under
+      if (prefix_cache_ && same_bind && i < slot_toks_.size()) {
         const auto& c = slot_toks_[i];
         const size_t lim = std::min(c.size(), (size_t)n - 1);
         while ((size_t)reuse < lim && c[reuse] == prompts_[i][reuse]) ++reuse;
@@ -1768,6 +1937,10 @@ void Engine::release(int slot) {
       }
     mask_state_[slot] = 0;
   }
+  if (lora_cap_ > 0 && !failed_ && slot >= 0 && slot < M_ * B_ && bind_state_[slot]) {
+    push_bindings({slot}, {-1}, {0.f});   // (the slot is idle by now: its KV tag stays what computed it)
+    bind_state_[slot] = 0;
+  }
 }
 
 void Engine::kv_grant(size_t slot, int n_tokens) {
@@ -1817,6 +1990,9 @@ void Engine::admit(const std::vector<int>& slots, const std::vector<std::vector<
   if (row_masks_)
     for (size_t i : seqs)
       if (mask_state_[i] == 1) mask_state_[i] = 2;   // set for this admission: in use from here on
+  if (lora_cap_ > 0)
+    for (size_t i : seqs)
+      if (bind_state_[i] == 1) bind_state_[i] = 2;
   for (auto& w : workers_) {
     Stage& st = *w->stage;
     if (!w->cpu) HIP_OK(hipSetDevice(w->device));
@@ -2435,6 +2611,8 @@ Json Engine::info() const {
     j["device_speed"] = ds;
   }
   j["kv_free_pages"] = pager_.free_pages();
+  j["lora_adapters"] = lora_cap_;
+  j["lora_max_rank"] = lora_max_rank_;
   {
     Json is = Json::array();
     for (int s : idle_slots()) is.push(s);

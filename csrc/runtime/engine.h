@@ -154,6 +154,24 @@ class Engine {
   // it: they survive it even when their slots are still busy with that generation
   void set_slot_masks(const std::vector<int>& slots, const uint32_t* const* bits, bool for_start = false);
   int mask_words() const { return (cfg_.vocab + 31) / 32; }
+  // LoRA adapters (config "lora_adapters": the capacity, 0 = off, <= 8; "lora_max_rank", default 64,
+  // <= 128; local mode).  load_adapter reads a llama.cpp adapter GGUF onto every stage (each its own
+  // layers) and returns its id, the lowest free one; it throws when all ids are in use or the file is
+  // refused (lora.h).  unload_adapter is refused while a slot is bound to the id.  set_slot_adapters
+  // binds slot slots[i] to adapter ids[i] (-1: none) at user scale scales[i]; one adapter per slot.
+  // Legal before start(), for idle slots before admit() and, for running slots, between decode_steps
+  // calls; never re-captures a graph.  A binding set for an idle slot holds for its next start() /
+  // admit(); start() clears the bindings of the generation before it, release() the slot's,
+  // load_state() all of them.  The prefix cache reuses a slot's KV only under the binding that computed
+  // it.  save_state throws while a slot is bound.
+  int lora_capacity() const { return lora_cap_; }
+  int load_adapter(const std::string& path);
+  void unload_adapter(int id);
+  Json adapters() const;   // [{"id", "path", "alpha", "rank_min", "rank_max", "bytes"}]
+  void set_slot_adapters(const std::vector<int>& slots, const std::vector<int>& ids, const std::vector<float>& scales,
+                         bool for_start = false);
+  // the slot's binding: id (-1: none) and scale
+  int slot_adapter(int slot, float* scale = nullptr) const;
   int32_t last_token(int slot) const { return slot < (int)gen_.size() && !gen_[slot].empty() ? gen_[slot].back() : -1; }
   int slot_position(int slot) const { return slot_pos((size_t)slot); }
   bool started() const { return started_; }
@@ -293,6 +311,22 @@ class Engine {
   void apply_slot_sampling(const std::vector<size_t>& seqs);   // before an admission's prefill
   void push_row_draws(int mb);                                 // after it: draw0 + tokens generated
   std::vector<Item> prefill_items(const std::vector<size_t>& seqs, bool admission);
+  // LoRA: the loaded adapters (serial: unique per load, so a reused id never matches an old KV tag), the
+  // slots' bindings with the masks' three states, and per slot the binding its cached KV was computed
+  // under (serial 0: the base model; kMixedTag: rebound mid-generation, never reused)
+  struct AdapterRec { bool used = false; std::string path; float alpha = 0.f; int r_min = 0, r_max = 0; size_t bytes = 0; uint64_t serial = 0; };
+  struct KvTag { uint64_t serial = 0; float scale = 0.f; };
+  static constexpr uint64_t kMixedTag = ~0ull;
+  int lora_cap_ = 0, lora_max_rank_ = 64;
+  uint64_t lora_serial_ = 0;
+  std::vector<AdapterRec> adapters_;
+  std::vector<int> bind_id_;
+  std::vector<float> bind_scale_;
+  std::vector<char> bind_state_;            // per slot: 0 none, 1 set for the next admission, 2 in use
+  std::vector<KvTag> kv_tag_;
+  KvTag bind_tag(size_t slot) const;
+  void push_bindings(const std::vector<int>& slots, const std::vector<int>& ids, const std::vector<float>& scales);
+  void clear_bindings(bool all);            // start(): those in use; load_state(): all
   double load_ms_ = 0;
   // persistent stage-worker threads of run_all (declared last: joined before anything they use
   // is destroyed)

@@ -114,12 +114,21 @@ GgufFile::GgufFile(const std::string& path) : path_(path) {
   for (size_t i = 0; i < tensors_.size(); ++i) {
     auto& t = tensors_[i];
     const int be = block_elems(t.type);
+    {
+      // the element count must fit the file many times over: checked here, before nelem() multiplies
+      uint64_t n = 1;
+      for (int64_t v : t.ne) {
+        if (v < 0 || (v > 0 && n > (1ull << 48) / (uint64_t)v)) throw std::runtime_error("gguf: tensor shape overflows: " + t.name);
+        n *= (uint64_t)v;
+      }
+    }
     if (be > 0) {
       if (t.ne[0] % be) throw std::runtime_error("gguf: tensor row not a block multiple: " + t.name);
       t.nbytes = (size_t)(t.nelem() / be) * block_bytes(t.type);
     }
+    if (t.offset > size_) throw std::runtime_error("gguf: tensor out of bounds: " + t.name);
     t.offset += data_start;
-    if (t.offset + t.nbytes > size_) throw std::runtime_error("gguf: tensor out of bounds: " + t.name);
+    if (t.offset > size_ || t.nbytes > size_ - t.offset) throw std::runtime_error("gguf: tensor out of bounds: " + t.name);
     t.data = map_ + t.offset;
     index_[t.name] = i;
   }

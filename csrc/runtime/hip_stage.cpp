@@ -83,6 +83,9 @@ HipStage::~HipStage() {
   for (void* p : allocs_) (void)hipFree(p);
   if (mask_host_) (void)hipHostFree(mask_host_);
   if (mask_on_host_) (void)hipHostFree(mask_on_host_);
+  if (lora_tab_host_) (void)hipHostFree(lora_tab_host_);
+  for (LoraDev& a : lora_)
+    for (void* p : a.bufs) (void)hipFree(p);
   if (stream_) (void)hipStreamDestroy(stream_);
 }
 
@@ -324,7 +327,8 @@ void HipStage::load_gguf(const GgufFile& f) {
     }
     const GgufTensor& tg = need(p + "ffn_gate.weight");
     const GgufTensor& tu = need(p + "ffn_up.weight");
-    if (tg.type == tu.type && cfg_.d_ff % 8 == 0) {
+    // (a lora_adapters stage needs gate and up as f32 before the SwiGLU: never fused)
+    if (tg.type == tu.type && cfg_.d_ff % 8 == 0 && !lora_on()) {
       L.fused_gateup = true;
       const size_t rb = row_bytes(tg.type, tg.ne[0]);
       const int64_t F = tg.ne[1];
@@ -405,8 +409,13 @@ void HipStage::init_synthetic(const std::string& ftype, uint64_t seed) {
       L.ex.down = experts(t.down, d, F, &L.ex.down_stride, s + 6);
       continue;
     }
-    L.fused_gateup = true;
-    L.gateup = alloc_packed_random(t.gate, 2 * F, d, s + 5);
+    L.fused_gateup = !lora_on();
+    if (L.fused_gateup) {
+      L.gateup = alloc_packed_random(t.gate, 2 * F, d, s + 5);
+    } else {
+      L.gate = alloc_packed_random(t.gate, F, d, s + 5);
+      L.up = alloc_packed_random(t.up, F, d, s + 8);
+    }
     L.down = alloc_packed_random(t.down, d, F, s + 6);
   }
   const SyntheticTypes t0 = SyntheticTypes::from_ftype(ftype, 0, cfg_.n_layer);
@@ -631,6 +640,32 @@ void HipStage::alloc_runtime() {
     std::memset(mask_host_, 0, words * 4);
     std::memset(mask_on_host_, 0, (size_t)n_slots * 4);
   }
+  if (lora_on()) {
+    if (opt_.lora_adapters > kLoraMaxAdapters) throw std::runtime_error("lora_adapters: at most " + std::to_string(kLoraMaxAdapters));
+    if (opt_.lora_max_rank < 1 || opt_.lora_max_rank > kLoraMaxRank)
+      throw std::runtime_error("lora_max_rank must be 1.." + std::to_string(kLoraMaxRank));
+    if (cfg_.d_model % 8 || cfg_.q_dim() % 8 || cfg_.d_ff % 8)
+      throw std::runtime_error("lora_adapters: d_model, n_head * head_dim and d_ff must be multiples of 8");
+    const int cap = opt_.lora_adapters;
+    lora_.resize(cap);
+    lora_rcap_ = lora_rank_pad(opt_.lora_max_rank);
+    lora_tgt_host_.assign((size_t)cap * layers_.size() * LORA_N_TARGETS, LoraTargetRec{});
+    lora_tgt_ = (LoraTargetRec*)zalloc(std::max<size_t>(lora_tgt_host_.size(), 1) * sizeof(LoraTargetRec));
+    lora_tiles_dec_ = lora_max_tiles(B, cap);
+    const size_t words = lora_table_words(lora_tiles_dec_);
+    for (int mb = 0; mb < NM; ++mb) lora_tab_.push_back((int32_t*)zalloc(words * 4));
+    HIP_OK(hipHostMalloc((void**)&lora_tab_host_, (size_t)NM * words * 4, hipHostMallocDefault));
+    std::memset(lora_tab_host_, 0, (size_t)NM * words * 4);
+    const int pf_tiles = lora_max_tiles(scratch_rows_, cap);
+    lora_tab_pf_ = (int32_t*)zalloc(lora_table_words(pf_tiles) * 4);
+    // the largest group: q|k|v and gate|up read d_model, o reads q_dim, down reads d_ff
+    const int mt = std::max(pf_tiles, lora_tiles_dec_);
+    lora_part_n_ = std::max({lora_part_floats(mt, cfg_.d_model, 3, lora_rcap_), lora_part_floats(mt, cfg_.q_dim(), 1, lora_rcap_),
+                             lora_part_floats(mt, cfg_.d_ff, 1, lora_rcap_)});
+    lora_part_ = (float*)dmalloc(lora_part_n_ * 4);
+    row_ad_.assign((size_t)n_slots, -1);
+    row_sc_.assign((size_t)n_slots, 0.f);
+  }
   HIP_OK(hipDeviceSynchronize());
   MP_LOGI("stage %d: layers %d-%d offloaded to GPU %d (%s), weights %.2f GiB, KV %.2f GiB (%d pages of 64 tokens; "
           "%d slots x <= %d ctx)",
@@ -796,6 +831,103 @@ void HipStage::set_row_masks(const std::vector<int>& slots, const uint32_t* cons
   }
   HIP_OK(hipMemcpyAsync(mask_on_, mask_on_host_, (size_t)n_slots * 4, hipMemcpyHostToDevice, stream_));
   HIP_OK(hipStreamSynchronize(stream_));
+}
+
+// ---- LoRA adapters (opt_.lora_adapters > 0)
+size_t HipStage::load_adapter(int id, const GgufFile& f) {
+  if (!lora_on()) return Stage::load_adapter(id, f);
+  if (id < 0 || id >= (int)lora_.size() || lora_[id].used) throw std::runtime_error("load_adapter: adapter id " + std::to_string(id) + " is not free");
+  const LoraFile lf = lora_read(f, cfg_, opt_.lora_max_rank, spec_.layer_begin, spec_.layer_end);
+  HIP_OK(hipSetDevice(spec_.device));
+  LoraDev a;
+  std::vector<LoraTargetRec> recs(layers_.size() * LORA_N_TARGETS);
+  try {
+    std::vector<uint16_t> A16, B16;
+    for (const LoraPair& p : lf.pairs) {
+      // the rows of B_q / B_k follow the base q / k rows' NEOX permutation; A reads the un-permuted input
+      const bool perm = cfg_.rope_neox && (p.target == LORA_Q || p.target == LORA_K);
+      lora_pack_f16(p, perm ? cfg_.head_dim : 0, &A16, &B16);
+      void* d[2] = {nullptr, nullptr};
+      const std::vector<uint16_t>* h[2] = {&A16, &B16};
+      for (int i = 0; i < 2; ++i) {
+        HIP_OK(hipMalloc(&d[i], std::max<size_t>(h[i]->size() * 2, 256)));
+        a.bufs.push_back(d[i]);
+        HIP_OK(hipMemcpy(d[i], h[i]->data(), h[i]->size() * 2, hipMemcpyHostToDevice));
+        a.bytes += h[i]->size() * 2;
+      }
+      LoraTargetRec& r = recs[(size_t)(p.layer - spec_.layer_begin) * LORA_N_TARGETS + p.target];
+      r.A = d[0]; r.B = d[1]; r.r_pad = lora_rank_pad(p.r);
+    }
+    HIP_OK(hipStreamSynchronize(stream_));   // no launch may read the table while it changes
+    std::copy(recs.begin(), recs.end(), lora_tgt_host_.begin() + (size_t)id * recs.size());
+    HIP_OK(hipMemcpy(lora_tgt_ + (size_t)id * recs.size(), recs.data(), recs.size() * sizeof(LoraTargetRec), hipMemcpyHostToDevice));
+  } catch (...) {
+    for (void* p : a.bufs) (void)hipFree(p);
+    throw;
+  }
+  a.used = true;
+  weight_bytes_ += a.bytes;
+  lora_[id] = std::move(a);
+  return lora_[id].bytes;
+}
+
+void HipStage::unload_adapter(int id) {
+  if (!lora_on()) return Stage::unload_adapter(id);
+  if (id < 0 || id >= (int)lora_.size() || !lora_[id].used) throw std::runtime_error("unload_adapter: adapter id " + std::to_string(id) + " is not loaded");
+  for (int32_t a : row_ad_)
+    if (a == id) throw std::runtime_error("unload_adapter: adapter " + std::to_string(id) + " is bound to a slot");
+  HIP_OK(hipSetDevice(spec_.device));
+  HIP_OK(hipStreamSynchronize(stream_));
+  const size_t n = layers_.size() * LORA_N_TARGETS;
+  std::fill(lora_tgt_host_.begin() + (size_t)id * n, lora_tgt_host_.begin() + (size_t)(id + 1) * n, LoraTargetRec{});
+  HIP_OK(hipMemcpy(lora_tgt_ + (size_t)id * n, lora_tgt_host_.data() + (size_t)id * n, n * sizeof(LoraTargetRec), hipMemcpyHostToDevice));
+  for (void* p : lora_[id].bufs) HIP_OK(hipFree(p));
+  weight_bytes_ -= lora_[id].bytes;
+  lora_[id] = LoraDev{};
+}
+
+// The tile tables of the micro-batches whose slots changed are rebuilt in the pinned mirror and copied
+// on the stage's stream; one synchronisation after the last copy (as set_row_masks).
+void HipStage::set_row_adapters(const std::vector<int>& slots, const std::vector<int>& ids, const std::vector<float>& scales) {
+  if (!lora_on()) return Stage::set_row_adapters(slots, ids, scales);
+  if (ids.size() != slots.size() || scales.size() != slots.size()) throw std::runtime_error("set_row_adapters: one id and one scale per slot");
+  const int B = opt_.mb_size;
+  for (size_t i = 0; i < slots.size(); ++i) {
+    if (slots[i] < 0 || slots[i] >= (int)row_ad_.size()) throw std::runtime_error("set_row_adapters: bad slot");
+    if (ids[i] < -1 || ids[i] >= (int)lora_.size() || (ids[i] >= 0 && !lora_[ids[i]].used))
+      throw std::runtime_error("set_row_adapters: adapter id " + std::to_string(ids[i]) + " is not loaded");
+    if (ids[i] >= 0 && !(scales[i] == scales[i] && scales[i] - scales[i] == 0.f)) throw std::runtime_error("set_row_adapters: scale is not finite");
+  }
+  if (slots.empty()) return;
+  std::vector<char> touched(opt_.n_mb, 0);
+  for (size_t i = 0; i < slots.size(); ++i) {
+    row_ad_[slots[i]] = ids[i];
+    row_sc_[slots[i]] = ids[i] >= 0 ? scales[i] : 0.f;
+    touched[slots[i] / B] = 1;
+  }
+  HIP_OK(hipSetDevice(spec_.device));
+  HIP_OK(hipStreamSynchronize(stream_));   // the mirror rows about to be rewritten are not in flight
+  const size_t words = lora_table_words(lora_tiles_dec_);
+  for (int mb = 0; mb < opt_.n_mb; ++mb) {
+    if (!touched[mb]) continue;
+    int32_t* h = lora_tab_host_ + (size_t)mb * words;
+    lora_build_tiles(row_ad_.data() + (size_t)mb * B, row_sc_.data() + (size_t)mb * B, B, opt_.lora_adapters, lora_tiles_dec_, h);
+    HIP_OK(hipMemcpyAsync(lora_tab_[mb], h, words * 4, hipMemcpyHostToDevice, stream_));
+  }
+  HIP_OK(hipStreamSynchronize(stream_));
+}
+
+void HipStage::lora_group(int li, const Fwd& f, int n_t, const int* tgt, const int* N, const int* yoff, const f16* X, int ldx,
+                          int K, float* Y, int ldy) {
+  if (!f.lora_tab) throw std::runtime_error("lora: the forward pass carries no tile table");
+  LoraGroupParams p{};
+  p.tiles = f.lora_tab; p.max_tiles = f.lora_tiles; p.targets = lora_tgt_;
+  p.n_adapters = opt_.lora_adapters; p.n_layers = (int)layers_.size(); p.layer = li; p.n_t = n_t;
+  for (int i = 0; i < n_t; ++i) { p.tgt[i] = tgt[i]; p.N[i] = N[i]; p.yoff[i] = yoff[i]; }
+  p.X = X; p.ldx = ldx; p.K = K; p.Y = Y; p.ldy = ldy;
+  p.part = lora_part_; p.part_floats = lora_part_n_; p.rcap = lora_rcap_;
+  launch_lora_shrink(p, f.st);
+  launch_lora_expand(p, f.st);
 }
 
 // token logprob buffers (last stage, n_probs != 0): allocated when recording is switched on and when
@@ -1153,7 +1285,7 @@ void HipStage::moe_ffn_rows(const LayerW& L, int r0, int M, hipStream_t st, floa
   if (opt_.deterministic) launch_moe_combine(moe_yslot_, d, k, M, d, x + (size_t)r0 * d, d, st);
 }
 
-void HipStage::ffn_tail(const LayerW& L, int M, float* x, bool small, bool fused, hipStream_t st) {
+void HipStage::ffn_tail(const LayerW& L, int M, float* x, bool small, bool fused, hipStream_t st, int li, const Fwd* f) {
   const int d = cfg_.d_model, F = cfg_.d_ff;
   auto up = [&](const PackedMat& m, int epi) {
     MatCall c = MatCall(m, epi, M).gemvs(small);
@@ -1164,10 +1296,18 @@ void HipStage::ffn_tail(const LayerW& L, int M, float* x, bool small, bool fused
   } else {
     gemv(up(L.gate, EPI_STORE).out(gu_, 2 * F, F), st);
     gemv(up(L.up, EPI_STORE).out(gu_ + F, 2 * F, F), st);
+    if (lora_on() && f) {   // gate and up are complete f32 rows here, before the SwiGLU consumes them
+      const int tg[2] = {LORA_GATE, LORA_UP}, n[2] = {F, F}, off[2] = {0, F};
+      lora_group(li, *f, 2, tg, n, off, xn_, Kd_, d, gu_, 2 * F);
+    }
     launch_swiglu(gu_, 2 * F, F, M, h_, Kff_, st);
   }
   // stored partials: absorbed by the next layer's attention norm (or flushed after the last layer)
   gemv(MatCall(L.down, EPI_ATOMIC, M).in(h_, Kff_).out(x, d, d).split(SplitK::DEFER).gemvs(small), st);
+  if (lora_on() && f) {   // (pending split-K partials of down and this delta are both plain adds into x, in stream order)
+    const int tg[1] = {LORA_DOWN}, n[1] = {d}, off[1] = {0};
+    lora_group(li, *f, 1, tg, n, off, h_, Kff_, F, x, d);
+  }
 }
 
 void HipStage::layer_forward(int li, float* x, const Fwd& f) {
@@ -1180,6 +1320,42 @@ void HipStage::layer_forward(int li, float* x, const Fwd& f) {
     return norm ? c.in_norm(x, L.attn_norm) : c.in(xn_, Kd_);
   };
   const MatCall wo = MatCall(L.wo, EPI_ATOMIC, M).in(attn_, Ko_).out(x, d, d);
+  const bool lora = lora_on();
+  // LoRA deltas of a group whose base projections have delivered (one shrink + one expand launch)
+  auto lora_qkv = [&] {
+    const int tg[3] = {LORA_Q, LORA_K, LORA_V}, n[3] = {cfg_.q_dim(), cfg_.kv_dim(), cfg_.kv_dim()};
+    const int off[3] = {0, cfg_.q_dim(), cfg_.q_dim() + cfg_.kv_dim()};
+    lora_group(li, f, 3, tg, n, off, xn_, Kd_, d, qkv_, qkv_n_);
+  };
+  auto lora_o = [&] {
+    const int tg[1] = {LORA_O}, n[1] = {d}, off[1] = {0};
+    lora_group(li, f, 1, tg, n, off, attn_, Ko_, cfg_.q_dim(), x, d);
+  };
+  if (lora && small_path(M)) {
+    // the gemvs family on a lora_adapters stage: the adapters read the normed f16 rows, so the norms run
+    // standalone into xn_; q|k|v stay complete and un-rotated until the delta is in (no RoPE + append
+    // epilogue, no fused attention + o), gate and up unfused (ffn_tail)
+    norm_x(x, L.attn_norm, M, nullptr, 0, st);
+    for (const MatSeg& s : L.qkv) {
+      MatCall c = qkv_seg(s, EPI_STORE, false).gemvs(true);
+      c.bias = L.qkv_bias ? L.qkv_bias + s.y_off : nullptr;
+      gemv(c, st);
+    }
+    lora_qkv();
+    qk_norm(L, M, st);
+    attention(li, f, false, false);
+    gemv(MatCall(wo).split().gemvs(true), st);
+    lora_o();
+    if (L.moe) {
+      launch_rmsnorm(x, d, L.ffn_norm, d, cfg_.eps, xn_, Kd_, M, moe_logits_, (int64_t)M * moe_ld_, st);
+      xq_src_ = nullptr;
+      moe_ffn(L, M, st, x);
+    } else {
+      norm_x(x, L.ffn_norm, M, nullptr, 0, st);
+      ffn_tail(L, M, x, true, false, st, li, &f);
+    }
+    return;
+  }
   if (small_path(M)) {
     // gemvs: RMSNorms fused into the qkv / gate-up GEMVs, complete outputs per workgroup (q|k|v
     // stored with its bias, o / down added into the residual by their single owner)
@@ -1227,7 +1403,7 @@ void HipStage::layer_forward(int li, float* x, const Fwd& f) {
   // attention applies rsqrt and the bias when it reads q|k|v.  The o-proj then clears ssq_ + the
   // q|k|v accumulator (invariant: zero outside [qkv GEMV, o-proj]; unfused forwards clear it after
   // their last layer).
-  const bool small = fuse_norm(M);
+  const bool small = fuse_norm(M) && !lora;   // (the deferred norm leaves no normed rows for the adapters)
   // (a q/k-normed layer normalises final q|k|v values: it takes the standalone attn_norm; the o-proj's
   // zero side job below still clears the range, so the invariant holds for the next layer)
   const bool qkv_deferred = small && f.decode && opt_.fused_attn && !L.q_norm;
@@ -1255,6 +1431,7 @@ void HipStage::layer_forward(int li, float* x, const Fwd& f) {
       gemv(c, st);
     }
   }
+  if (lora) lora_qkv();   // before the q / k norm and the rotation
   qk_norm(L, M, st);
   attention(li, f, qkv_deferred);
   if (small) {
@@ -1263,6 +1440,7 @@ void HipStage::layer_forward(int li, float* x, const Fwd& f) {
     gemv(c, st);
   } else {
     gemv(MatCall(wo).split(SplitK::DEFER), st);
+    if (lora) lora_o();
     if (opt_.fused_norm && li + 1 == (int)layers_.size())
       HIP_OK(hipMemsetAsync(ssq_, 0, (64 + (size_t)M * qkv_n_) * 4, st));
   }
@@ -1270,7 +1448,7 @@ void HipStage::layer_forward(int li, float* x, const Fwd& f) {
   // MoE: the same launch clears the router logits, which the router GEMV then accumulates split-K
   if (!ffn_fused) norm_x(x, L.ffn_norm, M, L.moe ? moe_logits_ : nullptr, L.moe ? (int64_t)M * moe_ld_ : 0, st);
   if (L.moe) moe_ffn(L, M, st, x);
-  else ffn_tail(L, M, x, false, ffn_fused, st);
+  else ffn_tail(L, M, x, false, ffn_fused, st, li, &f);
 }
 
 void HipStage::qk_norm(const LayerW& L, int M, hipStream_t st) {
@@ -1518,7 +1696,23 @@ void HipStage::prefill(int mb, const std::vector<PrefillSeg>& segs, hipStream_t 
     T += s.T;
   }
   if (T > opt_.prefill_chunk) throw std::runtime_error("prefill chunk too large");
-  const Fwd f{T, pf_pos_, pf_kvlen_, pf_slot_, false, -1, &segs, st};
+  Fwd f{T, pf_pos_, pf_kvlen_, pf_slot_, false, -1, &segs, st};
+  if (lora_on()) {
+    // the chunk's rows grouped by their slots' adapters; the table travels in kernel arguments, in
+    // stream order with the chunk's other metadata
+    std::vector<int32_t> ids;
+    std::vector<float> sc;
+    for (const PrefillSeg& s : segs) {
+      const size_t sl = (size_t)slot_of(mb, s.b);
+      ids.insert(ids.end(), s.T, row_ad_[sl]);
+      sc.insert(sc.end(), s.T, row_sc_[sl]);
+    }
+    const int mt = lora_max_tiles(T, opt_.lora_adapters);
+    std::vector<int32_t> tab(lora_table_words(mt));
+    lora_build_tiles(ids.data(), sc.data(), T, opt_.lora_adapters, mt, tab.data());
+    launch_lora_table(lora_tab_pf_, tab.data(), mt, st);
+    f.lora_tab = lora_tab_pf_; f.lora_tiles = std::max(mt, 1);
+  }
   for (size_t li = 0; li < layers_.size(); ++li) layer_forward((int)li, x, f);
   flush_sk(st);
   if (spec_.last() && !segs.empty() && segs[0].verify) {
@@ -1573,7 +1767,8 @@ void HipStage::decode_eager(int mb, hipStream_t st) {
   float* x = act_[mb];
   if (spec_.first())
     launch_embed(embd_type_, embd_raw_, (int64_t)embd_row_bytes_, cfg_.d_model, tok_[mb], B, x, cfg_.d_model, st);
-  const Fwd f{B, pos_[mb], kvlen_[mb], slot_[mb], true, slot_of(mb, 0), nullptr, st};   // slot_[mb][b] = slot0 + b
+  Fwd f{B, pos_[mb], kvlen_[mb], slot_[mb], true, slot_of(mb, 0), nullptr, st};   // slot_[mb][b] = slot0 + b
+  if (lora_on()) { f.lora_tab = lora_tab_[mb]; f.lora_tiles = lora_tiles_dec_; }
   for (size_t li = 0; li < layers_.size(); ++li) layer_forward((int)li, x, f);
   flush_sk(st);
   if (spec_.last()) head(mb, B, x, tok_[mb], (uint64_t)mb + 1, st, true);

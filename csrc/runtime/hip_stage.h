@@ -115,6 +115,7 @@ struct MatCall {
 struct Fwd {
   int M; const int32_t* pos; const int32_t* kvlen; const int32_t* slot; bool decode;
   int slot0; const std::vector<PrefillSeg>* segs; hipStream_t st;
+  const int32_t* lora_tab = nullptr; int lora_tiles = 0;   // lora_adapters: the call's tile table and its capacity
 };
 
 class HipStage : public Stage {
@@ -163,6 +164,9 @@ class HipStage : public Stage {
   void set_row_sampling(int mb, int row, const RowSampling& r) override;
   void set_row_draws(int mb, const std::vector<int32_t>& draws) override;
   void set_row_masks(const std::vector<int>& slots, const uint32_t* const* bits) override;
+  size_t load_adapter(int id, const GgufFile& f) override;
+  void unload_adapter(int id) override;
+  void set_row_adapters(const std::vector<int>& slots, const std::vector<int>& ids, const std::vector<float>& scales) override;
   long graph_captures() const override { return graph_captures_; }
 
   size_t weight_bytes() const override { return weight_bytes_; }
@@ -186,7 +190,8 @@ class HipStage : public Stage {
   void moe_ffn_rows(const LayerW& L, int r0, int M, hipStream_t st, float* x, bool grouped = false);
   // the dense FFN: gate/up (+ SwiGLU) into h_, down into the residual x.  small: the gemvs family;
   // fused: gate/up norm the f32 residual themselves (otherwise they read xn_)
-  void ffn_tail(const LayerW& L, int M, float* x, bool small, bool fused, hipStream_t st);
+  void ffn_tail(const LayerW& L, int M, float* x, bool small, bool fused, hipStream_t st, int li = -1,
+                const Fwd* f = nullptr);
   bool fuse_norm(int M) const;   // RMSNorm folded into the consuming GEMVs at this row count
   // Qwen3: per-head RMSNorm of the q and k heads of the complete q|k|v rows in qkv_ (no-op without weights)
   void qk_norm(const LayerW& L, int M, hipStream_t st);
@@ -318,6 +323,25 @@ class HipStage : public Stage {
   int32_t* mask_on_ = nullptr; int32_t* mask_on_host_ = nullptr;
   int mask_ldw_ = 0;
   long graph_captures_ = 0;
+  // LoRA (opt_.lora_adapters > 0; lora.h, lora.hip).  Per adapter id its device images; the target
+  // table [capacity][layers][7] on the device and its host copy; per micro-batch the decode tile table
+  // (rebuilt from the slots' bindings by set_row_adapters) and one table for the prefill chunk in
+  // flight (written on the stream by launch_lora_table); the shrink partials.
+  struct LoraDev { bool used = false; std::vector<void*> bufs; size_t bytes = 0; };
+  std::vector<LoraDev> lora_;
+  LoraTargetRec* lora_tgt_ = nullptr;
+  std::vector<LoraTargetRec> lora_tgt_host_;
+  std::vector<int32_t*> lora_tab_;
+  int32_t* lora_tab_pf_ = nullptr;
+  int32_t* lora_tab_host_ = nullptr;   // pinned mirror of the decode tables [n_mb][lora_table_words]
+  int lora_rcap_ = 0, lora_tiles_dec_ = 0;
+  float* lora_part_ = nullptr; size_t lora_part_n_ = 0;
+  std::vector<int32_t> row_ad_;        // per slot: bound adapter (-1: none) and user scale
+  std::vector<float> row_sc_;
+  bool lora_on() const { return opt_.lora_adapters > 0; }
+  // one shrink + one expand launch for a group of targets reading X [M][ldx] and adding into Y
+  void lora_group(int li, const Fwd& f, int n_t, const int* tgt, const int* N, const int* yoff, const f16* X, int ldx,
+                  int K, float* Y, int ldy);
   // prefill metadata
   int32_t* pf_pos_ = nullptr; int32_t* pf_kvlen_ = nullptr; int32_t* pf_slot_ = nullptr;
   int32_t* prompt_dev_ = nullptr;

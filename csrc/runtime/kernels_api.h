@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "gemm4_plan.h"   // Gemm4Plan, plan_gemm4, plan_moe_gemm4
+#include "lora.h"         // LoraTargetRec, LoraTile, lora_build_tiles
 
 typedef _Float16 f16;
 
@@ -460,5 +461,30 @@ void launch_moe_gemv(int ptype, int epi, MoeGemvParams p, int nsplit, hipStream_
 // (rows gathered by the A staging, epilogues scattered by slot).  SWIGLU (gate/up) or ATOMIC (down,
 // weighted; Yslot rows in the deterministic mode).  false = type not supported (nothing launched).
 bool launch_moe_gemm4(int ptype, int epi, const MoeGemvParams& p, hipStream_t st);
+
+// LoRA (lora.hip; tables and their host builder: lora.h).  One group = up to three targets that read
+// the same input rows: Y[row][yoff[i] + n] += scale[row] * sum_j B_i[n][j] (sum_k A_i[j][k] X[row][k])
+// for the rows listed in the tile table.  shrink stores per-K-split partials of t = A x into `part`,
+// expand sums them in a fixed order and adds into Y (plain f32 read-modify-write, one lane per
+// element, no atomics).  Both grids cover max_tiles; workgroups past the table's count return.
+struct LoraGroupParams {
+  const int32_t* tiles;            // device tile table, lora_table_words(max_tiles) words
+  int max_tiles;
+  const LoraTargetRec* targets;    // device [n_adapters][n_layers][LORA_N_TARGETS]
+  int n_adapters, n_layers, layer;
+  int n_t;                         // targets of the group, 1..3
+  int tgt[3], N[3], yoff[3];       // LoraTarget id, output columns, first column in Y
+  const f16* X; int ldx; int K;    // input rows (16-byte aligned, K % 8 == 0; indexed by the tiles' rows)
+  float* Y; int ldy;
+  float* part; size_t part_floats; // >= lora_part_floats(max_tiles, K, n_t, rcap)
+  int rcap;                        // partial row stride: lora_rank_pad of the largest rank allowed
+};
+int lora_ksplits(int K);
+size_t lora_part_floats(int max_tiles, int K, int n_t, int rcap);
+void launch_lora_shrink(const LoraGroupParams& p, hipStream_t st);
+void launch_lora_expand(const LoraGroupParams& p, hipStream_t st);
+// writes a host tile table (lora_build_tiles) into dev_tab with kernel launches that carry the tiles
+// by value: stream-ordered with the launches that read it, no host buffer to keep alive
+void launch_lora_table(int32_t* dev_tab, const int32_t* host_tab, int max_tiles, hipStream_t st);
 
 }  // namespace mp

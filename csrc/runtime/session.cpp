@@ -153,6 +153,9 @@ std::vector<GenResult> Session::run(std::vector<GenRequest>& reqs) {
   }
   if (any_grammar && eng_->config().get_int("draft_max", 0) > 0)
     throw std::runtime_error("a grammar cannot be combined with speculative decoding (draft_max)");
+  for (const GenRequest& r : reqs)
+    if (r.lora_id >= 0 && eng_->config().get_int("draft_max", 0) > 0)
+      throw std::runtime_error("a LoRA adapter cannot be combined with speculative decoding (draft_max)");
   auto sync_masks = [&](bool for_start) {
     std::vector<int> sl;
     std::vector<const GrammarState*> st;
@@ -259,6 +262,10 @@ std::vector<GenResult> Session::run(std::vector<GenRequest>& reqs) {
 }
 
 void Session::set_slot_record(int slot, const GenRequest& req, const GenResult& res) {
+  if (eng_->lora_capacity() > 0)
+    eng_->set_slot_adapters({slot}, {req.lora_id}, {req.lora_id >= 0 ? req.lora_scale : 0.f}, /*for_start=*/true);
+  else if (req.lora_id >= 0)
+    throw std::runtime_error("a LoRA adapter needs an engine built with lora_adapters");
   if (!eng_->row_sampling()) {
     if (req.has_sampling) throw std::runtime_error("per-request sampling needs an engine built with row_sampling");
     return;

@@ -31,6 +31,10 @@ struct GenRequest {
   // constrained output (engines built with row_masks): every token the request generates keeps its
   // text inside the grammar's language; it ends with stop "eog" as soon as nothing can follow
   std::shared_ptr<const Grammar> grammar;
+  // LoRA (engines built with lora_adapters): the adapter the request's slot is bound to (-1: the base
+  // model) and its user scale; bound in the same guarded call as the sampling record, kept across a failover
+  int lora_id = -1;
+  float lora_scale = 1.f;
   // receives text pieces (complete UTF-8); return false to cancel this sequence
   std::function<bool(const std::string& piece)> on_piece;
 };

@@ -53,6 +53,11 @@ struct StageOptions {
                                // bit is clear in the rows that are on (set_row_masks)
   bool small_gemv = true;   // M <= 4 rows: the gemvs kernels (gemvs.hip: x staged once per workgroup,
                             // RMSNorm fused into the qkv / gate-up / LM-head GEMVs, in-workgroup split-K)
+  int lora_adapters = 0;    // LoRA adapter capacity (0: off, <= 8).  > 0: the stage keeps complete, un-rotated f32
+                            // projection outputs and f16 input rows at every target (gate / up unfused, no RoPE +
+                            // append in the qkv GEMV, no deferred-norm qkv, no fused attention + o), whatever is
+                            // loaded or bound
+  int lora_max_rank = 64;   // largest rank an adapter tensor pair may have (<= 128)
 };
 
 struct PrefillSeg {
@@ -182,6 +187,25 @@ class Stage {
   // Captured graphs are not touched.  Throws on a stage built without the option.
   virtual void set_row_masks(const std::vector<int>& slots, const uint32_t* const* bits) {
     (void)slots; (void)bits;
+  }
+  // LoRA adapters (StageOptions::lora_adapters > 0), every stage, between engine calls.  load_adapter
+  // reads the pairs of this stage's layers from an adapter file (lora.h) into id `id` (free, < the
+  // capacity) and returns the bytes they take; unload_adapter frees them.  set_row_adapters binds
+  // sequence slot slots[i] (= mb * mb_size + row) to adapter ids[i] (-1: none) at user scale
+  // scales[i]: from the next prefill chunk / decode step on, the slot's rows get scale * B (A x) added
+  // to the projections the adapter covers.  None of the three touches a captured graph.  The defaults
+  // throw: the stage was built without the option.
+  virtual size_t load_adapter(int id, const GgufFile& f) {
+    (void)id; (void)f;
+    throw std::runtime_error("load_adapter: the stage was built without lora_adapters");
+  }
+  virtual void unload_adapter(int id) {
+    (void)id;
+    throw std::runtime_error("unload_adapter: the stage was built without lora_adapters");
+  }
+  virtual void set_row_adapters(const std::vector<int>& slots, const std::vector<int>& ids, const std::vector<float>& scales) {
+    (void)slots; (void)ids; (void)scales;
+    throw std::runtime_error("set_row_adapters: the stage was built without lora_adapters");
   }
   // how often capture_graphs() ran (health(): an admit on a row_sampling engine must not grow it)
   virtual long graph_captures() const { return 0; }

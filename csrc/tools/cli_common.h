@@ -31,6 +31,8 @@ struct CliOptions {
   std::string pooling;        // --pooling none|mean|cls|last ("" = the model's pooling_type, else last)
   int embd_normalize = 2;     // --embd-normalize: 2 = L2 (default), -1 = none
   std::string grammar;        // --grammar / --grammar-file / -j: the GBNF text the output must match ("" = free)
+  std::vector<std::pair<std::string, float>> lora;   // --lora FILE / --lora-scaled FILE SCALE, in id order
+  bool lora_init_without_apply = false;              // --lora-init-without-apply (server: no default adapter)
   int bench_prompt = 128, bench_warmup = 3, bench_steps = 20;
   std::string trace;
   std::string rpc;            // --rpc host:port,... (without --world): stage workers to attach to (rpc.h)
@@ -118,6 +120,11 @@ inline void print_common_usage(FILE* f) {
           "                            pooling_type, else last: in a causal model only the last row has seen the\n"
           "                            whole prompt); none prints one vector per token\n"
           "  --embd-normalize N        2: scale each vector to unit L2 length (default); -1: leave it as it is\n"
+          "  --lora FILE               LoRA adapter GGUF (llama.cpp's format); --lora-scaled FILE SCALE applies it at\n"
+          "                            SCALE.  mi-cli: exactly one, bound to every sequence; orchestrator: repeatable\n"
+          "                            (ids in order), one alone is every request's default unless\n"
+          "                            --lora-init-without-apply.  Sets the engine key lora_adapters (--lora-max-rank N,\n"
+          "                            default 64); not with --world or --rpc\n"
           "  --draft-max K             speculative decoding by prompt lookup: up to K drafted tokens per\n"
           "                            verify round (greedy; --lookup-ngram N, default 3)\n"
           "placement / pipeline:\n"
@@ -228,6 +235,16 @@ inline CliOptions parse_cli(int argc, char** argv,
     else if (a == "--n-probs") e["n_probs"] = std::atoi(val().c_str());
     else if (a == "--row-sampling") e["row_sampling"] = true;
     else if (a == "--row-masks") e["row_masks"] = true;
+    else if (a == "--lora") o.lora.push_back({val(), 1.f});
+    else if (a == "--lora-scaled") {
+      const std::string f = val(), sc = val();
+      char* end = nullptr;
+      const float v = std::strtof(sc.c_str(), &end);
+      if (end == sc.c_str() || *end || !(v - v == 0.f)) throw std::runtime_error("--lora-scaled " + f + ": bad scale " + sc);
+      o.lora.push_back({f, v});
+    }
+    else if (a == "--lora-init-without-apply") o.lora_init_without_apply = true;
+    else if (a == "--lora-max-rank") e["lora_max_rank"] = std::atoi(val().c_str());
     else if (a == "--grammar") { o.grammar = val(); ++n_grammar; }
     else if (a == "--grammar-file") { o.grammar = read_file(val()); ++n_grammar; }
     else if (a == "-j" || a == "--json-schema") {
@@ -262,6 +279,13 @@ inline CliOptions parse_cli(int argc, char** argv,
     if (e.get_int("draft_max", 0) > 0) throw std::runtime_error("a grammar cannot be combined with --draft-max");
     if (!e.has("gguf")) throw std::runtime_error("a grammar needs a model with a tokenizer (-m FILE)");
     e["row_masks"] = true;
+  }
+  if (!o.lora.empty()) {
+    if (world > 0) throw std::runtime_error("--lora needs every stage in this process (a multi-process ring, --world, is not supported)");
+    if (!rpc.empty()) throw std::runtime_error("--lora cannot be combined with --rpc workers");
+    if (e.get_int("draft_max", 0) > 0) throw std::runtime_error("--lora cannot be combined with --draft-max");
+    if ((int)o.lora.size() > 8) throw std::runtime_error("--lora: at most 8 adapters");
+    e["lora_adapters"] = (int)o.lora.size();
   }
   if (o.ngl == 0) e["backend"] = "cpu";
   else if (o.ngl > 0) e["gpu_layers"] = o.ngl;   // explicit -ngl only: >= n_layer puts every layer on the GPUs

@@ -198,6 +198,10 @@ int main(int argc, char** argv) {
   try {
     if (!o.grammar.empty() && (daemon || !state_load.empty()))
       throw std::runtime_error("a grammar cannot be combined with --daemon or --state-load");
+    if (o.lora.size() > 1)
+      throw std::runtime_error("--lora / --lora-scaled: exactly one adapter may be given (stacking adapters on a sequence is not supported)");
+    if (!o.lora.empty() && (daemon || !state_load.empty() || !state_save.empty() || o.bench))
+      throw std::runtime_error("--lora cannot be combined with --daemon, --state-load, --state-save or --bench");
     if (o.bench) {
       if (!o.eng.has("mb_size")) o.eng["mb_size"] = 16;
       const int need = o.bench_prompt + o.bench_warmup + o.bench_steps + 8;
@@ -214,6 +218,16 @@ int main(int argc, char** argv) {
       printf("%s\n", r.dump().c_str());
       if (!o.trace.empty()) eng.write_trace(o.trace);
       return 0;
+    }
+    // --lora: the one adapter, bound to every sequence slot (the prompt-scoring and embedding chunks of
+    // --perplexity / --embedding take the binding like any prefill chunk)
+    int lora_id = -1;
+    if (!o.lora.empty()) {
+      lora_id = eng.load_adapter(o.lora[0].first);
+      const int ns = eng.n_mb() * eng.mb_size();
+      std::vector<int> slots(ns), ids(ns, lora_id);
+      for (int i = 0; i < ns; ++i) slots[i] = i;
+      eng.set_slot_adapters(slots, ids, std::vector<float>(ns, o.lora[0].second));
     }
     Session s(eng, o.eng.get_str("gguf", ""));
     if (daemon) return run_daemon(s);
@@ -250,6 +264,7 @@ int main(int argc, char** argv) {
     reqs[0].prompt = o.prompt;
     reqs[0].n_predict = o.n_predict;
     if (!o.grammar.empty()) reqs[0].grammar = Grammar::parse(o.grammar);
+    if (lora_id >= 0) { reqs[0].lora_id = lora_id; reqs[0].lora_scale = o.lora[0].second; }
     reqs[0].on_piece = [](const std::string& p) {
       fwrite(p.data(), 1, p.size(), stdout);
       fflush(stdout);

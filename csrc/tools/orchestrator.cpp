@@ -83,6 +83,8 @@ struct Job {
   bool has_sampling = false, has_seed = false;
   RowSampling sampling;
   std::shared_ptr<const Grammar> grammar;   // constrained output (--row-masks): grammar | json_schema | response_format
+  int lora_id = -1;            // LoRA (--lora): the request's adapter (-1: the base model) and scale
+  float lora_scale = 1.f;
   double enqueued_ms = 0;   // fairness between models (serve_model)
   std::mutex mu;
   std::condition_variable cv;
@@ -177,6 +179,11 @@ struct Server {
   // messages, its stderr lines as "log" messages; a client disconnect kills the child
   std::string spawn_cli;
   std::vector<std::string> cli_args;
+  // --lora FILE ...: the default model's adapters in id order (loaded with its engine) and the scale
+  // each has by default; at most one is non-zero (one adapter per sequence)
+  std::vector<std::string> lora_paths;
+  std::vector<float> lora_scale;
+  std::mutex lora_mu;
 };
 
 Server* g_srv = nullptr;
@@ -223,6 +230,9 @@ void load_slot(Server& S, ModelSlot& m) {
     m.eng.reset();
   }
   std::unique_ptr<Engine> e(new Engine(m.cfg));
+  if (dflt && !m.cfg.has("lora_preload"))   // (a failover's replacement takes them over through its config)
+    for (size_t i = 0; i < S.lora_paths.size(); ++i)
+      if (e->load_adapter(S.lora_paths[i]) != (int)i) throw std::runtime_error("--lora: adapter ids out of order");
   std::unique_ptr<Session> ss(new Session(*e, m.cfg.get_str("gguf", "")));
   std::lock_guard<std::mutex> l(S.eng_mu);
   m.eng = std::move(e);
@@ -365,6 +375,7 @@ void serve_model(Server& S, ModelSlot* slot, const std::string& model) {
       sv.req.n_predict = j->n_predict;
       sv.req.has_sampling = j->has_sampling; sv.req.has_seed = j->has_seed; sv.req.sampling = j->sampling;
       sv.req.grammar = j->grammar;
+      sv.req.lora_id = j->lora_id; sv.req.lora_scale = j->lora_scale;
       Job* jp = j.get();
       sv.req.on_piece = [jp](const std::string& p) {
         if (jp->cancelled) return false;
@@ -540,6 +551,7 @@ void generation_loop(Server& S) {
           reqs[i].n_predict = batch[i]->n_predict;
           reqs[i].has_sampling = batch[i]->has_sampling; reqs[i].has_seed = batch[i]->has_seed;
           reqs[i].sampling = batch[i]->sampling;
+          reqs[i].lora_id = batch[i]->lora_id; reqs[i].lora_scale = batch[i]->lora_scale;
           reqs[i].grammar = batch[i]->grammar;
           Job* jp = batch[i].get();
           reqs[i].on_piece = [jp](const std::string& p) {
@@ -856,7 +868,58 @@ struct ReqSampling {
   bool has = false, has_seed = false;
   RowSampling rec;
   std::shared_ptr<const Grammar> grammar;
+  int lora_id = -1;
+  float lora_scale = 1.f;
 };
+
+// [{"id", "scale"}, ..] -> the one adapter with a non-zero scale (-1: none).  Throws naming the cause.
+void parse_lora_list(const Json& a, size_t n_adapters, int* id, float* scale) {
+  if (!a.is_arr()) throw std::runtime_error("lora: expected a list of {\"id\", \"scale\"} objects");
+  *id = -1;
+  *scale = 0.f;
+  for (const Json& e : a.arr()) {
+    if (!e.is_obj() || !e.has("id") || !e["id"].is_num()) throw std::runtime_error("lora: every entry needs a numeric \"id\"");
+    const double idv = e["id"].num();
+    if (idv < 0 || idv >= (double)n_adapters || idv != (double)(int)idv)
+      throw std::runtime_error("lora: unknown adapter id " + e["id"].dump() + " (" + std::to_string(n_adapters) + " loaded)");
+    if (e.has("scale") && !e["scale"].is_num()) throw std::runtime_error("lora: \"scale\" must be a number");
+    const double sc = e.has("scale") ? e["scale"].num() : 1.0;
+    if (!(sc - sc == 0.0)) throw std::runtime_error("lora: \"scale\" must be finite");
+    if (sc == 0.0) continue;
+    if (*id >= 0) throw std::runtime_error("lora: more than one adapter with a non-zero scale (one adapter per sequence)");
+    *id = (int)idv;
+    *scale = (float)sc;
+  }
+}
+
+// The request's adapter: its "lora" field, else the server's default.  false: a 400 was sent.
+bool parse_lora(Server& S, int fd, const Json& body, const std::string& model, ReqSampling* out) {
+  const bool has = body.has("lora") && !body["lora"].is_null();
+  ModelSlot* dm = S.models.empty() ? nullptr : S.models[0].get();
+  const bool dflt_model = model.empty() || (dm && model == dm->name);
+  if (has && (S.lora_paths.empty() || !S.spawn_cli.empty() || S.mock)) {
+    respond_text(fd, 400, "lora: this server was started without --lora");
+    return false;
+  }
+  if (has && !dflt_model) {
+    respond_text(fd, 400, "lora: the adapters belong to the default model");
+    return false;
+  }
+  if (!dflt_model || S.lora_paths.empty()) return true;
+  if (!has) {
+    std::lock_guard<std::mutex> l(S.lora_mu);
+    for (size_t i = 0; i < S.lora_scale.size(); ++i)
+      if (S.lora_scale[i] != 0.f) { out->lora_id = (int)i; out->lora_scale = S.lora_scale[i]; }
+    return true;
+  }
+  try {
+    parse_lora_list(body["lora"], S.lora_paths.size(), &out->lora_id, &out->lora_scale);
+  } catch (const std::exception& ex) {
+    respond_text(fd, 400, ex.what());
+    return false;
+  }
+  return true;
+}
 bool parse_sampling(Server& S, int fd, const Json& body, const std::string& model, ReqSampling* out) {
   static const char* const kFields[][2] = {{"temperature", "temp"}, {"top_k", "top_k"}, {"top_p", "top_p"},
                                            {"min_p", "min_p"}, {"seed", "seed"}, {"repeat_penalty", "repeat"},
@@ -976,6 +1039,7 @@ std::shared_ptr<Job> submit(Server& S, const std::string& prompt, int n, const s
                             const ReqSampling* rs = nullptr) {
   auto job = std::make_shared<Job>();
   if (rs) job->grammar = rs->grammar;
+  if (rs) { job->lora_id = rs->lora_id; job->lora_scale = rs->lora_scale; }
   if (rs && rs->has) { job->has_sampling = true; job->has_seed = rs->has_seed; job->sampling = rs->rec; }
   job->prompt = prompt;
   job->n_predict = n;
@@ -1019,7 +1083,7 @@ void handle_chat(Server& S, int fd, const Request& r) {
   Json body;
   if (!parse_prompt_body(fd, r, &prompt, &n, S.default_n, &model, &body) || !known_model(S, fd, &model)) return;
   ReqSampling rs;
-  if (!parse_sampling(S, fd, body, model, &rs) || !parse_grammar(S, fd, body, model, &rs)) return;
+  if (!parse_sampling(S, fd, body, model, &rs) || !parse_grammar(S, fd, body, model, &rs) || !parse_lora(S, fd, body, model, &rs)) return;
   auto job = submit(S, prompt, n, model, &rs);
   std::string h = "HTTP/1.1 200 OK\r\nContent-Type: text/event-stream\r\nCache-Control: no-cache\r\n";
   h += kCors;
@@ -1076,7 +1140,7 @@ void handle_completion(Server& S, int fd, const Request& r) {
     return;
   }
   ReqSampling rs;
-  if (!parse_sampling(S, fd, body, model, &rs) || !parse_grammar(S, fd, body, model, &rs)) return;
+  if (!parse_sampling(S, fd, body, model, &rs) || !parse_grammar(S, fd, body, model, &rs) || !parse_lora(S, fd, body, model, &rs)) return;
   auto job = submit(S, prompt, n, model, &rs);
   {
     std::unique_lock<std::mutex> l(job->mu);
@@ -1301,6 +1365,36 @@ void handle_metrics(Server& S, int fd) {
   respond(fd, 200, "text/plain; version=0.0.4", m);
 }
 
+// GET /lora-adapters: [{"id", "path", "scale"}], scale = the default every request without a "lora" field gets
+void handle_lora_get(Server& S, int fd) {
+  Json arr = Json::array();
+  std::lock_guard<std::mutex> l(S.lora_mu);
+  for (size_t i = 0; i < S.lora_paths.size(); ++i) {
+    Json o = Json::object();
+    o["id"] = (int)i; o["path"] = S.lora_paths[i]; o["scale"] = (double)S.lora_scale[i];
+    arr.push(o);
+  }
+  respond(fd, 200, "application/json", arr.dump());
+}
+
+// POST /lora-adapters [{"id", "scale"}]: the new defaults (adapters not listed go to 0)
+void handle_lora_post(Server& S, int fd, const Request& r) {
+  if (S.lora_paths.empty()) return respond_text(fd, 400, "lora: this server was started without --lora");
+  int id = -1;
+  float scale = 0.f;
+  try {
+    parse_lora_list(Json::parse(r.body), S.lora_paths.size(), &id, &scale);
+  } catch (const std::exception& e) {
+    return respond_text(fd, 400, e.what());
+  }
+  {
+    std::lock_guard<std::mutex> l(S.lora_mu);
+    std::fill(S.lora_scale.begin(), S.lora_scale.end(), 0.f);
+    if (id >= 0) S.lora_scale[id] = scale;
+  }
+  handle_lora_get(S, fd);
+}
+
 void handle_conn(Server& S, int fd, std::string peer) {
   S.connections++;
   Request r;
@@ -1320,6 +1414,10 @@ void handle_conn(Server& S, int fd, std::string peer) {
       } else if (r.path == "/embedding" || r.path == "/embeddings" || r.path == "/v1/embeddings") {
         if (r.method != "POST") respond(fd, 405, "text/plain; charset=utf-8", "Method Not Allowed", "Allow: POST\r\n");
         else if (authorized(S, fd, r)) handle_embedding(S, fd, r, r.path == "/v1/embeddings");
+      } else if (r.path == "/lora-adapters") {
+        if (r.method == "GET") handle_lora_get(S, fd);
+        else if (r.method != "POST") respond(fd, 405, "text/plain; charset=utf-8", "Method Not Allowed", "Allow: GET, POST\r\n");
+        else if (authorized(S, fd, r)) handle_lora_post(S, fd, r);
       } else if (r.path == "/metrics" && r.method == "GET") {
         handle_metrics(S, fd);
       } else if (r.path == "/health" && r.method == "GET") {
@@ -1425,6 +1523,9 @@ int main(int argc, char** argv) {
   }
   S.mock = mock;
   S.default_n = o.n_predict;
+  // --lora FILE ...: one adapter alone is every request's default (at its scale) unless --lora-init-without-apply
+  for (auto& a : o.lora) { S.lora_paths.push_back(a.first); S.lora_scale.push_back(0.f); }
+  if (o.lora.size() == 1 && !o.lora_init_without_apply) S.lora_scale[0] = o.lora[0].second;
   if (!S.spawn_cli.empty()) {
     // forward the model / engine flags to every child; the server's own flags stay here
     static const char* own1[] = {"--port", "--host", "--static", "--api-key", "--rate-limit", "--mock-delay-ms",

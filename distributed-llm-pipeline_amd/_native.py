@@ -148,6 +148,18 @@ _SIGS = {
     "mp_row_adjust": ([c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p], c_int),
     "mp_sample_rows": ([c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p], c_int),
     "mp_op_row_mask": ([c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p], c_int),
+    "mp_lora_max_tiles": ([c_int, c_int], c_int),
+    "mp_lora_table_words": ([c_int], c_int),
+    "mp_lora_rank_pad": ([c_int], c_int),
+    "mp_lora_target_rec_bytes": ([], c_int),
+    "mp_lora_part_floats": ([c_int, c_int, c_int, c_int], c_int64),
+    "mp_lora_build_tiles": ([c_void_p, c_void_p, c_int, c_int, c_int, c_void_p], c_int),
+    "mp_op_lora": ([c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                    c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_int64, c_int, c_void_p], c_int),
+    "mp_engine_load_adapter": ([c_void_p, c_char_p], c_int),
+    "mp_engine_unload_adapter": ([c_void_p, c_int], c_int),
+    "mp_engine_adapters": ([c_void_p], c_char_p),
+    "mp_engine_set_slot_adapters": ([c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int], c_int),
     "mp_engine_set_slot_masks": ([c_void_p, c_void_p, c_int, c_void_p, c_int], c_int),
     "mp_engine_row_masks": ([c_void_p], c_int),
     "mp_grammar_parse": ([c_char_p, c_void_p], c_void_p),

@@ -15,7 +15,9 @@ deterministic, fused_norm, small_gemv, act_dtype (stage-boundary wire: "auto" | 
 device_speed ("probe" or a list; Halda-style partition weights), n_probs (token logprobs: 0 off, -1 the
 chosen token's only, 1..20 plus that many alternatives; read with logprobs()), row_sampling (per-request
 sampling: every sequence slot has its own record, see set_slot_sampling), row_masks (a token mask per
-sequence slot for constrained output, see set_slot_masks and mipipe.grammar; switches row_sampling on).
+sequence slot for constrained output, see set_slot_masks and mipipe.grammar; switches row_sampling on),
+lora_adapters (LoRA adapter capacity, 0 off, at most 8; see load_adapter / set_slot_adapters) and
+lora_max_rank (largest rank of an adapter tensor pair, default 64, at most 128).
 """
 from __future__ import annotations
 
@@ -139,6 +141,50 @@ class Engine:
         N.check(N.lib().mp_engine_set_slot_masks(self._h, sl.ctypes.data, len(slots), ptrs, int(_for_start)),
                 "set_slot_masks")
 
+    def load_adapter(self, path: str) -> int:
+        """Load a llama.cpp LoRA adapter GGUF (Engine(lora_adapters=n)); returns its id, the lowest free
+        one.  Every stage takes the tensor pairs of its own layers.  Raises when all ids are in use or
+        the file is refused (wrong type / architecture, a tensor the engine takes no adapter on, a
+        shape or rank that does not fit), naming the tensor or field."""
+        return N.check(N.lib().mp_engine_load_adapter(self._h, N.cstr(str(path))), "load_adapter")
+
+    def unload_adapter(self, adapter_id: int):
+        """Free an adapter id; refused while a slot is bound to it."""
+        N.check(N.lib().mp_engine_unload_adapter(self._h, int(adapter_id)), "unload_adapter")
+
+    def adapters(self) -> list:
+        """The loaded adapters: [{"id", "path", "alpha", "rank_min", "rank_max", "bytes"}]."""
+        return N.jcall(N.lib().mp_engine_adapters, self._h, what="adapters")
+
+    def set_slot_adapters(self, slots, ids, scales=None, _for_start: bool = False):
+        """Bind sequence slot slots[i] to adapter ids[i] (-1 or None: the base model) at user scale
+        scales[i] (default 1): the slot's rows get scale * alpha / r * B (A x) added to the projections
+        the adapter covers, from its next prefill chunk or decode step on.  One adapter per slot.  Legal
+        for idle slots before admit() and between decode() calls for running slots; no graph is
+        re-captured.  Bindings of a generation's prompts go through start(..., adapters=) /
+        admit(..., adapters=).  release() clears a slot's binding, start() those of the generation
+        before it, load_state() all of them; save_state() raises while a slot is bound."""
+        slots = [int(s) for s in slots]
+        ids = [-1 if a is None else int(a) for a in ids]
+        scales = [1.0] * len(slots) if scales is None else [float(x) for x in scales]
+        if len(ids) != len(slots) or len(scales) != len(slots):
+            raise ValueError("set_slot_adapters: one adapter id and one scale per slot")
+        sl, ia, sc = np.asarray(slots, np.int32), np.asarray(ids, np.int32), np.asarray(scales, np.float32)
+        N.check(N.lib().mp_engine_set_slot_adapters(self._h, sl.ctypes.data, len(slots), ia.ctypes.data, sc.ctypes.data,
+                                                    int(_for_start)), "set_slot_adapters")
+
+    def _set_adapters(self, slots, adapters):
+        if adapters is None:
+            return
+        slots = list(slots)
+        if len(adapters) != len(slots):
+            raise ValueError("adapters: one (id, scale) pair or None per prompt")
+        for a in adapters:
+            if a is not None and (not isinstance(a, (tuple, list)) or len(a) != 2 or isinstance(a[0], (tuple, list))):
+                raise ValueError("adapters: one (id, scale) pair per prompt (stacking adapters is not supported)")
+        self.set_slot_adapters(slots, [None if a is None else a[0] for a in adapters],
+                               [1.0 if a is None else a[1] for a in adapters], _for_start=True)
+
     def _set_sampling(self, slots, sampling, for_start=False):
         if sampling is None:
             return
@@ -155,23 +201,27 @@ class Engine:
             raise ValueError("masks: one mask or None per prompt")
         self.set_slot_masks(list(slots), list(masks), _for_start=True)
 
-    def start(self, prompts, sampling=None, masks=None):
+    def start(self, prompts, sampling=None, masks=None, adapters=None):
         """sampling (row_sampling engines): one dict of set_slot_sampling fields or None per prompt.
         masks (row_masks engines): one set_slot_masks mask or None per prompt; they constrain the
-        prompts' first tokens and stay until changed, whatever the slots ran before."""
+        prompts' first tokens and stay until changed, whatever the slots ran before.
+        adapters (lora_adapters engines): one (adapter id, scale) pair or None (the base model) per
+        prompt; without the argument every prompt runs unbound."""
         flat, lens = self._flat(prompts)
         self._n_seq = len(prompts)
         self._set_sampling(range(len(prompts)), sampling, for_start=True)   # start() resets every slot
         self._set_masks(range(len(prompts)), masks)
+        self._set_adapters(range(len(prompts)), adapters)
         N.check(N.lib().mp_engine_start(self._h, flat.ctypes.data, lens.ctypes.data, len(prompts)), "start")
 
-    def admit(self, slots, prompts, sampling=None, masks=None):
+    def admit(self, slots, prompts, sampling=None, masks=None, adapters=None):
         """Continuous batching: between decode rounds, prefill `prompts` into the idle sequence slots
-        `slots` (slot = micro-batch * mb_size + row); the other slots keep generating.  sampling, masks: as
-        start()."""
+        `slots` (slot = micro-batch * mb_size + row); the other slots keep generating.  sampling, masks,
+        adapters: as start()."""
         flat, lens = self._flat(prompts)
         self._set_sampling(list(slots), sampling)
         self._set_masks(list(slots), masks)
+        self._set_adapters(list(slots), adapters)
         sl = np.asarray(slots, np.int32)
         N.check(N.lib().mp_engine_admit(self._h, sl.ctypes.data, flat.ctypes.data, lens.ctypes.data, len(prompts)),
                 "admit")

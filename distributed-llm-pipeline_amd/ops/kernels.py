@@ -545,6 +545,78 @@ def row_mask(logits: torch.Tensor, bits: torch.Tensor, on: torch.Tensor, n: int 
     return logits
 
 
+LORA_TARGETS = ("attn_q", "attn_k", "attn_v", "attn_output", "ffn_gate", "ffn_up", "ffn_down")
+
+
+def lora_rank_pad(r: int) -> int:
+    """The rank the LoRA kernels see (A [r_pad][K], B [N][r_pad], zero-filled)."""
+    return N.lib().mp_lora_rank_pad(int(r))
+
+
+def lora_max_tiles(M: int, n_adapters: int) -> int:
+    return N.lib().mp_lora_max_tiles(int(M), int(n_adapters))
+
+
+def lora_tile_table(ids, scales=None, n_adapters: int = 8, max_tiles: int | None = None) -> np.ndarray:
+    """The tile table of a row -> adapter list, built by the builder the stages use: ids[m] is row m's
+    adapter or -1, scales[m] its user scale.  int32 words: [0] the tile count, then from word 4 tiles
+    of (adapter, 3 unused, 16 row indices -1 padded, 16 f32 scales)."""
+    ids = np.ascontiguousarray(ids, np.int32)
+    sc = np.ascontiguousarray(np.ones(len(ids)) if scales is None else scales, np.float32)
+    assert sc.shape == ids.shape
+    mt = lora_max_tiles(len(ids), n_adapters) if max_tiles is None else int(max_tiles)
+    out = np.zeros(N.lib().mp_lora_table_words(max(mt, 1)), np.int32)
+    N.check(N.lib().mp_lora_build_tiles(ids.ctypes.data, sc.ctypes.data, len(ids), int(n_adapters), mt,
+                                        out.ctypes.data), "lora_tile_table")
+    return out
+
+
+def lora_target_table(pairs: dict, n_adapters: int, n_layers: int, device) -> torch.Tensor:
+    """The device table [n_adapters][n_layers][7] of (A pointer, B pointer, r_pad) from
+    {(adapter, layer, target): (A f16 [r_pad][K], B f16 [N][r_pad])} of device tensors the caller
+    keeps alive; a missing key leaves the target absent (null pointers)."""
+    rec = np.zeros((n_adapters, n_layers, len(LORA_TARGETS)),
+                   dtype=[("A", "<u8"), ("B", "<u8"), ("r_pad", "<i4"), ("pad", "<i4")])
+    assert rec.dtype.itemsize == N.lib().mp_lora_target_rec_bytes()
+    for (a, layer, t), (A, B) in pairs.items():
+        assert A.dtype == torch.float16 and B.dtype == torch.float16 and A.is_contiguous() and B.is_contiguous()
+        assert A.shape[0] == B.shape[1] and A.shape[0] % 32 == 0
+        rec[a, layer, t] = (A.data_ptr(), B.data_ptr(), A.shape[0], 0)
+    return torch.from_numpy(rec.view(np.uint8).reshape(-1).copy()).to(device)
+
+
+def lora_part(max_tiles: int, K: int, n_t: int, rcap: int, device) -> torch.Tensor:
+    """Split-K partial scratch of one shrink / expand pair (deliberately not zeroed by the kernels'
+    contract: every word expand reads was stored by shrink)."""
+    n = N.lib().mp_lora_part_floats(int(max_tiles), int(K), int(n_t), int(rcap))
+    return torch.full((max(n, 1),), float("nan"), dtype=torch.float32, device=device)
+
+
+def _lora(which, tiles, max_tiles, targets, n_adapters, n_layers, layer, tgt, n_cols, yoff, x, K, y, part, rcap):
+    assert x.dtype == torch.float16 and x.stride(1) == 1 and y.dtype == torch.float32 and y.stride(1) == 1
+    assert tiles.dtype == torch.int32 and tiles.numel() >= N.lib().mp_lora_table_words(max_tiles)
+    n_t = len(tgt)
+    arr = lambda v: np.ascontiguousarray(v, np.int32)
+    tg, nc, yo = arr(tgt), arr(n_cols), arr(yoff)
+    assert len(nc) == n_t and len(yo) == n_t
+    N.check(N.lib().mp_op_lora(which, _ptr(tiles), int(max_tiles), _ptr(targets), int(n_adapters), int(n_layers),
+                               int(layer), n_t, tg.ctypes.data, nc.ctypes.data, yo.ctypes.data, _ptr(x), x.stride(0),
+                               int(K), _ptr(y), y.stride(0), _ptr(part), part.numel(), int(rcap), _stream()),
+            "lora_expand" if which else "lora_shrink")
+
+
+def lora_shrink(tiles, max_tiles, targets, n_adapters, n_layers, layer, tgt, n_cols, yoff, x, K, y, part, rcap) -> None:
+    """Per tile of `tiles` (device int32 table of lora_tile_table) and K split: part <- A x for the
+    targets `tgt` (ids into LORA_TARGETS) of the tile's adapter at `layer`.  x f16 [M][ldx >= K]."""
+    _lora(0, tiles, max_tiles, targets, n_adapters, n_layers, layer, tgt, n_cols, yoff, x, K, y, part, rcap)
+
+
+def lora_expand(tiles, max_tiles, targets, n_adapters, n_layers, layer, tgt, n_cols, yoff, x, K, y, part, rcap) -> None:
+    """y[row][yoff[i] + n] += scale[row] * B_i[n] . (the partials of lora_shrink summed in split order),
+    n < n_cols[i], for the rows of the tiles; nothing else of y is written."""
+    _lora(1, tiles, max_tiles, targets, n_adapters, n_layers, layer, tgt, n_cols, yoff, x, K, y, part, rcap)
+
+
 LOGPROB_MAX_TOP = 20
 
 
