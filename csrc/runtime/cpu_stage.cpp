@@ -720,7 +720,7 @@ void CpuStage::set_row_masks(const std::vector<int>& slots, const uint32_t* cons
   }
 }
 
-// Host counterpart of HipStage::head_rows: bias and penalties in f32 as the kernels apply them, the
+// Host counterpart of HipHead::run's row form: bias and penalties in f32 as the kernels apply them, the
 // chain in double, the variate of the request's own stream (kernels_api.h, RowSampling)
 void CpuStage::head_rows(int mb, int M, int32_t* tok_out, bool advance) {
   const int B = opt_.mb_size, V = cfg_.vocab, top_n = std::max(n_probs_, 0);

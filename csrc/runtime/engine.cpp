@@ -411,7 +411,7 @@ Engine::Engine(const Json& j) : jcfg_(j) {
       throw std::runtime_error("\"row_masks\": true needs per-request sampling: \"row_sampling\": false contradicts it");
     if (mode_ == "mp") throw std::runtime_error("\"row_masks\": mode \"mp\" is not supported");
     row_sampling_ = true;
-    mask_state_.assign((size_t)M_ * B_, 0);
+    mask_life_.reset((size_t)M_ * B_);
   }
   so.row_sampling = row_sampling_;
   so.row_masks = row_masks_;
@@ -431,7 +431,7 @@ Engine::Engine(const Json& j) : jcfg_(j) {
     adapters_.assign((size_t)lora_cap_, AdapterRec{});
     bind_id_.assign((size_t)M_ * B_, -1);
     bind_scale_.assign((size_t)M_ * B_, 0.f);
-    bind_state_.assign((size_t)M_ * B_, 0);
+    bind_life_.reset((size_t)M_ * B_);
     kv_tag_.assign((size_t)M_ * B_, KvTag{});
   }
   packed_prefill_ = j.get_bool("packed_prefill", true);
@@ -1212,9 +1212,8 @@ void Engine::start(const std::vector<std::vector<int32_t>>& prompts) {
     apply_slot_sampling(all);
   }
   std::vector<Item> items;
-  for (auto& w : workers_) {
-    Stage& st = *w->stage;
-    if (!w->cpu) HIP_OK(hipSetDevice(w->device));
+  for_each_stage([&](Worker& w) {
+    Stage& st = *w.stage;
     for (int mb = 0; mb < M_; ++mb) {
       std::vector<int32_t> pos(B_, 0);
       for (int b = 0; b < B_; ++b) {
@@ -1233,12 +1232,12 @@ void Engine::start(const std::vector<std::vector<int32_t>>& prompts) {
     if (st.spec().first()) {
       for (size_t i = 0; i < prompts.size(); ++i) {
         if (prompts[i].empty() || (int)prompts[i].size() >= max_ctx_) throw std::runtime_error("bad prompt length");
-        if (w->cpu) std::memcpy(st.prompt_buf() + i * max_ctx_, prompts[i].data(), prompts[i].size() * 4);
+        if (w.cpu) std::memcpy(st.prompt_buf() + i * max_ctx_, prompts[i].data(), prompts[i].size() * 4);
         else HIP_OK(hipMemcpy(st.prompt_buf() + i * max_ctx_, prompts[i].data(), prompts[i].size() * 4,
                               hipMemcpyHostToDevice));
       }
     }
-  }
+  });
   {
     std::vector<size_t> seqs(prompts.size());
     std::iota(seqs.begin(), seqs.end(), (size_t)0);
@@ -1272,6 +1271,13 @@ void Engine::set_slot_sampling(int slot, const RowSampling& r, bool has_seed, bo
   slot_seed_given_[slot] = has_seed ? 1 : 0;
 }
 
+void Engine::check_slot_at(const char* fn, const std::vector<int>& slots, size_t i, const char* twice_suffix) const {
+  const int s = slots[i];
+  if (s < 0 || s >= M_ * B_) throw std::runtime_error(std::string(fn) + ": slot " + std::to_string(s) + " is out of range");
+  for (size_t k = 0; k < i; ++k)
+    if (slots[k] == s) throw std::runtime_error(std::string(fn) + ": slot " + std::to_string(s) + " is listed twice" + twice_suffix);
+}
+
 void Engine::set_slot_masks(const std::vector<int>& slots, const uint32_t* const* bits, bool for_start) {
   if (!row_masks_) throw std::runtime_error("set_slot_masks: the engine was built without row_masks");
   if (slots.empty()) return;
@@ -1279,9 +1285,7 @@ void Engine::set_slot_masks(const std::vector<int>& slots, const uint32_t* const
   const int V = cfg_.vocab, nw = mask_words();
   for (size_t i = 0; i < slots.size(); ++i) {
     const int s = slots[i];
-    if (s < 0 || s >= M_ * B_) throw std::runtime_error("set_slot_masks: slot " + std::to_string(s) + " is out of range");
-    for (size_t k = 0; k < i; ++k)
-      if (slots[k] == s) throw std::runtime_error("set_slot_masks: slot " + std::to_string(s) + " is listed twice");
+    check_slot_at("set_slot_masks", slots, i);
     if (!bits[i]) continue;
     bool any = false;
     for (int w = 0; w < nw && !any; ++w) {
@@ -1291,30 +1295,16 @@ void Engine::set_slot_masks(const std::vector<int>& slots, const uint32_t* const
     }
     if (!any) throw std::runtime_error("set_slot_masks: the mask of slot " + std::to_string(s) + " allows no token below the vocabulary size");
   }
-  for (auto& w : workers_)
-    if (w->stage->spec().last()) {
-      if (!w->cpu) HIP_OK(hipSetDevice(w->device));
-      w->stage->set_row_masks(slots, bits);
-    }
-  for (size_t i = 0; i < slots.size(); ++i)
-    mask_state_[slots[i]] = !bits[i] ? 0 : (!for_start && started_ && slot_active(slots[i])) ? 2 : 1;
+  for_each_last_stage([&](Worker& w) { w.stage->set_row_masks(slots, bits); });
+  for (size_t i = 0; i < slots.size(); ++i) mask_life_.set(slots[i], bits[i] != nullptr, slot_running(slots[i], for_start));
 }
 
 void Engine::clear_masks(bool all) {
   if (!row_masks_) return;
-  std::vector<int> slots;
-  for (int s = 0; s < M_ * B_; ++s)
-    if (mask_state_[s] == 2 || (all && mask_state_[s])) slots.push_back(s);
-  for (int s = 0; s < M_ * B_; ++s)
-    if (mask_state_[s] == 1 && !all) mask_state_[s] = 2;   // set for this start(): in use from here on
+  const std::vector<int> slots = all ? mask_life_.drain_all() : mask_life_.drain_for_start();
   if (slots.empty()) return;
-  std::vector<const uint32_t*> none(slots.size(), nullptr);
-  for (auto& w : workers_)
-    if (w->stage->spec().last()) {
-      if (!w->cpu) HIP_OK(hipSetDevice(w->device));
-      w->stage->set_row_masks(slots, none.data());
-    }
-  for (int s : slots) mask_state_[s] = 0;
+  const std::vector<const uint32_t*> none(slots.size(), nullptr);
+  for_each_last_stage([&](Worker& w) { w.stage->set_row_masks(slots, none.data()); });
 }
 
 // ---------------------------------------------------------------- LoRA adapters
@@ -1331,11 +1321,10 @@ int Engine::load_adapter(const std::string& path) {
   size_t bytes = 0;
   std::vector<Worker*> done;
   try {
-    for (auto& w : workers_) {
-      if (!w->cpu) HIP_OK(hipSetDevice(w->device));
-      bytes += w->stage->load_adapter(id, f);
-      done.push_back(w.get());
-    }
+    for_each_stage([&](Worker& w) {
+      bytes += w.stage->load_adapter(id, f);
+      done.push_back(&w);
+    });
   } catch (...) {
     for (Worker* w : done) w->stage->unload_adapter(id);
     throw;
@@ -1354,10 +1343,7 @@ void Engine::unload_adapter(int id) {
   for (size_t s = 0; s < bind_id_.size(); ++s)
     if (bind_id_[s] == id) throw std::runtime_error("unload_adapter: adapter " + std::to_string(id) + " is bound to slot " + std::to_string(s));
   sync_all();
-  for (auto& w : workers_) {
-    if (!w->cpu) HIP_OK(hipSetDevice(w->device));
-    w->stage->unload_adapter(id);
-  }
+  for_each_stage([&](Worker& w) { w.stage->unload_adapter(id); });
   adapters_[id] = AdapterRec{};
 }
 
@@ -1385,19 +1371,17 @@ int Engine::slot_adapter(int slot, float* scale) const {
   return bind_id_[slot];
 }
 
-void Engine::push_bindings(const std::vector<int>& slots, const std::vector<int>& ids, const std::vector<float>& scales) {
+void Engine::push_bindings(const std::vector<int>& slots, const std::vector<int>& ids, const std::vector<float>& scales,
+                           bool mark_mixed) {
   if (slots.empty()) return;
-  for (auto& w : workers_) {
-    if (!w->cpu) HIP_OK(hipSetDevice(w->device));
-    w->stage->set_row_adapters(slots, ids, scales);
-  }
+  for_each_stage([&](Worker& w) { w.stage->set_row_adapters(slots, ids, scales); });
   for (size_t i = 0; i < slots.size(); ++i) {
     const size_t s = (size_t)slots[i];
     const bool changed = bind_id_[s] != ids[i] || (ids[i] >= 0 && bind_scale_[s] != scales[i]);
     bind_id_[s] = ids[i];
     bind_scale_[s] = ids[i] >= 0 ? scales[i] : 0.f;
     // a running sequence's KV now mixes two bindings: no later prompt may reuse it as a prefix
-    if (changed && started_ && slot_active((int)s)) kv_tag_[s].serial = kMixedTag;
+    if (changed && mark_mixed && started_ && slot_active((int)s)) kv_tag_[s].serial = kMixedTag;
   }
 }
 
@@ -1407,35 +1391,22 @@ void Engine::set_slot_adapters(const std::vector<int>& slots, const std::vector<
   if (ids.size() != slots.size() || scales.size() != slots.size())
     throw std::runtime_error("set_slot_adapters: one adapter id and one scale per slot (stacking adapters on a sequence is not supported)");
   for (size_t i = 0; i < slots.size(); ++i) {
-    const int s = slots[i];
-    if (s < 0 || s >= M_ * B_) throw std::runtime_error("set_slot_adapters: slot " + std::to_string(s) + " is out of range");
-    for (size_t k = 0; k < i; ++k)
-      if (slots[k] == s)
-        throw std::runtime_error("set_slot_adapters: slot " + std::to_string(s) + " is listed twice (one adapter per sequence)");
+    check_slot_at("set_slot_adapters", slots, i, " (one adapter per sequence)");
     if (ids[i] < -1 || ids[i] >= lora_cap_ || (ids[i] >= 0 && !adapters_[ids[i]].used))
       throw std::runtime_error("set_slot_adapters: adapter id " + std::to_string(ids[i]) + " is not loaded");
     if (ids[i] >= 0 && !(scales[i] - scales[i] == 0.f)) throw std::runtime_error("set_slot_adapters: scale is not finite");
   }
   if (failed_) throw std::runtime_error("set_slot_adapters after a pipeline fault");
   sync_all();
-  push_bindings(slots, ids, scales);
-  for (size_t i = 0; i < slots.size(); ++i)
-    bind_state_[slots[i]] = ids[i] < 0 ? 0 : (!for_start && started_ && slot_active(slots[i])) ? 2 : 1;
+  push_bindings(slots, ids, scales, true);
+  for (size_t i = 0; i < slots.size(); ++i) bind_life_.set(slots[i], ids[i] >= 0, slot_running(slots[i], for_start));
 }
 
 void Engine::clear_bindings(bool all) {
   if (lora_cap_ <= 0) return;
-  std::vector<int> slots;
-  for (int s = 0; s < M_ * B_; ++s)
-    if (bind_state_[s] == 2 || (all && bind_state_[s])) slots.push_back(s);
-  for (int s = 0; s < M_ * B_; ++s)
-    if (bind_state_[s] == 1 && !all) bind_state_[s] = 2;   // set for this start(): in use from here on
-  if (slots.empty()) return;
-  const bool was = started_;
-  started_ = false;   // (the generation these bindings belonged to is over: nothing to mark as mixed)
-  push_bindings(slots, std::vector<int>(slots.size(), -1), std::vector<float>(slots.size(), 0.f));
-  started_ = was;
-  for (int s : slots) bind_state_[s] = 0;
+  const std::vector<int> slots = all ? bind_life_.drain_all() : bind_life_.drain_for_start();
+  // (the generation these bindings belonged to is over: nothing to mark as mixed)
+  push_bindings(slots, std::vector<int>(slots.size(), -1), std::vector<float>(slots.size(), 0.f), false);
 }
 
 RowSampling Engine::slot_sampling(int slot) const {
@@ -1453,11 +1424,7 @@ void Engine::apply_slot_sampling(const std::vector<size_t>& seqs) {
     if (!slot_seed_given_[i]) r.seed = seed_mix64(row_default_.seed ^ (0x9E3779B97F4A7C15ULL * (admissions_ + 1)));
     slot_seed_given_[i] = 1;   // the seed in use: a re-admission without release() keeps it
     ++admissions_;
-    for (auto& w : workers_)
-      if (w->stage->spec().last()) {
-        if (!w->cpu) HIP_OK(hipSetDevice(w->device));
-        w->stage->set_row_sampling((int)(i / B_), (int)(i % B_), r);
-      }
+    for_each_last_stage([&](Worker& w) { w.stage->set_row_sampling((int)(i / B_), (int)(i % B_), r); });
   }
 }
 
@@ -1470,11 +1437,7 @@ void Engine::push_row_draws(int mb) {
     const size_t i = (size_t)mb * B_ + b;
     d[b] = slot_rec_[i].draw0 + (i < gen_.size() ? (int32_t)gen_[i].size() : 0);
   }
-  for (auto& w : workers_)
-    if (w->stage->spec().last()) {
-      if (!w->cpu) HIP_OK(hipSetDevice(w->device));
-      w->stage->set_row_draws(mb, d);
-    }
+  for_each_last_stage([&](Worker& w) { w.stage->set_row_draws(mb, d); });
 }
 
 RowSampling Engine::sampling_from_json(const Json& j, bool* has_seed) const {
@@ -1827,11 +1790,7 @@ Json Engine::load_state(const std::string& dir) {
       slot_seed_given_[i] = 1;
       if (sj.has("draws") && (int)sj["draws"].arr()[i].num() != slot_rec_[i].draw0 + (int)gen_[i].size())
         throw std::runtime_error("load_state: bad session (draws)");
-      for (auto& w : workers_)
-        if (w->stage->spec().last()) {
-          if (!w->cpu) HIP_OK(hipSetDevice(w->device));
-          w->stage->set_row_sampling((int)(i / B_), (int)(i % B_), slot_rec_[i]);
-        }
+      for_each_last_stage([&](Worker& w) { w.stage->set_row_sampling((int)(i / B_), (int)(i % B_), slot_rec_[i]); });
     }
     for (size_t i = prompts_.size(); i < (size_t)M_ * B_; ++i) { slot_rec_[i] = row_default_; slot_seed_given_[i] = 0; }
     admissions_ = std::strtoull(sj.get_str("admissions", "0").c_str(), nullptr, 10);
@@ -1908,10 +1867,7 @@ std::vector<Item> Engine::prefill_items(const std::vector<size_t>& seqs, bool ad
 void Engine::push_positions(int mb) {
   std::vector<int32_t> pos(B_);
   for (int b = 0; b < B_; ++b) pos[b] = slot_pos((size_t)mb * B_ + b);
-  for (auto& w : workers_) {
-    if (!w->cpu) HIP_OK(hipSetDevice(w->device));
-    w->stage->set_positions(mb, pos);
-  }
+  for_each_stage([&](Worker& w) { w.stage->set_positions(mb, pos); });
 }
 
 void Engine::release(int slot) {
@@ -1921,25 +1877,17 @@ void Engine::release(int slot) {
     // the stage too: an idle row at the engine's values stops running a finished request's chain
     slot_rec_[slot] = row_default_;
     slot_seed_given_[slot] = 0;
-    for (auto& w : workers_)
-      if (w->stage->spec().last()) {
-        if (!w->cpu) HIP_OK(hipSetDevice(w->device));
-        w->stage->set_row_sampling(slot / B_, slot % B_, row_default_);
-      }
+    for_each_last_stage([&](Worker& w) { w.stage->set_row_sampling(slot / B_, slot % B_, row_default_); });
   }
-  if (row_masks_ && !failed_ && slot >= 0 && slot < M_ * B_ && mask_state_[slot]) {
+  if (row_masks_ && !failed_ && slot >= 0 && slot < M_ * B_ && mask_life_.on(slot)) {
     const std::vector<int> one{slot};
     const uint32_t* none = nullptr;
-    for (auto& w : workers_)
-      if (w->stage->spec().last()) {
-        if (!w->cpu) HIP_OK(hipSetDevice(w->device));
-        w->stage->set_row_masks(one, &none);
-      }
-    mask_state_[slot] = 0;
+    for_each_last_stage([&](Worker& w) { w.stage->set_row_masks(one, &none); });
+    mask_life_.clear(slot);
   }
-  if (lora_cap_ > 0 && !failed_ && slot >= 0 && slot < M_ * B_ && bind_state_[slot]) {
-    push_bindings({slot}, {-1}, {0.f});   // (the slot is idle by now: its KV tag stays what computed it)
-    bind_state_[slot] = 0;
+  if (lora_cap_ > 0 && !failed_ && slot >= 0 && slot < M_ * B_ && bind_life_.on(slot)) {
+    push_bindings({slot}, {-1}, {0.f}, true);   // (the slot is idle by now: its KV tag stays what computed it)
+    bind_life_.clear(slot);
   }
 }
 
@@ -1953,10 +1901,7 @@ void Engine::kv_grant(size_t slot, int n_tokens) {
 
 void Engine::kv_sync() {
   if (!pager_.dirty()) return;
-  for (auto& w : workers_) {
-    if (!w->cpu) HIP_OK(hipSetDevice(w->device));
-    w->stage->set_block_table(pager_.table());
-  }
+  for_each_stage([&](Worker& w) { w.stage->set_block_table(pager_.table()); });
   pager_.clean();
 }
 
@@ -1987,22 +1932,17 @@ void Engine::admit(const std::vector<int>& slots, const std::vector<std::vector<
   }
   kv_sync();
   apply_slot_sampling(seqs);
-  if (row_masks_)
-    for (size_t i : seqs)
-      if (mask_state_[i] == 1) mask_state_[i] = 2;   // set for this admission: in use from here on
-  if (lora_cap_ > 0)
-    for (size_t i : seqs)
-      if (bind_state_[i] == 1) bind_state_[i] = 2;
-  for (auto& w : workers_) {
-    Stage& st = *w->stage;
-    if (!w->cpu) HIP_OK(hipSetDevice(w->device));
+  if (row_masks_) mask_life_.admit(seqs);
+  if (lora_cap_ > 0) bind_life_.admit(seqs);
+  for_each_stage([&](Worker& w) {
+    Stage& st = *w.stage;
     if (st.spec().first())
       for (size_t i : seqs) {
-        if (w->cpu) std::memcpy(st.prompt_buf() + i * max_ctx_, prompts_[i].data(), prompts_[i].size() * 4);
+        if (w.cpu) std::memcpy(st.prompt_buf() + i * max_ctx_, prompts_[i].data(), prompts_[i].size() * 4);
         else HIP_OK(hipMemcpy(st.prompt_buf() + i * max_ctx_, prompts_[i].data(), prompts_[i].size() * 4,
                               hipMemcpyHostToDevice));
       }
-  }
+  });
   for (int mb = 0; mb < M_; ++mb)
     if (mbs[mb]) push_positions(mb);
   std::vector<Item> items = prefill_items(seqs, true);
@@ -2015,19 +1955,19 @@ void Engine::admit(const std::vector<int>& slots, const std::vector<std::vector<
     }
   // the head pushed a token into the penalty window of every row of these micro-batches: re-seed
   // them from the host (prompt + accepted tokens)
-  for (auto& w : workers_)
-    if (w->stage->spec().last())
-      for (int mb = 0; mb < M_; ++mb)
-        if (mbs[mb]) {
-          std::vector<std::vector<int32_t>> hs;
-          for (int b = 0; b < B_; ++b) {
-            const size_t i = (size_t)mb * B_ + b;
-            std::vector<int32_t> q = prompts_[i];
-            q.insert(q.end(), gen_[i].begin(), gen_[i].end());
-            hs.push_back(q);
-          }
-          w->stage->set_history(mb, hs);
+  for_each_last_stage([&](Worker& w) {
+    for (int mb = 0; mb < M_; ++mb)
+      if (mbs[mb]) {
+        std::vector<std::vector<int32_t>> hs;
+        for (int b = 0; b < B_; ++b) {
+          const size_t i = (size_t)mb * B_ + b;
+          std::vector<int32_t> q = prompts_[i];
+          q.insert(q.end(), gen_[i].begin(), gen_[i].end());
+          hs.push_back(q);
         }
+        w.stage->set_history(mb, hs);
+      }
+  });
   for (int mb = 0; mb < M_; ++mb)
     if (mbs[mb]) push_row_draws(mb);
   refresh_slot_cache();
@@ -2051,15 +1991,12 @@ StepStats Engine::decode_steps(int k) {
   for (size_t i = 0; i < (size_t)M_ * B_; ++i)
     if (i < active_.size() && active_[i]) kv_grant(i, slot_pos(i) + k + 1);
   kv_sync();
-  for (auto& w : workers_)
-    if (w->stage->spec().last() && w->cpu) {
-      w->tok_t.clear();
-    } else if (w->stage->spec().last()) {
-      HIP_OK(hipSetDevice(w->device));
-      for (auto e : w->tok_ev) (void)hipEventDestroy(e);
-      w->tok_ev.assign((size_t)k * M_, nullptr);
-      for (auto& e : w->tok_ev) HIP_OK(hipEventCreate(&e));
-    }
+  for_each_last_stage([&](Worker& w) {
+    if (w.cpu) return w.tok_t.clear();
+    for (auto e : w.tok_ev) (void)hipEventDestroy(e);
+    w.tok_ev.assign((size_t)k * M_, nullptr);
+    for (auto& e : w.tok_ev) HIP_OK(hipEventCreate(&e));
+  });
   std::vector<Item> items;
   for (int r = 0; r < k; ++r)
     for (int mb = 0; mb < M_; ++mb) {
@@ -2581,21 +2518,20 @@ Json Engine::bench(int prompt_len, int warmup, int steps) {
 
 int Engine::copy_logits(int mb, float* out, int rows) {
   (void)mb;
-  for (auto& w : workers_)
-    if (w->stage->spec().last()) {
-      if (w->cpu) {
-        for (int r = 0; r < rows; ++r)
-          std::memcpy(out + (size_t)r * cfg_.vocab, w->stage->logits_ptr() + (size_t)r * w->stage->logits_ld(),
-                      (size_t)cfg_.vocab * 4);
-        return 0;
-      }
-      HIP_OK(hipSetDevice(w->device));
-      HIP_OK(hipStreamSynchronize(w->stage->stream()));
-      HIP_OK(hipMemcpy2D(out, (size_t)cfg_.vocab * 4, w->stage->logits_ptr(), (size_t)w->stage->logits_ld() * 4,
-                         (size_t)cfg_.vocab * 4, rows, hipMemcpyDeviceToHost));
-      return 0;
+  int rc = -1;
+  for_each_last_stage([&](Worker& w) {
+    rc = 0;
+    if (w.cpu) {
+      for (int r = 0; r < rows; ++r)
+        std::memcpy(out + (size_t)r * cfg_.vocab, w.stage->logits_ptr() + (size_t)r * w.stage->logits_ld(),
+                    (size_t)cfg_.vocab * 4);
+      return;
     }
-  return -1;
+    HIP_OK(hipStreamSynchronize(w.stage->stream()));
+    HIP_OK(hipMemcpy2D(out, (size_t)cfg_.vocab * 4, w.stage->logits_ptr(), (size_t)w.stage->logits_ld() * 4,
+                       (size_t)cfg_.vocab * 4, rows, hipMemcpyDeviceToHost));
+  });
+  return rc;
 }
 
 Json Engine::info() const {

@@ -48,6 +48,39 @@ struct StepStats {
   double wall_ms = 0;
 };
 
+// The lifecycle of one per-slot setting (a token mask, an adapter binding).  A slot's setting is off,
+// pending (set for the slot's next admission) or live (in use by the running sequence).  A setting
+// made for a running slot is live at once; one made for an idle slot, or handed to start() for a slot
+// that is still busy with the generation before it, is pending until that admission.  start() ends
+// the live ones and keeps the pending, release() ends the slot's, load_state() ends them all.
+class SlotSettings {
+ public:
+  void reset(size_t n_slots) { st_.assign(n_slots, OFF); }
+  bool on(int slot) const { return st_[slot] != OFF; }
+  // running: the slot holds a running sequence and the setting is not meant for the next start()
+  void set(int slot, bool value, bool running) { st_[slot] = !value ? OFF : running ? LIVE : PENDING; }
+  void clear(int slot) { st_[slot] = OFF; }
+  template <class Slots> void admit(const Slots& slots) {   // set for this admission: in use from here on
+    for (auto s : slots) if (st_[s] == PENDING) st_[s] = LIVE;
+  }
+  // start(): the live slots, now off (the caller switches them off on the stages); the pending become live
+  std::vector<int> drain_for_start() { return drain(false); }
+  // load_state(): every slot that was on, now off
+  std::vector<int> drain_all() { return drain(true); }
+
+ private:
+  enum State : char { OFF, PENDING, LIVE };
+  std::vector<int> drain(bool all) {
+    std::vector<int> out;
+    for (size_t s = 0; s < st_.size(); ++s) {
+      if (st_[s] == LIVE || (all && st_[s] != OFF)) { out.push_back((int)s); st_[s] = OFF; }
+      else if (st_[s] == PENDING) st_[s] = LIVE;
+    }
+    return out;
+  }
+  std::vector<State> st_;
+};
+
 class Engine {
  public:
   explicit Engine(const Json& cfg);
@@ -238,6 +271,25 @@ class Engine {
   void run_all(const std::vector<Item>& items);
   void post_ring_recv(Worker& w, int mb);
   void sync_all();
+  // fn(Worker&) for every owned stage / for the owned last stage, its device current (HIP workers)
+  template <class F> void for_each_stage(F fn) {
+    for (auto& w : workers_) {
+      if (!w->cpu) HIP_OK(hipSetDevice(w->device));
+      fn(*w);
+    }
+  }
+  template <class F> void for_each_last_stage(F fn) {
+    for (auto& w : workers_) {
+      if (!w->stage->spec().last()) continue;
+      if (!w->cpu) HIP_OK(hipSetDevice(w->device));
+      fn(*w);
+    }
+  }
+  // whether a setting made now for `slot` is in use at once (see SlotSettings)
+  bool slot_running(int slot, bool for_start) const { return !for_start && started_ && slot_active(slot); }
+  // slots[i] is in range and none of slots[0 .. i) repeats it; throws "<fn>: slot <s> is out of range" /
+  // "<fn>: slot <s> is listed twice<twice_suffix>"
+  void check_slot_at(const char* fn, const std::vector<int>& slots, size_t i, const char* twice_suffix = "") const;
   // multi-process pipeline: the last stage's host vector (same length on every rank) reaches every
   // rank over the idle ring (S-1 -> 0 -> 1 -> .. -> S-2); no-op in local mode
   void ring_bcast_from_last(std::vector<int32_t>& v);
@@ -302,7 +354,7 @@ class Engine {
   void push_positions(int mb);
   bool row_sampling_ = false;
   bool row_masks_ = false;
-  std::vector<char> mask_state_;            // per slot: 0 off, 1 set for the next admission, 2 in use
+  SlotSettings mask_life_;
   void clear_masks(bool all);               // start(): those in use; load_state(): all
   RowSampling row_default_;                 // the engine keys as a record (seed: the engine's)
   std::vector<RowSampling> slot_rec_;       // per slot: set for the next admission / in use
@@ -322,10 +374,12 @@ class Engine {
   std::vector<AdapterRec> adapters_;
   std::vector<int> bind_id_;
   std::vector<float> bind_scale_;
-  std::vector<char> bind_state_;            // per slot: 0 none, 1 set for the next admission, 2 in use
+  SlotSettings bind_life_;
   std::vector<KvTag> kv_tag_;
   KvTag bind_tag(size_t slot) const;
-  void push_bindings(const std::vector<int>& slots, const std::vector<int>& ids, const std::vector<float>& scales);
+  // mark_mixed: a running slot whose binding changes keeps KV of two bindings (never a prefix again)
+  void push_bindings(const std::vector<int>& slots, const std::vector<int>& ids, const std::vector<float>& scales,
+                     bool mark_mixed);
   void clear_bindings(bool all);            // start(): those in use; load_state(): all
   double load_ms_ = 0;
   // persistent stage-worker threads of run_all (declared last: joined before anything they use

@@ -1,4 +1,6 @@
 #include "hip_stage.h"
+#include "hip_head.h"
+#include "hip_lora.h"
 
 #include <functional>
 #include "tuning.h"
@@ -80,12 +82,9 @@ HipStage::HipStage(const ModelConfig& cfg, const StageSpec& spec, const StageOpt
 HipStage::~HipStage() {
   (void)hipSetDevice(spec_.device);
   destroy_graphs();
+  head_.reset();
+  lora_.reset();
   for (void* p : allocs_) (void)hipFree(p);
-  if (mask_host_) (void)hipHostFree(mask_host_);
-  if (mask_on_host_) (void)hipHostFree(mask_on_host_);
-  if (lora_tab_host_) (void)hipHostFree(lora_tab_host_);
-  for (LoraDev& a : lora_)
-    for (void* p : a.bufs) (void)hipFree(p);
   if (stream_) (void)hipStreamDestroy(stream_);
 }
 
@@ -523,13 +522,6 @@ void HipStage::alloc_runtime() {
     moe_h_ = (f16*)zalloc((size_t)scratch_rows_ * k * Kff_ * 2);
     if (opt_.deterministic) moe_yslot_ = (float*)zalloc((size_t)std::min(scratch_rows_, 64) * k * cfg_.d_model * 4);
   }
-  if (spec_.last()) {
-    logits_ld_ = (int)round_up(cfg_.vocab, 16);
-    logits_ = (float*)zalloc((size_t)B * logits_ld_ * 4);
-    am_.rows = std::max(B, opt_.prefill_chunk);
-    am_.part = (float*)zalloc((size_t)am_.rows * kArgmaxChunks * 2 * 4);
-    am_.counters = (int32_t*)zalloc((size_t)am_.rows * 4);
-  }
   int split = opt_.attn_split_len;
   if (split <= 0) {
     // auto: enough (sequence, kv head, split) workgroups to cover the CUs, but >= 256 keys per
@@ -621,51 +613,9 @@ void HipStage::alloc_runtime() {
   pf_kvlen_ = (int32_t*)zalloc((size_t)opt_.prefill_chunk * 4);
   pf_slot_ = (int32_t*)zalloc((size_t)opt_.prefill_chunk * 4);
   prompt_dev_ = (int32_t*)zalloc((size_t)n_slots * opt_.max_ctx * 4);
-  if (spec_.last())
-    for (int mb = 0; mb < NM; ++mb) last_h_.push_back((float*)zalloc((size_t)B * d * 4));
-  if (spec_.last() && opt_.row_sampling) {   // every slot starts greedy and neutral, draw index 0
-    row_host_.assign((size_t)n_slots, RowSampling{});
-    row_tab_ = (RowSampling*)dmalloc(row_host_.size() * sizeof(RowSampling));
-    HIP_OK(hipMemcpy(row_tab_, row_host_.data(), row_host_.size() * sizeof(RowSampling), hipMemcpyHostToDevice));
-    row_draw_ = (int32_t*)zalloc((size_t)n_slots * 4);
-  }
   if (opt_.row_masks && !opt_.row_sampling) throw std::runtime_error("row_masks needs row_sampling");
-  if (spec_.last() && opt_.row_masks) {   // every slot starts unconstrained
-    mask_ldw_ = (cfg_.vocab + 31) / 32;
-    const size_t words = (size_t)n_slots * mask_ldw_;
-    mask_tab_ = (uint32_t*)zalloc(words * 4);
-    mask_on_ = (int32_t*)zalloc((size_t)n_slots * 4);
-    HIP_OK(hipHostMalloc((void**)&mask_host_, words * 4, hipHostMallocDefault));
-    HIP_OK(hipHostMalloc((void**)&mask_on_host_, (size_t)n_slots * 4, hipHostMallocDefault));
-    std::memset(mask_host_, 0, words * 4);
-    std::memset(mask_on_host_, 0, (size_t)n_slots * 4);
-  }
-  if (lora_on()) {
-    if (opt_.lora_adapters > kLoraMaxAdapters) throw std::runtime_error("lora_adapters: at most " + std::to_string(kLoraMaxAdapters));
-    if (opt_.lora_max_rank < 1 || opt_.lora_max_rank > kLoraMaxRank)
-      throw std::runtime_error("lora_max_rank must be 1.." + std::to_string(kLoraMaxRank));
-    if (cfg_.d_model % 8 || cfg_.q_dim() % 8 || cfg_.d_ff % 8)
-      throw std::runtime_error("lora_adapters: d_model, n_head * head_dim and d_ff must be multiples of 8");
-    const int cap = opt_.lora_adapters;
-    lora_.resize(cap);
-    lora_rcap_ = lora_rank_pad(opt_.lora_max_rank);
-    lora_tgt_host_.assign((size_t)cap * layers_.size() * LORA_N_TARGETS, LoraTargetRec{});
-    lora_tgt_ = (LoraTargetRec*)zalloc(std::max<size_t>(lora_tgt_host_.size(), 1) * sizeof(LoraTargetRec));
-    lora_tiles_dec_ = lora_max_tiles(B, cap);
-    const size_t words = lora_table_words(lora_tiles_dec_);
-    for (int mb = 0; mb < NM; ++mb) lora_tab_.push_back((int32_t*)zalloc(words * 4));
-    HIP_OK(hipHostMalloc((void**)&lora_tab_host_, (size_t)NM * words * 4, hipHostMallocDefault));
-    std::memset(lora_tab_host_, 0, (size_t)NM * words * 4);
-    const int pf_tiles = lora_max_tiles(scratch_rows_, cap);
-    lora_tab_pf_ = (int32_t*)zalloc(lora_table_words(pf_tiles) * 4);
-    // the largest group: q|k|v and gate|up read d_model, o reads q_dim, down reads d_ff
-    const int mt = std::max(pf_tiles, lora_tiles_dec_);
-    lora_part_n_ = std::max({lora_part_floats(mt, cfg_.d_model, 3, lora_rcap_), lora_part_floats(mt, cfg_.q_dim(), 1, lora_rcap_),
-                             lora_part_floats(mt, cfg_.d_ff, 1, lora_rcap_)});
-    lora_part_ = (float*)dmalloc(lora_part_n_ * 4);
-    row_ad_.assign((size_t)n_slots, -1);
-    row_sc_.assign((size_t)n_slots, 0.f);
-  }
+  if (spec_.last()) head_ = std::make_unique<HipHead>(*this);
+  if (lora_on()) lora_ = std::make_unique<HipLora>(*this, (int)layers_.size(), scratch_rows_);
   HIP_OK(hipDeviceSynchronize());
   MP_LOGI("stage %d: layers %d-%d offloaded to GPU %d (%s), weights %.2f GiB, KV %.2f GiB (%d pages of 64 tokens; "
           "%d slots x <= %d ctx)",
@@ -751,331 +701,63 @@ void HipStage::set_sample_step(uint64_t s) {
 void HipStage::set_sampling(float temp, int top_k, float top_p, float min_p, uint64_t seed) {
   const bool changed = temp != temp_ || top_k != top_k_ || top_p != top_p_ || min_p != min_p_ || seed != seed_;
   Stage::set_sampling(temp, top_k, top_p, min_p, seed);
-  if (changed && !graphs_.empty() && spec_.last()) capture_graphs();
+  if (changed && !graphs_.empty() && head_) capture_graphs();
 }
 
 void HipStage::set_penalties(int last_n, float repeat, float freq, float presence) {
   const bool changed = last_n != pen_last_n_ || repeat != pen_repeat_ || freq != pen_freq_ || presence != pen_presence_;
   Stage::set_penalties(last_n, repeat, freq, presence);
-  if (!spec_.last()) return;
-  ensure_hist();
-  ensure_logprob();
+  if (!head_) return;
+  head_->ensure_hist();
+  head_->ensure_logprob();
   if (changed && !graphs_.empty()) capture_graphs();
-}
-
-void HipStage::ensure_hist() {
-  // (row_sampling: the windows exist whatever the engine's penalties are, a request may bring its own)
-  if (!(penalties_on() || rows_on()) || (hist_ && hist_n_ == pen_last_n_)) return;
-  const size_t rows = (size_t)opt_.n_mb * opt_.mb_size;
-  hist_ld_ = pen_last_n_ + (rows_on() ? kMaxLogitBias : 0);
-  hist_ = (int32_t*)dmalloc(rows * hist_ld_ * 4);
-  HIP_OK(hipMemset(hist_, 0xFF, rows * hist_ld_ * 4));   // -1: empty
-  if (!hist_cnt_) hist_cnt_ = (int32_t*)dmalloc(rows * 4);
-  HIP_OK(hipMemset(hist_cnt_, 0, rows * 4));
-  hist_n_ = pen_last_n_;
-  if (rows_on())   // the bias ids the slots already have
-    for (size_t r = 0; r < rows; ++r) {
-      int32_t ids[kMaxLogitBias];
-      for (int i = 0; i < kMaxLogitBias; ++i) ids[i] = i < row_host_[r].n_bias ? row_host_[r].bias_id[i] : -1;
-      HIP_OK(hipMemcpy(hist_ + r * hist_ld_ + hist_n_, ids, sizeof(ids), hipMemcpyHostToDevice));
-    }
-}
-
-void HipStage::set_row_sampling(int mb, int row, const RowSampling& r) {
-  if (!spec_.last()) return;
-  if (!rows_on()) throw std::runtime_error("set_row_sampling: the stage was built without row_sampling");
-  if (mb < 0 || mb >= opt_.n_mb || row < 0 || row >= opt_.mb_size) throw std::runtime_error("set_row_sampling: bad row");
-  check_row_sampling(r, cfg_.vocab);
-  ensure_hist();
-  ensure_logprob();
-  const size_t s = (size_t)slot_of(mb, row);
-  row_host_[s] = r;
-  int32_t ids[kMaxLogitBias];
-  for (int i = 0; i < kMaxLogitBias; ++i) ids[i] = i < r.n_bias ? r.bias_id[i] : -1;
-  HIP_OK(hipSetDevice(spec_.device));
-  HIP_OK(hipStreamSynchronize(stream_));   // no launch may still read the old record
-  HIP_OK(hipMemcpy(row_tab_ + s, &r, sizeof(RowSampling), hipMemcpyHostToDevice));
-  HIP_OK(hipMemcpy(row_draw_ + s, &r.draw0, 4, hipMemcpyHostToDevice));
-  HIP_OK(hipMemcpy(hist_ + s * hist_ld_ + hist_n_, ids, sizeof(ids), hipMemcpyHostToDevice));
-}
-
-void HipStage::set_row_draws(int mb, const std::vector<int32_t>& draws) {
-  if (!spec_.last() || !rows_on()) return;
-  if (mb < 0 || mb >= opt_.n_mb || (int)draws.size() != opt_.mb_size) throw std::runtime_error("set_row_draws: bad size");
-  HIP_OK(hipSetDevice(spec_.device));
-  HIP_OK(hipStreamSynchronize(stream_));
-  HIP_OK(hipMemcpy(row_draw_ + (size_t)slot_of(mb, 0), draws.data(), draws.size() * 4, hipMemcpyHostToDevice));
-}
-
-// The changed rows go to the pinned mirror, then to the device on the stage's stream with the on
-// flags behind them; one synchronisation, after the last copy, so the mirror is free again and no
-// head() can run between a row and its flag.
-void HipStage::set_row_masks(const std::vector<int>& slots, const uint32_t* const* bits) {
-  if (!spec_.last()) return;
-  if (!mask_tab_) throw std::runtime_error("set_row_masks: the stage was built without row_masks");
-  const int n_slots = opt_.n_mb * opt_.mb_size;
-  for (size_t i = 0; i < slots.size(); ++i) {
-    if (slots[i] < 0 || slots[i] >= n_slots) throw std::runtime_error("set_row_masks: bad slot");
-    for (size_t k = 0; k < i; ++k)   // a second copy into the same mirror row would race the first one's stream copy
-      if (slots[k] == slots[i]) throw std::runtime_error("set_row_masks: a slot is listed twice");
-  }
-  if (slots.empty()) return;
-  HIP_OK(hipSetDevice(spec_.device));
-  const size_t row_bytes = (size_t)mask_ldw_ * 4;
-  for (size_t i = 0; i < slots.size(); ++i) {
-    const size_t s = (size_t)slots[i];
-    mask_on_host_[s] = bits[i] ? 1 : 0;
-    if (!bits[i]) continue;
-    std::memcpy(mask_host_ + s * mask_ldw_, bits[i], row_bytes);
-    HIP_OK(hipMemcpyAsync(mask_tab_ + s * mask_ldw_, mask_host_ + s * mask_ldw_, row_bytes, hipMemcpyHostToDevice, stream_));
-  }
-  HIP_OK(hipMemcpyAsync(mask_on_, mask_on_host_, (size_t)n_slots * 4, hipMemcpyHostToDevice, stream_));
-  HIP_OK(hipStreamSynchronize(stream_));
-}
-
-// ---- LoRA adapters (opt_.lora_adapters > 0)
-size_t HipStage::load_adapter(int id, const GgufFile& f) {
-  if (!lora_on()) return Stage::load_adapter(id, f);
-  if (id < 0 || id >= (int)lora_.size() || lora_[id].used) throw std::runtime_error("load_adapter: adapter id " + std::to_string(id) + " is not free");
-  const LoraFile lf = lora_read(f, cfg_, opt_.lora_max_rank, spec_.layer_begin, spec_.layer_end);
-  HIP_OK(hipSetDevice(spec_.device));
-  LoraDev a;
-  std::vector<LoraTargetRec> recs(layers_.size() * LORA_N_TARGETS);
-  try {
-    std::vector<uint16_t> A16, B16;
-    for (const LoraPair& p : lf.pairs) {
-      // the rows of B_q / B_k follow the base q / k rows' NEOX permutation; A reads the un-permuted input
-      const bool perm = cfg_.rope_neox && (p.target == LORA_Q || p.target == LORA_K);
-      lora_pack_f16(p, perm ? cfg_.head_dim : 0, &A16, &B16);
-      void* d[2] = {nullptr, nullptr};
-      const std::vector<uint16_t>* h[2] = {&A16, &B16};
-      for (int i = 0; i < 2; ++i) {
-        HIP_OK(hipMalloc(&d[i], std::max<size_t>(h[i]->size() * 2, 256)));
-        a.bufs.push_back(d[i]);
-        HIP_OK(hipMemcpy(d[i], h[i]->data(), h[i]->size() * 2, hipMemcpyHostToDevice));
-        a.bytes += h[i]->size() * 2;
-      }
-      LoraTargetRec& r = recs[(size_t)(p.layer - spec_.layer_begin) * LORA_N_TARGETS + p.target];
-      r.A = d[0]; r.B = d[1]; r.r_pad = lora_rank_pad(p.r);
-    }
-    HIP_OK(hipStreamSynchronize(stream_));   // no launch may read the table while it changes
-    std::copy(recs.begin(), recs.end(), lora_tgt_host_.begin() + (size_t)id * recs.size());
-    HIP_OK(hipMemcpy(lora_tgt_ + (size_t)id * recs.size(), recs.data(), recs.size() * sizeof(LoraTargetRec), hipMemcpyHostToDevice));
-  } catch (...) {
-    for (void* p : a.bufs) (void)hipFree(p);
-    throw;
-  }
-  a.used = true;
-  weight_bytes_ += a.bytes;
-  lora_[id] = std::move(a);
-  return lora_[id].bytes;
-}
-
-void HipStage::unload_adapter(int id) {
-  if (!lora_on()) return Stage::unload_adapter(id);
-  if (id < 0 || id >= (int)lora_.size() || !lora_[id].used) throw std::runtime_error("unload_adapter: adapter id " + std::to_string(id) + " is not loaded");
-  for (int32_t a : row_ad_)
-    if (a == id) throw std::runtime_error("unload_adapter: adapter " + std::to_string(id) + " is bound to a slot");
-  HIP_OK(hipSetDevice(spec_.device));
-  HIP_OK(hipStreamSynchronize(stream_));
-  const size_t n = layers_.size() * LORA_N_TARGETS;
-  std::fill(lora_tgt_host_.begin() + (size_t)id * n, lora_tgt_host_.begin() + (size_t)(id + 1) * n, LoraTargetRec{});
-  HIP_OK(hipMemcpy(lora_tgt_ + (size_t)id * n, lora_tgt_host_.data() + (size_t)id * n, n * sizeof(LoraTargetRec), hipMemcpyHostToDevice));
-  for (void* p : lora_[id].bufs) HIP_OK(hipFree(p));
-  weight_bytes_ -= lora_[id].bytes;
-  lora_[id] = LoraDev{};
-}
-
-// The tile tables of the micro-batches whose slots changed are rebuilt in the pinned mirror and copied
-// on the stage's stream; one synchronisation after the last copy (as set_row_masks).
-void HipStage::set_row_adapters(const std::vector<int>& slots, const std::vector<int>& ids, const std::vector<float>& scales) {
-  if (!lora_on()) return Stage::set_row_adapters(slots, ids, scales);
-  if (ids.size() != slots.size() || scales.size() != slots.size()) throw std::runtime_error("set_row_adapters: one id and one scale per slot");
-  const int B = opt_.mb_size;
-  for (size_t i = 0; i < slots.size(); ++i) {
-    if (slots[i] < 0 || slots[i] >= (int)row_ad_.size()) throw std::runtime_error("set_row_adapters: bad slot");
-    if (ids[i] < -1 || ids[i] >= (int)lora_.size() || (ids[i] >= 0 && !lora_[ids[i]].used))
-      throw std::runtime_error("set_row_adapters: adapter id " + std::to_string(ids[i]) + " is not loaded");
-    if (ids[i] >= 0 && !(scales[i] == scales[i] && scales[i] - scales[i] == 0.f)) throw std::runtime_error("set_row_adapters: scale is not finite");
-  }
-  if (slots.empty()) return;
-  std::vector<char> touched(opt_.n_mb, 0);
-  for (size_t i = 0; i < slots.size(); ++i) {
-    row_ad_[slots[i]] = ids[i];
-    row_sc_[slots[i]] = ids[i] >= 0 ? scales[i] : 0.f;
-    touched[slots[i] / B] = 1;
-  }
-  HIP_OK(hipSetDevice(spec_.device));
-  HIP_OK(hipStreamSynchronize(stream_));   // the mirror rows about to be rewritten are not in flight
-  const size_t words = lora_table_words(lora_tiles_dec_);
-  for (int mb = 0; mb < opt_.n_mb; ++mb) {
-    if (!touched[mb]) continue;
-    int32_t* h = lora_tab_host_ + (size_t)mb * words;
-    lora_build_tiles(row_ad_.data() + (size_t)mb * B, row_sc_.data() + (size_t)mb * B, B, opt_.lora_adapters, lora_tiles_dec_, h);
-    HIP_OK(hipMemcpyAsync(lora_tab_[mb], h, words * 4, hipMemcpyHostToDevice, stream_));
-  }
-  HIP_OK(hipStreamSynchronize(stream_));
-}
-
-void HipStage::lora_group(int li, const Fwd& f, int n_t, const int* tgt, const int* N, const int* yoff, const f16* X, int ldx,
-                          int K, float* Y, int ldy) {
-  if (!f.lora_tab) throw std::runtime_error("lora: the forward pass carries no tile table");
-  LoraGroupParams p{};
-  p.tiles = f.lora_tab; p.max_tiles = f.lora_tiles; p.targets = lora_tgt_;
-  p.n_adapters = opt_.lora_adapters; p.n_layers = (int)layers_.size(); p.layer = li; p.n_t = n_t;
-  for (int i = 0; i < n_t; ++i) { p.tgt[i] = tgt[i]; p.N[i] = N[i]; p.yoff[i] = yoff[i]; }
-  p.X = X; p.ldx = ldx; p.K = K; p.Y = Y; p.ldy = ldy;
-  p.part = lora_part_; p.part_floats = lora_part_n_; p.rcap = lora_rcap_;
-  launch_lora_shrink(p, f.st);
-  launch_lora_expand(p, f.st);
-}
-
-// token logprob buffers (last stage, n_probs != 0): allocated when recording is switched on and when
-// the penalty window changes size; nothing exists, and head() enqueues nothing more, with n_probs 0
-void HipStage::ensure_logprob() {
-  if (!spec_.last() || n_probs_ == 0) return;
-  const int B = opt_.mb_size;
-  if (lp_rec_.empty()) {
-    HIP_OK(hipSetDevice(spec_.device));
-    for (int mb = 0; mb < opt_.n_mb; ++mb) {
-      lp_rec_.push_back((float*)dmalloc(logprob_rec_words(B) * 4));
-      HIP_OK(hipMemset(lp_rec_.back(), 0xFF, logprob_rec_words(B) * 4));
-    }
-    lp_lse_ = (float*)dmalloc((size_t)B * 4);
-  }
-  if (hist_ && lp_hist_n_ != hist_ld_) {
-    lp_hist_raw_ = (float*)dmalloc((size_t)B * hist_ld_ * 4);
-    lp_hist_n_ = hist_ld_;
-  }
 }
 
 void HipStage::set_n_probs(int n) {
   if (n < -1 || n > kMaxProbs) throw std::runtime_error("n_probs must be -1 (chosen token only) or 0.." + std::to_string(kMaxProbs));
   const bool changed = n != n_probs_;
   n_probs_ = n;
-  if (!spec_.last()) return;
-  ensure_logprob();
+  if (!head_) return;
+  head_->ensure_logprob();
   if (changed && !graphs_.empty()) capture_graphs();
 }
 
-// the buffers of a chunk whose every row goes through the LM head (speculative verify chunks and
-// score chunks share them): the chunk's logits and, per micro-batch, the greedy token after each row
-void HipStage::ensure_chunk_head() {
-  if (!vlogits_) vlogits_ = (float*)dmalloc((size_t)opt_.prefill_chunk * logits_ld_ * 4);
-  if (!vtok_) vtok_ = (int32_t*)dmalloc((size_t)opt_.n_mb * opt_.prefill_chunk * 4);
+// ---- the head's state (hip_head.h): setters are no-ops on a stage without one, reads throw
+HipHead& HipStage::need_head(const char* what) const {
+  if (!head_) throw std::runtime_error(what);
+  return *head_;
 }
-
-void HipStage::set_score_targets(int mb, const int32_t* host, int n, int top_n) {
-  if (!spec_.last()) return;
-  if (n > opt_.prefill_chunk || top_n < 0 || top_n > kMaxProbs) throw std::runtime_error("set_score_targets: bad size");
-  HIP_OK(hipSetDevice(spec_.device));
-  const size_t rows = (size_t)opt_.n_mb * opt_.prefill_chunk;
-  if (!sc_tgt_) {
-    sc_tgt_ = (int32_t*)dmalloc(rows * 4);
-    sc_lp_ = (float*)dmalloc(rows * 4);
-    sc_lse_ = (float*)dmalloc(rows * 4);
-  }
-  if (top_n > 0 && !sc_top_id_) {
-    sc_top_id_ = (int32_t*)dmalloc(rows * kMaxProbs * 4);
-    sc_top_lp_ = (float*)dmalloc(rows * kMaxProbs * 4);
-  }
-  ensure_chunk_head();
-  sc_top_n_ = top_n;
-  HIP_OK(hipMemcpy(sc_tgt_ + (size_t)mb * opt_.prefill_chunk, host, (size_t)n * 4, hipMemcpyHostToDevice));
-}
-
+const float* HipStage::logits_ptr() const { return head_ ? head_->logits() : nullptr; }
+int HipStage::logits_ld() const { return head_ ? head_->logits_ld() : 0; }
+const void* HipStage::logprob_rec(int mb) const { return head_ ? head_->logprob_rec(mb) : nullptr; }
+void HipStage::set_history(int mb, const std::vector<std::vector<int32_t>>& seqs) { if (head_) head_->set_history(mb, seqs); }
+void HipStage::set_row_sampling(int mb, int row, const RowSampling& r) { if (head_) head_->set_row_sampling(mb, row, r); }
+void HipStage::set_row_draws(int mb, const std::vector<int32_t>& draws) { if (head_) head_->set_row_draws(mb, draws); }
+void HipStage::set_row_masks(const std::vector<int>& slots, const uint32_t* const* bits) { if (head_) head_->set_row_masks(slots, bits); }
+void HipStage::set_score_targets(int mb, const int32_t* host, int n, int top_n) { if (head_) head_->set_score_targets(mb, host, n, top_n); }
 void HipStage::copy_scores(int mb, int n, float* target_lp, int32_t* top_id, float* top_lp) {
-  if (!sc_lp_ || n > opt_.prefill_chunk) throw std::runtime_error("no scores");
-  HIP_OK(hipSetDevice(spec_.device));
-  HIP_OK(hipStreamSynchronize(stream_));
-  const size_t off = (size_t)mb * opt_.prefill_chunk;
-  HIP_OK(hipMemcpy(target_lp, sc_lp_ + off, (size_t)n * 4, hipMemcpyDeviceToHost));
-  if (sc_top_n_ > 0 && top_id && top_lp) {
-    HIP_OK(hipMemcpy2D(top_id, (size_t)sc_top_n_ * 4, sc_top_id_ + off * kMaxProbs, (size_t)kMaxProbs * 4,
-                       (size_t)sc_top_n_ * 4, n, hipMemcpyDeviceToHost));
-    HIP_OK(hipMemcpy2D(top_lp, (size_t)sc_top_n_ * 4, sc_top_lp_ + off * kMaxProbs, (size_t)kMaxProbs * 4,
-                       (size_t)sc_top_n_ * 4, n, hipMemcpyDeviceToHost));
-  }
+  need_head("no scores").copy_scores(mb, n, target_lp, top_id, top_lp);
 }
-
-void HipStage::ensure_pool(int mb) {
-  const size_t d = (size_t)cfg_.d_model, ns = (size_t)opt_.n_mb * opt_.mb_size;
-  if (!pool_tab_) {
-    pool_tab_cap_ = opt_.mb_size;   // a chunk holds at most one segment per sequence of its micro-batch
-    pool_tab_ = (PoolSeg*)dmalloc((size_t)pool_tab_cap_ * sizeof(PoolSeg));
-    pool_emb_ = (float*)dmalloc(ns * d * 4);
-  }
-  if (embed_pool_ == POOL_MEAN && !pool_acc_) {
-    pool_acc_ = (float*)dmalloc(ns * d * 4);
-    // every segment's last block may be short: ceil(T / rows) summed is at most chunk / rows + segments
-    pool_part_cap_ = opt_.prefill_chunk / kPoolBlockRows + opt_.mb_size + 1;
-    pool_part_ = (float*)dmalloc((size_t)pool_part_cap_ * d * 4);
-  }
-  if (embed_pool_ == POOL_MEAN || embed_pool_ == POOL_NONE) {
-    if (pool_h_.empty()) pool_h_.assign(opt_.n_mb, nullptr);
-    if (!pool_h_[mb]) pool_h_[mb] = (float*)dmalloc((size_t)opt_.prefill_chunk * d * 4);
-  }
-}
-
-// last stage, embed chunk: x [T][d] -> the slots' vectors (pool.hip)
-void HipStage::pool_chunk(int mb, const std::vector<PrefillSeg>& segs, const float* x, int T, hipStream_t st) {
-  ensure_pool(mb);
-  std::vector<PoolSeg> tab;
-  int row = 0;
-  for (const PrefillSeg& s : segs) {
-    if (!s.embed) throw std::runtime_error("embed chunk: a segment of another kind");
-    // an embed prompt is prefilled whole (no prefix reuse), so the segment that ends it tells its length
-    tab.push_back(PoolSeg{row, s.T, slot_of(mb, s.b), s.p0, s.p0 + s.T, s.last ? 1 : 0});
-    row += s.T;
-  }
-  PoolParams p{};
-  p.x = x; p.ldx = cfg_.d_model; p.w = out_norm_; p.d = cfg_.d_model; p.eps = cfg_.eps;
-  p.segs = tab.data(); p.n_seg = (int)tab.size(); p.seg_tab = pool_tab_; p.seg_cap = pool_tab_cap_;
-  p.T = T; p.pooling = embed_pool_; p.normalize = embed_norm_ ? 1 : 0; p.n_slots = opt_.n_mb * opt_.mb_size;
-  p.h = pool_h_.empty() ? nullptr : pool_h_[mb];
-  p.part = pool_part_; p.part_cap = pool_part_cap_; p.pool_acc = pool_acc_; p.emb = pool_emb_;
-  launch_pool_embed(p, st);
-}
-
-void HipStage::copy_embeddings(const std::vector<int>& slots, float* host) {
-  if (!pool_emb_) throw std::runtime_error("no embeddings");
-  HIP_OK(hipSetDevice(spec_.device));
-  HIP_OK(hipStreamSynchronize(stream_));
-  const size_t d = (size_t)cfg_.d_model;
-  for (size_t k = 0; k < slots.size(); ++k) {
-    if (slots[k] < 0 || slots[k] >= opt_.n_mb * opt_.mb_size) throw std::runtime_error("copy_embeddings: bad slot");
-    HIP_OK(hipMemcpy(host + k * d, pool_emb_ + (size_t)slots[k] * d, d * 4, hipMemcpyDeviceToHost));
-  }
-}
-
+void HipStage::copy_verify_tokens(int mb, int32_t* host, int n) { need_head("no verify tokens").copy_verify_tokens(mb, host, n); }
+void HipStage::copy_embeddings(const std::vector<int>& slots, float* host) { need_head("no embeddings").copy_embeddings(slots, host); }
 void HipStage::copy_token_embeddings(int mb, int n_rows, float* host) {
-  if ((size_t)mb >= pool_h_.size() || !pool_h_[mb] || n_rows > opt_.prefill_chunk) throw std::runtime_error("no token embeddings");
-  HIP_OK(hipSetDevice(spec_.device));
-  HIP_OK(hipStreamSynchronize(stream_));
-  HIP_OK(hipMemcpy(host, pool_h_[mb], (size_t)n_rows * cfg_.d_model * 4, hipMemcpyDeviceToHost));
+  need_head("no token embeddings").copy_token_embeddings(mb, n_rows, host);
 }
 
-void HipStage::set_history(int mb, const std::vector<std::vector<int32_t>>& seqs) {
-  if (!spec_.last() || !(penalties_on() || rows_on())) return;
-  ensure_hist();
-  ensure_logprob();
-  const int B = opt_.mb_size, n = hist_n_, ld = hist_ld_;
-  std::vector<int32_t> h((size_t)B * ld, -1), cnt(B, 0);
-  for (int b = 0; b < B; ++b) {
-    if (b < (int)seqs.size()) {
-      const auto& q = seqs[b];
-      const int take = std::min<int>(n, (int)q.size());
-      for (int i = 0; i < take; ++i) h[(size_t)b * ld + i] = q[q.size() - take + i];
-      cnt[b] = take;
-    }
-    if (rows_on()) {   // the row's bias ids stay behind its window
-      const RowSampling& r = row_host_[(size_t)slot_of(mb, b)];
-      for (int i = 0; i < r.n_bias; ++i) h[(size_t)b * ld + n + i] = r.bias_id[i];
-    }
-  }
-  HIP_OK(hipSetDevice(spec_.device));
-  HIP_OK(hipMemcpy(hist_ + (size_t)mb * B * ld, h.data(), h.size() * 4, hipMemcpyHostToDevice));
-  HIP_OK(hipMemcpy(hist_cnt_ + (size_t)mb * B, cnt.data(), cnt.size() * 4, hipMemcpyHostToDevice));
+// ---- LoRA adapters (hip_lora.h); without opt_.lora_adapters the Stage defaults throw
+size_t HipStage::load_adapter(int id, const GgufFile& f) {
+  if (!lora_) return Stage::load_adapter(id, f);
+  const size_t bytes = lora_->load_adapter(id, f);
+  weight_bytes_ += bytes;
+  return bytes;
+}
+void HipStage::unload_adapter(int id) {
+  if (!lora_) return Stage::unload_adapter(id);
+  weight_bytes_ -= lora_->unload_adapter(id);
+}
+void HipStage::set_row_adapters(const std::vector<int>& slots, const std::vector<int>& ids, const std::vector<float>& scales) {
+  if (!lora_) return Stage::set_row_adapters(slots, ids, scales);
+  lora_->set_row_adapters(slots, ids, scales);
 }
 
 // The kernel family of a projection call.  c.small (M <= 4): gemvs, unless its LDS plan overflows:
@@ -1298,7 +980,7 @@ void HipStage::ffn_tail(const LayerW& L, int M, float* x, bool small, bool fused
     gemv(up(L.up, EPI_STORE).out(gu_ + F, 2 * F, F), st);
     if (lora_on() && f) {   // gate and up are complete f32 rows here, before the SwiGLU consumes them
       const int tg[2] = {LORA_GATE, LORA_UP}, n[2] = {F, F}, off[2] = {0, F};
-      lora_group(li, *f, 2, tg, n, off, xn_, Kd_, d, gu_, 2 * F);
+      lora_->group(li, *f, 2, tg, n, off, xn_, Kd_, d, gu_, 2 * F);
     }
     launch_swiglu(gu_, 2 * F, F, M, h_, Kff_, st);
   }
@@ -1306,7 +988,7 @@ void HipStage::ffn_tail(const LayerW& L, int M, float* x, bool small, bool fused
   gemv(MatCall(L.down, EPI_ATOMIC, M).in(h_, Kff_).out(x, d, d).split(SplitK::DEFER).gemvs(small), st);
   if (lora_on() && f) {   // (pending split-K partials of down and this delta are both plain adds into x, in stream order)
     const int tg[1] = {LORA_DOWN}, n[1] = {d}, off[1] = {0};
-    lora_group(li, *f, 1, tg, n, off, h_, Kff_, F, x, d);
+    lora_->group(li, *f, 1, tg, n, off, h_, Kff_, F, x, d);
   }
 }
 
@@ -1325,11 +1007,11 @@ void HipStage::layer_forward(int li, float* x, const Fwd& f) {
   auto lora_qkv = [&] {
     const int tg[3] = {LORA_Q, LORA_K, LORA_V}, n[3] = {cfg_.q_dim(), cfg_.kv_dim(), cfg_.kv_dim()};
     const int off[3] = {0, cfg_.q_dim(), cfg_.q_dim() + cfg_.kv_dim()};
-    lora_group(li, f, 3, tg, n, off, xn_, Kd_, d, qkv_, qkv_n_);
+    lora_->group(li, f, 3, tg, n, off, xn_, Kd_, d, qkv_, qkv_n_);
   };
   auto lora_o = [&] {
     const int tg[1] = {LORA_O}, n[1] = {d}, off[1] = {0};
-    lora_group(li, f, 1, tg, n, off, attn_, Ko_, cfg_.q_dim(), x, d);
+    lora_->group(li, f, 1, tg, n, off, attn_, Ko_, cfg_.q_dim(), x, d);
   };
   if (lora && small_path(M)) {
     // the gemvs family on a lora_adapters stage: the adapters read the normed f16 rows, so the norms run
@@ -1586,100 +1268,13 @@ bool HipStage::fuse_norm(int M) const { return opt_.fused_norm && M <= 4; }
 
 void HipStage::lm_head(const float* x, int M, float* logits, bool small, hipStream_t st) {
   const int d = cfg_.d_model;
-  const MatCall c = MatCall(out_, EPI_STORE, M).out(logits, logits_ld_, cfg_.vocab);
+  const MatCall c = MatCall(out_, EPI_STORE, M).out(logits, head_->logits_ld(), cfg_.vocab);
   if (small) return gemv(MatCall(c).in_norm(x, out_norm_).gemvs(true), st);
   // (the LM head keeps the standalone norm: the deferred-norm GEMV variant needs ~50 more VGPRs,
   // which halves the head's occupancy: 90.5 vs 72.7 + 4.6 us at 8B, profiles/r2h_prof_8b_mb1.txt)
   launch_rmsnorm(x, d, out_norm_, d, cfg_.eps, xn_, Kd_, M, nullptr, 0, st);
   xq_src_ = nullptr;
   gemv(MatCall(c).in(xn_, Kd_), st);
-}
-
-// head() with row_sampling: every launch has fixed arguments and reads the rows' records, draw
-// indices and windows from device memory, so the decode graphs are captured once.  Raw-logit
-// statistics (n_probs) -> bias + penalties per row -> the slots' token masks (row_masks) -> arg-max of every row -> the sampled rows' draws
-// over it -> the chosen tokens' logprobs -> the windows.
-void HipStage::head_rows(int mb, int M, int32_t* tok_out, bool advance, hipStream_t st) {
-  const int B = opt_.mb_size;
-  const size_t r0 = (size_t)mb * B;
-  if (!hist_) throw std::runtime_error("row_sampling: the windows were not allocated (set_penalties)");
-  int32_t* hist = hist_ + r0 * hist_ld_;
-  const bool lp = n_probs_ != 0 && !lp_rec_.empty();
-  float* rec = lp ? lp_rec_[mb] : nullptr;
-  if (lp) {   // the ids whose raw logits are saved: the window, then the bias ids
-    LogprobParams q{};
-    q.logits = logits_; q.ld = logits_ld_; q.n = cfg_.vocab; q.M = M;
-    q.top_n = std::max(n_probs_, 0); q.lse = lp_lse_;
-    q.top_id = (int32_t*)(rec + B); q.top_lp = rec + B + (size_t)B * kMaxProbs; q.ld_top = kMaxProbs;
-    q.hist = hist; q.last_n = hist_ld_; q.hist_raw = lp_hist_raw_;
-    launch_logprob(q, st);
-  }
-  RowAdjustParams ra{};
-  ra.logits = logits_; ra.ld = logits_ld_; ra.n = cfg_.vocab; ra.M = M;
-  ra.rows = row_tab_ + r0; ra.hist = hist; ra.hist_ld = hist_ld_; ra.last_n = hist_n_;
-  launch_row_adjust(ra, st);
-  if (mask_tab_) {   // the slots' masks, after the bias and the penalties: the cuts and the draw see -inf
-    RowMaskParams rm{};
-    rm.logits = logits_; rm.ld = logits_ld_; rm.n = cfg_.vocab; rm.M = M;
-    rm.bits = mask_tab_ + r0 * mask_ldw_; rm.ldw = mask_ldw_; rm.on = mask_on_ + r0;
-    launch_row_mask(rm, st);
-  }
-  launch_argmax(logits_, logits_ld_, cfg_.vocab, M, tok_out, st, &am_);
-  SampleRowsParams sp{};
-  sp.logits = logits_; sp.ld = logits_ld_; sp.n = cfg_.vocab; sp.M = M;
-  sp.rows = row_tab_ + r0; sp.draw = row_draw_ + r0; sp.advance = advance ? 1 : 0; sp.tokens = tok_out;
-  launch_sample_rows(sp, st);
-  if (lp) {
-    LogprobChosenParams c{};
-    c.logits = logits_; c.ld = logits_ld_; c.n = cfg_.vocab; c.M = M; c.tokens = tok_out; c.lse = lp_lse_;
-    c.hist = hist; c.last_n = hist_ld_; c.hist_raw = lp_hist_raw_;
-    c.chosen_lp = rec;
-    launch_logprob_chosen(c, st);
-  }
-  launch_hist_push_ld(hist, hist_ld_, hist_cnt_ + r0, hist_n_, tok_out, M, st);
-}
-
-void HipStage::head(int mb, int M, const float* x, int32_t* tok_out, uint64_t salt, hipStream_t st, bool advance) {
-  lm_head(x, M, logits_, small_path(M), st);
-  if (rows_on()) return head_rows(mb, M, tok_out, advance, st);
-  const bool pen = penalties_on() && hist_;
-  int32_t* hist = pen ? hist_ + (size_t)mb * opt_.mb_size * hist_n_ : nullptr;
-  // token logprobs are those of the RAW logits: the statistics (and the raw logits of the ids the
-  // penalty is about to rewrite) are taken here, the chosen token's value after the sampler
-  const bool lp = n_probs_ != 0 && !lp_rec_.empty();
-  float* rec = lp ? lp_rec_[mb] : nullptr;
-  if (lp) {
-    const int B = opt_.mb_size;
-    LogprobParams q{};
-    q.logits = logits_; q.ld = logits_ld_; q.n = cfg_.vocab; q.M = M;
-    q.top_n = std::max(n_probs_, 0); q.lse = lp_lse_;
-    q.top_id = (int32_t*)(rec + B); q.top_lp = rec + B + (size_t)B * kMaxProbs; q.ld_top = kMaxProbs;
-    if (pen) { q.hist = hist; q.last_n = hist_n_; q.hist_raw = lp_hist_raw_; }
-    launch_logprob(q, st);
-  }
-  if (pen) {
-    PenaltyParams pp{};
-    pp.logits = logits_; pp.ld = logits_ld_; pp.n = cfg_.vocab; pp.M = M;
-    pp.hist = hist; pp.last_n = hist_n_; pp.repeat = pen_repeat_; pp.freq = pen_freq_; pp.presence = pen_presence_;
-    launch_penalize(pp, st);
-  }
-  if (temp_ > 0.f) {
-    SampleParams sp{};
-    sp.logits = logits_; sp.ld = logits_ld_; sp.n = cfg_.vocab; sp.M = M;
-    sp.temp = temp_; sp.top_k = top_k_; sp.top_p = top_p_; sp.min_p = min_p_;
-    sp.seed = seed_ ^ (salt * 0x9E3779B97F4A7C15ULL); sp.step = step_; sp.tokens = tok_out;
-    launch_sample(sp, st);
-  } else {
-    launch_argmax(logits_, logits_ld_, cfg_.vocab, M, tok_out, st, &am_);
-  }
-  if (lp) {
-    LogprobChosenParams c{};
-    c.logits = logits_; c.ld = logits_ld_; c.n = cfg_.vocab; c.M = M; c.tokens = tok_out; c.lse = lp_lse_;
-    if (pen) { c.hist = hist; c.last_n = hist_n_; c.hist_raw = lp_hist_raw_; }
-    c.chosen_lp = rec;
-    launch_logprob_chosen(c, st);
-  }
-  if (pen) launch_hist_push(hist, hist_cnt_ + (size_t)mb * opt_.mb_size, hist_n_, tok_out, M, st);
 }
 
 void HipStage::prefill(int mb, const std::vector<PrefillSeg>& segs, hipStream_t st) {
@@ -1697,69 +1292,14 @@ void HipStage::prefill(int mb, const std::vector<PrefillSeg>& segs, hipStream_t 
   }
   if (T > opt_.prefill_chunk) throw std::runtime_error("prefill chunk too large");
   Fwd f{T, pf_pos_, pf_kvlen_, pf_slot_, false, -1, &segs, st};
-  if (lora_on()) {
-    // the chunk's rows grouped by their slots' adapters; the table travels in kernel arguments, in
-    // stream order with the chunk's other metadata
-    std::vector<int32_t> ids;
-    std::vector<float> sc;
-    for (const PrefillSeg& s : segs) {
-      const size_t sl = (size_t)slot_of(mb, s.b);
-      ids.insert(ids.end(), s.T, row_ad_[sl]);
-      sc.insert(sc.end(), s.T, row_sc_[sl]);
-    }
-    const int mt = lora_max_tiles(T, opt_.lora_adapters);
-    std::vector<int32_t> tab(lora_table_words(mt));
-    lora_build_tiles(ids.data(), sc.data(), T, opt_.lora_adapters, mt, tab.data());
-    launch_lora_table(lora_tab_pf_, tab.data(), mt, st);
-    f.lora_tab = lora_tab_pf_; f.lora_tiles = std::max(mt, 1);
-  }
+  if (lora_) lora_->bind_prefill(mb, segs, T, f);
   for (size_t li = 0; li < layers_.size(); ++li) layer_forward((int)li, x, f);
   flush_sk(st);
-  if (spec_.last() && !segs.empty() && segs[0].verify) {
-    // speculative verification: LM head over every row of the chunk, greedy next token per row
-    ensure_chunk_head();
-    lm_head(x, T, vlogits_, false, st);
-    launch_argmax(vlogits_, logits_ld_, cfg_.vocab, T, vtok_ + (size_t)mb * opt_.prefill_chunk, st, &am_);
-  } else if (spec_.last() && !segs.empty() && segs[0].score) {
-    // prompt scoring: LM head over every row of the chunk, then each row's target logprob
-    if (!sc_tgt_ || !vlogits_) throw std::runtime_error("score chunk without targets");
-    lm_head(x, T, vlogits_, false, st);
-    const size_t off = (size_t)mb * opt_.prefill_chunk;
-    LogprobParams q{};
-    q.logits = vlogits_; q.ld = logits_ld_; q.n = cfg_.vocab; q.M = T;
-    q.target = sc_tgt_ + off; q.top_n = sc_top_n_; q.lse = sc_lse_ + off; q.target_lp = sc_lp_ + off;
-    if (sc_top_n_ > 0) { q.top_id = sc_top_id_ + off * kMaxProbs; q.top_lp = sc_top_lp_ + off * kMaxProbs; }
-    q.ld_top = kMaxProbs;
-    launch_logprob(q, st);
-  } else if (spec_.last() && !segs.empty() && segs[0].embed) {
-    // embeddings: output norm + pooling of the rows; no LM head, nothing kept for prefill_finish
-    pool_chunk(mb, segs, x, T, st);
-  } else if (spec_.last()) {
-    int row = 0;
-    for (const PrefillSeg& s : segs) {
-      row += s.T;
-      if (s.last)
-        HIP_OK(hipMemcpyAsync(last_h_[mb] + (size_t)s.b * d, x + (size_t)(row - 1) * d, (size_t)d * 4,
-                              hipMemcpyDeviceToDevice, st));
-    }
-  }
-}
-
-void HipStage::copy_verify_tokens(int mb, int32_t* host, int n) {
-  if (!vtok_ || n > opt_.prefill_chunk) throw std::runtime_error("no verify tokens");
-  HIP_OK(hipSetDevice(spec_.device));
-  HIP_OK(hipMemcpy(host, vtok_ + (size_t)mb * opt_.prefill_chunk, (size_t)n * 4, hipMemcpyDeviceToHost));
+  if (head_) head_->prefill_chunk(mb, segs, x, T, st);
 }
 
 void HipStage::prefill_finish(int mb, hipStream_t st, const std::vector<int>* rows) {
-  if (!spec_.last()) return;
-  if (!rows) {
-    head(mb, opt_.mb_size, last_h_[mb], tok_[mb], 1000003ULL + (uint64_t)mb, st);
-    return;
-  }
-  if (!tok_tmp_) tok_tmp_ = (int32_t*)dmalloc((size_t)std::max(opt_.mb_size, 16) * 4);
-  head(mb, opt_.mb_size, last_h_[mb], tok_tmp_, 1000003ULL + (uint64_t)mb, st);
-  for (int b : *rows) HIP_OK(hipMemcpyAsync(tok_[mb] + b, tok_tmp_ + b, 4, hipMemcpyDeviceToDevice, st));
+  if (head_) head_->prefill_finish(mb, tok_[mb], st, rows);
 }
 
 void HipStage::decode_eager(int mb, hipStream_t st) {
@@ -1768,10 +1308,10 @@ void HipStage::decode_eager(int mb, hipStream_t st) {
   if (spec_.first())
     launch_embed(embd_type_, embd_raw_, (int64_t)embd_row_bytes_, cfg_.d_model, tok_[mb], B, x, cfg_.d_model, st);
   Fwd f{B, pos_[mb], kvlen_[mb], slot_[mb], true, slot_of(mb, 0), nullptr, st};   // slot_[mb][b] = slot0 + b
-  if (lora_on()) { f.lora_tab = lora_tab_[mb]; f.lora_tiles = lora_tiles_dec_; }
+  if (lora_) lora_->bind_decode(mb, f);
   for (size_t li = 0; li < layers_.size(); ++li) layer_forward((int)li, x, f);
   flush_sk(st);
-  if (spec_.last()) head(mb, B, x, tok_[mb], (uint64_t)mb + 1, st, true);
+  if (head_) head_->run(mb, B, x, tok_[mb], (uint64_t)mb + 1, st, true);
   launch_advance(pos_[mb], kvlen_[mb], B, mb == 0 ? step_ : nullptr, st);
 }
 

@@ -19,6 +19,8 @@
 namespace mp {
 
 class GgufFile;
+class HipHead;
+class HipLora;
 
 #define HIP_OK(x)                                                                                  \
   do {                                                                                             \
@@ -26,6 +28,26 @@ class GgufFile;
     if (e_ != hipSuccess) throw std::runtime_error(std::string("HIP error ") + hipGetErrorString(e_) + \
                                                    " at " + __FILE__ + ":" + std::to_string(__LINE__)); \
   } while (0)
+
+// device allocations with one owner: freed when it goes (the device they were made on is current)
+struct DevAllocs {
+  std::vector<void*> ptrs;
+  DevAllocs() = default;
+  DevAllocs(const DevAllocs&) = delete;
+  DevAllocs& operator=(const DevAllocs&) = delete;
+  ~DevAllocs() { for (void* p : ptrs) (void)hipFree(p); }
+  void* get(size_t bytes) {
+    void* p = nullptr;
+    HIP_OK(hipMalloc(&p, bytes < 256 ? 256 : bytes));
+    ptrs.push_back(p);
+    return p;
+  }
+  void* zero(size_t bytes) {
+    void* p = get(bytes);
+    HIP_OK(hipMemset(p, 0, bytes));
+    return p;
+  }
+};
 
 // ggml types of the 2-D weights when initialising a synthetic model on device
 struct SyntheticTypes {
@@ -147,7 +169,7 @@ class HipStage : public Stage {
   void prefill_finish(int mb, hipStream_t st, const std::vector<int>* rows = nullptr) override;
   void copy_verify_tokens(int mb, int32_t* host, int n) override;
   void set_n_probs(int n) override;
-  const void* logprob_rec(int mb) const override { return lp_rec_.empty() ? nullptr : lp_rec_[mb]; }
+  const void* logprob_rec(int mb) const override;
   void set_score_targets(int mb, const int32_t* host, int n, int top_n) override;
   void copy_scores(int mb, int n, float* target_lp, int32_t* top_id, float* top_lp) override;
   void copy_embeddings(const std::vector<int>& slots, float* host) override;
@@ -178,8 +200,8 @@ class HipStage : public Stage {
   uint64_t sample_step() override;
   void set_sample_step(uint64_t s) override;
   const char* backend_name() const override { return "hip"; }
-  const float* logits_ptr() const override { return logits_; }
-  int logits_ld() const override { return logits_ld_; }
+  const float* logits_ptr() const override;
+  int logits_ld() const override;
 
   // decode body without graph (captured by capture_graphs)
   void decode_eager(int mb, hipStream_t st);
@@ -223,14 +245,17 @@ class HipStage : public Stage {
   MatRoute mat_route(const MatCall& c, size_t sk_cap) const;
   GemvParams params(const MatCall& c) const;
   void gemv(const MatCall& c, hipStream_t st);
-  // final RMSNorm + LM head of M rows of x into logits [M][logits_ld_].  small: the gemvs form with
+  // final RMSNorm + LM head of M rows of x into logits [M][head_->logits_ld()].  small: the gemvs form with
   // the norm fused (the decode head at M <= 4; the chunk heads of prefill keep the standalone norm)
   void lm_head(const float* x, int M, float* logits, bool small, hipStream_t st);
-  // advance: a decode step (row_sampling: the rows' draw indices move on)
-  void head(int mb, int M, const float* x, int32_t* tok_out, uint64_t salt, hipStream_t st, bool advance = false);
-  void ensure_hist();
-  void ensure_logprob();
-  void ensure_chunk_head();
+  friend class HipHead;
+  friend class HipLora;
+  // the last stage's head state and what runs on it (hip_head.h); null on every other stage
+  std::unique_ptr<HipHead> head_;
+  HipHead& need_head(const char* what) const;   // throws `what` on a stage without one
+  // the adapter state (hip_lora.h); null without opt_.lora_adapters
+  std::unique_ptr<HipLora> lora_;
+  bool lora_on() const { return opt_.lora_adapters > 0; }
   // pinned double-buffered weight staging (load_gguf)
   struct Staging {
     uint8_t* buf[2] = {nullptr, nullptr};
@@ -278,8 +303,6 @@ class HipStage : public Stage {
   float* ssq_ = nullptr;   // [64] deferred-norm sums of squares, immediately followed by qkv_
   f16* xn_ = nullptr; float* qkv_ = nullptr; f16* q_ = nullptr; f16* attn_ = nullptr; f16* h_ = nullptr;
   float* gu_ = nullptr;   // unfused gate|up f32
-  float* logits_ = nullptr; int logits_ld_ = 0;
-  ArgmaxScratch am_{nullptr, nullptr, 0};   // two-level argmax partials / arrival counters
   float* sk_part_ = nullptr; size_t sk_part_n_ = 0;   // gemm_splitk_store: per-split GEMM partials
   // split-K partials of the last o / down GEMM not yet added into the residual x: the next RMSNorm
   // of x absorbs them (norm_x), anything else reading x first calls flush_sk
@@ -302,70 +325,10 @@ class HipStage : public Stage {
   std::vector<float*> act_;
   std::vector<int32_t*> tok_, pos_, kvlen_, slot_;
   int32_t* step_ = nullptr;
-  int32_t* tok_tmp_ = nullptr;   // row-selective prefill_finish
-  // repetition-penalty windows (last stage): [n_mb][mb_size][hist_n_] token ring, -1 = empty,
-  // and the per-row count of accepted tokens (ring position)
-  int32_t* hist_ = nullptr;
-  int32_t* hist_cnt_ = nullptr;
-  int hist_n_ = 0;
-  int hist_ld_ = 0;   // row stride of hist_: hist_n_, plus kMaxLogitBias with row_sampling (the row's bias ids
-                      // follow its window, so launch_logprob saves their raw logits with the window's)
-  // per-request sampling (opt_.row_sampling, last stage): the slots' records [n_mb][mb_size] on the
-  // device and their host copy, and each slot's draw index
-  RowSampling* row_tab_ = nullptr;
-  std::vector<RowSampling> row_host_;
-  int32_t* row_draw_ = nullptr;
-  bool rows_on() const { return row_tab_ != nullptr; }
-  void head_rows(int mb, int M, int32_t* tok_out, bool advance, hipStream_t st);
-  // per-slot token masks (opt_.row_masks, last stage): the table [n_mb * mb_size][mask_ldw_] and the
-  // slots' on flags on the device, and their pinned host mirrors (the source of the stream copies)
-  uint32_t* mask_tab_ = nullptr; uint32_t* mask_host_ = nullptr;
-  int32_t* mask_on_ = nullptr; int32_t* mask_on_host_ = nullptr;
-  int mask_ldw_ = 0;
   long graph_captures_ = 0;
-  // LoRA (opt_.lora_adapters > 0; lora.h, lora.hip).  Per adapter id its device images; the target
-  // table [capacity][layers][7] on the device and its host copy; per micro-batch the decode tile table
-  // (rebuilt from the slots' bindings by set_row_adapters) and one table for the prefill chunk in
-  // flight (written on the stream by launch_lora_table); the shrink partials.
-  struct LoraDev { bool used = false; std::vector<void*> bufs; size_t bytes = 0; };
-  std::vector<LoraDev> lora_;
-  LoraTargetRec* lora_tgt_ = nullptr;
-  std::vector<LoraTargetRec> lora_tgt_host_;
-  std::vector<int32_t*> lora_tab_;
-  int32_t* lora_tab_pf_ = nullptr;
-  int32_t* lora_tab_host_ = nullptr;   // pinned mirror of the decode tables [n_mb][lora_table_words]
-  int lora_rcap_ = 0, lora_tiles_dec_ = 0;
-  float* lora_part_ = nullptr; size_t lora_part_n_ = 0;
-  std::vector<int32_t> row_ad_;        // per slot: bound adapter (-1: none) and user scale
-  std::vector<float> row_sc_;
-  bool lora_on() const { return opt_.lora_adapters > 0; }
-  // one shrink + one expand launch for a group of targets reading X [M][ldx] and adding into Y
-  void lora_group(int li, const Fwd& f, int n_t, const int* tgt, const int* N, const int* yoff, const f16* X, int ldx,
-                  int K, float* Y, int ldy);
   // prefill metadata
   int32_t* pf_pos_ = nullptr; int32_t* pf_kvlen_ = nullptr; int32_t* pf_slot_ = nullptr;
   int32_t* prompt_dev_ = nullptr;
-  std::vector<float*> last_h_;                       // last stage: [mb][B][d] final prompt rows
-  float* vlogits_ = nullptr;                          // last stage, speculative verify: [chunk][logits_ld_]
-  int32_t* vtok_ = nullptr;                           // [n_mb][chunk] greedy token after each verify row
-  // token logprobs (last stage, n_probs != 0): per micro-batch record (Stage::logprob_rec), the rows'
-  // log-sum-exp and the raw logits of the penalty window's ids saved before the in-place penalty
-  std::vector<float*> lp_rec_;
-  float* lp_lse_ = nullptr;                           // [mb_size]
-  float* lp_hist_raw_ = nullptr; int lp_hist_n_ = 0;  // [mb_size][hist_n_]
-  // prompt scoring (last stage): per micro-batch targets and results of a score chunk
-  int32_t* sc_tgt_ = nullptr; float* sc_lp_ = nullptr; float* sc_lse_ = nullptr;   // [n_mb][chunk]
-  int32_t* sc_top_id_ = nullptr; float* sc_top_lp_ = nullptr;                      // [n_mb][chunk][kMaxProbs]
-  int sc_top_n_ = 0;
-  // embeddings (last stage; allocated by the first embed chunk): the chunk's segment table, the
-  // slots' running sums and results [n_slots][d], the mean's block sums, and per micro-batch the
-  // chunk's normed rows [chunk][d] (none: the result; mean: the rows the block sums are taken over)
-  void ensure_pool(int mb);
-  void pool_chunk(int mb, const std::vector<PrefillSeg>& segs, const float* x, int T, hipStream_t st);
-  PoolSeg* pool_tab_ = nullptr; int pool_tab_cap_ = 0;
-  float* pool_acc_ = nullptr; float* pool_emb_ = nullptr;
-  float* pool_part_ = nullptr; int pool_part_cap_ = 0;
-  std::vector<float*> pool_h_;
   // graphs
   std::vector<hipGraphExec_t> graphs_;
 };
