@@ -8,7 +8,9 @@
 // exponentiated scores already sit in the lanes/registers of the B operand of the P.V product
 // (O^T = V^T P^T, A = V^T read from the transposed V page) -- no LDS round trip, no shuffles for P.
 // Online softmax in registers; 4 waves interleave chunks and are merged through LDS; splits are
-// merged by attn_combine (LSE merge).  KV pages hold 64 tokens: K [64][Dp], V^T [Dp][64].
+// merged by attn_combine (LSE merge).  KV pages hold 64 tokens: K [64][Dp]; V either V^T [Dp][64]
+// (legacy) or blocked [64 / 8][Dp][8] (one contiguous 2 KB key block per 8 tokens): both are the two
+// strides (v_kb, v_d) of kernels_api.h, and in both the 8 keys of a fragment are 16 contiguous bytes.
 #include <stdexcept>
 #include <type_traits>
 #include "../runtime/tuning.h"
@@ -87,7 +89,7 @@ __global__ __launch_bounds__(256) void attn_kernel(const AttnParams p) {
     half8_t vf[DT];
 #pragma unroll
     for (int dt = 0; dt < DT; ++dt)
-      vf[dt] = *reinterpret_cast<const half8_t*>(vbase + (size_t)(16 * dt + col) * 64 + in_page + 8 * q4);
+      vf[dt] = *reinterpret_cast<const half8_t*>(vbase + (size_t)(16 * dt + col) * p.v_d + (size_t)((in_page >> 3) + q4) * p.v_kb);
 
     f32x4 s[2];
 #pragma unroll
@@ -423,6 +425,8 @@ __device__ __forceinline__ void attn_decode_body(const DecodeAttnParams& p, cons
 
   const int start = z * p.split_len;
   const int krow0 = 8 * (col >> 2) + (col & 3);
+  // V fragment of (dim 16 dt + col, keys 8 q4 ..): the lane's part of the element offset in the page
+  const uint32_t vlane = (uint32_t)(col * p.v_d + q4 * p.v_kb);
   const int wv = __builtin_amdgcn_readfirstlane(wave);
   constexpr int EB = F8 ? 1 : 2;   // bytes per cached element
   auto load = [&](int ci, KR (&kf)[2][KK], KR (&vf)[DT]) {
@@ -438,7 +442,7 @@ __device__ __forceinline__ void attn_decode_body(const DecodeAttnParams& p, cons
         kf[c][kk] = *reinterpret_cast<const KR*>(kbase + ((size_t)(in_page + krow0 + 4 * c) * DP + 32 * kk + 8 * q4) * EB);
 #pragma unroll
     for (int dt = 0; dt < DT; ++dt)
-      vf[dt] = *reinterpret_cast<const KR*>(vbase + ((size_t)(16 * dt + col) * 64 + in_page + 8 * q4) * EB);
+      vf[dt] = *reinterpret_cast<const KR*>(vbase + (vlane + (uint32_t)((in_page >> 3) * p.v_kb + 16 * dt * p.v_d)) * EB);
   };
   KR kA[2][KK], vA[DT], kB[2][KK], vB[DT];
   // one split (short contexts): each wave's first chunk is loaded before the position arrives
@@ -499,7 +503,7 @@ __device__ __forceinline__ void attn_decode_body(const DecodeAttnParams& p, cons
   if (owns) {
     const int page = a_page, idx = pos & 63;
     const size_t koff = (((size_t)page * p.Hkv + kvh) * 64 + idx) * DP;     // element offsets
-    const size_t voff = ((size_t)page * p.Hkv + kvh) * DP * 64 + idx;
+    const size_t voff = ((size_t)page * p.Hkv + kvh) * DP * 64 + (size_t)(idx >> 3) * p.v_kb + (idx & 7);
     if (j < DP / 2) {
       const float x0 = fmaf(nrs, kx.x, kb.x), x1 = fmaf(nrs, kx.y, kb.y);
       const float r0 = kin ? x0 * c.x - x1 * c.y : 0.f, r1 = kin ? x0 * c.y + x1 * c.x : 0.f;
@@ -519,11 +523,11 @@ __device__ __forceinline__ void attn_decode_body(const DecodeAttnParams& p, cons
       f16 v;
       if constexpr (F8) {
         const uint32_t q = f8x2_pack(vv, 0.f);
-        reinterpret_cast<uint8_t*>(p.v_cache)[voff + (size_t)j * 64] = (uint8_t)q;
+        reinterpret_cast<uint8_t*>(p.v_cache)[voff + (size_t)j * p.v_d] = (uint8_t)q;
         v = f8x2_lo(q).x;
       } else {
         v = (f16)vv;
-        if (!(p.probe & 1)) p.v_cache[voff + (size_t)j * 64] = v;
+        if (!(p.probe & 1)) p.v_cache[voff + (size_t)j * p.v_d] = v;
       }
       sm_vn[j] = v;
     }
@@ -769,6 +773,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void a
   const float nrs = p.ssq ? rsqrtf(p.ssq[t] / (float)p.d_model + p.eps) : 1.f;
   const int nch = (end - start + 31) / 32;
   const int krow0 = 8 * (col >> 2) + (col & 3);
+  const uint32_t vlane = (uint32_t)(col * p.v_d + q4 * p.v_kb);   // the lane's part of a V fragment's offset
 
   auto load = [&](int ci, KR (&kf)[2][KK], KR (&vf)[DT]) {
     const int P0 = start + ci * 32;
@@ -783,7 +788,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void a
         kf[c][kk] = *reinterpret_cast<const KR*>(kbase + ((size_t)(in_page + krow0 + 4 * c) * DP + 32 * kk + 8 * q4) * EB);
 #pragma unroll
     for (int dt = 0; dt < DT; ++dt)
-      vf[dt] = *reinterpret_cast<const KR*>(vbase + ((size_t)(16 * dt + col) * 64 + in_page + 8 * q4) * EB);
+      vf[dt] = *reinterpret_cast<const KR*>(vbase + (vlane + (uint32_t)((in_page >> 3) * p.v_kb + 16 * dt * p.v_d)) * EB);
   };
   KR kA[2][KK], vA[DT], kB[2][KK], vB[DT];
   load(0, kA, vA);   // in flight during the q build and the append
@@ -831,7 +836,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void a
   if (owns) {
     const int page = a_page, idx = pos & 63;
     const size_t koff = (((size_t)page * p.Hkv + kvh) * 64 + idx) * DP;
-    const size_t voff = ((size_t)page * p.Hkv + kvh) * DP * 64 + idx;
+    const size_t voff = ((size_t)page * p.Hkv + kvh) * DP * 64 + (size_t)(idx >> 3) * p.v_kb + (idx & 7);
 #pragma unroll
     for (int jj = 0; jj < KJ; ++jj) {
       const int j = lane + 64 * jj;
@@ -847,6 +852,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void a
         o = f8x2_lo(q);
       } else {
         o = half2_t{(f16)r0, (f16)r1};
+#ifdef MIPIPE_TIMING_PROBES
+        if (!(p.probe & 2))
+#endif
         *reinterpret_cast<half2_t*>(p.k_cache + koff + 2 * j) = o;
       }
       *reinterpret_cast<half2_t*>(kn + 2 * j) = o;
@@ -859,11 +867,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void a
       f16 v;
       if constexpr (F8) {
         const uint32_t q = f8x2_pack(vv, 0.f);
-        reinterpret_cast<uint8_t*>(p.v_cache)[voff + (size_t)j * 64] = (uint8_t)q;
+        reinterpret_cast<uint8_t*>(p.v_cache)[voff + (size_t)j * p.v_d] = (uint8_t)q;
         v = f8x2_lo(q).x;
       } else {
         v = (f16)vv;
-        p.v_cache[voff + (size_t)j * 64] = v;
+#ifdef MIPIPE_TIMING_PROBES
+        if (!(p.probe & 1))
+#endif
+        p.v_cache[voff + (size_t)j * p.v_d] = v;
       }
       vn[j] = v;
     }
@@ -1093,7 +1104,9 @@ __global__ __launch_bounds__(512) void attn_o_kernel(const DecodeAttnParams p, c
 
 namespace mp {
 
-void launch_attention(const AttnParams& p, hipStream_t st) {
+void launch_attention(const AttnParams& p_in, hipStream_t st) {
+  AttnParams p = p_in;
+  v_strides_or_legacy(p.v_kb, p.v_d);
   const int ng = (p.M + p.tq - 1) / p.tq;
   dim3 grid(ng, p.Hkv, p.n_split);
   if (p.Dp == 128) {
@@ -1139,7 +1152,9 @@ static void attn_o_go(const DecodeAttnParams& p, const AttnOParams& o, hipStream
   else hipLaunchKernelGGL((mpk::attn_o_kernel<128, F8, PT, kAttnOTpw, 2, false>), grid, dim3(512), 0, st, p, o);
 }
 
-void launch_attn_o(const DecodeAttnParams& p, const AttnOParams& o, hipStream_t st) {
+void launch_attn_o(const DecodeAttnParams& p_in, const AttnOParams& o, hipStream_t st) {
+  DecodeAttnParams p = p_in;
+  v_strides_or_legacy(p.v_kb, p.v_d);
   if (!attn_o_supported(p, o)) throw std::runtime_error("launch_attn_o: unsupported shape");
   switch (o.ptype) {
     case P_Q4_K: return p.kv_fp8 ? attn_o_go<true, P_Q4_K>(p, o, st) : attn_o_go<false, P_Q4_K>(p, o, st);
@@ -1184,7 +1199,9 @@ AttnDecodeForm attn_decode_form(const DecodeAttnParams& p) {
   return ATTN_FORM_NP;
 }
 
-void launch_attn_decode(const DecodeAttnParams& p, hipStream_t st) {
+void launch_attn_decode(const DecodeAttnParams& p_in, hipStream_t st) {
+  DecodeAttnParams p = p_in;
+  v_strides_or_legacy(p.v_kb, p.v_d);
   // q rotated and K / V appended by the qkv GEMV (gemvs QkvAppend): the prefetch forms only
   if (p.pre && !attn_decode_pre_ok(p))
     throw std::runtime_error("launch_attn_decode: pre-appended inputs need the one-split kernel");

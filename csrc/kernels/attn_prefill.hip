@@ -84,10 +84,15 @@ __global__ __launch_bounds__(NW * 64) void attn_prefill_kernel(const PrefillAttn
       qf[rg][kk] = v;
     }
 
-  // page staging: thread owns K chunks (key = c / (DP/8), d8 = c % (DP/8)) and V^T chunks
-  // (d = c / 8, k8 = c % 8), c = tid + NT j
+  // page staging: thread owns K chunks (key = c / (DP/8), d8 = c % (DP/8)) and V chunks (dim d, key
+  // block k8), c = tid + NT j.  Consecutive threads read consecutive 16 B of the page in either V
+  // layout (kernels_api.h): d = c / 8, k8 = c % 8 for V^T [Dp][64], d = c % DP, k8 = c / DP for the
+  // blocked [8][Dp][8]; the LDS image is V^T [Dp][VLD] for both.
   KR kr[KCH], vr[KCH];
   constexpr int EB = F8 ? 1 : 2;   // bytes per cached element
+  const bool vblk = p.v_d == 8;
+  auto v_d_of = [&](int c) { return vblk ? c % DP : c / 8; };
+  auto v_k8_of = [&](int c) { return vblk ? c / DP : c % 8; };
   auto load_page = [&](int kt) {
     const int page = bt[kt];
     const uint8_t* kb = reinterpret_cast<const uint8_t*>(p.k_cache) + ((size_t)page * p.Hkv + kvh) * 64 * DP * EB;
@@ -96,7 +101,7 @@ __global__ __launch_bounds__(NW * 64) void attn_prefill_kernel(const PrefillAttn
     for (int j = 0; j < KCH; ++j) {
       const int c = tid + NT * j;
       kr[j] = *reinterpret_cast<const KR*>(kb + (size_t)c * 8 * EB);
-      vr[j] = *reinterpret_cast<const KR*>(vb + (size_t)c * 8 * EB);
+      vr[j] = *reinterpret_cast<const KR*>(vb + (size_t)(v_k8_of(c) * p.v_kb + v_d_of(c) * p.v_d) * EB);
     }
   };
   auto as16 = [](const KR& r) -> u32x4 {
@@ -108,7 +113,7 @@ __global__ __launch_bounds__(NW * 64) void attn_prefill_kernel(const PrefillAttn
     for (int j = 0; j < KCH; ++j) {
       const int c = tid + NT * j;
       *reinterpret_cast<u32x4*>(&ks[buf][(c / (DP / 8)) * KLD + (c % (DP / 8)) * 8]) = as16(kr[j]);
-      *reinterpret_cast<u32x4*>(&vs[buf][(c / 8) * VLD + (c % 8) * 8]) = as16(vr[j]);
+      *reinterpret_cast<u32x4*>(&vs[buf][v_d_of(c) * VLD + v_k8_of(c) * 8]) = as16(vr[j]);
     }
   };
 
@@ -247,8 +252,10 @@ int prefill_attn_rows_per_tile(int G) { return 128 / G; }
 
 void launch_attn_combine(const AttnParams& p, hipStream_t st);
 
-void launch_attn_prefill(const PrefillAttnParams& p, hipStream_t st) {
-  if (p.n_tiles <= 0) return;
+void launch_attn_prefill(const PrefillAttnParams& p_in, hipStream_t st) {
+  if (p_in.n_tiles <= 0) return;
+  PrefillAttnParams p = p_in;
+  v_strides_or_legacy(p.v_kb, p.v_d);
   if (p.n_tiles > kPrefillAttnMaxTiles) throw std::runtime_error("launch_attn_prefill: too many tiles");
   if (p.Hq % p.Hkv || p.Hq / p.Hkv > 128) throw std::runtime_error("launch_attn_prefill: bad GQA group");
   if (p.n_split > 1 && (!p.o_part || !p.ml_part || p.split_pages < 1))

@@ -333,21 +333,21 @@ __global__ __launch_bounds__(256) void rope_kv_kernel(const RopeKvParams p) {
       if (isq) *reinterpret_cast<half2_t*>(p.q_out + ((size_t)m * p.Hq + h) * p.Dp + 2 * j) = o;
       else if (p.kv_fp8) *reinterpret_cast<uint16_t*>(reinterpret_cast<uint8_t*>(p.k_cache) + ko) = (uint16_t)f8x2_pack(r0, r1);
       else *reinterpret_cast<half2_t*>(p.k_cache + ko) = o;
-    } else {                                        // v head: transposed page layout [Dp][64]
+    } else {                                        // v head: page layout (v_kb, v_d), kernels_api.h
       const int h = hg - p.Hq - p.Hkv;
       const float* vr = row + (p.Hq + p.Hkv) * p.hd + h * p.hd;
-      const size_t vo = (((size_t)page * p.Hkv + h) * p.Dp) * 64 + idx;
+      const size_t vo = (((size_t)page * p.Hkv + h) * p.Dp) * 64 + (size_t)(idx >> 3) * p.v_kb + (idx & 7);
       const int d0 = 2 * j;
       const float v0 = d0 < p.hd ? vr[d0] : 0.f, v1 = d0 + 1 < p.hd ? vr[d0 + 1] : 0.f;
       if (p.kv_fp8) {
         uint8_t* vd = reinterpret_cast<uint8_t*>(p.v_cache) + vo;
         const uint32_t q = f8x2_pack(v0, v1);
-        vd[(size_t)d0 * 64] = (uint8_t)q;
-        vd[(size_t)(d0 + 1) * 64] = (uint8_t)(q >> 8);
+        vd[(size_t)d0 * p.v_d] = (uint8_t)q;
+        vd[(size_t)(d0 + 1) * p.v_d] = (uint8_t)(q >> 8);
       } else {
         f16* vd = p.v_cache + vo;
-        vd[(size_t)d0 * 64] = (f16)v0;
-        vd[(size_t)(d0 + 1) * 64] = (f16)v1;
+        vd[(size_t)d0 * p.v_d] = (f16)v0;
+        vd[(size_t)(d0 + 1) * p.v_d] = (f16)v1;
       }
     }
   }
@@ -620,7 +620,9 @@ void launch_requant_i8(const f16* W, int ldw, int n, int n_pad, int nsb, uint8_t
   hipLaunchKernelGGL(mpk::requant_i8_kernel, dim3(n_pad), dim3(256), 0, st, W, ldw, n, nsb, out, ws);
 }
 
-void launch_rope_kv(const RopeKvParams& p, hipStream_t st) {
+void launch_rope_kv(const RopeKvParams& p_in, hipStream_t st) {
+  RopeKvParams p = p_in;
+  v_strides_or_legacy(p.v_kb, p.v_d);
   hipLaunchKernelGGL(mpk::rope_kv_kernel, dim3(p.M, (p.Hq + 2 * p.Hkv + 3) / 4), dim3(256), 0, st, p);
 }
 

@@ -384,7 +384,7 @@ __device__ __forceinline__ void gemvs_body(const GemvParams& p, const int nsplit
         }
       } else {
         const int h = (c - qn - kn) / q.hd, d = (c - qn - kn) % q.hd;
-        const size_t vo = (((size_t)qa_page * q.Hkv + h) * q.Dp + d) * 64 + idx;
+        const size_t vo = ((size_t)qa_page * q.Hkv + h) * q.Dp * 64 + (size_t)(idx >> 3) * q.v_kb + (size_t)d * q.v_d + (idx & 7);
         if (q.kv_fp8) reinterpret_cast<uint8_t*>(q.v_cache)[vo] = (uint8_t)f8x2_pack(out, 0.f);
         else q.v_cache[vo] = (f16)out;
       }
@@ -572,6 +572,8 @@ void launch_gemvs2(int pt, int pt2, GemvParams p, GemvParams p2, hipStream_t st)
   if (pl.nsplit != 1 || pl.lds + (size_t)pl.sb_per_split * 64 > 150 * 1024)
     throw std::runtime_error("launch_gemvs2: x k-range does not fit LDS");
   p.sb_per_split = p2.sb_per_split = pl.sb_per_split;
+  v_strides_or_legacy(p.qa.v_kb, p.qa.v_d);
+  v_strides_or_legacy(p2.qa.v_kb, p2.qa.v_d);
 #ifdef MIPIPE_TIMING_PROBES
   p.probe = p2.probe = knob(KNOB_GEMVS_PROBE);
 #endif
@@ -591,6 +593,7 @@ void launch_gemvs(int ptype, int epi, GemvParams p, bool deterministic, hipStrea
   if (!p.Xf && !p.X) throw std::runtime_error("launch_gemvs: no input");
   if (p.qa.pos && (epi != EPI_STORE || !p.Xf || p.qa.hd % 16 || p.qa.col0 % 16 || p.qa.hd > p.qa.Dp))
     throw std::runtime_error("launch_gemvs: the q|k|v append epilogue needs STORE, the fused norm and 16-aligned heads");
+  v_strides_or_legacy(p.qa.v_kb, p.qa.v_d);
   GemvsPlan pl = plan_gemvs(p.ntiles, p.nsb, p.M, epi, p.Xf != nullptr, deterministic);
   if (force_G) pl.G = force_G;
   if (force_split) {   // tests: an explicit k-split over grid.y

@@ -403,6 +403,45 @@ int mp_op_gemvs(int ptype, int epi, const void* W, int ntiles, int nsb, const vo
   API_CATCH(-1)
 }
 
+// V page layout of the op-level entry points below that read or append V pages (rope_kv, attention,
+// attn_prefill, attn_decode, attn_o, gemvs_qkv), for the calling thread: 0 (the default) = V^T
+// [Dp][64], 1 = blocked [8][Dp][8] (kernels_api.h).  Returns the previous value.
+static thread_local int t_v_blocked = 0;
+int mp_op_v_layout(int blocked) {
+  const int old = t_v_blocked;
+  t_v_blocked = blocked ? 1 : 0;
+  return old;
+}
+static void op_v_strides(int Dp, int& v_kb, int& v_d) {
+  if (t_v_blocked) v_strides_blocked(Dp, v_kb, v_d);
+}
+
+// the decode q|k|v GEMV with the RoPE + KV append epilogue (GemvParams::qa): STORE, RMSNorm fused;
+// q lands rotated in Y, k (rotated) and v in the pages of slot slot0 + m at pos[m]; V pages in the
+// thread's mp_op_v_layout
+int mp_op_gemvs_qkv(int ptype, const void* W, int ntiles, int nsb, int M, void* Y, int ldy, int n_valid, const void* Xf,
+                    int ldxf, const void* gamma, float eps, int d_norm, const void* bias, const void* pos, int slot0,
+                    const void* block_table, int max_pages, const void* rope_cs, void* k_cache, void* v_cache, int Hq,
+                    int Hkv, int hd, int Dp, int kv_fp8, void* stream) {
+  API_TRY
+  if (!pos || !block_table || !rope_cs || !k_cache || !v_cache || !Xf || !gamma || !Y)
+    throw std::runtime_error("gemvs_qkv: null pointer");
+  if (Hkv < 1 || Hq < Hkv || (Dp != 64 && Dp != 128) || hd > Dp || n_valid != (Hq + 2 * Hkv) * hd || slot0 < 0)
+    throw std::runtime_error("gemvs_qkv: bad shape");
+  GemvParams p = gemv_params(W, ntiles, nsb, nullptr, 0, M, Y, ldy, nullptr, 0, n_valid);
+  p.Xf = (const float*)Xf; p.ldxf = ldxf; p.gamma = (const float*)gamma; p.eps = eps; p.d_norm = d_norm;
+  p.bias = (const float*)bias;
+  QkvAppend& q = p.qa;
+  q.pos = (const int32_t*)pos; q.slot0 = slot0; q.block_table = (const int32_t*)block_table; q.max_pages = max_pages;
+  q.rope_cs = (const float2*)rope_cs; q.k_cache = (f16*)k_cache; q.v_cache = (f16*)v_cache;
+  q.Hq = Hq; q.Hkv = Hkv; q.hd = hd; q.Dp = Dp; q.kv_fp8 = kv_fp8 ? 1 : 0; q.col0 = 0;
+  op_v_strides(Dp, q.v_kb, q.v_d);
+  launch_gemvs(ptype, EPI_STORE, p, true, (hipStream_t)stream, 0, 0);
+  HIP_OK(hipGetLastError());
+  return 0;
+  API_CATCH(-1)
+}
+
 int mp_op_rmsnorm(const void* x, int ldx, const void* w, int d, float eps, void* out, int ldo, int M, void* stream) {
   API_TRY
   launch_rmsnorm((const float*)x, ldx, (const float*)w, d, eps, (f16*)out, ldo, M, nullptr, 0, (hipStream_t)stream);
@@ -532,6 +571,7 @@ int mp_op_rope_kv(const void* qkv, int ldqkv, int M, int Hq, int Hkv, int hd, in
   p.pos = (const int32_t*)pos; p.slot = (const int32_t*)slot; p.block_table = (const int32_t*)block_table;
   p.max_pages = max_pages; p.rope_cs = (const float2*)rope_cs; p.q_scale = q_scale; p.q_out = (f16*)q_out;
   p.k_cache = (f16*)k_cache; p.v_cache = (f16*)v_cache; p.kv_fp8 = kv_fp8;
+  op_v_strides(Dp, p.v_kb, p.v_d);
   launch_rope_kv(p, (hipStream_t)stream);
   HIP_OK(hipGetLastError());
   return 0;
@@ -561,6 +601,7 @@ int mp_op_attention(const void* q, const void* kvlen, const void* slot, const vo
   p.v_cache = (const f16*)v_cache; p.M = M; p.Hq = Hq; p.Hkv = Hkv; p.hd = hd; p.Dp = Dp; p.tq = tq;
   p.split_len = split_len; p.n_split = n_split; p.o_part = (float*)o_part; p.ml_part = (float*)ml_part;
   p.out = (f16*)out; p.ldo = ldo;
+  op_v_strides(Dp, p.v_kb, p.v_d);
   launch_attention(p, (hipStream_t)stream);
   HIP_OK(hipGetLastError());
   return 0;
@@ -581,6 +622,7 @@ int mp_op_attn_prefill(const void* q, const void* pos, const void* slot, const v
   p.Hq = Hq; p.Hkv = Hkv; p.hd = hd; p.Dp = Dp; p.out = (f16*)out; p.ldo = ldo;
   p.M = M; p.n_split = n_split; p.split_pages = split_pages; p.o_part = (float*)o_part; p.ml_part = (float*)ml_part;
   p.kv_fp8 = kv_fp8;
+  op_v_strides(Dp, p.v_kb, p.v_d);
   const int bt = prefill_attn_rows_per_tile(Hq / Hkv);
   for (int s = 0; s < n_segs; ++s)
     for (int r = 0; r < segs[2 * s + 1]; r += bt) {
@@ -627,6 +669,7 @@ static DecodeAttnParams decode_attn_args(const void* qkv, int ldqkv, const void*
   p.out = (f16*)out; p.ldo = ldo;
   p.ssq = (const float*)ssq; p.eps = eps; p.d_model = d_model; p.bias = (const float*)bias;
   p.kv_fp8 = kv_fp8 ? 1 : 0; p.pre = pre ? 1 : 0;
+  op_v_strides(Dp, p.v_kb, p.v_d);
   return p;
 }
 

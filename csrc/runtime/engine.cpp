@@ -402,6 +402,7 @@ Engine::Engine(const Json& j) : jcfg_(j) {
   so.deterministic = j.get_bool("deterministic", false);
   so.prefill_flash = j.get_bool("prefill_flash", true);
   so.kv_fp8 = j.get_str("kv_dtype", "f16") == "fp8";
+  so.v_blocked = j.get_bool("v_blocked", true);
   so.fused_norm = j.get_bool("fused_norm", false) && !so.deterministic;   // its sums of squares are atomics
   so.small_gemv = j.get_bool("small_gemv", true);
   row_sampling_ = j.get_bool("row_sampling", false);

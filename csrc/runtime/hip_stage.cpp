@@ -644,7 +644,23 @@ void HipStage::set_block_table(const std::vector<int32_t>& t) {
 }
 
 // KV of one slot: per layer the first ceil(n_tok / 64) pages of K, then of V, each page
-// [Hkv][64][Dp] (K) / [Hkv][Dp][64] (V) f16 (or e4m3 bytes), located through the slot's block-table row
+// [Hkv][64][Dp] (K) / [Hkv][Dp][64] (V) f16 (or e4m3 bytes), located through the slot's block-table row.
+// The state holds V pages as V^T [Dp][64] whatever the stage's layout: a v_blocked stage permutes
+// them on the host ([8][Dp][8] <-> [Dp][8][8], 8-key runs moved whole), so state moves between builds
+// and layouts.
+void HipStage::v_page_permute(const uint8_t* src, uint8_t* dst, bool to_state) const {
+  const size_t run = 8 * kv_eb();   // 8 consecutive keys of one dim
+  for (int h = 0; h < cfg_.n_head_kv; ++h) {
+    const size_t hb = (size_t)h * Dp_ * 64 * kv_eb();
+    for (int kb = 0; kb < 8; ++kb)
+      for (int d = 0; d < Dp_; ++d) {
+        const size_t blocked = hb + ((size_t)kb * Dp_ + d) * run, state = hb + ((size_t)d * 8 + kb) * run;
+        if (to_state) memcpy(dst + state, src + blocked, run);
+        else memcpy(dst + blocked, src + state, run);
+      }
+  }
+}
+
 size_t HipStage::kv_state_bytes(int n_tok) const {
   const size_t page = (size_t)cfg_.n_head_kv * 64 * Dp_ * kv_eb();
   return kc_.size() * 2 * (size_t)((n_tok + 63) / 64) * page;
@@ -657,13 +673,20 @@ void HipStage::kv_export(int slot, int n_tok, std::vector<uint8_t>& out) {
   const size_t base = out.size();
   out.resize(base + kv_state_bytes(n_tok));
   uint8_t* dst = out.data() + base;
+  std::vector<uint8_t> tmp(opt_.v_blocked ? page : 0);
   HIP_OK(hipStreamSynchronize(stream_));
   for (size_t li = 0; li < kc_.size(); ++li)
     for (f16* c : {kc_[li], vc_[li]})
       for (int k = 0; k < np; ++k) {
         const int32_t pg = host_bt_[(size_t)slot * max_pages_ + k];
         if (pg >= n_pages_) throw std::runtime_error("kv_export: slot has no page for its tokens");
-        HIP_OK(hipMemcpy(dst, reinterpret_cast<const uint8_t*>(c) + (size_t)pg * page, page, hipMemcpyDeviceToHost));
+        const uint8_t* src = reinterpret_cast<const uint8_t*>(c) + (size_t)pg * page;
+        if (opt_.v_blocked && c == vc_[li]) {
+          HIP_OK(hipMemcpy(tmp.data(), src, page, hipMemcpyDeviceToHost));
+          v_page_permute(tmp.data(), dst, true);
+        } else {
+          HIP_OK(hipMemcpy(dst, src, page, hipMemcpyDeviceToHost));
+        }
         dst += page;
       }
 }
@@ -673,13 +696,20 @@ void HipStage::kv_import(int slot, int n_tok, const uint8_t* data, size_t bytes)
   HIP_OK(hipSetDevice(spec_.device));
   const size_t page = (size_t)cfg_.n_head_kv * 64 * Dp_ * kv_eb();
   const int np = (n_tok + 63) / 64;
+  std::vector<uint8_t> tmp(opt_.v_blocked ? page : 0);
   HIP_OK(hipStreamSynchronize(stream_));
   for (size_t li = 0; li < kc_.size(); ++li)
     for (f16* c : {kc_[li], vc_[li]})
       for (int k = 0; k < np; ++k) {
         const int32_t pg = host_bt_[(size_t)slot * max_pages_ + k];
         if (pg >= n_pages_) throw std::runtime_error("kv_import: slot has no page for its tokens");
-        HIP_OK(hipMemcpy(reinterpret_cast<uint8_t*>(c) + (size_t)pg * page, data, page, hipMemcpyHostToDevice));
+        uint8_t* dstp = reinterpret_cast<uint8_t*>(c) + (size_t)pg * page;
+        if (opt_.v_blocked && c == vc_[li]) {
+          v_page_permute(data, tmp.data(), false);
+          HIP_OK(hipMemcpy(dstp, tmp.data(), page, hipMemcpyHostToDevice));
+        } else {
+          HIP_OK(hipMemcpy(dstp, data, page, hipMemcpyHostToDevice));
+        }
         data += page;
       }
 }
@@ -1054,6 +1084,7 @@ void HipStage::layer_forward(int li, float* x, const Fwd& f) {
         c.qa.pos = f.pos; c.qa.slot0 = f.slot0; c.qa.block_table = block_table_; c.qa.max_pages = max_pages_;
         c.qa.rope_cs = rope_cs_; c.qa.k_cache = kc_[li]; c.qa.v_cache = vc_[li]; c.qa.col0 = (int)s.y_off;
         c.qa.Hq = cfg_.n_head; c.qa.Hkv = cfg_.n_head_kv; c.qa.hd = cfg_.head_dim; c.qa.Dp = Dp_; c.qa.kv_fp8 = opt_.kv_fp8;
+        set_v_strides(c.qa.v_kb, c.qa.v_d);
       }
       return c;
     };
@@ -1169,6 +1200,7 @@ DecodeAttnParams HipStage::decode_attn_params(int li, const Fwd& f, bool qkv_def
   dp.max_pages = max_pages_; dp.rope_cs = rope_cs_; dp.q_scale = 1.0f / std::sqrt((float)cfg_.head_dim);
   dp.k_cache = kc_[li]; dp.v_cache = vc_[li]; dp.M = f.M; dp.Hq = cfg_.n_head; dp.Hkv = cfg_.n_head_kv;
   dp.kv_fp8 = opt_.kv_fp8;
+  set_v_strides(dp.v_kb, dp.v_d);
   dp.hd = cfg_.head_dim; dp.Dp = Dp_; dp.split_len = opt_.attn_split_len; dp.n_split = n_split_;
   dp.o_part = o_part_; dp.ml_part = ml_part_; dp.counters = attn_cnt_; dp.out = attn_; dp.ldo = Ko_;
   if (qkv_deferred) { dp.ssq = ssq_; dp.eps = cfg_.eps; dp.d_model = cfg_.d_model; dp.bias = L.qkv_bias; }
@@ -1194,12 +1226,14 @@ void HipStage::attention(int li, const Fwd& f, bool qkv_deferred, bool pre) {
     rp.hd = cfg_.head_dim; rp.Dp = Dp_; rp.pos = pos; rp.slot = slot; rp.block_table = block_table_;
     rp.max_pages = max_pages_; rp.rope_cs = rope_cs_; rp.q_scale = 1.0f / std::sqrt((float)cfg_.head_dim);
     rp.q_out = q_; rp.k_cache = kc_[li]; rp.v_cache = vc_[li]; rp.kv_fp8 = opt_.kv_fp8;
+    set_v_strides(rp.v_kb, rp.v_d);
     launch_rope_kv(rp, st);
     if (!decode && opt_.prefill_flash) {
       PrefillAttnParams pa{};
       pa.q = q_; pa.pos = pos; pa.slot = slot; pa.block_table = block_table_; pa.max_pages = max_pages_;
       pa.k_cache = kc_[li]; pa.v_cache = vc_[li]; pa.Hq = cfg_.n_head; pa.Hkv = cfg_.n_head_kv;
       pa.kv_fp8 = opt_.kv_fp8;
+      set_v_strides(pa.v_kb, pa.v_d);
       pa.hd = cfg_.head_dim; pa.Dp = Dp_; pa.out = attn_; pa.ldo = Ko_;
       const int bt = prefill_attn_rows_per_tile(cfg_.n_head / cfg_.n_head_kv);
       auto add_rows = [&](int row0, int T) {
@@ -1235,6 +1269,7 @@ void HipStage::attention(int li, const Fwd& f, bool qkv_deferred, bool pre) {
     if (opt_.kv_fp8) throw std::runtime_error("kv_dtype fp8: the unfused attention path reads f16 pages");
     ap.k_cache = kc_[li]; ap.v_cache = vc_[li]; ap.M = M; ap.Hq = cfg_.n_head; ap.Hkv = cfg_.n_head_kv;
     ap.hd = cfg_.head_dim; ap.Dp = Dp_; ap.max_kv = opt_.max_ctx; ap.out = attn_; ap.ldo = Ko_;
+    set_v_strides(ap.v_kb, ap.v_d);
     if (decode) {
       ap.tq = 1;
       ap.split_len = opt_.attn_split_len;

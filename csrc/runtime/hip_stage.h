@@ -225,6 +225,13 @@ class HipStage : public Stage {
   DecodeAttnParams decode_attn_params(int li, const Fwd& f, bool qkv_deferred) const;
   bool small_path(int M) const { return opt_.small_gemv && M <= 4; }
   size_t kv_eb() const { return opt_.kv_fp8 ? 1 : 2; }   // bytes per cached K/V element
+  // the V page strides of this stage's layout (kernels_api.h): blocked by default (opt_.v_blocked)
+  void set_v_strides(int& v_kb, int& v_d) const {
+    if (opt_.v_blocked) v_strides_blocked(Dp_, v_kb, v_d);
+    else v_strides_or_legacy(v_kb, v_d);
+  }
+  // one V page between this stage's blocked layout and the state format's V^T (host buffers)
+  void v_page_permute(const uint8_t* src, uint8_t* dst, bool to_state) const;
   void flush_sk(hipStream_t st);
   // RMSNorm of the residual x into xn_ (absorbing pending split-K partials of x first)
   void norm_x(float* x, const float* w, int M, float* zero, int64_t zero_n, hipStream_t st, const float* bias = nullptr,

@@ -12,6 +12,19 @@ typedef _Float16 f16;
 
 namespace mp {
 
+// V page layout.  Inside a page and KV head, element (key, d) of V sits at element offset
+//   (key >> 3) * v_kb + d * v_d + (key & 7)
+// so the 8 consecutive keys of one dim (one 16-byte MFMA fragment of f16) are always contiguous.
+//   legacy  V^T [Dp][64]:      v_kb = 8,      v_d = 64   (a token's V: Dp 2-byte pieces, 128 B apart)
+//   blocked [64 / 8][Dp][8]:   v_kb = Dp * 8, v_d = 8    (a token's V: 16 B per dim inside ONE 2 KB key
+//                                                        block; a 32-key chunk is contiguous)
+// Every parameter struct below carries the two strides; v_kb == 0 (a zero-initialised struct) means
+// legacy.  fp8 pages use the same element offsets with 1-byte elements.  K pages are [64][Dp] always.
+inline void v_strides_or_legacy(int& v_kb, int& v_d) {
+  if (v_kb == 0) { v_kb = 8; v_d = 64; }
+}
+inline void v_strides_blocked(int Dp, int& v_kb, int& v_d) { v_kb = Dp * 8; v_d = 8; }
+
 enum Epilogue : int { EPI_STORE = 0, EPI_ATOMIC = 1, EPI_SWIGLU = 2 };
 
 // Decode q|k|v epilogue of the small-M GEMV (gemvs, single stream): instead of storing raw q|k|v
@@ -24,7 +37,8 @@ struct QkvAppend {
   int slot0 = 0;                   // row m's slot is slot0 + m
   const int32_t* block_table = nullptr; int max_pages = 0;
   const float2* rope_cs = nullptr; // [max_pos][hd / 2] (cos, sin)
-  f16* k_cache = nullptr; f16* v_cache = nullptr;   // K [page][Hkv][64][Dp], V^T [page][Hkv][Dp][64]
+  f16* k_cache = nullptr; f16* v_cache = nullptr;   // K [page][Hkv][64][Dp], V [page][Hkv] x (v_kb, v_d)
+  int v_kb = 0, v_d = 0;           // V page strides (v_strides_or_legacy: 0 = legacy V^T [Dp][64])
   int Hq = 0, Hkv = 0, hd = 0, Dp = 0, kv_fp8 = 0;
   int col0 = 0;                    // q|k|v column of this GEMV's output column 0
 };
@@ -178,8 +192,9 @@ struct RopeKvParams {
   float q_scale;         // 1/sqrt(hd)
   f16* q_out;            // [M][Hq][Dp]
   f16* k_cache;          // pages: [n_pages][Hkv][64][Dp]
-  f16* v_cache;          // pages: [n_pages][Hkv][Dp][64] (transposed)
+  f16* v_cache;          // pages: [n_pages][Hkv] x the (v_kb, v_d) layout (legacy: [Dp][64], transposed)
   int kv_fp8 = 0;        // caches hold e4m3 bytes (same element layout, 1 byte each)
+  int v_kb = 0, v_d = 0; // V page strides (0 = legacy)
 };
 void launch_rope_kv(const RopeKvParams& p, hipStream_t st);
 
@@ -218,6 +233,7 @@ struct AttnParams {
   float* ml_part;        // [n_split][M*Hq][2] (running max, running sum)
   f16* out;              // [M][ldo] with head h at columns h*hd..
   int ldo;
+  int v_kb = 0, v_d = 0; // V page strides (0 = legacy)
 };
 void launch_attention(const AttnParams& p, hipStream_t st);
 
@@ -237,6 +253,7 @@ struct PrefillAttnParams {
   int n_split = 1, split_pages = 1;   // KV splits (grid.z), pages per split
   float* o_part = nullptr; float* ml_part = nullptr;   // [n_split][M*Hq][Dp], [n_split][M*Hq][2]
   int kv_fp8 = 0;                // caches hold e4m3 bytes (kv_dtype "fp8")
+  int v_kb = 0, v_d = 0;         // V page strides (0 = legacy)
   int n_tiles;
   uint32_t tiles[kPrefillAttnMaxTiles];
 };
@@ -268,6 +285,7 @@ struct DecodeAttnParams {
   int pre = 0;                     // q already rotated, new K / V already appended (gemvs QkvAppend)
   int probe = 0;                   // timing probes only (knob ATTN_PROBE): bit 0 skips the global V append,
                                    // bit 1 the K append (results wrong; never in production runs)
+  int v_kb = 0, v_d = 0;           // V page strides (0 = legacy)
 };
 void launch_attn_decode(const DecodeAttnParams& p, hipStream_t st);
 // the device form launch_attn_decode takes for p (host only: M, Hkv, n_split and the knobs decide)

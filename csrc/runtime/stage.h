@@ -40,6 +40,8 @@ struct StageOptions {
                              // 128 x 256 gemm2 is retired); 1: 64 x 64
   bool prefill_flash = true; // prompt chunks: the LDS-tiled prefill flash attention (attn_prefill.hip)
   bool kv_fp8 = false;       // kv_dtype "fp8": KV pages hold OCP e4m3 bytes
+  bool v_blocked = true;     // HIP V pages blocked [8][Dp][8] (a token's V lands in one 2 KB key block, a 32-key
+                             // chunk is contiguous) instead of V^T [Dp][64]; the saved state format is V^T either way
   int kv_pages = 0;          // KV pool pages per stage (64 tokens each; 0: n_slots x max_ctx / 64)
   bool deterministic = false;  // split-K and MoE partials reduced in a fixed order (no float atomics
                                // on shared outputs): bitwise-reproducible logits, PP=1 == PP=S

@@ -94,6 +94,10 @@ _SIGS = {
                       c_void_p, c_int, c_void_p, c_float, c_int, c_void_p, c_int, c_int,
                       c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p], c_int),
     "mp_attn_decode_form": ([c_int, c_int, c_int], c_int),
+    "mp_op_v_layout": ([c_int], c_int),
+    "mp_op_gemvs_qkv": ([c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p,
+                         c_float, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
+                         c_int, c_int, c_int, c_int, c_int, c_void_p], c_int),
     "mp_gemm4_plan": ([c_int, c_int, c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(c_int)], c_int),
     "mp_moe_gemm4_plan": ([c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(c_int)], c_int),
     "mp_gemm4_geometry_count": ([], c_int),

@@ -678,6 +678,52 @@ def rope_cs_table(max_pos: int, hd: int, base: float, freq_factors=None) -> torc
     return torch.from_numpy(cs)
 
 
+class v_layout:
+    """V page layout the V-touching ops of this thread use (rope_kv, attention, attn_prefill,
+    attn_decode, attn_o, gemv_small_qkv) inside the `with` block: blocked=False (the default outside
+    any block) is V^T [page][Hkv][Dp][64]; blocked=True is [page][Hkv][8][Dp][8], element (key, d) at
+    (key >> 3) * Dp * 8 + d * 8 + (key & 7), the engine's default (`v_blocked`)."""
+
+    def __init__(self, blocked: bool):
+        self.blocked = bool(blocked)
+
+    def __enter__(self):
+        self.old = N.lib().mp_op_v_layout(int(self.blocked))
+        return self
+
+    def __exit__(self, *exc):
+        N.lib().mp_op_v_layout(self.old)
+        return False
+
+
+def v_pages_to_blocked(v: torch.Tensor) -> torch.Tensor:
+    """V^T pages [P][H][Dp][64] -> blocked pages (same shape and bytes, elements permuted)."""
+    P, H, Dp, _ = v.shape
+    return v.view(P, H, Dp, 8, 8).permute(0, 1, 3, 2, 4).contiguous().view(P, H, Dp, 64)
+
+
+def v_pages_from_blocked(v: torch.Tensor) -> torch.Tensor:
+    P, H, Dp, _ = v.shape
+    return v.view(P, H, 8, Dp, 8).permute(0, 1, 3, 2, 4).contiguous().view(P, H, Dp, 64)
+
+
+def gemv_small_qkv(w: PackedWeight, xf, gamma, eps, pos, slot0, block_table, rope_cs, k_cache, v_cache, Hq, Hkv, hd, Dp,
+                   *, bias=None, kv_fp8=False) -> torch.Tensor:
+    """The single-stream q|k|v GEMV with the RoPE + KV append epilogue (gemvs QkvAppend): fused
+    RMSNorm of xf f32 [M <= 4][d]; returns y f32 [M][(Hq + 2 Hkv) hd] whose q columns hold the rotated
+    q (k / v columns are not written); k (rotated) and v land in the pages of slot slot0 + m at pos[m]."""
+    assert xf.dtype == torch.float32 and xf.is_contiguous() and pos.dtype == torch.int32
+    assert block_table.dtype == torch.int32 and block_table.is_contiguous()
+    assert k_cache.is_contiguous() and v_cache.is_contiguous() and w.n == (Hq + 2 * Hkv) * hd
+    M, d = xf.shape
+    y = torch.zeros(M, w.n, dtype=torch.float32, device=xf.device)
+    N.check(N.lib().mp_op_gemvs_qkv(w.ptype, _ptr(w.dev), w.ntiles, w.nsb, M, _ptr(y), y.stride(0), w.n, _ptr(xf), d,
+                                    _ptr(gamma), eps, d, _ptr(bias), _ptr(pos), int(slot0), _ptr(block_table),
+                                    block_table.shape[1], _ptr(rope_cs), _ptr(k_cache), _ptr(v_cache), Hq, Hkv, hd, Dp,
+                                    int(kv_fp8), _stream()), "gemv_small_qkv")
+    return y
+
+
 def rope_kv(qkv, pos, slot, block_table, rope_cs, Hq, Hkv, hd, Dp, q_scale, k_cache, v_cache, kv_fp8=False):
     """kv_fp8: the caches hold e4m3 bytes (uint8 tensors of the same element layout)."""
     M = qkv.shape[0]
@@ -770,8 +816,8 @@ def attn_decode(qkv, pos, block_table, rope_cs, k_cache, v_cache, Hq, Hkv, hd, D
     """The fused decode attention step (attention.hip: RoPE of q and the new k, KV append, split
     flash-decoding, last-arriver merge) as the engine launches it: qkv f32 [M][>= (Hq + 2 Hkv) hd]
     pre-RoPE (with ssq: before the deferred RMSNorm scale / bias), row t in slot slot0 + t or slot[t]
-    at position pos[t]; K pages [page][Hkv][64][Dp], V pages [page][Hkv][Dp][64], f16 or (kv_fp8)
-    e4m3 bytes.  pre: q rotated, the new K / V already in the cache.  Returns out f16 [M][Hq * hd];
+    at position pos[t]; K pages [page][Hkv][64][Dp], V pages [page][Hkv][Dp][64] (or blocked, inside
+    `with v_layout(True)`), f16 or (kv_fp8) e4m3 bytes.  pre: q rotated, the new K / V already in the cache.  Returns out f16 [M][Hq * hd];
     the form is chosen by the launcher (attn_decode_form)."""
     M = qkv.shape[0]
     if out is None:
