@@ -724,10 +724,13 @@ def gemv_small_qkv(w: PackedWeight, xf, gamma, eps, pos, slot0, block_table, rop
     return y
 
 
-def rope_kv(qkv, pos, slot, block_table, rope_cs, Hq, Hkv, hd, Dp, q_scale, k_cache, v_cache, kv_fp8=False):
-    """kv_fp8: the caches hold e4m3 bytes (uint8 tensors of the same element layout)."""
+def rope_kv(qkv, pos, slot, block_table, rope_cs, Hq, Hkv, hd, Dp, q_scale, k_cache, v_cache, kv_fp8=False, q_out=None):
+    """kv_fp8: the caches hold e4m3 bytes (uint8 tensors of the same element layout).  q_out: the
+    f16 [M][Hq][Dp] buffer to write (the kernel writes every element of it); default a new one."""
     M = qkv.shape[0]
-    q_out = torch.zeros(M, Hq, Dp, dtype=torch.float16, device=qkv.device)
+    if q_out is None:
+        q_out = torch.zeros(M, Hq, Dp, dtype=torch.float16, device=qkv.device)
+    assert q_out.shape == (M, Hq, Dp) and q_out.dtype == torch.float16 and q_out.is_contiguous()
     N.check(N.lib().mp_op_rope_kv(_ptr(qkv), qkv.stride(0), M, Hq, Hkv, hd, Dp, _ptr(pos), _ptr(slot),
                                   _ptr(block_table), block_table.shape[1], _ptr(rope_cs), q_scale, _ptr(q_out),
                                   _ptr(k_cache), _ptr(v_cache), int(kv_fp8), _stream()), "rope_kv")
