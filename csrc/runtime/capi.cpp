@@ -578,6 +578,36 @@ int mp_op_rope_kv(const void* qkv, int ldqkv, int M, int Hq, int Hkv, int hd, in
   API_CATCH(-1)
 }
 
+// context shift of one layer's caches (launch_kv_shift): recs = n_rec x {slot, n_keep, n_discard, old_len,
+// merge_src_page} int32 on the HOST, block_table the new table on the device; any number of records
+// (kKvShiftMaxRec per launch); V pages in the thread's mp_op_v_layout
+int mp_op_kv_shift(void* k_cache, void* v_cache, const void* block_table, int n_slots, int max_pages, int n_pages, int Hkv,
+                   int hd, int Dp, int kv_fp8, const void* rope_cs, int rope_rows, const int32_t* recs, int n_rec,
+                   void* stream) {
+  API_TRY
+  if (n_rec < 0 || (n_rec > 0 && !recs)) throw std::runtime_error("kv_shift: bad records");
+  KvShiftParams p{};
+  p.k_cache = (f16*)k_cache; p.v_cache = (f16*)v_cache; p.block_table = (const int32_t*)block_table;
+  p.n_slots = n_slots; p.max_pages = max_pages; p.n_pages = n_pages; p.Hkv = Hkv; p.hd = hd; p.Dp = Dp; p.kv_fp8 = kv_fp8;
+  p.rope_cs = (const float2*)rope_cs; p.rope_rows = rope_rows;
+  op_v_strides(Dp, p.v_kb, p.v_d);
+  // records of one call name distinct slots, across the launches too
+  for (int i = 0; i < n_rec; ++i)
+    for (int k = 0; k < i; ++k)
+      if (recs[5 * i] == recs[5 * k]) throw std::runtime_error("kv_shift: record " + std::to_string(i) + ": slot listed twice");
+  for (int r0 = 0; r0 < n_rec; r0 += kKvShiftMaxRec) {
+    p.n_rec = std::min(n_rec - r0, kKvShiftMaxRec);
+    for (int i = 0; i < p.n_rec; ++i) {
+      const int32_t* r = recs + 5 * (size_t)(r0 + i);
+      p.rec[i] = KvShiftRec{r[0], r[1], r[2], r[3], r[4]};
+    }
+    launch_kv_shift(p, (hipStream_t)stream);
+  }
+  HIP_OK(hipGetLastError());
+  return 0;
+  API_CATCH(-1)
+}
+
 // per-head Q/K RMSNorm (Qwen3), in place on the f32 q|k|v rows
 int mp_op_qk_norm(void* qkv, int ldqkv, int M, int Hq, int Hkv, int hd, const void* wq, const void* wk, float eps,
                   void* stream) {
@@ -1207,6 +1237,53 @@ int mp_engine_set_slot_adapters(void* h, const int32_t* slots, int n, const int3
   return 0;
   API_CATCH(-1)
 }
+// Context shift (Engine::context_shift): n slots, one n_keep and one n_discard each
+int mp_engine_context_shift(void* h, const int32_t* slots, int n, const int32_t* n_keep, const int32_t* n_discard) {
+  API_TRY
+  if (n < 0 || (n > 0 && (!slots || !n_keep || !n_discard))) throw std::runtime_error("context_shift: bad arguments");
+  static_cast<Engine*>(h)->context_shift(std::vector<int>(slots, slots + n), std::vector<int>(n_keep, n_keep + n),
+                                         std::vector<int>(n_discard, n_discard + n));
+  return 0;
+  API_CATCH(-1)
+}
+int mp_engine_set_slot_keep(void* h, int slot, int n_keep) {
+  API_TRY
+  static_cast<Engine*>(h)->set_slot_keep(slot, n_keep);
+  return 0;
+  API_CATCH(-1)
+}
+int mp_engine_slot_position(void* h, int slot) {
+  API_TRY
+  Engine* e = static_cast<Engine*>(h);
+  if (slot < 0 || slot >= e->n_mb() * e->mb_size()) throw std::runtime_error("slot_position: slot out of range");
+  return e->slot_position(slot);
+  API_CATCH(-1)
+}
+int mp_engine_slot_shifts(void* h, int slot) {
+  API_TRY
+  return static_cast<Engine*>(h)->slot_shifts(slot);
+  API_CATCH(-1)
+}
+// KvPager::shift on a fresh pager (host only; the unit-test hook): slot s is first granted
+// tokens[s] positions, s ascending, then `slot` is shifted.  Out: the table [n_slots][max_pages], the
+// free list in the order the next grants take its pages ([n_pages] room; *n_free entries), the
+// merge source page.
+int mp_kvpager_shift(int n_slots, int max_pages, int n_pages, const int32_t* tokens, int slot, int n_keep, int n_discard,
+                     int32_t* table_out, int32_t* free_out, int32_t* n_free, int32_t* merge_out) {
+  API_TRY
+  KvPager pg;
+  pg.init(n_slots, max_pages, n_pages);
+  for (int s = 0; s < n_slots; ++s)
+    if (tokens && tokens[s] > 0 && !pg.ensure(s, tokens[s])) throw std::runtime_error("kvpager_shift: pool exhausted");
+  const int merge = pg.shift(slot, n_keep, n_discard);
+  if (merge_out) *merge_out = merge;
+  if (table_out) std::copy(pg.table().begin(), pg.table().end(), table_out);
+  const std::vector<int32_t>& fl = pg.free_list();
+  if (n_free) *n_free = (int32_t)fl.size();
+  if (free_out) std::copy(fl.rbegin(), fl.rend(), free_out);
+  return pg.owned(slot);
+  API_CATCH(-1)
+}
 int mp_engine_release(void* h, int slot) {
   API_TRY
   static_cast<Engine*>(h)->release(slot);
@@ -1235,6 +1312,14 @@ int mp_engine_tokens(void* h, int32_t* out, int n_seq, int cap) {
     for (int j = 0; j < cap; ++j) out[(size_t)i * cap + j] = j < (int)t[i].size() ? t[i][j] : -1;
   }
   return n;
+  API_CATCH(-1)
+}
+// tokens of the longest sequence (a context_shift engine generates past max_ctx: size buffers by this)
+int mp_engine_tokens_longest(void* h) {
+  API_TRY
+  size_t n = 0;
+  for (const auto& t : static_cast<Engine*>(h)->tokens()) n = std::max(n, t.size());
+  return (int)n;
   API_CATCH(-1)
 }
 // log-probabilities of the generated tokens (engine config n_probs != 0), aligned with

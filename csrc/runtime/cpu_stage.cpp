@@ -606,6 +606,47 @@ void CpuStage::set_block_table(const std::vector<int32_t>& t) {
   bt_ = t;
 }
 
+// Context shift on the f32 rows: the same definition as kv_shift.hip, in the model's own pair layout
+// (adjacent pairs, or NEOX (i, i + hd / 2)), with the angle n_discard * inv_freq the forward pass
+// would use for that distance.  Rows are gathered through the OLD table and stored through the new
+// one in ascending position: a destination row is never a source row still to be read, because the
+// tail pages keep their place (the move is the identity on them) and the merge source is a page the
+// new row no longer holds.
+void CpuStage::kv_shift(const std::vector<KvShiftRec>& recs, const std::vector<int32_t>& table) {
+  const std::vector<int32_t> old_bt = bt_;
+  set_block_table(table);
+  const int hd = cfg_.head_dim, half = hd / 2, Hkv = cfg_.n_head_kv;
+  const int pstride = cfg_.rope_neox ? 1 : 2, poff = cfg_.rope_neox ? half : 1;
+  const size_t kvd = (size_t)cfg_.kv_dim();
+  std::vector<float> c(half), s(half);
+  for (const KvShiftRec& r : recs) {
+    if (r.slot < 0 || (size_t)r.slot * max_pages_ >= bt_.size()) throw std::runtime_error("kv_shift: slot out of range");
+    if (r.n_keep < 0 || r.n_discard <= 0 || r.n_discard % 64 != 0 || r.n_keep + r.n_discard > r.old_len ||
+        r.old_len > max_pages_ * 64)
+      throw std::runtime_error("kv_shift: bad record");
+    for (int i = 0; i < half; ++i) {
+      const float a = r.n_discard * inv_freq_[i];
+      c[i] = std::cos(a); s[i] = std::sin(a);
+    }
+    for (int p = r.n_keep + r.n_discard; p < r.old_len; ++p) {
+      const size_t src = ((size_t)old_bt[(size_t)r.slot * max_pages_ + p / 64] * 64 + p % 64) * kvd;
+      const size_t dst = kv_row(r.slot, p - r.n_discard) * kvd;
+      for (size_t li = 0; li < kc_.size(); ++li) {
+        if (dst != src) std::memmove(&vc_[li][dst], &vc_[li][src], kvd * 4);
+        const float* ks = &kc_[li][src];
+        float* kd = &kc_[li][dst];
+        for (int h = 0; h < Hkv; ++h)
+          for (int i = 0; i < half; ++i) {
+            const size_t e0 = (size_t)h * hd + (size_t)pstride * i, e1 = e0 + poff;
+            const float x0 = ks[e0], x1 = ks[e1];
+            kd[e0] = x0 * c[i] + x1 * s[i];
+            kd[e1] = x1 * c[i] - x0 * s[i];
+          }
+      }
+    }
+  }
+}
+
 void CpuStage::kv_export(int slot, int n_tok, std::vector<uint8_t>& out) {
   const size_t row = (size_t)cfg_.kv_dim();
   for (size_t li = 0; li < kc_.size(); ++li)

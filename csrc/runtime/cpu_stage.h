@@ -88,6 +88,7 @@ class CpuStage : public Stage {
   void kv_export(int slot, int n_tok, std::vector<uint8_t>& out) override;
   void set_block_table(const std::vector<int32_t>& table) override;
   void kv_import(int slot, int n_tok, const uint8_t* data, size_t bytes) override;
+  void kv_shift(const std::vector<KvShiftRec>& recs, const std::vector<int32_t>& table) override;
   size_t kv_state_bytes(int n_tok) const override;
   uint64_t sample_step() override { return step_; }
   void set_sample_step(uint64_t s) override { step_ = s; }

@@ -435,6 +435,13 @@ Engine::Engine(const Json& j) : jcfg_(j) {
     bind_life_.reset((size_t)M_ * B_);
     kv_tag_.assign((size_t)M_ * B_, KvTag{});
   }
+  auto_shift_ = j.get_bool("context_shift", false);
+  n_keep_ = j.get_int("n_keep", 0);
+  if (n_keep_ < -1) throw std::runtime_error("\"n_keep\" must be >= 0, or -1 for the whole prompt");
+  if (auto_shift_) check_shift_supported("\"context_shift\"");
+  shifted_.assign((size_t)M_ * B_, 0);
+  n_shifts_.assign((size_t)M_ * B_, 0);
+  slot_keep_.assign((size_t)M_ * B_, n_keep_);
   packed_prefill_ = j.get_bool("packed_prefill", true);
   prefix_cache_ = j.get_bool("prefix_cache", true);
   n_probs_ = j.get_int("n_probs", 0);
@@ -1058,6 +1065,7 @@ Json Engine::health() const {
   j["ok"] = !failed_;
   j["backend"] = cpu_ ? "cpu" : hybrid_ ? "hybrid" : "hip";
   j["prefix_reused_tokens"] = (int64_t)reused_tokens_;
+  j["context_shifts"] = (int64_t)context_shifts_;
   if (failed_stage_ >= 0) {
     j["failed_stage"] = failed_stage_;
     j["failed_device"] = specs_[failed_stage_].device;
@@ -1198,6 +1206,7 @@ void Engine::start(const std::vector<std::vector<int32_t>>& prompts) {
   resumable_ = true;
   base_round_.assign((size_t)M_ * B_, 0);
   active_.assign((size_t)M_ * B_, 0);
+  for (size_t i = 0; i < (size_t)M_ * B_; ++i) reset_shift(i, false);
   for (size_t i = 0; i < prompts.size(); ++i) active_[i] = 1;
   // KV pages: each prompt + its first decode position; slots without a prompt give theirs back
   // (a reused prefix keeps the pages it already owns)
@@ -1543,9 +1552,10 @@ void Engine::refresh_slot_cache() {
   // a released slot's KV is not guaranteed (load_state restores active slots only; live idle rows
   // keep overwriting theirs): never offer it for prefix reuse
   for (size_t i = 0; i < slot_toks_.size(); ++i)
-    if (i < active_.size() && !active_[i]) slot_toks_[i].clear();
+    if ((i < active_.size() && !active_[i]) || (i < n_shifts_.size() && n_shifts_[i] > 0)) slot_toks_[i].clear();
   if (!resumable_ || !owns_first() || !owns_last()) return;
   for (size_t i = 0; i < slot_toks_.size() && i < gen_.size(); ++i) {
+    if (i < n_shifts_.size() && n_shifts_[i] > 0) continue;   // a shifted slot's KV is no token prefix
     const int since = rounds_done_ - (i < base_round_.size() ? base_round_[i] : 0);
     const size_t n = std::min(gen_[i].size(), (size_t)std::max(0, since));
     slot_toks_[i].insert(slot_toks_[i].end(), gen_[i].begin(), gen_[i].begin() + n);
@@ -1569,6 +1579,10 @@ Json Engine::save_state(const std::string& dir) {
   if (!started_) throw std::runtime_error("save_state before start");
   if (failed_) throw std::runtime_error("save_state after a pipeline fault");
   if (!resumable_) throw std::runtime_error("save_state: not supported after speculative decoding");
+  for (size_t i = 0; i < shifted_.size(); ++i)
+    if (shifted_[i] > 0 && i < active_.size() && active_[i])
+      throw std::runtime_error("save_state: not supported after a context shift (slot " + std::to_string(i) +
+                               " has discarded " + std::to_string(shifted_[i]) + " positions)");
   for (size_t s = 0; s < bind_id_.size(); ++s)
     if (bind_id_[s] >= 0)
       throw std::runtime_error("save_state: slot " + std::to_string(s) + " is bound to LoRA adapter " + std::to_string(bind_id_[s]) +
@@ -1695,6 +1709,7 @@ Json Engine::load_state(const std::string& dir) {
   }
   base_round_.assign((size_t)M_ * B_, 0);
   active_.assign((size_t)M_ * B_, 0);
+  for (size_t i = 0; i < (size_t)M_ * B_; ++i) reset_shift(i, false);
   for (size_t i = 0; i < prompts_.size(); ++i) {
     base_round_[i] = sj.has("base_round") ? (int)sj["base_round"].arr()[i].num() : 0;
     active_[i] = sj.has("active") ? (char)sj["active"].arr()[i].num() : 1;
@@ -1874,6 +1889,7 @@ void Engine::push_positions(int mb) {
 void Engine::release(int slot) {
   if (slot >= 0 && slot < (int)active_.size()) active_[slot] = 0;
   if (slot >= 0 && slot < M_ * B_) pager_.release(slot);   // table pushed before the next engine call
+  if (slot >= 0 && slot < M_ * B_) reset_shift((size_t)slot, true);
   if (row_sampling_ && !failed_ && slot >= 0 && slot < M_ * B_) {
     // the stage too: an idle row at the engine's values stops running a finished request's chain
     slot_rec_[slot] = row_default_;
@@ -1890,6 +1906,83 @@ void Engine::release(int slot) {
     push_bindings({slot}, {-1}, {0.f}, true);   // (the slot is idle by now: its KV tag stays what computed it)
     bind_life_.clear(slot);
   }
+}
+
+// ---------------------------------------------------------------- context shift
+void Engine::reset_shift(size_t slot, bool keep_too) {
+  if (slot < shifted_.size()) { shifted_[slot] = 0; n_shifts_[slot] = 0; }
+  if (keep_too && slot < slot_keep_.size()) slot_keep_[slot] = n_keep_;
+}
+
+void Engine::check_shift_supported(const char* fn) const {
+  const std::string f = std::string(fn) + ": ";
+  if (mode_ == "mp") throw std::runtime_error(f + "mode \"mp\" is not supported");
+  if (jcfg_.get_int("world", 1) > 1) throw std::runtime_error(f + "a multi-process ring (\"world\" > 1) is not supported");
+  if (jcfg_.has("rpc")) throw std::runtime_error(f + "rpc workers (\"rpc\") are not supported");
+}
+
+void Engine::set_slot_keep(int slot, int n_keep) {
+  if (slot < 0 || slot >= M_ * B_) throw std::runtime_error("set_slot_keep: slot " + std::to_string(slot) + " is out of range");
+  if (n_keep < -1) throw std::runtime_error("set_slot_keep: n_keep must be >= 0, or -1 for the whole prompt");
+  slot_keep_[slot] = n_keep;
+}
+
+int Engine::shift_discard(int slot) const {
+  if (slot < 0 || slot >= M_ * B_) return 0;
+  const size_t i = (size_t)slot;
+  const int plen = i < prompts_.size() ? (int)prompts_[i].size() : 0;
+  const int keep = slot_keep_[i] < 0 ? plen : std::min(slot_keep_[i], plen);
+  return std::max(0, ((slot_pos(i) - keep) / 2) / KvPager::kPage * KvPager::kPage);
+}
+
+int Engine::context_room() const {
+  int room = rounds_cap_ - 2;
+  for (size_t i = 0; i < active_.size(); ++i)
+    if (active_[i]) room = std::min(room, max_ctx_ - slot_pos(i) - 1);
+  return room;
+}
+
+void Engine::context_shift(const std::vector<int>& slots, const std::vector<int>& n_keep, const std::vector<int>& n_discard) {
+  check_shift_supported("context_shift");
+  if ((int)workers_.size() != S_) throw std::runtime_error("context_shift: needs every stage in this process");
+  if (!resumable_) throw std::runtime_error("context_shift: not supported after speculative decoding");
+  if (!started_) throw std::runtime_error("context_shift before start");
+  if (failed_) throw std::runtime_error("context_shift after a pipeline fault");
+  if (slots.size() != n_keep.size() || slots.size() != n_discard.size())
+    throw std::runtime_error("context_shift: one n_keep and one n_discard per slot");
+  for (size_t k = 0; k < slots.size(); ++k) {   // everything is checked before anything changes
+    check_slot_at("context_shift", slots, k);
+    const std::string id = "context_shift: slot " + std::to_string(slots[k]);
+    if (!slot_active(slots[k])) throw std::runtime_error(id + " is idle");
+    if (n_keep[k] < 0) throw std::runtime_error(id + ": n_keep < 0");
+    if (n_discard[k] <= 0) throw std::runtime_error(id + ": n_discard must be > 0");
+    if (n_discard[k] % KvPager::kPage != 0)
+      throw std::runtime_error(id + ": n_discard " + std::to_string(n_discard[k]) + " is not a multiple of " +
+                               std::to_string(KvPager::kPage));
+    if ((int64_t)n_keep[k] + n_discard[k] > slot_pos((size_t)slots[k]))
+      throw std::runtime_error(id + ": n_keep + n_discard exceeds its " + std::to_string(slot_pos((size_t)slots[k])) +
+                               " cached positions");
+  }
+  if (slots.empty()) return;
+  std::vector<KvShiftRec> recs;
+  std::vector<char> mbs(M_, 0);
+  for (size_t k = 0; k < slots.size(); ++k) {
+    const size_t i = (size_t)slots[k];
+    KvShiftRec r{};
+    r.slot = slots[k]; r.n_keep = n_keep[k]; r.n_discard = n_discard[k]; r.old_len = slot_pos(i);
+    r.merge_src_page = pager_.shift(slots[k], n_keep[k], n_discard[k]);
+    recs.push_back(r);
+    shifted_[i] += n_discard[k];
+    n_shifts_[i] += 1;
+    context_shifts_ += 1;
+    if (i < slot_toks_.size()) slot_toks_[i].clear();   // no token prefix any more
+    mbs[i / B_] = 1;
+  }
+  // (the merge source pages are on the free list by now; nothing is granted before the stages are done)
+  for_each_stage([&](Worker& w) { w.stage->kv_shift(recs, pager_.table()); });
+  pager_.clean();
+  for (int mb = 0; mb < M_; ++mb)
+    if (mbs[mb]) push_positions(mb);
 }
 
 void Engine::kv_grant(size_t slot, int n_tokens) {
@@ -1927,6 +2020,7 @@ void Engine::admit(const std::vector<int>& slots, const std::vector<std::vector<
     gen_[i].clear();
     gen_lp_[i] = {};
     base_round_[i] = rounds_done_;
+    reset_shift((size_t)i, false);
     active_[i] = 1;
     seqs.push_back((size_t)i);
     mbs[i / B_] = 1;
@@ -1977,6 +2071,24 @@ void Engine::admit(const std::vector<int>& slots, const std::vector<std::vector<
 StepStats Engine::decode_steps(int k) {
   if (!started_) throw std::runtime_error("decode_steps before start");
   if (k + 1 >= rounds_cap_) throw std::runtime_error("decode_steps: too many rounds in one call");
+  // "context_shift": a running sequence that these k rounds would carry past max_ctx first gives up
+  // half of what follows its kept prefix (llama.cpp's rule, rounded down to whole pages)
+  if (auto_shift_) {
+    std::vector<int> ss, kp, nd;
+    for (size_t i = 0; i < (size_t)M_ * B_ && i < active_.size(); ++i) {
+      const int pos = slot_pos(i);
+      if (!active_[i] || pos + k + 1 <= max_ctx_) continue;
+      const int d = shift_discard((int)i);
+      // decided for every slot before any is shifted: a call that fails changes nothing
+      if (d <= 0 || pos - d + k + 1 > max_ctx_)
+        throw std::runtime_error("context capacity exhausted (prompt + generated tokens > max_ctx): a context shift of slot " +
+                                 std::to_string(i) + " can discard " + std::to_string(d) + " of its " + std::to_string(pos) +
+                                 " positions, too few for " + std::to_string(k) + " more rounds");
+      const int plen = i < prompts_.size() ? (int)prompts_[i].size() : 0;
+      ss.push_back((int)i); kp.push_back(slot_keep_[i] < 0 ? plen : std::min(slot_keep_[i], plen)); nd.push_back(d);
+    }
+    if (!ss.empty()) context_shift(ss, kp, nd);
+  }
   // running sequences must fit their slot's KV pages; idle rows (which still compute) restart at
   // position 0 before they could run past them
   for (size_t i = 0; i < (size_t)M_ * B_; ++i) {
@@ -2106,6 +2218,7 @@ void Engine::score(const std::vector<std::vector<int32_t>>& prompts, int n_top, 
   rounds_done_ = 0;
   base_round_.assign((size_t)M_ * B_, 0);
   active_.assign((size_t)M_ * B_, 0);
+  for (size_t i = 0; i < (size_t)M_ * B_; ++i) reset_shift(i, false);
   for (size_t i = n; i < (size_t)M_ * B_; ++i) pager_.release((int)i);
   for (size_t i = 0; i < n; ++i)
     if (prompts[i].size() > 1) kv_grant(i, (int)prompts[i].size() - 1);
@@ -2308,15 +2421,25 @@ void Engine::embed(const std::vector<int>& slots, const std::vector<std::vector<
 Json Engine::generate(const std::vector<std::vector<int32_t>>& prompts, int n_predict,
                       std::vector<std::vector<int32_t>>* out) {
   const double t0 = now_ms();
+  const long shifts0 = context_shifts_;
   start(prompts);
   const double t1 = now_ms();
   StepStats ss;
-  if (n_predict > 1) ss = decode_steps(n_predict - 1);
+  if (n_predict > 1 && !auto_shift_) ss = decode_steps(n_predict - 1);
+  // "context_shift": each call runs up to the round that fills the fullest slot, the next one shifts it
+  for (int left = n_predict - 1; auto_shift_ && left > 0;) {
+    const int k = std::min(left, std::max(1, context_room()));
+    const StepStats s1 = decode_steps(k);
+    ss.token_ms.insert(ss.token_ms.end(), s1.token_ms.begin(), s1.token_ms.end());
+    ss.wall_ms += s1.wall_ms;
+    left -= k;
+  }
   const double t2 = now_ms();
   if (out) *out = gen_;
   size_t n_prompt = 0;
   for (auto& p : prompts) n_prompt += p.size();
   Json j = Json::object();
+  if (auto_shift_) j["context_shifts"] = (int64_t)(context_shifts_ - shifts0);   // of this call
   j["prefill_ms"] = t1 - t0;
   j["decode_ms"] = t2 - t1;
   j["n_prompt_tokens"] = (int64_t)n_prompt;
@@ -2358,6 +2481,9 @@ Json Engine::spec_generate(const std::vector<std::vector<int32_t>>& prompts, int
   // drafts, grants KV and builds the identical next verify chunk
   const bool mp = mode_ == "mp" && S_ > 1;
   if (!mp && (int)workers_.size() != S_) throw std::runtime_error("speculative decoding needs every stage in this process");
+  if (auto_shift_)
+    throw std::runtime_error("speculative decoding (draft_max > 0) is not supported with \"context_shift\": "
+                             "its sequences advance by different amounts");
   if (row_sampling_)
     throw std::runtime_error(std::string("speculative decoding is greedy: not on a row_sampling engine") +
                              (row_masks_ ? " (row_masks switches row_sampling on)" : ""));
@@ -2548,6 +2674,9 @@ Json Engine::info() const {
     j["device_speed"] = ds;
   }
   j["kv_free_pages"] = pager_.free_pages();
+  j["context_shift"] = auto_shift_;
+  j["n_keep"] = n_keep_;
+  j["context_shifts"] = (int64_t)context_shifts_;
   j["lora_adapters"] = lora_cap_;
   j["lora_max_rank"] = lora_max_rank_;
   {

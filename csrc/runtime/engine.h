@@ -205,6 +205,33 @@ class Engine {
                          bool for_start = false);
   // the slot's binding: id (-1: none) and scale
   int slot_adapter(int slot, float* scale = nullptr) const;
+  // Context shift (llama.cpp's answer to a full context; local mode, every stage in this process):
+  // for each listed running slot, positions [n_keep, n_keep + n_discard) leave its KV and every later
+  // position moves n_discard back -- V as it is, K rotated by minus n_discard positions (Stage::kv_shift),
+  // nothing recomputed.  n_discard > 0 and a multiple of 64, n_keep >= 0, n_keep + n_discard <=
+  // slot_position(slot).  Between engine calls; the slot's position drops by n_discard, n_discard / 64
+  // pages return to the pool, no graph is re-captured.  The sampler state of the slot (penalty window,
+  // draws, mask, logprobs) and its adapter binding stay.  A shifted slot's KV is no token prefix any
+  // more: it is never a prefix-cache hit until re-admitted, and save_state refuses while one is running.
+  // Throws naming the cause: mode "mp" / world > 1 / rpc, an idle slot, a violated precondition, a
+  // generation that ran speculative decoding.
+  void context_shift(const std::vector<int>& slots, const std::vector<int>& n_keep, const std::vector<int>& n_discard);
+  // Automatic shifting (config "context_shift": true; "n_keep": tokens of the prompt that stay, default 0):
+  // decode_steps(k) first shifts every running slot with position + k + 1 > max_ctx by llama.cpp's rule,
+  // page-aligned: n_keep_eff = min(n_keep, prompt length), n_discard = ((pos - n_keep_eff) / 2) / 64 * 64;
+  // it throws "context capacity exhausted" as without the option when that is 0 or not enough for k.
+  // set_slot_keep: the slot's own n_keep (-1: the whole prompt) from now on; release() puts the
+  // engine's value back.
+  bool auto_shift() const { return auto_shift_; }
+  void set_slot_keep(int slot, int n_keep);
+  long context_shifts() const { return context_shifts_; }
+  // shifts of the slot's running sequence
+  int slot_shifts(int slot) const { return slot >= 0 && slot < (int)n_shifts_.size() ? n_shifts_[slot] : 0; }
+  // the most rounds the next decode_steps call can take before a running slot's context is full
+  // (<= 0: one is full now; with automatic shifting a call of 1 round shifts it)
+  int context_room() const;
+  // what an automatic shift of `slot` would discard now (0: nothing, the kept prefix fills the context)
+  int shift_discard(int slot) const;
   int32_t last_token(int slot) const { return slot < (int)gen_.size() && !gen_[slot].empty() ? gen_[slot].back() : -1; }
   int slot_position(int slot) const { return slot_pos((size_t)slot); }
   bool started() const { return started_; }
@@ -349,8 +376,17 @@ class Engine {
   void kv_grant(size_t slot, int n_tokens);   // throws when the pool is exhausted
   void kv_sync();            // push a changed table to the stages (between engine calls)
   int slot_pos(size_t i) const {
-    return (i < prompts_.size() ? (int)prompts_[i].size() : 0) + rounds_done_ - (i < base_round_.size() ? base_round_[i] : 0);
+    return (i < prompts_.size() ? (int)prompts_[i].size() : 0) + rounds_done_ - (i < base_round_.size() ? base_round_[i] : 0) -
+           (i < shifted_.size() ? shifted_[i] : 0);
   }
+  // context shift: per slot the positions its running sequence has discarded and how often, the
+  // slot's n_keep; reset by start, admit, release and load_state
+  bool auto_shift_ = false;
+  int n_keep_ = 0;
+  long context_shifts_ = 0;
+  std::vector<int> shifted_, n_shifts_, slot_keep_;
+  void reset_shift(size_t slot, bool keep_too);
+  void check_shift_supported(const char* fn) const;
   void push_positions(int mb);
   bool row_sampling_ = false;
   bool row_masks_ = false;

@@ -643,6 +643,28 @@ void HipStage::set_block_table(const std::vector<int32_t>& t) {
   HIP_OK(hipMemcpy(block_table_, host_bt_.data(), host_bt_.size() * 4, hipMemcpyHostToDevice));
 }
 
+// Context shift: the new table, then one launch_kv_shift per layer (and per kKvShiftMaxRec records)
+// on the stage's stream.  Plain launches outside the captured decode graphs, which read the table
+// and the positions from device memory: nothing is re-captured.
+void HipStage::kv_shift(const std::vector<KvShiftRec>& recs, const std::vector<int32_t>& table) {
+  set_block_table(table);   // synchronises the stream first
+  KvShiftParams p{};
+  p.block_table = block_table_; p.max_pages = max_pages_; p.n_slots = opt_.n_mb * opt_.mb_size; p.n_pages = n_pages_;
+  p.Hkv = cfg_.n_head_kv; p.hd = cfg_.head_dim; p.Dp = Dp_; p.kv_fp8 = opt_.kv_fp8 ? 1 : 0;
+  set_v_strides(p.v_kb, p.v_d);
+  p.rope_cs = rope_cs_; p.rope_rows = opt_.max_ctx;
+  for (size_t r0 = 0; r0 < recs.size(); r0 += kKvShiftMaxRec) {
+    p.n_rec = (int)std::min(recs.size() - r0, (size_t)kKvShiftMaxRec);
+    std::copy(recs.begin() + r0, recs.begin() + r0 + p.n_rec, p.rec);
+    for (size_t li = 0; li < layers_.size(); ++li) {
+      p.k_cache = kc_[li]; p.v_cache = vc_[li];
+      launch_kv_shift(p, stream_);
+    }
+  }
+  HIP_OK(hipGetLastError());
+  HIP_OK(hipStreamSynchronize(stream_));
+}
+
 // KV of one slot: per layer the first ceil(n_tok / 64) pages of K, then of V, each page
 // [Hkv][64][Dp] (K) / [Hkv][Dp][64] (V) f16 (or e4m3 bytes), located through the slot's block-table row.
 // The state holds V pages as V^T [Dp][64] whatever the stage's layout: a v_blocked stage permutes

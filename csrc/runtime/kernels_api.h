@@ -198,6 +198,30 @@ struct RopeKvParams {
 };
 void launch_rope_kv(const RopeKvParams& p, hipStream_t st);
 
+// Context shift (kv_shift.hip): positions [n_keep, n_keep + n_discard) of a slot leave one layer's
+// cache and every later entry moves n_discard (a multiple of 64) positions back.  block_table is the
+// table AFTER KvPager::shift: the tail pages stay where they are and the kernel rotates their K rows
+// in place by minus n_discard positions ((c, s) = rope_cs[n_discard][j]: (x0, x1) -> (x0 c + x1 s,
+// x1 c - x0 s), f32 from the stored code, rounded to f16 / e4m3; dims hd..Dp zero).  With
+// n_keep % 64 != 0 the page holding n_keep takes rows [n_keep % 64, 64) of merge_src_page (K rotated,
+// V copied in the (v_kb, v_d) layout); merge_src_page is -1 otherwise.  Nothing but the slot's tail
+// pages and those destination rows is written.  Records name distinct slots.
+constexpr int kKvShiftMaxRec = 16;
+struct KvShiftRec { int32_t slot, n_keep, n_discard, old_len, merge_src_page; };
+struct KvShiftParams {
+  f16* k_cache; f16* v_cache;    // one layer: K [page][Hkv][64][Dp], V [page][Hkv] x (v_kb, v_d)
+  const int32_t* block_table;    // [n_slots][max_pages], the new table
+  int max_pages, n_slots;
+  int n_pages;                   // pool pages: ids >= n_pages (TRASH) are never touched
+  int Hkv, hd, Dp, kv_fp8;
+  int v_kb = 0, v_d = 0;         // V page strides (0 = legacy)
+  const float2* rope_cs; int rope_rows;   // [rope_rows][hd / 2] (cos, sin)
+  int n_rec;
+  KvShiftRec rec[kKvShiftMaxRec];
+};
+// throws, naming it, on a shape or record the kernel cannot take (host-side checks only)
+void launch_kv_shift(const KvShiftParams& p, hipStream_t st);
+
 // Qwen3: RMSNorm over each q and k head of the f32 projection rows, in place, before RoPE:
 // h[:] = h[:] * rsqrt(mean_j(h[j]^2) + eps) * w[:], mean over the hd real elements.  v, the row
 // padding and rows >= M are not written.  Even hd <= 128 (throws otherwise).

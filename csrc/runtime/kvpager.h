@@ -65,8 +65,38 @@ class KvPager {
     owned_[slot] = 0;
   }
 
+  // Context shift: positions [n_keep, n_keep + n_discard) of `slot` leave its KV and every later
+  // position moves n_discard (a multiple of the page size) back, so a row keeps its index inside its
+  // page and the tail pages only move n_discard / 64 entries down the slot's row.  With
+  // r0 = n_keep % 64 != 0 the page holding n_keep stays (rows < r0 are kept) and the old page
+  // n_keep / 64 + n_discard / 64, whose rows [r0, 64) the caller merges into it, is freed with the
+  // discarded ones: it is returned, -1 when n_keep is page-aligned.  n_discard / 64 pages go back
+  // to the free list, highest table entry first (the order release() uses).
+  int shift(int slot, int n_keep, int n_discard) {
+    check(slot);
+    if (n_keep < 0) throw std::runtime_error("KvPager::shift: n_keep < 0");
+    if (n_discard <= 0) throw std::runtime_error("KvPager::shift: n_discard must be > 0");
+    if (n_discard % kPage != 0)
+      throw std::runtime_error("KvPager::shift: n_discard " + std::to_string(n_discard) + " is not a multiple of " +
+                               std::to_string(kPage));
+    if ((int64_t)n_keep + n_discard > (int64_t)owned_[slot] * kPage)
+      throw std::runtime_error("KvPager::shift: n_keep + n_discard exceeds the " + std::to_string(owned_[slot]) +
+                               " pages slot " + std::to_string(slot) + " owns");
+    int32_t* row = &table_[(size_t)slot * max_pages_];
+    const int nd = n_discard / kPage, r0 = n_keep % kPage;
+    const int first = n_keep / kPage + (r0 ? 1 : 0);   // first entry that leaves the row
+    const int merge = r0 ? row[first + nd - 1] : -1;
+    for (int k = first + nd - 1; k >= first; --k) free_.push_back(row[k]);
+    for (int k = first + nd; k < owned_[slot]; ++k) row[k - nd] = row[k];
+    for (int k = owned_[slot] - nd; k < owned_[slot]; ++k) row[k] = n_pages_;
+    owned_[slot] -= nd;
+    dirty_ = true;
+    return merge;
+  }
+
   int owned(int slot) const { check(slot); return owned_[slot]; }
   int free_pages() const { return (int)free_.size(); }
+  const std::vector<int32_t>& free_list() const { return free_; }   // the next grant takes back()
   int n_pages() const { return n_pages_; }
   int max_pages() const { return max_pages_; }
   int trash() const { return n_pages_; }

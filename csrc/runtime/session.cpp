@@ -136,7 +136,9 @@ std::vector<GenResult> Session::run(std::vector<GenRequest>& reqs) {
   }
   int n_max = 0;
   for (auto& r : reqs) n_max = std::max(n_max, r.n_predict);
-  n_max = std::max(0, std::min(n_max, max_ctx - max_prompt - 1));
+  // a context_shift engine makes room when a sequence fills its context: n_predict is not capped by it
+  const bool shift = eng_->auto_shift();
+  if (!shift) n_max = std::max(0, std::min(n_max, max_ctx - max_prompt - 1));
   // all ranks of a multi-process pipeline must run the same number of rounds: early stop only
   // when this process owns the whole pipeline
   const bool early_stop = eng_->owns_first() && eng_->owns_last();
@@ -192,6 +194,11 @@ std::vector<GenResult> Session::run(std::vector<GenRequest>& reqs) {
   };
   const double t0 = now_ms();
   const int draft_max = eng_->config().get_int("draft_max", 0);
+  if (shift && draft_max > 0)
+    throw std::runtime_error("context_shift cannot be combined with speculative decoding (draft_max)");
+  if (shift)
+    for (size_t i = 0; i < reqs.size(); ++i)
+      eng_->set_slot_keep((int)i, reqs[i].has_keep ? reqs[i].n_keep : eng_->config().get_int("n_keep", 0));
   if (draft_max > 0 && early_stop) {
     // speculative decoding by prompt lookup (greedy): tokens arrive in accepted runs per round
     std::vector<int> steps(reqs.size(), 0);
@@ -239,7 +246,23 @@ std::vector<GenResult> Session::run(std::vector<GenRequest>& reqs) {
   }
   int step = 1;
   auto any_active = [&] { return std::any_of(active.begin(), active.end(), [](bool b) { return b; }); };
+  // context_shift: a full slot whose kept prefix leaves a shift nothing to discard cannot go on.  Its
+  // request (if it still runs) ends with stop "context", and the slot is released so that the round
+  // below does not fail for everyone; requests that have finished keep running in the engine until then.
+  std::vector<int> shifts_at_release(reqs.size(), -1);
+  auto retire_full_slots = [&] {
+    for (size_t i = 0; i < reqs.size(); ++i) {
+      if (!eng_->slot_active((int)i) || eng_->slot_position((int)i) + 2 <= max_ctx || eng_->shift_discard((int)i) > 0) continue;
+      if (active[i]) { active[i] = false; res[i].stop = "context"; if (gs[i].valid()) dirty[i] = 1; }
+      shifts_at_release[i] = eng_->slot_shifts((int)i);
+      eng_->release((int)i);
+    }
+  };
   while (step < n_max && (!early_stop || any_active())) {
+    if (shift) {
+      retire_full_slots();
+      if (early_stop && !any_active()) break;
+    }
     sync_masks(false);
     eng_->decode_steps(1);
     const auto toks = eng_->tokens();
@@ -250,6 +273,8 @@ std::vector<GenResult> Session::run(std::vector<GenRequest>& reqs) {
   const double t2 = now_ms();
   for (size_t i = 0; i < reqs.size(); ++i) {
     if (active[i]) res[i].stop = n_max < reqs[i].n_predict ? "context" : "length";
+    res[i].n_shifts = shifts_at_release[i] >= 0 ? shifts_at_release[i] : eng_->slot_shifts((int)i);
+    res[i].context_shift = shift;
     const std::string tail = acc[i].buf;
     if (!tail.empty()) {
       res[i].text += tail;
@@ -387,8 +412,15 @@ void Session::serve(const std::function<std::vector<Served>(int free)>& next) {
     if (!p.empty() && L.s.req.on_piece && !L.s.req.on_piece(p)) { r.stop = "cancelled"; return false; }
     if (L.gs.valid() && L.gs.only_end()) { r.stop = "eog"; return false; }   // nothing can follow
     if (L.step >= L.s.req.n_predict) { r.stop = "length"; return false; }
-    // the context or the request's share of the KV pool is full
-    if (eng_->slot_position(slot) + 1 >= std::min(max_ctx, L.pages * 64)) { r.stop = "context"; return false; }
+    // the context or the request's share of the KV pool is full (a context_shift engine makes room in
+    // the context at the next round; a share below max_ctx still ends the request)
+    const int room = eng_->auto_shift() && L.pages * 64 >= max_ctx ? max_ctx + 1 : std::min(max_ctx, L.pages * 64);
+    if (eng_->slot_position(slot) + 1 >= room) { r.stop = "context"; return false; }
+    // full, and its kept prefix leaves a shift nothing to discard: the request ends like without the option
+    if (eng_->auto_shift() && eng_->slot_position(slot) + 2 > max_ctx && eng_->shift_discard(slot) <= 0) {
+      r.stop = "context";
+      return false;
+    }
     return true;
   };
   // the masks of the given slots' grammar requests, one engine call (made inside guarded(): it copies
@@ -413,6 +445,8 @@ void Session::serve(const std::function<std::vector<Served>(int free)>& next) {
       if (L.s.req.on_piece && L.res.stop != "cancelled") L.s.req.on_piece(L.acc.buf);
     }
     L.res.decode_ms = now_ms() - L.t1;
+    L.res.n_shifts += eng_->slot_shifts(slot);   // (+=: a failover re-admits the request with a fresh count)
+    L.res.context_shift = eng_->auto_shift();
     if (L.s.done) L.s.done(L.res);
     eng_->release(slot);
     reserved -= L.pages;
@@ -574,6 +608,11 @@ void Session::serve(const std::function<std::vector<Served>(int free)>& next) {
       // nothing running: a plain start() of slots 0..n-1 (resets the engine's rounds)
       const bool ok = guarded([&] {
         for (int sl : slots) set_slot_record(sl, live[sl]->s.req, live[sl]->res);
+        if (eng_->auto_shift())
+          for (int sl : slots) {
+            const GenRequest& rq = live[sl]->s.req;
+            eng_->set_slot_keep(sl, rq.has_keep ? rq.n_keep : eng_->config().get_int("n_keep", 0));
+          }
         const bool as_start = idle && slots.back() == (int)slots.size() - 1;
         sync_masks(slots, true);   // the first token is constrained too
         if (as_start) eng_->start(prompts);

@@ -35,6 +35,10 @@ struct GenRequest {
   // model) and its user scale; bound in the same guarded call as the sampling record, kept across a failover
   int lora_id = -1;
   float lora_scale = 1.f;
+  // context shift (engines built with context_shift): the prompt tokens a shift of this request keeps
+  // (-1: the whole prompt); without has_keep the engine's n_keep
+  bool has_keep = false;
+  int n_keep = 0;
   // receives text pieces (complete UTF-8); return false to cancel this sequence
   std::function<bool(const std::string& piece)> on_piece;
 };
@@ -53,7 +57,10 @@ struct GenResult {
   int n_prompt = 0, n_gen = 0;
   double prefill_ms = 0, decode_ms = 0;
   std::string text;
-  std::string stop;   // "eog" | "length" | "cancelled" | "context"
+  std::string stop;   // "eog" | "length" | "cancelled" | "context" (never "context" on a context_shift engine
+                      // whose pool holds max_ctx per request)
+  int n_shifts = 0;   // context shifts the request went through
+  bool context_shift = false;   // it ran on a context_shift engine
   std::vector<int32_t> tokens;
   std::vector<TokenProb> probs;   // one per token of `tokens` when the engine records logprobs
   bool has_seed = false;          // row_sampling engines: the seed of the request's random stream

@@ -222,6 +222,12 @@ class Stage {
   // installed between engine calls (the stage's stream is idle or synchronised first)
   virtual void set_block_table(const std::vector<int32_t>& table) = 0;
   virtual void kv_import(int slot, int n_tok, const uint8_t* data, size_t bytes) = 0;
+  // Context shift, between engine calls: `table` is the block table after KvPager::shift of every
+  // record's slot.  Installs it, then, in every layer of this stage, moves each record's entries of
+  // positions >= n_keep + n_discard back by n_discard (KvShiftRec, kernels_api.h): V as it is, K
+  // rotated by minus n_discard positions; positions < n_keep and every other slot are not touched.
+  // Returns with the work done.  Never touches a captured graph.
+  virtual void kv_shift(const std::vector<KvShiftRec>& recs, const std::vector<int32_t>& table) = 0;
   virtual size_t kv_state_bytes(int n_tok) const = 0;   // bytes kv_export appends for n_tok
   // sampling step counter (seeds the per-row RNG streams of the sampler)
   virtual uint64_t sample_step() = 0;

@@ -125,6 +125,10 @@ inline void print_common_usage(FILE* f) {
           "                            (ids in order), one alone is every request's default unless\n"
           "                            --lora-init-without-apply.  Sets the engine key lora_adapters (--lora-max-rank N,\n"
           "                            default 64); not with --world or --rpc\n"
+          "  --context-shift           when a sequence fills the context (-c), drop half of what follows the first\n"
+          "                            --keep tokens of its prompt (in whole 64-token pages) and go on generating:\n"
+          "                            -n is no longer capped by -c.  --no-context-shift (default): it ends there\n"
+          "  --keep N                  prompt tokens a context shift keeps (default 0; -1: the whole prompt)\n"
           "  --draft-max K             speculative decoding by prompt lookup: up to K drafted tokens per\n"
           "                            verify round (greedy; --lookup-ngram N, default 3)\n"
           "placement / pipeline:\n"
@@ -196,6 +200,9 @@ inline CliOptions parse_cli(int argc, char** argv,
     else if (a == "--prefill-chunk" || a == "-ub" || a == "--ubatch-size") e["prefill_chunk"] = std::atoi(val().c_str());
     else if (a == "--no-graphs") e["graphs"] = false;
     else if (a == "--draft-max" || a == "--draft") e["draft_max"] = std::atoi(val().c_str());   // prompt-lookup speculation
+    else if (a == "--context-shift") e["context_shift"] = true;
+    else if (a == "--no-context-shift") e["context_shift"] = false;
+    else if (a == "--keep") e["n_keep"] = std::atoi(val().c_str());
     else if (a == "--lookup-ngram") e["lookup_ngram"] = std::atoi(val().c_str());
     else if (a == "--threads" || a == "-t") e["threads"] = std::atoi(val().c_str());
     else if (a == "--cpu-act") e["cpu_act"] = val();   // CPU stages: q8 (integer dots, default) | f32
@@ -279,6 +286,12 @@ inline CliOptions parse_cli(int argc, char** argv,
     if (e.get_int("draft_max", 0) > 0) throw std::runtime_error("a grammar cannot be combined with --draft-max");
     if (!e.has("gguf")) throw std::runtime_error("a grammar needs a model with a tokenizer (-m FILE)");
     e["row_masks"] = true;
+  }
+  if (e.get_bool("context_shift", false)) {
+    if (world > 0) throw std::runtime_error("--context-shift needs every stage in this process (not with --world)");
+    if (!rpc.empty()) throw std::runtime_error("--context-shift cannot be combined with --rpc");
+    if (e.get_int("draft_max", 0) > 0) throw std::runtime_error("--context-shift cannot be combined with --draft-max");
+    if (e.get_int("n_keep", 0) < -1) throw std::runtime_error("--keep must be >= 0, or -1 for the whole prompt");
   }
   if (!o.lora.empty()) {
     if (world > 0) throw std::runtime_error("--lora needs every stage in this process (a multi-process ring, --world, is not supported)");

@@ -127,6 +127,7 @@ static int run_daemon(Session& s) {
     std::vector<GenRequest> reqs(1);
     reqs[0].prompt = rq.get_str("prompt", "");
     reqs[0].n_predict = rq.get_int("n_predict", 200);
+    if (rq.has("n_keep")) { reqs[0].has_keep = true; reqs[0].n_keep = rq.get_int("n_keep", 0); }
     reqs[0].on_piece = [](const std::string& p) {
       Json o = Json::object();
       o["piece"] = p;
@@ -142,6 +143,7 @@ static int run_daemon(Session& s) {
     d["prefill_ms"] = r.prefill_ms;
     d["decode_ms"] = r.decode_ms;
     d["stop"] = r.stop;
+    d["n_shifts"] = r.n_shifts;
     printf("%s\n", d.dump().c_str());
     fflush(stdout);
   }
@@ -275,6 +277,7 @@ int main(int argc, char** argv) {
       fputs("\n", stdout);
       fflush(stdout);
       MP_LOGI("\n%s", Session::perf_summary(r, eng.load_ms()).c_str());
+      if (eng.auto_shift()) MP_LOGI("stop: %s after %d tokens, %d context shifts", r.stop.c_str(), r.n_gen, r.n_shifts);
     }
     if (!state_save.empty()) eng.save_state(state_save);
     if (!o.trace.empty()) eng.write_trace(o.trace);

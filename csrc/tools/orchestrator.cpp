@@ -85,6 +85,8 @@ struct Job {
   std::shared_ptr<const Grammar> grammar;   // constrained output (--row-masks): grammar | json_schema | response_format
   int lora_id = -1;            // LoRA (--lora): the request's adapter (-1: the base model) and scale
   float lora_scale = 1.f;
+  bool has_keep = false;       // context shift (--context-shift): the request's own n_keep (-1: its whole prompt)
+  int n_keep = 0;
   double enqueued_ms = 0;   // fairness between models (serve_model)
   std::mutex mu;
   std::condition_variable cv;
@@ -122,6 +124,7 @@ struct Metrics {
   std::mutex mu;
   uint64_t requests = 0, completed = 0, cancelled = 0, errors = 0, prompt_tokens = 0, gen_tokens = 0;
   uint64_t embed_requests = 0, embed_tokens = 0;
+  uint64_t context_shifts = 0;
   double last_decode_tok_s = 0, last_prefill_tok_s = 0;
   std::vector<double> token_ms;   // recent per-token latencies
   void add_latency(double ms) {
@@ -272,8 +275,10 @@ void record_result(Server& S, Job& j, const GenResult& r, double load_ms) {
   const std::string perf = Session::perf_summary(r, load_ms);
   j.push({"log", perf});
   fputs(perf.c_str(), stderr);
+  if (r.n_shifts > 0) j.push({"log", "context shifts: " + std::to_string(r.n_shifts) + "\n"});
   std::lock_guard<std::mutex> l(S.metrics.mu);
   S.metrics.completed++;
+  S.metrics.context_shifts += (uint64_t)std::max(0, r.n_shifts);
   if (r.stop == "cancelled") S.metrics.cancelled++;
   S.metrics.prompt_tokens += r.n_prompt;
   S.metrics.gen_tokens += r.n_gen;
@@ -376,6 +381,7 @@ void serve_model(Server& S, ModelSlot* slot, const std::string& model) {
       sv.req.has_sampling = j->has_sampling; sv.req.has_seed = j->has_seed; sv.req.sampling = j->sampling;
       sv.req.grammar = j->grammar;
       sv.req.lora_id = j->lora_id; sv.req.lora_scale = j->lora_scale;
+      sv.req.has_keep = j->has_keep; sv.req.n_keep = j->n_keep;
       Job* jp = j.get();
       sv.req.on_piece = [jp](const std::string& p) {
         if (jp->cancelled) return false;
@@ -552,6 +558,7 @@ void generation_loop(Server& S) {
           reqs[i].has_sampling = batch[i]->has_sampling; reqs[i].has_seed = batch[i]->has_seed;
           reqs[i].sampling = batch[i]->sampling;
           reqs[i].lora_id = batch[i]->lora_id; reqs[i].lora_scale = batch[i]->lora_scale;
+          reqs[i].has_keep = batch[i]->has_keep; reqs[i].n_keep = batch[i]->n_keep;
           reqs[i].grammar = batch[i]->grammar;
           Job* jp = batch[i].get();
           reqs[i].on_piece = [jp](const std::string& p) {
@@ -870,7 +877,23 @@ struct ReqSampling {
   std::shared_ptr<const Grammar> grammar;
   int lora_id = -1;
   float lora_scale = 1.f;
+  bool has_keep = false;
+  int n_keep = 0;
 };
+
+// "n_keep": the prompt tokens a context shift of this request keeps (-1: the whole prompt); the field
+// is accepted on every server and used by one started with --context-shift
+bool parse_keep(int fd, const Json& body, ReqSampling* out) {
+  if (!body.has("n_keep") || body["n_keep"].is_null()) return true;
+  const Json& v = body["n_keep"];
+  if (!v.is_num() || v.num() != std::floor(v.num()) || v.num() < -1 || v.num() > 1e9) {
+    respond_text(fd, 400, "n_keep must be an integer >= 0, or -1 for the whole prompt");
+    return false;
+  }
+  out->has_keep = true;
+  out->n_keep = (int)v.num();
+  return true;
+}
 
 // [{"id", "scale"}, ..] -> the one adapter with a non-zero scale (-1: none).  Throws naming the cause.
 void parse_lora_list(const Json& a, size_t n_adapters, int* id, float* scale) {
@@ -1040,6 +1063,7 @@ std::shared_ptr<Job> submit(Server& S, const std::string& prompt, int n, const s
   auto job = std::make_shared<Job>();
   if (rs) job->grammar = rs->grammar;
   if (rs) { job->lora_id = rs->lora_id; job->lora_scale = rs->lora_scale; }
+  if (rs) { job->has_keep = rs->has_keep; job->n_keep = rs->n_keep; }
   if (rs && rs->has) { job->has_sampling = true; job->has_seed = rs->has_seed; job->sampling = rs->rec; }
   job->prompt = prompt;
   job->n_predict = n;
@@ -1083,7 +1107,9 @@ void handle_chat(Server& S, int fd, const Request& r) {
   Json body;
   if (!parse_prompt_body(fd, r, &prompt, &n, S.default_n, &model, &body) || !known_model(S, fd, &model)) return;
   ReqSampling rs;
-  if (!parse_sampling(S, fd, body, model, &rs) || !parse_grammar(S, fd, body, model, &rs) || !parse_lora(S, fd, body, model, &rs)) return;
+  if (!parse_sampling(S, fd, body, model, &rs) || !parse_grammar(S, fd, body, model, &rs) || !parse_lora(S, fd, body, model, &rs) ||
+      !parse_keep(fd, body, &rs))
+    return;
   auto job = submit(S, prompt, n, model, &rs);
   std::string h = "HTTP/1.1 200 OK\r\nContent-Type: text/event-stream\r\nCache-Control: no-cache\r\n";
   h += kCors;
@@ -1140,7 +1166,9 @@ void handle_completion(Server& S, int fd, const Request& r) {
     return;
   }
   ReqSampling rs;
-  if (!parse_sampling(S, fd, body, model, &rs) || !parse_grammar(S, fd, body, model, &rs) || !parse_lora(S, fd, body, model, &rs)) return;
+  if (!parse_sampling(S, fd, body, model, &rs) || !parse_grammar(S, fd, body, model, &rs) || !parse_lora(S, fd, body, model, &rs) ||
+      !parse_keep(fd, body, &rs))
+    return;
   auto job = submit(S, prompt, n, model, &rs);
   {
     std::unique_lock<std::mutex> l(job->mu);
@@ -1173,6 +1201,7 @@ void handle_completion(Server& S, int fd, const Request& r) {
   }
   o["tokens_evaluated"] = g.n_prompt;
   o["stop_reason"] = g.stop;
+  if (g.context_shift) o["context_shifts"] = g.n_shifts;   // --context-shift servers only: every other reply keeps its fields
   Json t = Json::object();
   t["prompt_ms"] = g.prefill_ms;
   t["predicted_ms"] = g.decode_ms;
@@ -1324,6 +1353,9 @@ void handle_metrics(Server& S, int fd) {
              "# TYPE mipipe_embedding_requests_total counter\nmipipe_embedding_requests_total %llu\n"
              "# TYPE mipipe_embedding_tokens_total counter\nmipipe_embedding_tokens_total %llu\n",
              (unsigned long long)M.embed_requests, (unsigned long long)M.embed_tokens);
+    m += b;
+    snprintf(b, sizeof(b), "# TYPE mipipe_context_shifts_total counter\nmipipe_context_shifts_total %llu\n",
+             (unsigned long long)M.context_shifts);
     m += b;
     snprintf(b, sizeof(b),
              "# TYPE mipipe_decode_tokens_per_second gauge\nmipipe_decode_tokens_per_second %.3f\n"

@@ -146,6 +146,14 @@ _SIGS = {
     "mp_engine_start": ([c_void_p, c_void_p, c_void_p, c_int], c_int),
     "mp_engine_admit": ([c_void_p, c_void_p, c_void_p, c_void_p, c_int], c_int),
     "mp_engine_release": ([c_void_p, c_int], c_int),
+    "mp_engine_context_shift": ([c_void_p, c_void_p, c_int, c_void_p, c_void_p], c_int),
+    "mp_engine_set_slot_keep": ([c_void_p, c_int, c_int], c_int),
+    "mp_engine_slot_position": ([c_void_p, c_int], c_int),
+    "mp_engine_slot_shifts": ([c_void_p, c_int], c_int),
+    "mp_kvpager_shift": ([c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
+                         c_int),
+    "mp_op_kv_shift": ([c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int,
+                        c_void_p, c_int, c_void_p], c_int),
     "mp_engine_set_slot_sampling": ([c_void_p, c_int, c_char_p, c_int], c_int),
     "mp_engine_slot_sampling": ([c_void_p, c_int], c_char_p),
     "mp_row_sampling_bytes": ([], c_int),
@@ -180,6 +188,7 @@ _SIGS = {
     "mp_json_schema_to_gbnf": ([c_char_p], c_char_p),
     "mp_engine_decode": ([c_void_p, c_int], c_char_p),
     "mp_engine_tokens": ([c_void_p, c_void_p, c_int, c_int], c_int),
+    "mp_engine_tokens_longest": ([c_void_p], c_int),
     "mp_engine_logprobs": ([c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int], c_int),
     "mp_engine_score": ([c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p], c_int),
     "mp_engine_embed": ([c_void_p, c_char_p, c_void_p, ctypes.c_long], ctypes.c_long),

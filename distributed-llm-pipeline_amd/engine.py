@@ -18,7 +18,10 @@ chosen token's only, 1..20 plus that many alternatives; read with logprobs()), r
 sampling: every sequence slot has its own record, see set_slot_sampling), row_masks (a token mask per
 sequence slot for constrained output, see set_slot_masks and mipipe.grammar; switches row_sampling on),
 lora_adapters (LoRA adapter capacity, 0 off, at most 8; see load_adapter / set_slot_adapters) and
-lora_max_rank (largest rank of an adapter tensor pair, default 64, at most 128).
+lora_max_rank (largest rank of an adapter tensor pair, default 64, at most 128), context_shift (default
+False: a sequence that fills max_ctx ends; True: decode() / generate() first drop half of what follows the
+first n_keep prompt tokens, in whole 64-token pages, and go on, see context_shift) and n_keep (default 0;
+-1: the whole prompt).
 """
 from __future__ import annotations
 
@@ -233,6 +236,36 @@ class Engine:
         j = N.jcall(N.lib().mp_engine_info, self._h, what="engine info")
         return {"kv_pages": j["kv_pages"], "kv_free_pages": j["kv_free_pages"]}
 
+    def context_shift(self, slots, n_keep, n_discard):
+        """Context shift, between decode() calls: for each running slot slots[i], the cached positions
+        [n_keep[i], n_keep[i] + n_discard[i]) leave its KV and every later one moves n_discard[i] back: V
+        as it is, K rotated by minus n_discard[i] positions on the device, nothing recomputed.
+        n_discard > 0 and a multiple of 64; n_keep + n_discard <= slot_position(slot).  The slot's
+        position drops by n_discard, n_discard / 64 pages return to the pool, no graph is re-captured.
+        Sampler state, masks and adapter bindings stay.  A shifted slot is no prefix-cache hit until it
+        is admitted again, and save_state() raises while one is running.  Raises, naming the cause, for
+        an idle slot, a violated precondition, mode "mp" / rpc engines and after spec_generate()."""
+        sl = np.asarray([int(s) for s in slots], np.int32)
+        kp = np.asarray([int(k) for k in n_keep], np.int32)
+        nd = np.asarray([int(d) for d in n_discard], np.int32)
+        if len(kp) != len(sl) or len(nd) != len(sl):
+            raise ValueError("context_shift: one n_keep and one n_discard per slot")
+        N.check(N.lib().mp_engine_context_shift(self._h, sl.ctypes.data, len(sl), kp.ctypes.data, nd.ctypes.data),
+                "context_shift")
+
+    def set_slot_keep(self, slot: int, n_keep: int):
+        """Automatic shifting (Engine(context_shift=True)): the prompt tokens of `slot` a shift keeps
+        (-1: the whole prompt) from now on; release() puts the engine's n_keep back."""
+        N.check(N.lib().mp_engine_set_slot_keep(self._h, int(slot), int(n_keep)), "set_slot_keep")
+
+    def slot_position(self, slot: int) -> int:
+        """Positions the slot's KV holds (prompt + decoded tokens - discarded positions)."""
+        return N.check(N.lib().mp_engine_slot_position(self._h, int(slot)), "slot_position")
+
+    def slot_shifts(self, slot: int) -> int:
+        """Context shifts of the slot's running sequence."""
+        return N.check(N.lib().mp_engine_slot_shifts(self._h, int(slot)), "slot_shifts")
+
     def release(self, slot: int):
         """Mark a slot idle (its sequence is finished); it can be admitted again."""
         N.check(N.lib().mp_engine_release(self._h, int(slot)), "release")
@@ -240,7 +273,10 @@ class Engine:
     def decode(self, k: int):
         return N.jcall(N.lib().mp_engine_decode, self._h, k, what="decode")
 
-    def tokens(self, cap: int = 4096):
+    def tokens(self, cap: int | None = None):
+        """Generated tokens per sequence; cap: at most that many each (default: all of them)."""
+        if cap is None:
+            cap = max(N.check(N.lib().mp_engine_tokens_longest(self._h), "tokens"), 1)
         out = np.full((self._n_seq, cap), -1, np.int32)
         n = N.check(N.lib().mp_engine_tokens(self._h, out.ctypes.data, self._n_seq, cap), "tokens")
         return [[t for t in row if t >= 0] for row in out[:, :n].tolist()]
@@ -252,7 +288,7 @@ class Engine:
         [n_tokens][n_probs] alternatives by descending probability (empty with n_probs = -1)."""
         nt = max(int(self.cfg.get("n_probs", 0)), 0)
         # one record per token: the buffers are sized by the longest sequence, the counts are tokens()'s
-        counts = [len(t) for t in self.tokens(cap=self.info["max_ctx"] + 2)]
+        counts = [len(t) for t in self.tokens()]
         cap = max(counts + [1])
         lp = np.zeros((self._n_seq, cap), np.float32)
         tid = np.zeros((self._n_seq, cap, nt), np.int32)

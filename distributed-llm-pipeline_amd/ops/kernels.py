@@ -737,6 +737,24 @@ def rope_kv(qkv, pos, slot, block_table, rope_cs, Hq, Hkv, hd, Dp, q_scale, k_ca
     return q_out
 
 
+def kv_shift(k_cache, v_cache, block_table, rope_cs, records, Hkv, hd, Dp, n_pages, kv_fp8=False):
+    """Context shift of one layer's paged caches, in place.  records: (slot, n_keep, n_discard, old_len,
+    merge_src_page) tuples naming distinct slots; block_table int32 [n_slots][max_pages] is the table
+    AFTER the page edit (KvPager::shift): the tail pages of a record's slot are rotated in place by
+    minus n_discard positions with rope_cs[n_discard] (f32 from the stored code, rounded to f16 /
+    e4m3, dims hd..Dp zero); with n_keep % 64 != 0 the page holding n_keep takes rows
+    [n_keep % 64, 64) of merge_src_page (K rotated, V copied in the thread's `v_layout`), else
+    merge_src_page is -1.  n_pages: pool pages (ids >= n_pages are never touched).  The host checks
+    the records and raises, naming the first bad one."""
+    assert block_table.dtype == torch.int32 and block_table.is_contiguous() and block_table.dim() == 2
+    assert k_cache.is_contiguous() and v_cache.is_contiguous()
+    assert rope_cs.dtype == torch.float32 and rope_cs.is_contiguous() and rope_cs.shape[1] == hd // 2
+    rec = np.ascontiguousarray(np.asarray(records, np.int32).reshape(-1, 5))
+    N.check(N.lib().mp_op_kv_shift(_ptr(k_cache), _ptr(v_cache), _ptr(block_table), block_table.shape[0],
+                                   block_table.shape[1], int(n_pages), Hkv, hd, Dp, int(kv_fp8), _ptr(rope_cs),
+                                   rope_cs.shape[0], rec.ctypes.data, rec.shape[0], _stream()), "kv_shift")
+
+
 def qk_norm(qkv, wq, wk, Hq, Hkv, hd, eps):
     """Qwen3 per-head RMSNorm of the q and k heads of the f32 rows qkv [M, >= (Hq + 2 Hkv) hd], in
     place, before RoPE; wq / wk: f32 [hd].  Returns qkv."""
