@@ -412,7 +412,6 @@ Engine::Engine(const Json& j) : jcfg_(j) {
       throw std::runtime_error("\"row_masks\": true needs per-request sampling: \"row_sampling\": false contradicts it");
     if (mode_ == "mp") throw std::runtime_error("\"row_masks\": mode \"mp\" is not supported");
     row_sampling_ = true;
-    mask_life_.reset((size_t)M_ * B_);
   }
   so.row_sampling = row_sampling_;
   so.row_masks = row_masks_;
@@ -430,18 +429,11 @@ Engine::Engine(const Json& j) : jcfg_(j) {
     so.lora_adapters = lora_cap_;
     so.lora_max_rank = lora_max_rank_;
     adapters_.assign((size_t)lora_cap_, AdapterRec{});
-    bind_id_.assign((size_t)M_ * B_, -1);
-    bind_scale_.assign((size_t)M_ * B_, 0.f);
-    bind_life_.reset((size_t)M_ * B_);
-    kv_tag_.assign((size_t)M_ * B_, KvTag{});
   }
   auto_shift_ = j.get_bool("context_shift", false);
   n_keep_ = j.get_int("n_keep", 0);
   if (n_keep_ < -1) throw std::runtime_error("\"n_keep\" must be >= 0, or -1 for the whole prompt");
   if (auto_shift_) check_shift_supported("\"context_shift\"");
-  shifted_.assign((size_t)M_ * B_, 0);
-  n_shifts_.assign((size_t)M_ * B_, 0);
-  slot_keep_.assign((size_t)M_ * B_, n_keep_);
   packed_prefill_ = j.get_bool("packed_prefill", true);
   prefix_cache_ = j.get_bool("prefix_cache", true);
   n_probs_ = j.get_int("n_probs", 0);
@@ -456,8 +448,12 @@ Engine::Engine(const Json& j) : jcfg_(j) {
     row_default_.presence = (float)j.get_num("presence_penalty", 0.0);
     row_default_.seed = seed;
     check_row_sampling(row_default_, cfg_.vocab);
-    slot_rec_.assign((size_t)M_ * B_, row_default_);
-    slot_seed_given_.assign((size_t)M_ * B_, 0);
+  }
+  {
+    Slot idle;   // every slot starts at the engine's values
+    idle.n_keep = n_keep_;
+    idle.rec = row_default_;
+    slots_.assign((size_t)M_ * B_, idle);
   }
   // ---- stages this process owns
   for (int s = 0; s < S_; ++s) {
@@ -608,14 +604,16 @@ Engine::~Engine() {
   if (lp_host_ && !cpu_) (void)hipHostFree(lp_host_);
 }
 
-bool Engine::owns_last() const {
-  for (auto& w : workers_) if (w->stage->spec().last()) return true;
-  return false;
+Engine::Worker* Engine::first_worker() const {
+  for (auto& w : workers_) if (w->stage->spec().first()) return w.get();
+  return nullptr;
 }
-bool Engine::owns_first() const {
-  for (auto& w : workers_) if (w->stage->spec().first()) return true;
-  return false;
+Engine::Worker* Engine::last_worker() const {
+  for (auto& w : workers_) if (w->stage->spec().last()) return w.get();
+  return nullptr;
 }
+bool Engine::owns_last() const { return last_worker() != nullptr; }
+bool Engine::owns_first() const { return first_worker() != nullptr; }
 
 void Engine::build_links(const Json& j) {
   if (S_ == 1) return;
@@ -1197,72 +1195,86 @@ void Engine::sync_all() {
   }
 }
 
-void Engine::start(const std::vector<std::vector<int32_t>>& prompts) {
-  if ((int)prompts.size() > M_ * B_) throw std::runtime_error("more prompts than micro-batch slots");
-  prompts_ = prompts;
-  gen_.assign(prompts.size(), {});
-  gen_lp_.assign(prompts.size(), {});
+// ---------------------------------------------------------------- slot lifecycle
+void Engine::reset_slots(size_t n_seqs) {
+  for (Slot& s : slots_) {
+    s.prompt.clear();
+    s.gen.clear();
+    s.lp = {};
+    s.base_round = 0;
+    s.active = false;
+    s.shifted = s.n_shifts = 0;
+  }
+  n_seqs_ = n_seqs;
   rounds_done_ = 0;
+}
+
+void Engine::begin_sequence(size_t slot, const std::vector<int32_t>& prompt) {
+  Slot& s = slots_[slot];
+  s.prompt = prompt;
+  s.gen.clear();
+  s.lp = {};
+  s.base_round = rounds_done_;
+  s.shifted = s.n_shifts = 0;
+  s.active = true;
+  s.mask.admit();
+  s.bind.admit();
+}
+
+std::vector<int> Engine::drain_settings(SlotSetting Slot::*which, bool all) {
+  std::vector<int> ended;
+  for (size_t i = 0; i < slots_.size(); ++i)
+    if ((slots_[i].*which).drain(all)) ended.push_back((int)i);
+  return ended;
+}
+
+void Engine::upload_tokens(size_t slot, int pos0, const int32_t* toks, size_t n) {
+  Worker* w = first_worker();
+  if (!w) return;
+  int32_t* dst = w->stage->prompt_buf() + slot * max_ctx_ + pos0;
+  if (w->cpu) {
+    std::memcpy(dst, toks, n * 4);
+  } else {
+    HIP_OK(hipSetDevice(w->device));
+    HIP_OK(hipMemcpy(dst, toks, n * 4, hipMemcpyHostToDevice));
+  }
+}
+
+void Engine::start(const std::vector<std::vector<int32_t>>& prompts) {
+  const size_t n = prompts.size();
+  if ((int)n > M_ * B_) throw std::runtime_error("more prompts than micro-batch slots");
+  reset_slots(n);
   resumable_ = true;
-  base_round_.assign((size_t)M_ * B_, 0);
-  active_.assign((size_t)M_ * B_, 0);
-  for (size_t i = 0; i < (size_t)M_ * B_; ++i) reset_shift(i, false);
-  for (size_t i = 0; i < prompts.size(); ++i) active_[i] = 1;
   // KV pages: each prompt + its first decode position; slots without a prompt give theirs back
   // (a reused prefix keeps the pages it already owns)
-  for (size_t i = prompts.size(); i < (size_t)M_ * B_; ++i) pager_.release((int)i);
-  for (size_t i = 0; i < prompts.size(); ++i)
+  for (size_t i = n; i < slots_.size(); ++i) pager_.release((int)i);
+  for (size_t i = 0; i < n; ++i)
     if (!prompts[i].empty() && (int)prompts[i].size() < max_ctx_) kv_grant(i, (int)prompts[i].size() + 1);
   kv_sync();
-  clear_masks(false);
+  clear_masks(false);   // (before the admissions: what is pending for them becomes live here)
   clear_bindings(false);
-  {
-    std::vector<size_t> all(prompts.size());
-    std::iota(all.begin(), all.end(), (size_t)0);
-    apply_slot_sampling(all);
-  }
-  std::vector<Item> items;
-  for_each_stage([&](Worker& w) {
-    Stage& st = *w.stage;
-    for (int mb = 0; mb < M_; ++mb) {
-      std::vector<int32_t> pos(B_, 0);
-      for (int b = 0; b < B_; ++b) {
-        const size_t i = (size_t)mb * B_ + b;
-        if (i < prompts.size()) pos[b] = (int)prompts[i].size();
-      }
-      st.set_positions(mb, pos);
+  std::vector<size_t> seqs(n);
+  std::iota(seqs.begin(), seqs.end(), (size_t)0);
+  for (size_t i : seqs) begin_sequence(i, prompts[i]);
+  apply_slot_sampling(seqs);
+  for (int mb = 0; mb < M_; ++mb) push_positions(mb);
+  for (int mb = 0; mb < M_; ++mb) push_history(mb);   // the penalty windows start with the prompts (llama-cli accepts them)
+  if (owns_first())
+    for (size_t i : seqs) {
+      if (prompts[i].empty() || (int)prompts[i].size() >= max_ctx_) throw std::runtime_error("bad prompt length");
+      upload_tokens(i, 0, prompts[i].data(), prompts[i].size());
     }
-    if (st.spec().last()) {   // repetition-penalty windows start with the prompts (llama-cli accepts them)
-      for (int mb = 0; mb < M_; ++mb) {
-        std::vector<std::vector<int32_t>> seqs;
-        for (int b = 0; b < B_ && (size_t)mb * B_ + b < prompts.size(); ++b) seqs.push_back(prompts[(size_t)mb * B_ + b]);
-        st.set_history(mb, seqs);
-      }
-    }
-    if (st.spec().first()) {
-      for (size_t i = 0; i < prompts.size(); ++i) {
-        if (prompts[i].empty() || (int)prompts[i].size() >= max_ctx_) throw std::runtime_error("bad prompt length");
-        if (w.cpu) std::memcpy(st.prompt_buf() + i * max_ctx_, prompts[i].data(), prompts[i].size() * 4);
-        else HIP_OK(hipMemcpy(st.prompt_buf() + i * max_ctx_, prompts[i].data(), prompts[i].size() * 4,
-                              hipMemcpyHostToDevice));
-      }
-    }
-  });
-  {
-    std::vector<size_t> seqs(prompts.size());
-    std::iota(seqs.begin(), seqs.end(), (size_t)0);
-    items = prefill_items(seqs, false);
-  }
-  slot_toks_.clear();   // KV content unknown until this prefill has completed
+  const std::vector<Item> items = prefill_items(seqs, false);
+  forget_kv_toks();   // KV content unknown until this prefill has completed
   run_all(items);
   started_ = true;
   if (owns_last())
-    for (size_t i = 0; i < prompts.size(); ++i) {
-      gen_[i].push_back(out_host_[i]);
+    for (size_t i : seqs) {
+      slots_[i].gen.push_back(out_host_[i]);
       take_logprobs(i, 0);
     }
   for (int mb = 0; mb < M_; ++mb) push_row_draws(mb);
-  slot_toks_ = prompts;
+  refresh_slot_cache();   // (no round yet: the prompts)
 }
 
 // ---------------------------------------------------------------- per-request sampling
@@ -1277,8 +1289,8 @@ void Engine::set_slot_sampling(int slot, const RowSampling& r, bool has_seed, bo
   if (slot < 0 || slot >= M_ * B_) throw std::runtime_error("set_slot_sampling: bad slot");
   if (!for_start && started_ && slot_active(slot)) throw std::runtime_error("set_slot_sampling: slot " + std::to_string(slot) + " is busy");
   check_row_sampling(r, cfg_.vocab);
-  slot_rec_[slot] = r;
-  slot_seed_given_[slot] = has_seed ? 1 : 0;
+  slots_[slot].rec = r;
+  slots_[slot].seed_given = has_seed;
 }
 
 void Engine::check_slot_at(const char* fn, const std::vector<int>& slots, size_t i, const char* twice_suffix) const {
@@ -1306,12 +1318,12 @@ void Engine::set_slot_masks(const std::vector<int>& slots, const uint32_t* const
     if (!any) throw std::runtime_error("set_slot_masks: the mask of slot " + std::to_string(s) + " allows no token below the vocabulary size");
   }
   for_each_last_stage([&](Worker& w) { w.stage->set_row_masks(slots, bits); });
-  for (size_t i = 0; i < slots.size(); ++i) mask_life_.set(slots[i], bits[i] != nullptr, slot_running(slots[i], for_start));
+  for (size_t i = 0; i < slots.size(); ++i) slots_[slots[i]].mask.set(bits[i] != nullptr, slot_running(slots[i], for_start));
 }
 
 void Engine::clear_masks(bool all) {
   if (!row_masks_) return;
-  const std::vector<int> slots = all ? mask_life_.drain_all() : mask_life_.drain_for_start();
+  const std::vector<int> slots = drain_settings(&Slot::mask, all);
   if (slots.empty()) return;
   const std::vector<const uint32_t*> none(slots.size(), nullptr);
   for_each_last_stage([&](Worker& w) { w.stage->set_row_masks(slots, none.data()); });
@@ -1350,8 +1362,8 @@ int Engine::load_adapter(const std::string& path) {
 void Engine::unload_adapter(int id) {
   if (lora_cap_ <= 0) throw std::runtime_error("unload_adapter: the engine was built without \"lora_adapters\"");
   if (id < 0 || id >= lora_cap_ || !adapters_[id].used) throw std::runtime_error("unload_adapter: adapter id " + std::to_string(id) + " is not loaded");
-  for (size_t s = 0; s < bind_id_.size(); ++s)
-    if (bind_id_[s] == id) throw std::runtime_error("unload_adapter: adapter " + std::to_string(id) + " is bound to slot " + std::to_string(s));
+  for (size_t s = 0; s < slots_.size(); ++s)
+    if (slots_[s].bind_id == id) throw std::runtime_error("unload_adapter: adapter " + std::to_string(id) + " is bound to slot " + std::to_string(s));
   sync_all();
   for_each_stage([&](Worker& w) { w.stage->unload_adapter(id); });
   adapters_[id] = AdapterRec{};
@@ -1370,15 +1382,14 @@ Json Engine::adapters() const {
 }
 
 Engine::KvTag Engine::bind_tag(size_t slot) const {
-  KvTag t;
-  if (slot < bind_id_.size() && bind_id_[slot] >= 0) { t.serial = adapters_[bind_id_[slot]].serial; t.scale = bind_scale_[slot]; }
-  return t;
+  const Slot& s = slots_[slot];
+  return s.bind_id >= 0 ? KvTag{adapters_[s.bind_id].serial, s.bind_scale} : KvTag{};
 }
 
 int Engine::slot_adapter(int slot, float* scale) const {
-  if (lora_cap_ <= 0 || slot < 0 || slot >= M_ * B_) return -1;
-  if (scale) *scale = bind_scale_[slot];
-  return bind_id_[slot];
+  if (lora_cap_ <= 0 || !slot_in_range(slot)) return -1;
+  if (scale) *scale = slots_[slot].bind_scale;
+  return slots_[slot].bind_id;
 }
 
 void Engine::push_bindings(const std::vector<int>& slots, const std::vector<int>& ids, const std::vector<float>& scales,
@@ -1386,12 +1397,12 @@ void Engine::push_bindings(const std::vector<int>& slots, const std::vector<int>
   if (slots.empty()) return;
   for_each_stage([&](Worker& w) { w.stage->set_row_adapters(slots, ids, scales); });
   for (size_t i = 0; i < slots.size(); ++i) {
-    const size_t s = (size_t)slots[i];
-    const bool changed = bind_id_[s] != ids[i] || (ids[i] >= 0 && bind_scale_[s] != scales[i]);
-    bind_id_[s] = ids[i];
-    bind_scale_[s] = ids[i] >= 0 ? scales[i] : 0.f;
+    Slot& s = slots_[slots[i]];
+    const bool changed = s.bind_id != ids[i] || (ids[i] >= 0 && s.bind_scale != scales[i]);
+    s.bind_id = ids[i];
+    s.bind_scale = ids[i] >= 0 ? scales[i] : 0.f;
     // a running sequence's KV now mixes two bindings: no later prompt may reuse it as a prefix
-    if (changed && mark_mixed && started_ && slot_active((int)s)) kv_tag_[s].serial = kMixedTag;
+    if (changed && mark_mixed && started_ && s.active) s.kv_tag.serial = kMixedTag;
   }
 }
 
@@ -1409,12 +1420,12 @@ void Engine::set_slot_adapters(const std::vector<int>& slots, const std::vector<
   if (failed_) throw std::runtime_error("set_slot_adapters after a pipeline fault");
   sync_all();
   push_bindings(slots, ids, scales, true);
-  for (size_t i = 0; i < slots.size(); ++i) bind_life_.set(slots[i], ids[i] >= 0, slot_running(slots[i], for_start));
+  for (size_t i = 0; i < slots.size(); ++i) slots_[slots[i]].bind.set(ids[i] >= 0, slot_running(slots[i], for_start));
 }
 
 void Engine::clear_bindings(bool all) {
   if (lora_cap_ <= 0) return;
-  const std::vector<int> slots = all ? bind_life_.drain_all() : bind_life_.drain_for_start();
+  const std::vector<int> slots = drain_settings(&Slot::bind, all);
   // (the generation these bindings belonged to is over: nothing to mark as mixed)
   push_bindings(slots, std::vector<int>(slots.size(), -1), std::vector<float>(slots.size(), 0.f), false);
 }
@@ -1422,7 +1433,7 @@ void Engine::clear_bindings(bool all) {
 RowSampling Engine::slot_sampling(int slot) const {
   if (!row_sampling_) throw std::runtime_error("slot_sampling: the engine was built without row_sampling");
   if (slot < 0 || slot >= M_ * B_) throw std::runtime_error("slot_sampling: bad slot");
-  return slot_rec_[slot];
+  return slots_[slot].rec;
 }
 
 // the records of the slots about to be prefilled -> the last stage (draw index = draw0); a slot
@@ -1430,9 +1441,9 @@ RowSampling Engine::slot_sampling(int slot) const {
 void Engine::apply_slot_sampling(const std::vector<size_t>& seqs) {
   if (!row_sampling_) return;
   for (size_t i : seqs) {
-    RowSampling& r = slot_rec_[i];
-    if (!slot_seed_given_[i]) r.seed = seed_mix64(row_default_.seed ^ (0x9E3779B97F4A7C15ULL * (admissions_ + 1)));
-    slot_seed_given_[i] = 1;   // the seed in use: a re-admission without release() keeps it
+    RowSampling& r = slots_[i].rec;
+    if (!slots_[i].seed_given) r.seed = seed_mix64(row_default_.seed ^ (0x9E3779B97F4A7C15ULL * (admissions_ + 1)));
+    slots_[i].seed_given = true;   // the seed in use: a re-admission without release() keeps it
     ++admissions_;
     for_each_last_stage([&](Worker& w) { w.stage->set_row_sampling((int)(i / B_), (int)(i % B_), r); });
   }
@@ -1444,8 +1455,8 @@ void Engine::push_row_draws(int mb) {
   if (!row_sampling_) return;
   std::vector<int32_t> d(B_, 0);
   for (int b = 0; b < B_; ++b) {
-    const size_t i = (size_t)mb * B_ + b;
-    d[b] = slot_rec_[i].draw0 + (i < gen_.size() ? (int32_t)gen_[i].size() : 0);
+    const Slot& s = slots_[(size_t)mb * B_ + b];
+    d[b] = s.rec.draw0 + (int32_t)s.gen.size();
   }
   for_each_last_stage([&](Worker& w) { w.stage->set_row_draws(mb, d); });
 }
@@ -1548,17 +1559,15 @@ Json Engine::sampling_to_json(const RowSampling& r) {
 // through a decode step (all but the newest).  The generated part is only known where the last
 // stage lives, so a multi-process pipeline caches prompts only (every rank must agree on reuse).
 void Engine::refresh_slot_cache() {
-  slot_toks_ = prompts_;
-  // a released slot's KV is not guaranteed (load_state restores active slots only; live idle rows
-  // keep overwriting theirs): never offer it for prefix reuse
-  for (size_t i = 0; i < slot_toks_.size(); ++i)
-    if ((i < active_.size() && !active_[i]) || (i < n_shifts_.size() && n_shifts_[i] > 0)) slot_toks_[i].clear();
-  if (!resumable_ || !owns_first() || !owns_last()) return;
-  for (size_t i = 0; i < slot_toks_.size() && i < gen_.size(); ++i) {
-    if (i < n_shifts_.size() && n_shifts_[i] > 0) continue;   // a shifted slot's KV is no token prefix
-    const int since = rounds_done_ - (i < base_round_.size() ? base_round_[i] : 0);
-    const size_t n = std::min(gen_[i].size(), (size_t)std::max(0, since));
-    slot_toks_[i].insert(slot_toks_[i].end(), gen_[i].begin(), gen_[i].begin() + n);
+  const bool with_gen = resumable_ && owns_first() && owns_last();
+  for (Slot& s : slots_) {
+    // a released slot's KV is not guaranteed (load_state restores active slots only; live idle rows
+    // keep overwriting theirs) and a shifted slot's KV is no token prefix: never offer them for reuse
+    if (!s.active || s.n_shifts > 0) { s.kv_toks.clear(); continue; }
+    s.kv_toks = s.prompt;
+    if (!with_gen) continue;
+    const size_t n = std::min(s.gen.size(), (size_t)std::max(0, rounds_done_ - s.base_round));
+    s.kv_toks.insert(s.kv_toks.end(), s.gen.begin(), s.gen.begin() + n);
   }
 }
 
@@ -1579,21 +1588,21 @@ Json Engine::save_state(const std::string& dir) {
   if (!started_) throw std::runtime_error("save_state before start");
   if (failed_) throw std::runtime_error("save_state after a pipeline fault");
   if (!resumable_) throw std::runtime_error("save_state: not supported after speculative decoding");
-  for (size_t i = 0; i < shifted_.size(); ++i)
-    if (shifted_[i] > 0 && i < active_.size() && active_[i])
+  for (size_t i = 0; i < slots_.size(); ++i)
+    if (slots_[i].shifted > 0 && slots_[i].active)
       throw std::runtime_error("save_state: not supported after a context shift (slot " + std::to_string(i) +
-                               " has discarded " + std::to_string(shifted_[i]) + " positions)");
-  for (size_t s = 0; s < bind_id_.size(); ++s)
-    if (bind_id_[s] >= 0)
-      throw std::runtime_error("save_state: slot " + std::to_string(s) + " is bound to LoRA adapter " + std::to_string(bind_id_[s]) +
+                               " has discarded " + std::to_string(slots_[i].shifted) + " positions)");
+  for (size_t s = 0; s < slots_.size(); ++s)
+    if (slots_[s].bind_id >= 0)
+      throw std::runtime_error("save_state: slot " + std::to_string(s) + " is bound to LoRA adapter " + std::to_string(slots_[s].bind_id) +
                                " (a checkpoint does not carry adapters: release or unbind the slots first)");
   ::mkdir(dir.c_str(), 0755);
   sync_all();
   const Json fp = state_fingerprint(cfg_, S_, M_, B_, max_ctx_, cpu_, kv_fp8_);
   // tokens already in each slot's KV: prompt + generated - 1 (the newest token is the next input)
   std::vector<int> n_tok((size_t)M_ * B_, 0);
-  for (size_t i = 0; i < prompts_.size(); ++i)
-    if (i < active_.size() && active_[i]) n_tok[i] = slot_pos(i);
+  for (size_t i = 0; i < n_seqs_; ++i)
+    if (slots_[i].active) n_tok[i] = slot_pos(i);
   size_t total = 0;
   for (auto& wp : workers_) {
     Stage& st = *wp->stage;
@@ -1631,28 +1640,24 @@ Json Engine::save_state(const std::string& dir) {
     Json sj = Json::object();
     sj["magic"] = "mipipe-session"; sj["version"] = 1; sj["fingerprint"] = fp; sj["rounds_done"] = rounds_done_;
     Json ps = Json::array(), gs = Json::array();
-    for (size_t i = 0; i < prompts_.size(); ++i) {
+    Json br = Json::array(), ac = Json::array(), rs = Json::array(), ds = Json::array();
+    for (size_t i = 0; i < n_seqs_; ++i) {
+      const Slot& s = slots_[i];
       Json p = Json::array(), g = Json::array();
-      for (int32_t t : prompts_[i]) p.push(t);
-      for (int32_t t : gen_[i]) g.push(t);
+      for (int32_t t : s.prompt) p.push(t);
+      for (int32_t t : s.gen) g.push(t);
       ps.push(p);
       gs.push(g);
+      br.push(s.base_round);
+      ac.push(s.active ? 1 : 0);
+      rs.push(sampling_to_json(s.rec));
+      ds.push((int)(s.rec.draw0 + (int32_t)s.gen.size()));
     }
     sj["prompts"] = ps;
     sj["generated"] = gs;
-    Json br = Json::array(), ac = Json::array();
-    for (size_t i = 0; i < prompts_.size(); ++i) {
-      br.push(i < base_round_.size() ? base_round_[i] : 0);
-      ac.push(i < active_.size() && active_[i] ? 1 : 0);
-    }
     sj["base_round"] = br;
     sj["active"] = ac;
     if (row_sampling_) {   // the slots' records and the draws each has consumed (draw0 + one per generated token)
-      Json rs = Json::array(), ds = Json::array();
-      for (size_t i = 0; i < prompts_.size(); ++i) {
-        rs.push(sampling_to_json(slot_rec_[i]));
-        ds.push((int)(slot_rec_[i].draw0 + (int32_t)gen_[i].size()));
-      }
       sj["sampling"] = rs;
       sj["draws"] = ds;
       sj["admissions"] = std::to_string(admissions_);
@@ -1661,10 +1666,10 @@ Json Engine::save_state(const std::string& dir) {
     f << sj.dump() << "\n";
     if (!f) throw std::runtime_error("save_state: cannot write session.json");
   }
-  MP_LOGI("state saved to %s: %zu sequences, %d rounds, %.1f MiB", dir.c_str(), prompts_.size(), rounds_done_,
+  MP_LOGI("state saved to %s: %zu sequences, %d rounds, %.1f MiB", dir.c_str(), n_seqs_, rounds_done_,
           total / 1048576.0);
   Json r = Json::object();
-  r["bytes"] = (double)total; r["rounds_done"] = rounds_done_; r["sequences"] = (int)prompts_.size();
+  r["bytes"] = (double)total; r["rounds_done"] = rounds_done_; r["sequences"] = (int)n_seqs_;
   return r;
 }
 
@@ -1678,49 +1683,54 @@ Json Engine::load_state(const std::string& dir) {
   const Json sj = Json::parse(slurp(dir + "/session.json"));
   if (sj.get_str("magic", "") != "mipipe-session" || sj["fingerprint"].dump() != fp.dump())
     throw std::runtime_error("load_state: session was saved by a different model / pipeline shape");
-  prompts_.clear();
-  gen_.clear();
-  for (const Json& p : sj["prompts"].arr()) {
-    std::vector<int32_t> v;
-    for (const Json& t : p.arr()) v.push_back((int32_t)t.num());
-    prompts_.push_back(v);
-  }
-  for (const Json& g : sj["generated"].arr()) {
-    std::vector<int32_t> v;
-    for (const Json& t : g.arr()) v.push_back((int32_t)t.num());
-    gen_.push_back(v);
-  }
-  rounds_done_ = sj.get_int("rounds_done", 0);
-  // session.json is untrusted input: validate every index and size before it reaches a buffer
-  if (prompts_.empty() || (int)prompts_.size() > M_ * B_ || gen_.size() != prompts_.size() || rounds_done_ < 0)
-    throw std::runtime_error("load_state: bad session");
-  if ((sj.has("base_round") && sj["base_round"].arr().size() != prompts_.size()) ||
-      (sj.has("active") && sj["active"].arr().size() != prompts_.size()))
+  // session.json is untrusted input: it is parsed into locals and every index and size validated
+  // before anything of the engine changes (a rejected session leaves a running engine as it was)
+  auto token_lists = [](const Json& a) {
+    std::vector<std::vector<int32_t>> out;
+    for (const Json& l : a.arr()) {
+      out.emplace_back();
+      for (const Json& t : l.arr()) out.back().push_back((int32_t)t.num());
+    }
+    return out;
+  };
+  std::vector<std::vector<int32_t>> prompts = token_lists(sj["prompts"]), gen = token_lists(sj["generated"]);
+  const int rounds = sj.get_int("rounds_done", 0);
+  const size_t n = prompts.size();
+  if (n == 0 || (int)n > M_ * B_ || gen.size() != n || rounds < 0) throw std::runtime_error("load_state: bad session");
+  if ((sj.has("base_round") && sj["base_round"].arr().size() != n) || (sj.has("active") && sj["active"].arr().size() != n))
     throw std::runtime_error("load_state: bad session (base_round / active size)");
   auto check_ids = [&](const std::vector<int32_t>& v) {
     for (int32_t t : v)
       if (t < 0 || t >= cfg_.vocab) throw std::runtime_error("load_state: token id out of range");
   };
-  for (size_t i = 0; i < prompts_.size(); ++i) {
-    if (prompts_[i].empty() || (int)prompts_[i].size() >= max_ctx_)
+  for (size_t i = 0; i < n; ++i) {
+    if (prompts[i].empty() || (int)prompts[i].size() >= max_ctx_)
       throw std::runtime_error("load_state: prompt length out of range");
-    check_ids(prompts_[i]);
-    check_ids(gen_[i]);
+    check_ids(prompts[i]);
+    check_ids(gen[i]);
   }
-  base_round_.assign((size_t)M_ * B_, 0);
-  active_.assign((size_t)M_ * B_, 0);
-  for (size_t i = 0; i < (size_t)M_ * B_; ++i) reset_shift(i, false);
-  for (size_t i = 0; i < prompts_.size(); ++i) {
-    base_round_[i] = sj.has("base_round") ? (int)sj["base_round"].arr()[i].num() : 0;
-    active_[i] = sj.has("active") ? (char)sj["active"].arr()[i].num() : 1;
-    if (base_round_[i] < 0 || base_round_[i] > rounds_done_)
-      throw std::runtime_error("load_state: bad session (base_round)");
-    if (active_[i] && slot_pos(i) >= max_ctx_) throw std::runtime_error("load_state: sequence longer than max_ctx");
+  std::vector<int> base_round(n, 0);
+  std::vector<char> active(n, 1);
+  for (size_t i = 0; i < n; ++i) {
+    if (sj.has("base_round")) base_round[i] = (int)sj["base_round"].arr()[i].num();
+    if (sj.has("active")) active[i] = (char)sj["active"].arr()[i].num();
+    if (base_round[i] < 0 || base_round[i] > rounds) throw std::runtime_error("load_state: bad session (base_round)");
+    if (active[i] && (int)prompts[i].size() + rounds - base_round[i] >= max_ctx_)
+      throw std::runtime_error("load_state: sequence longer than max_ctx");
+  }
+  reset_slots(n);
+  rounds_done_ = rounds;
+  for (size_t i = 0; i < n; ++i) {
+    Slot& s = slots_[i];
+    s.prompt = std::move(prompts[i]);
+    s.gen = std::move(gen[i]);
+    s.base_round = base_round[i];
+    s.active = active[i] != 0;
   }
   // KV pages for the restored sequences (their KV bytes are imported page by page below)
   for (int i = 0; i < M_ * B_; ++i) pager_.release(i);
-  for (size_t i = 0; i < prompts_.size(); ++i)
-    if (active_[i]) kv_grant(i, slot_pos(i) + 1);
+  for (size_t i = 0; i < n; ++i)
+    if (slots_[i].active) kv_grant(i, slot_pos(i) + 1);
   kv_sync();
   for (auto& wp : workers_) {
     Stage& st = *wp->stage;
@@ -1750,7 +1760,7 @@ Json Engine::load_state(const std::string& dir) {
     for (size_t i = 0; i < lens.size(); ++i) {
       const int n = (int)lens[i].num();
       // the stage file must describe exactly the KV the session implies (active slots only)
-      const int want = i < prompts_.size() && active_[i] ? slot_pos(i) : 0;
+      const int want = slots_[i].active ? slot_pos(i) : 0;
       if (n != want) throw std::runtime_error("load_state: " + path + " KV length disagrees with session.json");
       if (n <= 0) continue;
       if (n >= max_ctx_) throw std::runtime_error("load_state: sequence longer than max_ctx");
@@ -1760,11 +1770,6 @@ Json Engine::load_state(const std::string& dir) {
       kv += nb;
     }
     st.set_sample_step((uint64_t)h.get_num("sample_step", 0));
-    for (int mb = 0; mb < M_; ++mb) {   // next decode position: prompt + rounds since admission
-      std::vector<int32_t> pos(B_);
-      for (int b = 0; b < B_; ++b) pos[b] = slot_pos((size_t)mb * B_ + b);
-      st.set_positions(mb, pos);
-    }
     if (st.spec().first()) {
       const auto& toks = h["tokens"].arr();
       if ((int)toks.size() != M_ * B_) throw std::runtime_error("load_state: missing first-stage tokens");
@@ -1777,38 +1782,25 @@ Json Engine::load_state(const std::string& dir) {
         if (wp->cpu) std::memcpy(st.tokens(mb), t.data(), (size_t)B_ * 4);
         else HIP_OK(hipMemcpy(st.tokens(mb), t.data(), (size_t)B_ * 4, hipMemcpyHostToDevice));
       }
-      for (size_t i = 0; i < prompts_.size(); ++i) {
-        if (wp->cpu) std::memcpy(st.prompt_buf() + i * max_ctx_, prompts_[i].data(), prompts_[i].size() * 4);
-        else HIP_OK(hipMemcpy(st.prompt_buf() + i * max_ctx_, prompts_[i].data(), prompts_[i].size() * 4,
-                              hipMemcpyHostToDevice));
-      }
       if (wp->cpu) std::fill(wp->ring_pending.begin(), wp->ring_pending.end(), false);
     }
-    if (st.spec().last()) {   // penalty windows: prompt + accepted tokens
-      for (int mb = 0; mb < M_; ++mb) {
-        std::vector<std::vector<int32_t>> seqs;
-        for (int b = 0; b < B_ && (size_t)mb * B_ + b < prompts_.size(); ++b) {
-          const size_t i = (size_t)mb * B_ + b;
-          std::vector<int32_t> q = prompts_[i];
-          q.insert(q.end(), gen_[i].begin(), gen_[i].end());
-          seqs.push_back(q);
-        }
-        st.set_history(mb, seqs);
-      }
-    }
   }
+  for (int mb = 0; mb < M_; ++mb) push_positions(mb);
+  for (size_t i = 0; i < n; ++i) upload_tokens(i, 0, slots_[i].prompt.data(), slots_[i].prompt.size());
+  for (int mb = 0; mb < M_; ++mb) push_history(mb);
   if (row_sampling_) {   // the slots' records; the draw indices follow from the generated tokens
-    if (!sj.has("sampling") || sj["sampling"].arr().size() != prompts_.size())
+    if (!sj.has("sampling") || sj["sampling"].arr().size() != n)
       throw std::runtime_error("load_state: the session was saved without row_sampling");
-    for (size_t i = 0; i < prompts_.size(); ++i) {
+    for (size_t i = 0; i < n; ++i) {
+      Slot& s = slots_[i];
       bool seeded = false;
-      slot_rec_[i] = sampling_from_json(sj["sampling"].arr()[i], &seeded);
-      slot_seed_given_[i] = 1;
-      if (sj.has("draws") && (int)sj["draws"].arr()[i].num() != slot_rec_[i].draw0 + (int)gen_[i].size())
+      s.rec = sampling_from_json(sj["sampling"].arr()[i], &seeded);
+      s.seed_given = true;
+      if (sj.has("draws") && (int)sj["draws"].arr()[i].num() != s.rec.draw0 + (int)s.gen.size())
         throw std::runtime_error("load_state: bad session (draws)");
-      for_each_last_stage([&](Worker& w) { w.stage->set_row_sampling((int)(i / B_), (int)(i % B_), slot_rec_[i]); });
+      for_each_last_stage([&](Worker& w) { w.stage->set_row_sampling((int)(i / B_), (int)(i % B_), s.rec); });
     }
-    for (size_t i = prompts_.size(); i < (size_t)M_ * B_; ++i) { slot_rec_[i] = row_default_; slot_seed_given_[i] = 0; }
+    for (size_t i = n; i < slots_.size(); ++i) { slots_[i].rec = row_default_; slots_[i].seed_given = false; }
     admissions_ = std::strtoull(sj.get_str("admissions", "0").c_str(), nullptr, 10);
     for (int mb = 0; mb < M_; ++mb) push_row_draws(mb);
   } else if (sj.has("sampling")) {
@@ -1816,13 +1808,13 @@ Json Engine::load_state(const std::string& dir) {
   }
   clear_masks(true);   // masks are not part of a checkpoint: every slot resumes unconstrained
   clear_bindings(true);
-  for (KvTag& t : kv_tag_) t = KvTag{};   // a checkpoint is taken unbound: its KV is the base model's
+  for (Slot& s : slots_) s.kv_tag = KvTag{};   // a checkpoint is taken unbound: its KV is the base model's
   started_ = true;
   resumable_ = true;
   refresh_slot_cache();
-  MP_LOGI("state loaded from %s: %zu sequences, %d rounds", dir.c_str(), prompts_.size(), rounds_done_);
+  MP_LOGI("state loaded from %s: %zu sequences, %d rounds", dir.c_str(), n_seqs_, rounds_done_);
   Json r = Json::object();
-  r["rounds_done"] = rounds_done_; r["sequences"] = (int)prompts_.size();
+  r["rounds_done"] = rounds_done_; r["sequences"] = (int)n_seqs_;
   return r;
 }
 
@@ -1831,6 +1823,29 @@ Json Engine::load_state(const std::string& dir) {
 // of up to chunk_ rows that may hold several sequences, so each projection reads its weights once
 // per chunk (not per sequence).  start(): every micro-batch gets a PREFILL_END (head over all its
 // rows); admission: only the micro-batches of admitted slots, restricted to their rows.
+std::vector<Item> Engine::pack_chunks(int mb, const std::vector<PackRow>& rows, const PrefillSeg& flags) const {
+  std::vector<Item> chunks;
+  Item it{Item::PREFILL};
+  it.mb = mb;
+  auto flush = [&] {
+    if (it.T > 0) chunks.push_back(it);
+    it.segs.clear();
+    it.T = 0;
+  };
+  for (const PackRow& r : rows)
+    for (int p0 = r.p0, end = r.p0 + r.len; p0 < end;) {
+      PrefillSeg sg = flags;
+      sg.b = r.b; sg.p0 = p0; sg.T = std::min(chunk_ - it.T, end - p0);
+      sg.last = !flags.score && p0 + sg.T >= end;   // (a scored prompt's last token is never sent)
+      it.segs.push_back(sg);
+      it.T += sg.T;
+      p0 += sg.T;
+      if (it.T == chunk_ || !packed_prefill_) flush();
+    }
+  flush();
+  return chunks;
+}
+
 std::vector<Item> Engine::prefill_items(const std::vector<size_t>& seqs, bool admission) {
   std::vector<Item> items;
   std::vector<std::vector<size_t>> by_mb(M_);
@@ -1838,39 +1853,26 @@ std::vector<Item> Engine::prefill_items(const std::vector<size_t>& seqs, bool ad
   for (int mb = 0; mb < M_; ++mb) {
     if (admission && by_mb[mb].empty()) continue;
     std::sort(by_mb[mb].begin(), by_mb[mb].end());
-    Item it{Item::PREFILL};
-    it.mb = mb;
-    auto flush = [&] {
-      if (it.T > 0) items.push_back(it);
-      it.segs.clear();
-      it.T = 0;
-    };
+    std::vector<PackRow> rows;
     for (size_t i : by_mb[mb]) {
-      const int b = (int)(i % B_);
-      const int n = (int)prompts_[i].size();
-      // prefix cache: the slot's KV already holds the tokens of slot_toks_[i]; only the part after
-      // the common prefix is prefilled (at least the last prompt token, whose row feeds the head)
+      Slot& s = slots_[i];
+      const int n = (int)s.prompt.size();
+      // prefix cache: the slot's KV already holds the tokens of kv_toks; only the part after the
+      // common prefix is prefilled (at least the last prompt token, whose row feeds the head)
       int reuse = 0;
       // (a lora_adapters engine: only KV computed under the slot's present binding)
-      const bool same_bind = lora_cap_ <= 0 || (kv_tag_[i].serial == bind_tag(i).serial && kv_tag_[i].scale == bind_tag(i).scale);
-      if (lora_cap_ > 0) kv_tag_[i] = bind_tag(i);   // what this prefill computes the slot's KV under
-      if (prefix_cache_ && same_bind && i < slot_toks_.size()) {
-        const auto& c = slot_toks_[i];
-        const size_t lim = std::min(c.size(), (size_t)n - 1);
-        while ((size_t)reuse < lim && c[reuse] == prompts_[i][reuse]) ++reuse;
+      const KvTag now = bind_tag(i);
+      const bool same_bind = s.kv_tag.serial == now.serial && s.kv_tag.scale == now.scale;
+      s.kv_tag = now;   // what this prefill computes the slot's KV under
+      if (prefix_cache_ && same_bind) {
+        const size_t lim = std::min(s.kv_toks.size(), (size_t)n - 1);
+        while ((size_t)reuse < lim && s.kv_toks[reuse] == s.prompt[reuse]) ++reuse;
       }
       reused_tokens_ += reuse;
-      for (int p0 = reuse; p0 < n;) {
-        const int take = std::min(chunk_ - it.T, n - p0);
-        PrefillSeg sg;
-        sg.b = b; sg.p0 = p0; sg.T = take; sg.last = p0 + take >= n;
-        it.segs.push_back(sg);
-        it.T += take;
-        p0 += take;
-        if (it.T == chunk_ || !packed_prefill_) flush();
-      }
+      rows.push_back({(int)(i % B_), reuse, n - reuse});
     }
-    flush();
+    const std::vector<Item> chunks = pack_chunks(mb, rows, PrefillSeg{});
+    items.insert(items.end(), chunks.begin(), chunks.end());
     Item e{Item::PREFILL_END};
     e.mb = mb;
     if (admission)
@@ -1886,34 +1888,44 @@ void Engine::push_positions(int mb) {
   for_each_stage([&](Worker& w) { w.stage->set_positions(mb, pos); });
 }
 
+void Engine::push_history(int mb) {
+  std::vector<std::vector<int32_t>> hs;
+  for (int b = 0; b < B_; ++b) {
+    const Slot& s = slots_[(size_t)mb * B_ + b];
+    hs.push_back(s.prompt);
+    hs.back().insert(hs.back().end(), s.gen.begin(), s.gen.end());
+  }
+  for_each_last_stage([&](Worker& w) { w.stage->set_history(mb, hs); });
+}
+
+// the slot's sequence ends: the slot is idle and back at the engine's values
 void Engine::release(int slot) {
-  if (slot >= 0 && slot < (int)active_.size()) active_[slot] = 0;
-  if (slot >= 0 && slot < M_ * B_) pager_.release(slot);   // table pushed before the next engine call
-  if (slot >= 0 && slot < M_ * B_) reset_shift((size_t)slot, true);
-  if (row_sampling_ && !failed_ && slot >= 0 && slot < M_ * B_) {
+  if (!slot_in_range(slot)) return;
+  Slot& s = slots_[slot];
+  s.active = false;
+  pager_.release(slot);   // table pushed before the next engine call
+  s.shifted = s.n_shifts = 0;
+  s.n_keep = n_keep_;
+  if (failed_) return;
+  if (row_sampling_) {
     // the stage too: an idle row at the engine's values stops running a finished request's chain
-    slot_rec_[slot] = row_default_;
-    slot_seed_given_[slot] = 0;
+    s.rec = row_default_;
+    s.seed_given = false;
     for_each_last_stage([&](Worker& w) { w.stage->set_row_sampling(slot / B_, slot % B_, row_default_); });
   }
-  if (row_masks_ && !failed_ && slot >= 0 && slot < M_ * B_ && mask_life_.on(slot)) {
+  if (s.mask.on()) {
     const std::vector<int> one{slot};
     const uint32_t* none = nullptr;
     for_each_last_stage([&](Worker& w) { w.stage->set_row_masks(one, &none); });
-    mask_life_.clear(slot);
+    s.mask.clear();
   }
-  if (lora_cap_ > 0 && !failed_ && slot >= 0 && slot < M_ * B_ && bind_life_.on(slot)) {
+  if (s.bind.on()) {
     push_bindings({slot}, {-1}, {0.f}, true);   // (the slot is idle by now: its KV tag stays what computed it)
-    bind_life_.clear(slot);
+    s.bind.clear();
   }
 }
 
 // ---------------------------------------------------------------- context shift
-void Engine::reset_shift(size_t slot, bool keep_too) {
-  if (slot < shifted_.size()) { shifted_[slot] = 0; n_shifts_[slot] = 0; }
-  if (keep_too && slot < slot_keep_.size()) slot_keep_[slot] = n_keep_;
-}
-
 void Engine::check_shift_supported(const char* fn) const {
   const std::string f = std::string(fn) + ": ";
   if (mode_ == "mp") throw std::runtime_error(f + "mode \"mp\" is not supported");
@@ -1924,21 +1936,18 @@ void Engine::check_shift_supported(const char* fn) const {
 void Engine::set_slot_keep(int slot, int n_keep) {
   if (slot < 0 || slot >= M_ * B_) throw std::runtime_error("set_slot_keep: slot " + std::to_string(slot) + " is out of range");
   if (n_keep < -1) throw std::runtime_error("set_slot_keep: n_keep must be >= 0, or -1 for the whole prompt");
-  slot_keep_[slot] = n_keep;
+  slots_[slot].n_keep = n_keep;
 }
 
 int Engine::shift_discard(int slot) const {
-  if (slot < 0 || slot >= M_ * B_) return 0;
-  const size_t i = (size_t)slot;
-  const int plen = i < prompts_.size() ? (int)prompts_[i].size() : 0;
-  const int keep = slot_keep_[i] < 0 ? plen : std::min(slot_keep_[i], plen);
-  return std::max(0, ((slot_pos(i) - keep) / 2) / KvPager::kPage * KvPager::kPage);
+  if (!slot_in_range(slot)) return 0;
+  return std::max(0, ((slot_pos((size_t)slot) - slots_[slot].keep()) / 2) / KvPager::kPage * KvPager::kPage);
 }
 
 int Engine::context_room() const {
   int room = rounds_cap_ - 2;
-  for (size_t i = 0; i < active_.size(); ++i)
-    if (active_[i]) room = std::min(room, max_ctx_ - slot_pos(i) - 1);
+  for (size_t i = 0; i < slots_.size(); ++i)
+    if (slots_[i].active) room = std::min(room, max_ctx_ - slot_pos(i) - 1);
   return room;
 }
 
@@ -1972,10 +1981,10 @@ void Engine::context_shift(const std::vector<int>& slots, const std::vector<int>
     r.slot = slots[k]; r.n_keep = n_keep[k]; r.n_discard = n_discard[k]; r.old_len = slot_pos(i);
     r.merge_src_page = pager_.shift(slots[k], n_keep[k], n_discard[k]);
     recs.push_back(r);
-    shifted_[i] += n_discard[k];
-    n_shifts_[i] += 1;
+    slots_[i].shifted += n_discard[k];
+    slots_[i].n_shifts += 1;
     context_shifts_ += 1;
-    if (i < slot_toks_.size()) slot_toks_[i].clear();   // no token prefix any more
+    slots_[i].kv_toks.clear();   // no token prefix any more
     mbs[i / B_] = 1;
   }
   // (the merge source pages are on the free list by now; nothing is granted before the stages are done)
@@ -2003,66 +2012,36 @@ void Engine::admit(const std::vector<int>& slots, const std::vector<std::vector<
   if (!started_) throw std::runtime_error("admit before start");
   if (!resumable_) throw std::runtime_error("admit after speculative decoding");
   if (slots.size() != prompts.size()) throw std::runtime_error("admit: one prompt per slot");
-  const size_t NS = (size_t)M_ * B_;
-  if (prompts_.size() < NS) { prompts_.resize(NS); gen_.resize(NS); }
-  gen_lp_.resize(gen_.size());
-  base_round_.resize(NS, 0);
-  active_.resize(NS, 0);
+  n_seqs_ = slots_.size();   // from the first admission on, every slot is listed
   std::vector<size_t> seqs;
   std::vector<char> mbs(M_, 0);
   for (size_t k = 0; k < slots.size(); ++k) {
     const int i = slots[k];
-    if (i < 0 || (size_t)i >= NS) throw std::runtime_error("admit: bad slot");
-    if (active_[i]) throw std::runtime_error("admit: slot " + std::to_string(i) + " is busy");
+    if (!slot_in_range(i)) throw std::runtime_error("admit: bad slot");
+    if (slots_[i].active) throw std::runtime_error("admit: slot " + std::to_string(i) + " is busy");
     if (prompts[k].empty() || (int)prompts[k].size() >= max_ctx_) throw std::runtime_error("bad prompt length");
     kv_grant((size_t)i, (int)prompts[k].size() + 1);
-    prompts_[i] = prompts[k];
-    gen_[i].clear();
-    gen_lp_[i] = {};
-    base_round_[i] = rounds_done_;
-    reset_shift((size_t)i, false);
-    active_[i] = 1;
+    begin_sequence((size_t)i, prompts[k]);
     seqs.push_back((size_t)i);
     mbs[i / B_] = 1;
   }
   kv_sync();
   apply_slot_sampling(seqs);
-  if (row_masks_) mask_life_.admit(seqs);
-  if (lora_cap_ > 0) bind_life_.admit(seqs);
-  for_each_stage([&](Worker& w) {
-    Stage& st = *w.stage;
-    if (st.spec().first())
-      for (size_t i : seqs) {
-        if (w.cpu) std::memcpy(st.prompt_buf() + i * max_ctx_, prompts_[i].data(), prompts_[i].size() * 4);
-        else HIP_OK(hipMemcpy(st.prompt_buf() + i * max_ctx_, prompts_[i].data(), prompts_[i].size() * 4,
-                              hipMemcpyHostToDevice));
-      }
-  });
+  for (size_t i : seqs) upload_tokens(i, 0, slots_[i].prompt.data(), slots_[i].prompt.size());
   for (int mb = 0; mb < M_; ++mb)
     if (mbs[mb]) push_positions(mb);
   std::vector<Item> items = prefill_items(seqs, true);
-  slot_toks_.clear();
+  forget_kv_toks();
   run_all(items);
   if (owns_last())
     for (size_t i : seqs) {
-      gen_[i].push_back(out_host_[i]);
+      slots_[i].gen.push_back(out_host_[i]);
       take_logprobs(i, 0);
     }
   // the head pushed a token into the penalty window of every row of these micro-batches: re-seed
   // them from the host (prompt + accepted tokens)
-  for_each_last_stage([&](Worker& w) {
-    for (int mb = 0; mb < M_; ++mb)
-      if (mbs[mb]) {
-        std::vector<std::vector<int32_t>> hs;
-        for (int b = 0; b < B_; ++b) {
-          const size_t i = (size_t)mb * B_ + b;
-          std::vector<int32_t> q = prompts_[i];
-          q.insert(q.end(), gen_[i].begin(), gen_[i].end());
-          hs.push_back(q);
-        }
-        w.stage->set_history(mb, hs);
-      }
-  });
+  for (int mb = 0; mb < M_; ++mb)
+    if (mbs[mb]) push_history(mb);
   for (int mb = 0; mb < M_; ++mb)
     if (mbs[mb]) push_row_draws(mb);
   refresh_slot_cache();
@@ -2075,34 +2054,32 @@ StepStats Engine::decode_steps(int k) {
   // half of what follows its kept prefix (llama.cpp's rule, rounded down to whole pages)
   if (auto_shift_) {
     std::vector<int> ss, kp, nd;
-    for (size_t i = 0; i < (size_t)M_ * B_ && i < active_.size(); ++i) {
+    for (size_t i = 0; i < slots_.size(); ++i) {
       const int pos = slot_pos(i);
-      if (!active_[i] || pos + k + 1 <= max_ctx_) continue;
+      if (!slots_[i].active || pos + k + 1 <= max_ctx_) continue;
       const int d = shift_discard((int)i);
       // decided for every slot before any is shifted: a call that fails changes nothing
       if (d <= 0 || pos - d + k + 1 > max_ctx_)
         throw std::runtime_error("context capacity exhausted (prompt + generated tokens > max_ctx): a context shift of slot " +
                                  std::to_string(i) + " can discard " + std::to_string(d) + " of its " + std::to_string(pos) +
                                  " positions, too few for " + std::to_string(k) + " more rounds");
-      const int plen = i < prompts_.size() ? (int)prompts_[i].size() : 0;
-      ss.push_back((int)i); kp.push_back(slot_keep_[i] < 0 ? plen : std::min(slot_keep_[i], plen)); nd.push_back(d);
+      ss.push_back((int)i); kp.push_back(slots_[i].keep()); nd.push_back(d);
     }
     if (!ss.empty()) context_shift(ss, kp, nd);
   }
   // running sequences must fit their slot's KV pages; idle rows (which still compute) restart at
   // position 0 before they could run past them
-  for (size_t i = 0; i < (size_t)M_ * B_; ++i) {
-    const bool act = i < active_.size() && active_[i];
+  for (size_t i = 0; i < slots_.size(); ++i) {
+    Slot& s = slots_[i];
     if (slot_pos(i) + k + 1 <= max_ctx_) continue;
-    if (act) throw std::runtime_error("context capacity exhausted (prompt + generated tokens > max_ctx)");
-    if (i < prompts_.size()) prompts_[i].clear();
-    if (base_round_.size() < (size_t)M_ * B_) base_round_.resize((size_t)M_ * B_, 0);
-    base_round_[i] = rounds_done_;
+    if (s.active) throw std::runtime_error("context capacity exhausted (prompt + generated tokens > max_ctx)");
+    s.prompt.clear();
+    s.base_round = rounds_done_;
     push_positions((int)(i / B_));
   }
   // KV pages for the k positions every running sequence is about to write
-  for (size_t i = 0; i < (size_t)M_ * B_; ++i)
-    if (i < active_.size() && active_[i]) kv_grant(i, slot_pos(i) + k + 1);
+  for (size_t i = 0; i < slots_.size(); ++i)
+    if (slots_[i].active) kv_grant(i, slot_pos(i) + k + 1);
   kv_sync();
   for_each_last_stage([&](Worker& w) {
     if (w.cpu) return w.tok_t.clear();
@@ -2135,11 +2112,11 @@ StepStats Engine::decode_steps(int k) {
     }
   if (owns_last())
     for (int r = 0; r < k; ++r)
-      for (size_t i = 0; i < prompts_.size(); ++i) {
+      for (size_t i = 0; i < n_seqs_; ++i) {
         const int32_t t = out_host_[(size_t)((rounds_done_ + r + 1) % rounds_cap_) * M_ * B_ + i];
-        gen_[i].push_back(t);
-        // (released slots too, like their tokens just above: gen_lp_ stays aligned with gen_, which is
-        // what logprobs() checks; admit() resets both when the slot gets its next sequence)
+        slots_[i].gen.push_back(t);
+        // (released slots too, like their tokens just above: lp stays aligned with gen, which is what
+        // logprobs() checks; admit() resets both when the slot gets its next sequence)
         take_logprobs(i, (size_t)((rounds_done_ + r + 1) % rounds_cap_));
         if (on_token) on_token((int)i, t);
       }
@@ -2148,27 +2125,30 @@ StepStats Engine::decode_steps(int k) {
   return ss;
 }
 
-std::vector<std::vector<int32_t>> Engine::tokens() const { return gen_; }
+std::vector<std::vector<int32_t>> Engine::tokens() const {
+  std::vector<std::vector<int32_t>> out(n_seqs_);
+  for (size_t i = 0; i < n_seqs_; ++i) out[i] = slots_[i].gen;
+  return out;
+}
 
-// sequence i's record of the round stored at ring slot `round_slot` -> gen_lp_[i]
+// sequence i's record of the round stored at ring slot `round_slot` -> its slot's lp
 void Engine::take_logprobs(size_t i, size_t round_slot) {
   if (!lp_host_) return;
-  if (gen_lp_.size() <= i) gen_lp_.resize(i + 1);
   const size_t mb = i / B_, b = i % B_;
   const uint32_t* rec = lp_host_ + (round_slot * M_ + mb) * lp_words_;
   const float* chosen = reinterpret_cast<const float*>(rec);
   const int32_t* ids = reinterpret_cast<const int32_t*>(rec + B_) + b * Stage::kMaxProbs;
   const float* lps = reinterpret_cast<const float*>(rec + B_ + (size_t)B_ * Stage::kMaxProbs) + b * Stage::kMaxProbs;
-  SeqLogprobs& g = gen_lp_[i];
+  SeqLogprobs& g = slots_[i].lp;
   g.lp.push_back(chosen[b]);
   g.top_id.insert(g.top_id.end(), ids, ids + n_top());
   g.top_lp.insert(g.top_lp.end(), lps, lps + n_top());
 }
 
 bool Engine::last_logprob(int slot, float* lp, std::vector<int32_t>* top_id, std::vector<float>* top_lp) const {
-  if (n_probs_ == 0 || slot < 0 || (size_t)slot >= gen_lp_.size() || (size_t)slot >= gen_.size()) return false;
-  const SeqLogprobs& g = gen_lp_[slot];
-  if (g.lp.empty() || g.lp.size() != gen_[slot].size()) return false;
+  if (n_probs_ == 0 || !slot_in_range(slot)) return false;
+  const SeqLogprobs& g = slots_[slot].lp;
+  if (g.lp.empty() || g.lp.size() != slots_[slot].gen.size()) return false;
   const size_t nt = (size_t)n_top();
   *lp = g.lp.back();
   if (top_id) top_id->assign(g.top_id.end() - nt, g.top_id.end());
@@ -2176,14 +2156,17 @@ bool Engine::last_logprob(int slot, float* lp, std::vector<int32_t>* top_id, std
   return true;
 }
 
-const std::vector<Engine::SeqLogprobs>& Engine::logprobs() const {
+std::vector<Engine::SeqLogprobs> Engine::logprobs() const {
   if (n_probs_ == 0) throw std::runtime_error("logprobs: the engine was built with n_probs = 0");
   if (!owns_last()) throw std::runtime_error("logprobs live where the last stage does");
-  for (size_t i = 0; i < gen_.size(); ++i)
-    if (i >= gen_lp_.size() || gen_lp_[i].lp.size() != gen_[i].size())
+  std::vector<SeqLogprobs> out(n_seqs_);
+  for (size_t i = 0; i < n_seqs_; ++i) {
+    if (slots_[i].lp.lp.size() != slots_[i].gen.size())
       throw std::runtime_error("logprobs were not recorded for every token (speculative decoding and restored "
                                "checkpoints do not record them)");
-  return gen_lp_;
+    out[i] = slots_[i].lp;
+  }
+  return out;
 }
 
 // Prompt scoring.  Each pass sends at most one packed chunk per micro-batch through the pipeline
@@ -2203,62 +2186,42 @@ void Engine::score(const std::vector<std::vector<int32_t>>& prompts, int n_top, 
     for (int32_t t : p)
       if (t < 0 || t >= cfg_.vocab) throw std::runtime_error("token id out of range");
   }
-  Worker* wf = nullptr;
-  Worker* wl = nullptr;
-  for (auto& w : workers_) {
-    if (w->stage->spec().first()) wf = w.get();
-    if (w->stage->spec().last()) wl = w.get();
-  }
+  Worker* wl = last_worker();
   // the slots' KV is overwritten: whatever ran before is over
   started_ = false;
-  slot_toks_.clear();
-  prompts_.clear();
-  gen_.clear();
-  gen_lp_.clear();
-  rounds_done_ = 0;
-  base_round_.assign((size_t)M_ * B_, 0);
-  active_.assign((size_t)M_ * B_, 0);
-  for (size_t i = 0; i < (size_t)M_ * B_; ++i) reset_shift(i, false);
-  for (size_t i = n; i < (size_t)M_ * B_; ++i) pager_.release((int)i);
+  forget_kv_toks();
+  reset_slots(0);
+  for (size_t i = n; i < slots_.size(); ++i) pager_.release((int)i);
   for (size_t i = 0; i < n; ++i)
     if (prompts[i].size() > 1) kv_grant(i, (int)prompts[i].size() - 1);
   kv_sync();
-  for (size_t i = 0; i < n; ++i) {
-    if (wf->cpu) std::memcpy(wf->stage->prompt_buf() + i * max_ctx_, prompts[i].data(), prompts[i].size() * 4);
-    else {
-      HIP_OK(hipSetDevice(wf->device));
-      HIP_OK(hipMemcpy(wf->stage->prompt_buf() + i * max_ctx_, prompts[i].data(), prompts[i].size() * 4, hipMemcpyHostToDevice));
-    }
-  }
+  for (size_t i = 0; i < n; ++i) upload_tokens(i, 0, prompts[i].data(), prompts[i].size());
   out->assign(n, {});
   for (size_t i = 0; i < n; ++i) {
     (*out)[i].lp.assign(prompts[i].size() - 1, 0.f);
     (*out)[i].top_id.assign((prompts[i].size() - 1) * n_top, -1);
     (*out)[i].top_lp.assign((prompts[i].size() - 1) * n_top, 0.f);
   }
-  std::vector<int> done(n, 0);   // rows of each prompt already scored
+  // the chunks of each micro-batch, in order: every row of a prompt but its last (which has no target)
+  std::vector<std::vector<Item>> chunks(M_);
+  PrefillSeg scored;
+  scored.score = true;
+  for (int mb = 0; mb < M_; ++mb) {
+    std::vector<PackRow> rows;
+    for (int b = 0; b < B_ && (size_t)mb * B_ + b < n; ++b) rows.push_back({b, 0, (int)prompts[(size_t)mb * B_ + b].size() - 1});
+    chunks[mb] = pack_chunks(mb, rows, scored);
+  }
   std::vector<int32_t> tgt;
   std::vector<float> lp((size_t)chunk_), tl((size_t)chunk_ * std::max(1, n_top));
   std::vector<int32_t> ti((size_t)chunk_ * std::max(1, n_top));
-  for (;;) {
+  for (size_t pass = 0;; ++pass) {
     std::vector<Item> items;
     for (int mb = 0; mb < M_; ++mb) {
-      Item it{Item::PREFILL};
-      it.mb = mb;
+      if (pass >= chunks[mb].size()) continue;
+      const Item& it = chunks[mb][pass];
       tgt.clear();
-      for (int b = 0; b < B_ && it.T < chunk_; ++b) {
-        const size_t i = (size_t)mb * B_ + b;
-        if (i >= n) break;
-        const int rows = (int)prompts[i].size() - 1;
-        if (done[i] >= rows) continue;
-        PrefillSeg sg;
-        sg.b = b; sg.p0 = done[i]; sg.T = std::min(chunk_ - it.T, rows - done[i]); sg.score = true;
-        for (int t = 0; t < sg.T; ++t) tgt.push_back(prompts[i][sg.p0 + t + 1]);
-        it.segs.push_back(sg);
-        it.T += sg.T;
-        if (!packed_prefill_) break;
-      }
-      if (it.T == 0) continue;
+      for (const PrefillSeg& sg : it.segs)
+        for (int t = 0; t < sg.T; ++t) tgt.push_back(prompts[(size_t)mb * B_ + sg.b][sg.p0 + t + 1]);
       if (!wl->cpu) HIP_OK(hipSetDevice(wl->device));
       wl->stage->set_score_targets(mb, tgt.data(), it.T, n_top);
       items.push_back(it);
@@ -2274,7 +2237,6 @@ void Engine::score(const std::vector<std::vector<int32_t>>& prompts, int n_top, 
         std::copy(lp.begin() + row, lp.begin() + row + sg.T, (*out)[i].lp.begin() + sg.p0);
         std::copy(ti.begin() + (size_t)row * n_top, ti.begin() + (size_t)(row + sg.T) * n_top, (*out)[i].top_id.begin() + (size_t)sg.p0 * n_top);
         std::copy(tl.begin() + (size_t)row * n_top, tl.begin() + (size_t)(row + sg.T) * n_top, (*out)[i].top_lp.begin() + (size_t)sg.p0 * n_top);
-        done[i] += sg.T;
         row += sg.T;
       }
     }
@@ -2284,7 +2246,7 @@ void Engine::score(const std::vector<std::vector<int32_t>>& prompts, int n_top, 
 std::vector<int> Engine::idle_slots() const {
   std::vector<int> s;
   for (int i = 0; i < M_ * B_; ++i)
-    if (!((size_t)i < active_.size() && active_[i])) s.push_back(i);
+    if (!slots_[i].active) s.push_back(i);
   return s;
 }
 
@@ -2311,7 +2273,7 @@ void Engine::embed(const std::vector<int>& slots, const std::vector<std::vector<
     const int i = slots[k];
     if (i < 0 || (size_t)i >= NS) throw std::runtime_error("embed: bad slot " + std::to_string(i));
     if (k_of[i] >= 0) throw std::runtime_error("embed: slot " + std::to_string(i) + " given twice");
-    if ((size_t)i < active_.size() && active_[i]) throw std::runtime_error("embed: slot " + std::to_string(i) + " is busy");
+    if (slots_[i].active) throw std::runtime_error("embed: slot " + std::to_string(i) + " is busy");
     if (prompts[k].empty()) throw std::runtime_error("embed: prompt " + std::to_string(k) + " is empty");
     if ((int)prompts[k].size() > max_ctx_)
       throw std::runtime_error("embed: prompt " + std::to_string(k) + " has " + std::to_string(prompts[k].size()) +
@@ -2323,12 +2285,7 @@ void Engine::embed(const std::vector<int>& slots, const std::vector<std::vector<
   }
   out->assign(n, {});
   if (n == 0) return;
-  Worker* wf = nullptr;
-  Worker* wl = nullptr;
-  for (auto& w : workers_) {
-    if (w->stage->spec().first()) wf = w.get();
-    if (w->stage->spec().last()) wl = w.get();
-  }
+  Worker* wl = last_worker();
   // KV pages for the prompts (all or none: a pool too small for this call leaves the slots as they were)
   try {
     for (size_t k = 0; k < n; ++k) kv_grant((size_t)slots[k], (int)prompts[k].size());
@@ -2338,40 +2295,20 @@ void Engine::embed(const std::vector<int>& slots, const std::vector<std::vector<
   }
   kv_sync();
   for (size_t k = 0; k < n; ++k) {
-    const size_t i = (size_t)slots[k];
-    if (i < slot_toks_.size()) slot_toks_[i].clear();   // the slot's KV is overwritten: no prefix to reuse
-    if (wf->cpu) std::memcpy(wf->stage->prompt_buf() + i * max_ctx_, prompts[k].data(), prompts[k].size() * 4);
-    else {
-      HIP_OK(hipSetDevice(wf->device));
-      HIP_OK(hipMemcpy(wf->stage->prompt_buf() + i * max_ctx_, prompts[k].data(), prompts[k].size() * 4, hipMemcpyHostToDevice));
-    }
+    slots_[slots[k]].kv_toks.clear();   // the slot's KV is overwritten: no prefix to reuse
+    upload_tokens((size_t)slots[k], 0, prompts[k].data(), prompts[k].size());
   }
   if (!wl->cpu) HIP_OK(hipSetDevice(wl->device));
   wl->stage->set_embed(pooling, normalize);
   // the chunks of each micro-batch, in order (prefill_items without prefix reuse or a head item)
   std::vector<std::vector<Item>> chunks(M_);
+  PrefillSeg embedded;
+  embedded.embed = true;
   for (int mb = 0; mb < M_; ++mb) {
-    Item it{Item::PREFILL};
-    it.mb = mb;
-    auto flush = [&] {
-      if (it.T > 0) chunks[mb].push_back(it);
-      it.segs.clear();
-      it.T = 0;
-    };
-    for (int b = 0; b < B_; ++b) {
-      const int k = k_of[(size_t)mb * B_ + b];
-      if (k < 0) continue;
-      const int len = (int)prompts[k].size();
-      for (int p0 = 0; p0 < len;) {
-        PrefillSeg sg;
-        sg.b = b; sg.p0 = p0; sg.T = std::min(chunk_ - it.T, len - p0); sg.last = p0 + sg.T >= len; sg.embed = true;
-        it.segs.push_back(sg);
-        it.T += sg.T;
-        p0 += sg.T;
-        if (it.T == chunk_ || !packed_prefill_) flush();
-      }
-    }
-    flush();
+    std::vector<PackRow> rows;
+    for (int b = 0; b < B_; ++b)
+      if (const int k = k_of[(size_t)mb * B_ + b]; k >= 0) rows.push_back({b, 0, (int)prompts[k].size()});
+    chunks[mb] = pack_chunks(mb, rows, embedded);
   }
   for (size_t k = 0; k < n; ++k) {
     (*out)[k].n_rows = pooling == POOL_NONE ? (int)prompts[k].size() : 1;
@@ -2435,7 +2372,7 @@ Json Engine::generate(const std::vector<std::vector<int32_t>>& prompts, int n_pr
     left -= k;
   }
   const double t2 = now_ms();
-  if (out) *out = gen_;
+  if (out) *out = tokens();
   size_t n_prompt = 0;
   for (auto& p : prompts) n_prompt += p.size();
   Json j = Json::object();
@@ -2495,32 +2432,28 @@ Json Engine::spec_generate(const std::vector<std::vector<int32_t>>& prompts, int
   const int k = std::max(1, std::min(draft_max, chunk_ / B_ - 1));
   if (k < 1 || chunk_ / B_ < 2) throw std::runtime_error("prefill chunk too small for speculative decoding");
   ngram = std::max(1, ngram);
-  Worker* wf = nullptr;
-  Worker* wl = nullptr;
-  for (auto& w : workers_) {
-    if (w->stage->spec().first()) wf = w.get();
-    if (w->stage->spec().last()) wl = w.get();
-  }
+  Worker* wl = last_worker();
+  auto gen = [&](size_t i) -> std::vector<int32_t>& { return slots_[i].gen; };
   const double t0 = now_ms();
   start(prompts);
   resumable_ = false;   // sequences advance by different amounts: positions are not prompt + rounds
-  slot_toks_.clear();   // the verify chunks write draft rows past the accepted tokens
+  forget_kv_toks();     // the verify chunks write draft rows past the accepted tokens
   const double t1 = now_ms();
   const size_t n = prompts.size();
   if (mp) {   // the first token of every sequence is known where the last stage lives
     std::vector<int32_t> ft(n, 0);
     if (owns_last())
-      for (size_t i = 0; i < n; ++i) ft[i] = gen_[i][0];
+      for (size_t i = 0; i < n; ++i) ft[i] = gen(i)[0];
     ring_bcast_from_last(ft);
     if (!owns_last())
-      for (size_t i = 0; i < n; ++i) gen_[i].assign(1, ft[i]);
+      for (size_t i = 0; i < n; ++i) gen(i).assign(1, ft[i]);
   }
   if (on_token)
-    for (size_t i = 0; i < n; ++i) on_token((int)i, gen_[i][0]);
+    for (size_t i = 0; i < n; ++i) on_token((int)i, gen(i)[0]);
   std::vector<std::vector<int32_t>> ctx(n);
   for (size_t i = 0; i < n; ++i) {
     ctx[i] = prompts[i];
-    ctx[i].insert(ctx[i].end(), gen_[i].begin(), gen_[i].end());
+    ctx[i].insert(ctx[i].end(), gen(i).begin(), gen(i).end());
   }
   long rounds = 0, drafted = 0, accepted = 0;
   std::vector<int32_t> vt(chunk_);
@@ -2532,24 +2465,17 @@ Json Engine::spec_generate(const std::vector<std::vector<int32_t>>& prompts, int
       it.mb = mb;
       for (int b = 0; b < B_; ++b) {
         const size_t i = (size_t)mb * B_ + b;
-        if (i >= n || (int)gen_[i].size() >= n_predict || (int)ctx[i].size() >= max_ctx_) continue;
+        if (i >= n || (int)gen(i).size() >= n_predict || (int)ctx[i].size() >= max_ctx_) continue;
         if (keep_going && !keep_going((int)i)) continue;
         const int pos = (int)ctx[i].size() - 1;   // the last token is not in the KV cache yet
         std::vector<int32_t> d = lookup_draft(ctx[i], k, ngram);
-        const int room = std::min(max_ctx_ - pos - 1, n_predict - (int)gen_[i].size() - 1);
+        const int room = std::min(max_ctx_ - pos - 1, n_predict - (int)gen(i).size() - 1);
         if ((int)d.size() > room) d.resize(std::max(0, room));
         chunk[i].push_back(ctx[i].back());
         chunk[i].insert(chunk[i].end(), d.begin(), d.end());
         kv_grant(i, pos + (int)chunk[i].size());
         drafted += (long)d.size();
-        if (!wf) {
-        } else if (wf->cpu) {
-          std::memcpy(wf->stage->prompt_buf() + i * max_ctx_ + pos, chunk[i].data(), chunk[i].size() * 4);
-        } else {
-          HIP_OK(hipSetDevice(wf->device));
-          HIP_OK(hipMemcpy(wf->stage->prompt_buf() + i * max_ctx_ + pos, chunk[i].data(), chunk[i].size() * 4,
-                           hipMemcpyHostToDevice));
-        }
+        upload_tokens(i, pos, chunk[i].data(), chunk[i].size());
         PrefillSeg sg;
         sg.b = b; sg.p0 = pos; sg.T = (int)chunk[i].size(); sg.last = true; sg.verify = true;
         it.segs.push_back(sg);
@@ -2588,21 +2514,21 @@ Json Engine::spec_generate(const std::vector<std::vector<int32_t>>& prompts, int
         accepted += a;
         for (int j = 0; j <= a; ++j) {
           const int32_t t = vt[row + j];   // = c[1 + j] for j < a, the target's own token at j = a
-          gen_[i].push_back(t);
+          gen(i).push_back(t);
           ctx[i].push_back(t);
           if (on_token) on_token((int)i, t);
         }
-        if ((int)gen_[i].size() > n_predict) gen_[i].resize(n_predict);
+        if ((int)gen(i).size() > n_predict) gen(i).resize(n_predict);
         row += sg.T;
       }
     }
   }
   started_ = false;   // positions on the devices no longer follow the decode schedule
   const double t2 = now_ms();
-  if (out) *out = gen_;
+  if (out) *out = tokens();
   size_t n_prompt = 0, n_gen = 0;
   for (auto& p : prompts) n_prompt += p.size();
-  for (auto& g : gen_) n_gen += g.size() > 0 ? g.size() - 1 : 0;
+  for (size_t i = 0; i < n; ++i) n_gen += gen(i).size() > 0 ? gen(i).size() - 1 : 0;
   Json j = Json::object();
   j["prefill_ms"] = t1 - t0;
   j["decode_ms"] = t2 - t1;

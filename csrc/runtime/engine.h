@@ -14,6 +14,7 @@
 //   "mp"    : one stage per process (torch.distributed / torchrun launch): config carries
 //             "world", "rank" and the RCCL unique ids of the links this rank participates in.
 #pragma once
+#include <algorithm>
 #include <atomic>
 #include <condition_variable>
 #include <functional>
@@ -53,32 +54,25 @@ struct StepStats {
 // made for a running slot is live at once; one made for an idle slot, or handed to start() for a slot
 // that is still busy with the generation before it, is pending until that admission.  start() ends
 // the live ones and keeps the pending, release() ends the slot's, load_state() ends them all.
-class SlotSettings {
+// One value per slot and setting (Engine::Slot); Engine::drain_settings runs start()'s and load_state()'s
+// transition over every slot.
+class SlotSetting {
  public:
-  void reset(size_t n_slots) { st_.assign(n_slots, OFF); }
-  bool on(int slot) const { return st_[slot] != OFF; }
+  bool on() const { return st_ != OFF; }
   // running: the slot holds a running sequence and the setting is not meant for the next start()
-  void set(int slot, bool value, bool running) { st_[slot] = !value ? OFF : running ? LIVE : PENDING; }
-  void clear(int slot) { st_[slot] = OFF; }
-  template <class Slots> void admit(const Slots& slots) {   // set for this admission: in use from here on
-    for (auto s : slots) if (st_[s] == PENDING) st_[s] = LIVE;
+  void set(bool value, bool running) { st_ = !value ? OFF : running ? LIVE : PENDING; }
+  void clear() { st_ = OFF; }
+  void admit() { if (st_ == PENDING) st_ = LIVE; }   // set for this admission: in use from here on
+  // start() (all = false): a live setting ends and a pending one becomes live; load_state() (all = true):
+  // whatever is on ends.  True when it ended: the caller switches it off on the stages.
+  bool drain(bool all) {
+    const bool ended = st_ == LIVE || (all && st_ != OFF);
+    st_ = ended ? OFF : st_ == PENDING ? LIVE : st_;
+    return ended;
   }
-  // start(): the live slots, now off (the caller switches them off on the stages); the pending become live
-  std::vector<int> drain_for_start() { return drain(false); }
-  // load_state(): every slot that was on, now off
-  std::vector<int> drain_all() { return drain(true); }
 
  private:
-  enum State : char { OFF, PENDING, LIVE };
-  std::vector<int> drain(bool all) {
-    std::vector<int> out;
-    for (size_t s = 0; s < st_.size(); ++s) {
-      if (st_[s] == LIVE || (all && st_[s] != OFF)) { out.push_back((int)s); st_[s] = OFF; }
-      else if (st_[s] == PENDING) st_[s] = LIVE;
-    }
-    return out;
-  }
-  std::vector<State> st_;
+  enum State : char { OFF, PENDING, LIVE } st_ = OFF;
 };
 
 class Engine {
@@ -116,7 +110,7 @@ class Engine {
   };
   int n_probs() const { return n_probs_; }
   int n_top() const { return n_probs_ > 0 ? n_probs_ : 0; }
-  const std::vector<SeqLogprobs>& logprobs() const;
+  std::vector<SeqLogprobs> logprobs() const;
   // the record of last_token(slot): false when none was taken (n_probs = 0, speculative decoding)
   bool last_logprob(int slot, float* lp, std::vector<int32_t>* top_id, std::vector<float>* top_lp) const;
   // Prompt scoring: out[i].lp[t] = log p(prompts[i][t + 1] | prompts[i][:t + 1]), t < len - 1, with
@@ -226,16 +220,18 @@ class Engine {
   void set_slot_keep(int slot, int n_keep);
   long context_shifts() const { return context_shifts_; }
   // shifts of the slot's running sequence
-  int slot_shifts(int slot) const { return slot >= 0 && slot < (int)n_shifts_.size() ? n_shifts_[slot] : 0; }
+  int slot_shifts(int slot) const { return slot_in_range(slot) ? slots_[slot].n_shifts : 0; }
   // the most rounds the next decode_steps call can take before a running slot's context is full
   // (<= 0: one is full now; with automatic shifting a call of 1 round shifts it)
   int context_room() const;
   // what an automatic shift of `slot` would discard now (0: nothing, the kept prefix fills the context)
   int shift_discard(int slot) const;
-  int32_t last_token(int slot) const { return slot < (int)gen_.size() && !gen_[slot].empty() ? gen_[slot].back() : -1; }
-  int slot_position(int slot) const { return slot_pos((size_t)slot); }
+  int32_t last_token(int slot) const {
+    return slot_in_range(slot) && !slots_[slot].gen.empty() ? slots_[slot].gen.back() : -1;
+  }
+  int slot_position(int slot) const { return slot_in_range(slot) ? slot_pos((size_t)slot) : 0; }
   bool started() const { return started_; }
-  bool slot_active(int slot) const { return slot >= 0 && slot < (int)active_.size() && active_[slot]; }
+  bool slot_active(int slot) const { return slot_in_range(slot) && slots_[slot].active; }
 
   Json generate(const std::vector<std::vector<int32_t>>& prompts, int n_predict,
                 std::vector<std::vector<int32_t>>* out);
@@ -312,8 +308,12 @@ class Engine {
       fn(*w);
     }
   }
-  // whether a setting made now for `slot` is in use at once (see SlotSettings)
+  // the owned first / last stage's worker, null when another process owns it
+  Worker* first_worker() const;
+  Worker* last_worker() const;
+  // whether a setting made now for `slot` is in use at once (see SlotSetting)
   bool slot_running(int slot, bool for_start) const { return !for_start && started_ && slot_active(slot); }
+  bool slot_in_range(int slot) const { return slot >= 0 && slot < M_ * B_; }
   // slots[i] is in range and none of slots[0 .. i) repeats it; throws "<fn>: slot <s> is out of range" /
   // "<fn>: slot <s> is listed twice<twice_suffix>"
   void check_slot_at(const char* fn, const std::vector<int>& slots, size_t i, const char* twice_suffix = "") const;
@@ -331,18 +331,56 @@ class Engine {
   std::vector<std::unique_ptr<Worker>> workers_;   // owned stages (all in local mode)
   std::vector<std::unique_ptr<Link>> links_;
   std::unique_ptr<GgufFile> gguf_;
-  // sequences
-  std::vector<std::vector<int32_t>> prompts_;
-  std::vector<std::vector<int32_t>> gen_;          // generated tokens per sequence
+  // Everything the engine knows about one sequence slot (slot = mb * mb_size + row).  slots_ holds
+  // n_mb * mb_size of them from the constructor on and is never resized; a field whose feature is off
+  // keeps its default.  Three transitions move a slot: begin_sequence (admission: start, admit),
+  // release (the sequence ends) and reset_slots (every slot: start, score, load_state).
+  struct KvTag { uint64_t serial = 0; float scale = 0.f; };
+  struct Slot {
+    std::vector<int32_t> prompt, gen;   // the sequence: its prompt and the tokens generated so far
+    SeqLogprobs lp;                     // n_probs != 0: one record per token of gen
+    // prefix cache (config "prefix_cache", default on): the tokens the slot's KV holds; an admission
+    // prefills only what follows the common prefix (multi-turn chat re-sends the whole history)
+    std::vector<int32_t> kv_toks;
+    int base_round = 0;                 // the round at which the sequence was admitted
+    bool active = false;                // a sequence is running
+    // context shift: the positions the running sequence has discarded and how often; the slot's n_keep
+    int shifted = 0, n_shifts = 0, n_keep = 0;
+    // the prompt tokens an automatic shift keeps (n_keep -1: the whole prompt)
+    int keep() const { return n_keep < 0 ? (int)prompt.size() : std::min(n_keep, (int)prompt.size()); }
+    RowSampling rec;                    // row_sampling: set for the next admission / in use
+    bool seed_given = false;
+    int bind_id = -1;                   // LoRA: the bound adapter (-1: none) and its user scale
+    float bind_scale = 0.f;
+    // the binding the cached KV was computed under (serial 0: the base model; kMixedTag: rebound
+    // mid-generation, never reused)
+    KvTag kv_tag;
+    SlotSetting mask, bind;             // the lifecycle of the slot's token mask / adapter binding
+  };
+  std::vector<Slot> slots_;
+  // the sequences tokens(), logprobs() and session.json list, slots [0, n_seqs_): the prompt count
+  // after start / load_state / spec_generate, every slot from the first admit on, none after score
+  size_t n_seqs_ = 0;
+  void reset_slots(size_t n_seqs);      // every sequence is over; the slots' settings and n_keep stay
+  void begin_sequence(size_t slot, const std::vector<int32_t>& prompt);
+  void forget_kv_toks() { for (Slot& s : slots_) s.kv_toks.clear(); }   // KV content unknown: no prefix to reuse
+  std::vector<int> drain_settings(SlotSetting Slot::*which, bool all);  // the slots whose setting ended
+  // the one writer of the first stage's prompt_buf: n tokens of `slot` from position pos0 on (nothing
+  // where another process owns the first stage)
+  void upload_tokens(size_t slot, int pos0, const int32_t* toks, size_t n);
+  // The chunks of one micro-batch, in order: the rows [p0, p0 + len) of sequence row b, cut into
+  // packed chunks of at most chunk_ rows (a chunk may hold several sequences; without packed_prefill
+  // every segment is its own chunk).  `flags` gives every segment its score / verify / embed marks.
+  struct PackRow { int b, p0, len; };
+  std::vector<Item> pack_chunks(int mb, const std::vector<PackRow>& rows, const PrefillSeg& flags) const;
   int32_t* out_host_ = nullptr;                    // pinned [rounds_cap][M*B]
   std::vector<int32_t> out_vec_;                   // CPU backend storage of out_host_
   // n_probs != 0: the rounds' logprob records beside the tokens, [rounds_cap][M] records of
-  // lp_words_ 4-byte words (Stage::logprob_rec), and what has been collected from them per sequence
+  // lp_words_ 4-byte words (Stage::logprob_rec); take_logprobs collects one into the slot's lp
   int n_probs_ = 0;
   size_t lp_words_ = 0;
   uint32_t* lp_host_ = nullptr;
   std::vector<uint32_t> lp_vec_;
-  std::vector<SeqLogprobs> gen_lp_;
   void take_logprobs(size_t seq, size_t round_slot);
   bool cpu_ = false;          // every stage on the CPU backend
   bool hybrid_ = false;       // gpu_layers (-ngl N) < n_layer: stage 0 on the CPU, the rest on GPUs
@@ -360,58 +398,44 @@ class Engine {
   bool resumable_ = true;   // false after spec_generate (per-sequence positions)
   int32_t* bcast_dev_ = nullptr;   // ring_bcast_from_last device staging (RCCL / device links)
   size_t bcast_cap_ = 0;
-  // prefix cache (config "prefix_cache", default on): per slot, the tokens its KV holds; start()
-  // prefills only what follows the common prefix (multi-turn chat re-sends the whole history)
-  bool prefix_cache_ = true;
-  std::vector<std::vector<int32_t>> slot_toks_;
+  bool prefix_cache_ = true;   // Slot::kv_toks
   long reused_tokens_ = 0;
   void refresh_slot_cache();
-  // per slot: the round at which its sequence was admitted, and whether one is running
-  std::vector<int> base_round_;
-  std::vector<char> active_;
-  KvPager pager_;            // paged KV: one logical table, installed on every stage
+  KvPager pager_;           // paged KV: one logical table, installed on every stage
   int kv_pages_ = 0;         // pool pages per stage
-  std::vector<double> device_speed_;
-  int failed_stage_ = -1;    // stage whose worker raised the fault (health()["failed_stage"])   // partitioner weights per stage (given or probed)
+  std::vector<double> device_speed_;   // partitioner weights per stage (given or probed)
+  int failed_stage_ = -1;    // stage whose worker raised the fault (health()["failed_stage"])
   void kv_grant(size_t slot, int n_tokens);   // throws when the pool is exhausted
   void kv_sync();            // push a changed table to the stages (between engine calls)
+  // the next decode position: prompt + rounds since the admission - discarded positions
   int slot_pos(size_t i) const {
-    return (i < prompts_.size() ? (int)prompts_[i].size() : 0) + rounds_done_ - (i < base_round_.size() ? base_round_[i] : 0) -
-           (i < shifted_.size() ? shifted_[i] : 0);
+    const Slot& s = slots_[i];
+    return (int)s.prompt.size() + rounds_done_ - s.base_round - s.shifted;
   }
-  // context shift: per slot the positions its running sequence has discarded and how often, the
-  // slot's n_keep; reset by start, admit, release and load_state
+  // context shift (Slot::shifted, n_shifts, n_keep)
   bool auto_shift_ = false;
   int n_keep_ = 0;
   long context_shifts_ = 0;
-  std::vector<int> shifted_, n_shifts_, slot_keep_;
-  void reset_shift(size_t slot, bool keep_too);
   void check_shift_supported(const char* fn) const;
+  // the micro-batch's positions -> every stage; its penalty windows (prompt + accepted tokens of
+  // every row) -> the last stage
   void push_positions(int mb);
+  void push_history(int mb);
   bool row_sampling_ = false;
   bool row_masks_ = false;
-  SlotSettings mask_life_;
   void clear_masks(bool all);               // start(): those in use; load_state(): all
   RowSampling row_default_;                 // the engine keys as a record (seed: the engine's)
-  std::vector<RowSampling> slot_rec_;       // per slot: set for the next admission / in use
-  std::vector<char> slot_seed_given_;
   uint64_t admissions_ = 0;
   void apply_slot_sampling(const std::vector<size_t>& seqs);   // before an admission's prefill
   void push_row_draws(int mb);                                 // after it: draw0 + tokens generated
   std::vector<Item> prefill_items(const std::vector<size_t>& seqs, bool admission);
-  // LoRA: the loaded adapters (serial: unique per load, so a reused id never matches an old KV tag), the
-  // slots' bindings with the masks' three states, and per slot the binding its cached KV was computed
-  // under (serial 0: the base model; kMixedTag: rebound mid-generation, never reused)
+  // LoRA: the loaded adapters (serial: unique per load, so a reused id never matches an old KV tag);
+  // the slots' bindings and KV tags live in their Slot
   struct AdapterRec { bool used = false; std::string path; float alpha = 0.f; int r_min = 0, r_max = 0; size_t bytes = 0; uint64_t serial = 0; };
-  struct KvTag { uint64_t serial = 0; float scale = 0.f; };
   static constexpr uint64_t kMixedTag = ~0ull;
   int lora_cap_ = 0, lora_max_rank_ = 64;
   uint64_t lora_serial_ = 0;
   std::vector<AdapterRec> adapters_;
-  std::vector<int> bind_id_;
-  std::vector<float> bind_scale_;
-  SlotSettings bind_life_;
-  std::vector<KvTag> kv_tag_;
   KvTag bind_tag(size_t slot) const;
   // mark_mixed: a running slot whose binding changes keeps KV of two bindings (never a prefix again)
   void push_bindings(const std::vector<int>& slots, const std::vector<int>& ids, const std::vector<float>& scales,

@@ -34,12 +34,12 @@ def main():
     ap.add_argument("--target", type=int, default=2048)
     ap.add_argument("--epi", type=int, default=-1, help="override the epilogue (0 store, 1 atomic): timing probes")
     ap.add_argument("--copies", type=int, default=0, help="weight copies cycled (default: enough to defeat the 256 MiB MALL; 1 = hot)")
-    ap.add_argument("--gemm", type=int, default=0,
-                    help="time the prompt GEMM instead (1: 64x64 tiles, 2: 128x256 per-wave dequant, 3: LDS-shared dequant, "
+    ap.add_argument("--gemm", type=int, default=0, choices=[0, 1, 3, 4, 8],
+                    help="time the prompt GEMM instead (1: 64x64 tiles, 3: LDS-shared dequant, "
                          "4: gemm3's stream on the 32x32x16 MFMA, 8: the int8-activation prototype on per-row int8 "
                          "weights, gemm3 P_I8)")
     ap.add_argument("--sk", action="store_true",
-                    help="ATOMIC shapes with --gemm 2 / 4: the engine's split-K (per-split partial stores + the "
+                    help="ATOMIC shapes with --gemm 4: the engine's split-K (per-split partial stores + the "
                          "fixed-order reduction into Y) instead of atomics")
     ap.add_argument("--g3", default="0,0,0", help="v3 GEMM tuning BM,BN,nsplit (0 = auto); ';'-separated list sweeps")
     ap.add_argument("--knob", action="append", default=[], metavar="NAME=V[,V..]",
@@ -107,11 +107,11 @@ def main():
                                                          n if epi != EPI_SWIGLU else n // 2, ctypes.c_void_p(xs.data_ptr()),
                                                          ctypes.c_void_p(ws.data_ptr()), 1, st()), "gemm3_i8")
                                 return
-                            if a.sk and a.gemm in (2, 4) and epi == EPI_ATOMIC:
-                                fn = L.mp_op_gemm4_splitk if a.gemm == 4 else L.mp_op_gemm2_splitk
-                                N.check(fn(pt, ctypes.c_void_p(W.data_ptr()), ntiles, nsb, ctypes.c_void_p(X.data_ptr()),
-                                           k_pad, M, ctypes.c_void_p(Y.data_ptr()), n, n,
-                                           ctypes.c_void_p(SK.data_ptr()), SK.numel(), st()), "gemm splitk")
+                            if a.sk and a.gemm == 4 and epi == EPI_ATOMIC:
+                                N.check(L.mp_op_gemm4_splitk(pt, ctypes.c_void_p(W.data_ptr()), ntiles, nsb,
+                                                             ctypes.c_void_p(X.data_ptr()), k_pad, M,
+                                                             ctypes.c_void_p(Y.data_ptr()), n, n,
+                                                             ctypes.c_void_p(SK.data_ptr()), SK.numel(), st()), "gemm splitk")
                                 return
                             if a.gemm == 4:
                                 N.check(L.mp_op_gemm4(pt, epi, ctypes.c_void_p(W.data_ptr()), ntiles, nsb,
@@ -126,11 +126,10 @@ def main():
                                                       n if epi != EPI_SWIGLU else n // 2, 1, st()), "gemm3")
                                 return
                             if a.gemm:
-                                fn = L.mp_op_gemm2 if a.gemm == 2 else L.mp_op_gemm
-                                N.check(fn(pt, epi, ctypes.c_void_p(W.data_ptr()), ntiles, nsb,
-                                           ctypes.c_void_p(X.data_ptr()), k_pad, M, ctypes.c_void_p(Y.data_ptr()),
-                                           n, ctypes.c_void_p(H.data_ptr()), n // 2,
-                                           n if epi != EPI_SWIGLU else n // 2, st()), "gemm")
+                                N.check(L.mp_op_gemm(pt, epi, ctypes.c_void_p(W.data_ptr()), ntiles, nsb,
+                                                     ctypes.c_void_p(X.data_ptr()), k_pad, M, ctypes.c_void_p(Y.data_ptr()),
+                                                     n, ctypes.c_void_p(H.data_ptr()), n // 2,
+                                                     n if epi != EPI_SWIGLU else n // 2, st()), "gemm")
                                 return
                             N.check(L.mp_op_gemv(pt, epi, ctypes.c_void_p(W.data_ptr()), ntiles, nsb,
                                                  ctypes.c_void_p(X.data_ptr()), k_pad, M, ctypes.c_void_p(Y.data_ptr()),
