@@ -17,6 +17,7 @@
 
 #include "kcommon.h"
 #include "dequant.h"
+#include "attn_qfrag.h"
 #include "../runtime/kernels_api.h"
 
 namespace mpk {
@@ -275,105 +276,7 @@ __device__ __forceinline__ half8_t softmax_chunk(f32x4 (&sc)[2], bool mask, int 
                  (f16)pv[1][0], (f16)pv[1][1], (f16)pv[1][2], (f16)pv[1][3]};
 }
 
-// ROT = false: q is already rotated (the qkv GEMV's append epilogue, DecodeAttnParams::pre)
-template <int KK, bool ROT = true>
-__device__ __forceinline__ void decode_q_frags(const DecodeAttnParams& p, const float* row, const float2* cs, float nrs,
-                                               int kvh, int G, int q4, int col, half8_t (&qf)[KK]) {
-  const int g = col;
-  const bool rvalid = col < G;
-  const int h = kvh * G + g;
-  const float qsc = p.q_scale * 1.4426950408889634f;   // exp2-domain scores (softmax_chunk)
-  auto qkv_at = [&](int i) { return p.bias ? fmaf(nrs, row[i], p.bias[i]) : nrs * row[i]; };
-  // q fragments with RoPE applied in registers: lane holds q[h][d = 32kk + 8q4 + j].  Built
-  // before the append so its loads overlap the append's, and (head_dim % 8 == 0) from
-  // unconditional 16-byte loads issued together: written as guarded scalar reads (qkv_at per
-  // element) the compiler serialised ~32 dependent load round trips here, ~10 us of fixed cost per
-  // call whatever the context (measured: 12.7 us at 20 keys, mb64).
-  if ((p.hd & 7) == 0) {
-    const int hs = rvalid ? h : kvh * G;          // idle MFMA columns read a valid head, then zero
-    // bias / no-bias as two straight-line bodies: a bias branch inside the loop split the loads
-    // into per-kk groups, each waited for before the next was issued
-    // two k-slices per batch of loads: all KK at once peaked at ~180 VGPRs for DP=128 (occupancy 2)
-    constexpr int KH = KK < 2 ? KK : 2;
-    auto build = [&](auto with_bias) {
-      constexpr bool HB = decltype(with_bias)::value;
-#pragma unroll
-      for (int k0 = 0; k0 < KK; k0 += KH) {
-      float4 xa[KH][2], ca[KH][2], ba[KH][2];
-#pragma unroll
-      for (int kh = 0; kh < KH; ++kh) {
-        const int kk = k0 + kh;
-        const int d0 = 32 * kk + 8 * q4;
-        const int dl = d0 < p.hd ? d0 : 0;
-        const float4* xs = reinterpret_cast<const float4*>(row + hs * p.hd + dl);
-        const float4* cp = reinterpret_cast<const float4*>(cs + dl / 2);
-        xa[kh][0] = xs[0]; xa[kh][1] = xs[1];
-        if constexpr (ROT) { ca[kh][0] = cp[0]; ca[kh][1] = cp[1]; }
-        if constexpr (HB) {
-          const float4* bs = reinterpret_cast<const float4*>(p.bias + hs * p.hd + dl);
-          ba[kh][0] = bs[0]; ba[kh][1] = bs[1];
-        }
-      }
-#pragma unroll
-      for (int kh = 0; kh < KH; ++kh) {
-        const int kk = k0 + kh;
-        const int d0 = 32 * kk + 8 * q4;
-        const bool ok = rvalid && d0 < p.hd;
-        float x[8] = {xa[kh][0].x, xa[kh][0].y, xa[kh][0].z, xa[kh][0].w, xa[kh][1].x, xa[kh][1].y, xa[kh][1].z, xa[kh][1].w};
-        float c[8] = {};
-        if constexpr (ROT) {
-          const float cc[8] = {ca[kh][0].x, ca[kh][0].y, ca[kh][0].z, ca[kh][0].w, ca[kh][1].x, ca[kh][1].y, ca[kh][1].z, ca[kh][1].w};
-#pragma unroll
-          for (int j = 0; j < 8; ++j) c[j] = cc[j];
-        }
-        if constexpr (HB) {
-          const float b[8] = {ba[kh][0].x, ba[kh][0].y, ba[kh][0].z, ba[kh][0].w, ba[kh][1].x, ba[kh][1].y, ba[kh][1].z, ba[kh][1].w};
-#pragma unroll
-          for (int j = 0; j < 8; ++j) x[j] = fmaf(nrs, x[j], b[j]);
-        } else {
-#pragma unroll
-          for (int j = 0; j < 8; ++j) x[j] *= nrs;
-        }
-        half8_t v = {};
-#pragma unroll
-        for (int j = 0; j < 8; j += 2) {
-          if constexpr (ROT) {
-            v[j] = ok ? (f16)((x[j] * c[j] - x[j + 1] * c[j + 1]) * qsc) : (f16)0.f;
-            v[j + 1] = ok ? (f16)((x[j] * c[j + 1] + x[j + 1] * c[j]) * qsc) : (f16)0.f;
-          } else {
-            v[j] = ok ? (f16)(x[j] * qsc) : (f16)0.f;
-            v[j + 1] = ok ? (f16)(x[j + 1] * qsc) : (f16)0.f;
-          }
-        }
-        qf[kk] = v;
-      }
-      }
-    };
-    if (p.bias) build(std::true_type{});
-    else build(std::false_type{});
-  } else {
-#pragma unroll
-    for (int kk = 0; kk < KK; ++kk) {
-      half8_t v = {};
-      if (rvalid) {
-        const int d0 = 32 * kk + 8 * q4;
-        const int qr = h * p.hd;
-#pragma unroll
-        for (int j = 0; j < 8; j += 2) {
-          const int d = d0 + j;
-          if (d < p.hd) {
-            const float x0 = qkv_at(qr + d), x1 = qkv_at(qr + d + 1);
-            const float2 c = ROT ? cs[d >> 1] : make_float2(1.f, 0.f);
-            v[j] = (f16)((x0 * c.x - x1 * c.y) * qsc);
-            v[j + 1] = (f16)((x0 * c.y + x1 * c.x) * qsc);
-          }
-        }
-      }
-      qf[kk] = v;
-    }
-  }
-
-}
+// decode_q_frags (attn_qfrag.h): ROT = false: q is already rotated (DecodeAttnParams::pre)
 
 #ifdef MIPIPE_TIMING_PROBES
 __device__ int g_attn_probe_calls = 0;
@@ -381,7 +284,9 @@ __device__ int g_attn_probe_calls = 0;
 
 // PRE: q arrives rotated and the new token's K / V are already in the cache (the qkv GEMV's append
 // epilogue, DecodeAttnParams::pre): no append, no RoPE, and no dependent position -> page chain
-template <int DP, bool F8, bool PF, int NW = 4, bool PRE = false>
+// SP: shared prompt prefixes (DecodeAttnParams::kv_begin ..): the row's keys start at kv_begin[t], and
+// the n_psplit partials attn_shared wrote for the keys below it join the split merge
+template <int DP, bool F8, bool PF, int NW = 4, bool PRE = false, bool SP = false>
 __device__ __forceinline__ void attn_decode_body(const DecodeAttnParams& p, const int t, const int kvh, const int z,
                                                  f16* xo = nullptr) {
   using KR = std::conditional_t<F8, u32x2, half8_t>;   // raw fragment: 8 elements
@@ -423,7 +328,13 @@ __device__ __forceinline__ void attn_decode_body(const DecodeAttnParams& p, cons
   // deferred RMSNorm of the projection GEMV: value i of q|k|v = nrs * row[i] + bias[i]
   const float nrs = p.ssq ? rsqrtf(p.ssq[t] / (float)p.d_model + p.eps) : 1.f;
 
-  const int start = z * p.split_len;
+  int kv0 = 0, n_pfx = 0, prow = -1;
+  if constexpr (SP) {
+    kv0 = p.kv_begin[t];
+    prow = p.pfx_row[t];
+    n_pfx = prow >= 0 ? p.n_psplit : 0;
+  }
+  const int start = kv0 + z * p.split_len;
   const int krow0 = 8 * (col >> 2) + (col & 3);
   // V fragment of (dim 16 dt + col, keys 8 q4 ..): the lane's part of the element offset in the page
   const uint32_t vlane = (uint32_t)(col * p.v_d + q4 * p.v_kb);
@@ -459,8 +370,10 @@ __device__ __forceinline__ void attn_decode_body(const DecodeAttnParams& p, cons
   const int end = min(start + p.split_len, kvlen);
   // splits past the sequence's length take no part (no partials, no counter): with n_act == 1 the
   // single active split writes the output directly, so short contexts pay no merge round trip
-  const int n_act = (kvlen + p.split_len - 1) / p.split_len;
+  const int n_act = (kvlen - kv0 + p.split_len - 1) / p.split_len;
   if (z >= n_act) return;
+  // a row with prefix partials always merges: its one suffix split is its own last arriver
+  const bool direct = n_act == 1 && n_pfx == 0;
   ATT_STAMP(1);
 
   // 1. the new token's K / V inputs (the split that owns the position) and, without the pre-load,
@@ -635,7 +548,7 @@ __device__ __forceinline__ void attn_decode_body(const DecodeAttnParams& p, cons
     }
     const int hh = kvh * G + r;
     const size_t rid = (size_t)t * p.Hq + hh;
-    if (n_act == 1) {
+    if (direct) {
       if (d < p.hd) {
         const f16 v = (f16)(L > 0.f ? O / L : 0.f);
         if (xo) xo[r * p.hd + d] = v;
@@ -658,7 +571,7 @@ __device__ __forceinline__ void attn_decode_body(const DecodeAttnParams& p, cons
              (int)(ts[1] - ts[0]), (int)(ts[2] - ts[0]), (int)(ts[3] - ts[0]), (int)(ts[4] - ts[0]), (int)(ts[5] - ts[0]));
   }
 #endif
-  if (n_act == 1) return;
+  if (direct) return;
   // 4. last arriver of this (token, kv head) merges the splits.
   // Hand-off invariant (MI355X_MICROARCH.md 'Valid forms', first row of the sc1 table, measured on
   // gfx950 / ROCm 7.2 rather than guaranteed by the memory model): EVERY store of the partials is an
@@ -687,14 +600,23 @@ __device__ __forceinline__ void attn_decode_body(const DecodeAttnParams& p, cons
     sm_mz[r][zz] = ld_sc1(p.ml_part + (zz * stride + rid) * 2);
     sm_lz[r][zz] = ld_sc1(p.ml_part + (zz * stride + rid) * 2 + 1);
   }
+  const int n_tot = n_act + n_pfx;   // the prefix partials (written by the kernel before this one) follow
+  if constexpr (SP) {
+    for (int i = threadIdx.x; i < G * n_pfx; i += NW * 64) {
+      const int r = i / n_pfx, zz = i - r * n_pfx;
+      const size_t rid = (size_t)prow * p.Hq + kvh * G + r;
+      sm_mz[r][n_act + zz] = p.pfx_ml[(zz * stride + rid) * 2];
+      sm_lz[r][n_act + zz] = p.pfx_ml[(zz * stride + rid) * 2 + 1];
+    }
+  }
   __syncthreads();
   for (int r = wave; r < G; r += NW) {
     float M = -INFINITY;
-    for (int zz = lane; zz < n_act; zz += 64) M = fmaxf(M, sm_mz[r][zz]);
+    for (int zz = lane; zz < n_tot; zz += 64) M = fmaxf(M, sm_mz[r][zz]);
 #pragma unroll
     for (int o = 32; o >= 1; o >>= 1) M = fmaxf(M, __shfl_xor(M, o));
     float L = 0.f;
-    for (int zz = lane; zz < n_act; zz += 64) {
+    for (int zz = lane; zz < n_tot; zz += 64) {
       const float mz = sm_mz[r][zz];
       const float f = mz == -INFINITY ? 0.f : __builtin_amdgcn_exp2f(mz - M);
       sm_mz[r][zz] = f;   // becomes the split's weight
@@ -711,6 +633,10 @@ __device__ __forceinline__ void attn_decode_body(const DecodeAttnParams& p, cons
     float O = 0.f;
 #pragma unroll 8
     for (int zz = 0; zz < n_act; ++zz) O += sm_mz[r][zz] * ld_sc1(p.o_part + (zz * stride + rid) * DP + d);
+    if constexpr (SP) {
+      const size_t prid = (size_t)prow * p.Hq + hh;
+      for (int zz = 0; zz < n_pfx; ++zz) O += sm_mz[r][n_act + zz] * p.pfx_o[(zz * stride + prid) * DP + d];
+    }
     const float L = sm_m[0][r];
     if (d < p.hd) p.out[(size_t)t * p.ldo + hh * p.hd + d] = (f16)(L > 0.f ? O / L : 0.f);
   }
@@ -728,6 +654,20 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const DecodeAttnParams
 template <int DP, bool F8, bool PRE = false>
 __global__ __launch_bounds__(512) void attn_decode_kernel8(const DecodeAttnParams p) {
   attn_decode_body<DP, F8, true, 8, PRE>(p, blockIdx.x, blockIdx.y, blockIdx.z);
+}
+// the same three workgroup forms over the private suffix of rows with shared prefix pages (SP)
+template <int DP, bool F8>
+__global__ __launch_bounds__(256) void attn_decode_sp_kernel(const DecodeAttnParams p) {
+  attn_decode_body<DP, F8, true, 4, false, true>(p, blockIdx.x, blockIdx.y, blockIdx.z);
+}
+template <int DP, bool F8>
+__global__ __launch_bounds__(512) void attn_decode_sp_kernel8(const DecodeAttnParams p) {
+  attn_decode_body<DP, F8, true, 8, false, true>(p, blockIdx.x, blockIdx.y, blockIdx.z);
+}
+template <int DP, bool F8>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void attn_decode_sp_kernel_np(
+    const DecodeAttnParams p) {
+  attn_decode_body<DP, F8, false, 4, false, true>(p, blockIdx.x, blockIdx.y, blockIdx.z);
 }
 // many-split long contexts: 3 workgroups per CU (occupancy, not per-wave latency, is what they need)
 template <int DP, bool F8>
@@ -1138,6 +1078,7 @@ static int attn_o_ks(const DecodeAttnParams& p) { return (p.Hq / p.Hkv) * p.hd /
 
 bool attn_o_supported(const DecodeAttnParams& p, const AttnOParams& o) {
   const int G = p.Hq / p.Hkv;
+  if (p.kv_begin) return false;   // shared prefixes: the workgroup forms only
   if (p.M < 1 || p.M > 4 || p.Dp != 128 || p.hd != 128 || p.ssq || p.n_split != 1) return false;
   if (G * p.hd % 256 || attn_o_ks(p) != 2 || o.ntiles % kAttnOTpw) return false;
   if (o.ptype != P_Q4_K && o.ptype != P_Q6_K && o.ptype != P_Q8_0) return false;
@@ -1164,6 +1105,7 @@ void launch_attn_o(const DecodeAttnParams& p_in, const AttnOParams& o, hipStream
 }
 
 bool attn_decode_wave_selected(const DecodeAttnParams& p) {
+  if (p.kv_begin) return false;   // shared prefixes: the workgroup forms only
   const int mode = knob(KNOB_ATTN_WAVE);   // 0 off, 1 on, 2 auto
   if (mode == 0) return false;
   if (mode == 1) return true;
@@ -1171,7 +1113,7 @@ bool attn_decode_wave_selected(const DecodeAttnParams& p) {
 }
 
 bool attn_decode_pre_ok(const DecodeAttnParams& p) {
-  return !attn_decode_wave_selected(p) && p.n_split == 1 && p.M * p.Hkv <= knob(KNOB_ATTN_PF_MAXWG) && !p.ssq &&
+  return !p.kv_begin && !attn_decode_wave_selected(p) && p.n_split == 1 && p.M * p.Hkv <= knob(KNOB_ATTN_PF_MAXWG) && !p.ssq &&
          (p.Dp == 128 || p.Dp == 64);
 }
 
@@ -1199,9 +1141,34 @@ AttnDecodeForm attn_decode_form(const DecodeAttnParams& p) {
   return ATTN_FORM_NP;
 }
 
+// the workgroup forms over the suffix [kv_begin, pos] with the prefix partials in the merge
+template <bool F8>
+static void attn_decode_sp(const DecodeAttnParams& p, AttnDecodeForm form, hipStream_t st) {
+  const dim3 grid(p.M, p.Hkv, p.n_split);
+  if (form == ATTN_FORM_PF8) {
+    if (p.Dp == 128) hipLaunchKernelGGL((mpk::attn_decode_sp_kernel8<128, F8>), grid, dim3(512), 0, st, p);
+    else hipLaunchKernelGGL((mpk::attn_decode_sp_kernel8<64, F8>), grid, dim3(512), 0, st, p);
+  } else if (form == ATTN_FORM_PF4) {
+    if (p.Dp == 128) hipLaunchKernelGGL((mpk::attn_decode_sp_kernel<128, F8>), grid, dim3(256), 0, st, p);
+    else hipLaunchKernelGGL((mpk::attn_decode_sp_kernel<64, F8>), grid, dim3(256), 0, st, p);
+  } else {
+    if (p.Dp == 128) hipLaunchKernelGGL((mpk::attn_decode_sp_kernel_np<128, F8>), grid, dim3(256), 0, st, p);
+    else hipLaunchKernelGGL((mpk::attn_decode_sp_kernel_np<64, F8>), grid, dim3(256), 0, st, p);
+  }
+}
+
 void launch_attn_decode(const DecodeAttnParams& p_in, hipStream_t st) {
   DecodeAttnParams p = p_in;
   v_strides_or_legacy(p.v_kb, p.v_d);
+  if (p.kv_begin || p.pfx_row || p.pfx_o || p.pfx_ml || p.n_psplit) {
+    if (!p.kv_begin || !p.pfx_row || !p.pfx_o || !p.pfx_ml || p.n_psplit < 1)
+      throw std::runtime_error("launch_attn_decode: kv_begin, pfx_row, pfx_o, pfx_ml and n_psplit go together");
+    if (p.pre) throw std::runtime_error("launch_attn_decode: pre and shared prefixes (kv_begin) exclude each other");
+    if (p.n_split + p.n_psplit > mpk::ATTN_MAX_SPLITS)
+      throw std::runtime_error("launch_attn_decode: n_split + n_psplit exceeds the merge's 128 entries");
+    const AttnDecodeForm form = attn_decode_form(p);
+    return p.kv_fp8 ? attn_decode_sp<true>(p, form, st) : attn_decode_sp<false>(p, form, st);
+  }
   // q rotated and K / V appended by the qkv GEMV (gemvs QkvAppend): the prefetch forms only
   if (p.pre && !attn_decode_pre_ok(p))
     throw std::runtime_error("launch_attn_decode: pre-appended inputs need the one-split kernel");

@@ -718,6 +718,58 @@ int mp_op_attn_decode(const void* qkv, int ldqkv, const void* pos, const void* s
   API_CATCH(-1)
 }
 
+// Shared prompt prefixes at op level: the prefix phase (attn_shared.hip) and the decode step over
+// the rows' private suffixes that merges its partials.  kv_begin / pfx_row [M]; pfx_o
+// [n_psplit][M * Hq][Dp], pfx_ml [n_psplit][M * Hq][2]; groups [max_groups] SharedAttnGroup records
+// and rows [<= M] on the device (the caller checked them against M, max_pages and the slot count).
+static void shared_attn_fields(DecodeAttnParams& p, const void* kv_begin, const void* pfx_row, void* pfx_o,
+                               void* pfx_ml, int n_psplit) {
+  if (!kv_begin || !pfx_row || !pfx_o || !pfx_ml || n_psplit < 1)
+    throw std::runtime_error("attn_shared: kv_begin, pfx_row, pfx_o, pfx_ml, n_psplit");
+  p.kv_begin = (const int32_t*)kv_begin; p.pfx_row = (const int32_t*)pfx_row;
+  p.pfx_o = (float*)pfx_o; p.pfx_ml = (float*)pfx_ml; p.n_psplit = n_psplit;
+}
+
+int mp_op_attn_decode_shared(const void* qkv, int ldqkv, const void* pos, const void* slot, int slot0,
+                             const void* block_table, int max_pages, const void* rope_cs, float q_scale, void* k_cache,
+                             void* v_cache, int M, int Hq, int Hkv, int hd, int Dp, int split_len, int n_split,
+                             void* o_part, void* ml_part, void* counters, void* out, int ldo, const void* ssq, float eps,
+                             int d_model, const void* bias, int kv_fp8, const void* kv_begin, const void* pfx_row,
+                             void* pfx_o, void* pfx_ml, int n_psplit, void* stream) {
+  API_TRY
+  DecodeAttnParams p = decode_attn_args(qkv, ldqkv, pos, slot, slot0, block_table, max_pages, rope_cs, q_scale, k_cache,
+                                        v_cache, M, Hq, Hkv, hd, Dp, split_len, n_split, o_part, ml_part, counters,
+                                        out, ldo, ssq, eps, d_model, bias, kv_fp8, 0);
+  if (!o_part || !ml_part) throw std::runtime_error("attn_decode: split partials (rows with a prefix always merge)");
+  shared_attn_fields(p, kv_begin, pfx_row, pfx_o, pfx_ml, n_psplit);
+  launch_attn_decode(p, (hipStream_t)stream);
+  HIP_OK(hipGetLastError());
+  return 0;
+  API_CATCH(-1)
+}
+
+int mp_op_attn_shared(const void* qkv, int ldqkv, const void* pos, const void* block_table, int max_pages,
+                      const void* rope_cs, float q_scale, void* k_cache, void* v_cache, int M, int Hq, int Hkv, int hd,
+                      int Dp, const void* ssq, float eps, int d_model, const void* bias, int kv_fp8,
+                      const void* pfx_row, void* pfx_o, void* pfx_ml, int n_psplit, const void* groups,
+                      const void* rows, int max_groups, void* stream) {
+  API_TRY
+  SharedAttnParams sp{};
+  DecodeAttnParams& p = sp.d;
+  p.qkv = (const float*)qkv; p.ldqkv = ldqkv; p.pos = (const int32_t*)pos; p.block_table = (const int32_t*)block_table;
+  p.max_pages = max_pages; p.rope_cs = (const float2*)rope_cs; p.q_scale = q_scale;
+  p.k_cache = (f16*)k_cache; p.v_cache = (f16*)v_cache; p.M = M; p.Hq = Hq; p.Hkv = Hkv; p.hd = hd; p.Dp = Dp;
+  p.ssq = (const float*)ssq; p.eps = eps; p.d_model = d_model; p.bias = (const float*)bias; p.kv_fp8 = kv_fp8 ? 1 : 0;
+  p.pfx_row = (const int32_t*)pfx_row; p.pfx_o = (float*)pfx_o; p.pfx_ml = (float*)pfx_ml; p.n_psplit = n_psplit;
+  if (Hkv >= 1 && (ldqkv < (Hq + 2 * Hkv) * hd || ldqkv % 4)) throw std::runtime_error("attn_shared: ldqkv");
+  op_v_strides(Dp, p.v_kb, p.v_d);
+  sp.groups = (const SharedAttnGroup*)groups; sp.rows = (const int32_t*)rows; sp.max_groups = max_groups;
+  launch_attn_shared(sp, (hipStream_t)stream);
+  HIP_OK(hipGetLastError());
+  return 0;
+  API_CATCH(-1)
+}
+
 // attention + o-projection in one launch: Y [M][ldy] += attn [M][Hq * hd] . W_o^T (W T16-packed)
 int mp_op_attn_o(const void* qkv, int ldqkv, const void* pos, const void* slot, int slot0, const void* block_table,
                  int max_pages, const void* rope_cs, float q_scale, void* k_cache, void* v_cache, int M, int Hq,
@@ -1282,6 +1334,38 @@ int mp_kvpager_shift(int n_slots, int max_pages, int n_pages, const int32_t* tok
   if (n_free) *n_free = (int32_t)fl.size();
   if (free_out) std::copy(fl.rbegin(), fl.rend(), free_out);
   return pg.owned(slot);
+  API_CATCH(-1)
+}
+// A script of KvPager calls on a fresh pager (host only; the unit-test hook for shared pages).
+// ops [n_ops][4] = (op, a, b, c): 0 ensure(slot a, b tokens), 1 share(dst a, src b, c pages),
+// 2 release(slot a), 3 shift(slot a, keep b, discard c), 4 grant(slot a, first position b, c tokens).
+// Out: the table, the free list in the order the next grants take its pages ([n_pages] room),
+// shared_pages per slot.  Returns the pool-wide count of shared pages; a throwing call -> -1.
+int mp_kvpager_script(int n_slots, int max_pages, int n_pages, const int32_t* ops, int n_ops, int32_t* table_out,
+                      int32_t* free_out, int32_t* n_free, int32_t* shared_out) {
+  API_TRY
+  KvPager pg;
+  pg.init(n_slots, max_pages, n_pages);
+  for (int i = 0; i < n_ops; ++i) {
+    const int32_t* o = ops + 4 * i;
+    bool ok = true;
+    switch (o[0]) {
+      case 0: ok = pg.ensure(o[1], o[2]); break;
+      case 1: pg.share(o[1], o[2], o[3]); break;
+      case 2: pg.release(o[1]); break;
+      case 3: pg.shift(o[1], o[2], o[3]); break;
+      case 4: ok = pg.grant(o[1], o[2], o[3]); break;
+      default: throw std::runtime_error("kvpager_script: unknown op");
+    }
+    if (!ok) throw std::runtime_error("kvpager_script: pool exhausted at op " + std::to_string(i));
+  }
+  if (table_out) std::copy(pg.table().begin(), pg.table().end(), table_out);
+  const std::vector<int32_t>& fl = pg.free_list();
+  if (n_free) *n_free = (int32_t)fl.size();
+  if (free_out) std::copy(fl.rbegin(), fl.rend(), free_out);
+  if (shared_out)
+    for (int s = 0; s < n_slots; ++s) shared_out[s] = pg.shared_pages(s);
+  return pg.shared_total();
   API_CATCH(-1)
 }
 int mp_engine_release(void* h, int slot) {

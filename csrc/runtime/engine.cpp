@@ -436,6 +436,19 @@ Engine::Engine(const Json& j) : jcfg_(j) {
   if (auto_shift_) check_shift_supported("\"context_shift\"");
   packed_prefill_ = j.get_bool("packed_prefill", true);
   prefix_cache_ = j.get_bool("prefix_cache", true);
+  shared_prefix_ = j.get_bool("shared_prefix", false);
+  if (shared_prefix_) {
+    const std::string o = "\"shared_prefix\": ";
+    if (auto_shift_) throw std::runtime_error(o + "\"context_shift\" is not supported (a shift would move shared pages)");
+    if (!prefix_cache_) throw std::runtime_error(o + "\"prefix_cache\": false contradicts it");
+    if (mode_ == "mp") throw std::runtime_error(o + "mode \"mp\" is not supported");
+    if (j.get_int("world", 1) > 1) throw std::runtime_error(o + "a multi-process ring (\"world\" > 1) is not supported");
+    if (j.has("rpc")) throw std::runtime_error(o + "rpc workers (\"rpc\") are not supported");
+    for (int s = 0; s < S_; ++s)
+      if (stage_cpu(s))
+        throw std::runtime_error(o + "stage " + std::to_string(s) + " is a CPU stage (\"backend\": \"cpu\" / \"gpu_layers\"), which does not page its KV");
+    so.shared_prefix = true;
+  }
   n_probs_ = j.get_int("n_probs", 0);
   if (n_probs_ < -1 || n_probs_ > Stage::kMaxProbs)
     throw std::runtime_error("n_probs must be -1 (chosen token only) or 0.." + std::to_string(Stage::kMaxProbs));
@@ -1063,6 +1076,8 @@ Json Engine::health() const {
   j["ok"] = !failed_;
   j["backend"] = cpu_ ? "cpu" : hybrid_ ? "hybrid" : "hip";
   j["prefix_reused_tokens"] = (int64_t)reused_tokens_;
+  j["kv_shared_pages"] = pager_.shared_total();
+  j["shared_prefix_skipped_tokens"] = (int64_t)shared_skipped_;
   j["context_shifts"] = (int64_t)context_shifts_;
   if (failed_stage_ >= 0) {
     j["failed_stage"] = failed_stage_;
@@ -1246,10 +1261,11 @@ void Engine::start(const std::vector<std::vector<int32_t>>& prompts) {
   reset_slots(n);
   resumable_ = true;
   // KV pages: each prompt + its first decode position; slots without a prompt give theirs back
-  // (a reused prefix keeps the pages it already owns)
+  // (a reused prefix keeps the pages it already owns; "shared_prefix": share_prefixes grants below,
+  // once it knows which leading pages a prompt takes from a donor, so the pool only has to hold the tails)
   for (size_t i = n; i < slots_.size(); ++i) pager_.release((int)i);
-  for (size_t i = 0; i < n; ++i)
-    if (!prompts[i].empty() && (int)prompts[i].size() < max_ctx_) kv_grant(i, (int)prompts[i].size() + 1);
+  for (size_t i = 0; i < n && !shared_prefix_; ++i)
+    if (!prompts[i].empty() && (int)prompts[i].size() < max_ctx_) kv_grant(i, 0, (int)prompts[i].size() + 1);
   kv_sync();
   clear_masks(false);   // (before the admissions: what is pending for them becomes live here)
   clear_bindings(false);
@@ -1264,6 +1280,7 @@ void Engine::start(const std::vector<std::vector<int32_t>>& prompts) {
       if (prompts[i].empty() || (int)prompts[i].size() >= max_ctx_) throw std::runtime_error("bad prompt length");
       upload_tokens(i, 0, prompts[i].data(), prompts[i].size());
     }
+  if (shared_prefix_) share_prefixes(seqs);
   const std::vector<Item> items = prefill_items(seqs, false);
   forget_kv_toks();   // KV content unknown until this prefill has completed
   run_all(items);
@@ -1730,7 +1747,7 @@ Json Engine::load_state(const std::string& dir) {
   // KV pages for the restored sequences (their KV bytes are imported page by page below)
   for (int i = 0; i < M_ * B_; ++i) pager_.release(i);
   for (size_t i = 0; i < n; ++i)
-    if (slots_[i].active) kv_grant(i, slot_pos(i) + 1);
+    if (slots_[i].active) kv_grant(i, 0, slot_pos(i) + 1);
   kv_sync();
   for (auto& wp : workers_) {
     Stage& st = *wp->stage;
@@ -1994,12 +2011,70 @@ void Engine::context_shift(const std::vector<int>& slots, const std::vector<int>
     if (mbs[mb]) push_positions(mb);
 }
 
-void Engine::kv_grant(size_t slot, int n_tokens) {
-  if (pager_.ensure((int)slot, n_tokens)) return;
+void Engine::kv_restart(size_t slot) {
+  if (pager_.shared_pages((int)slot) > 0) pager_.release((int)slot);
+}
+
+void Engine::kv_grant(size_t slot, int first_pos, int n_tokens) {
+  if (pager_.grant((int)slot, first_pos, n_tokens)) return;
   throw std::runtime_error("KV page pool exhausted: slot " + std::to_string(slot) + " needs " +
                            std::to_string((n_tokens + 63) / 64) + " pages, owns " +
                            std::to_string(pager_.owned((int)slot)) + ", " + std::to_string(pager_.free_pages()) +
                            " of " + std::to_string(pager_.n_pages()) + " free (kv_pool_tokens / max_ctx auto)");
+}
+
+// "shared_prefix": for each newly admitted slot (ascending, so a donor of the same batch comes first
+// and its prefill runs first: chunks go through every stage in this order), the live slot or earlier
+// slot of this batch whose KV tokens share the longest prefix with its prompt, in whole pages and
+// leaving at least one token to prefill.  If that beats the slot's own prefix cache the slot gives
+// its pages back, takes the donor's leading pages and records their tokens as its kv_toks, so
+// prefill_items prefills only the tail.  Same eligibility as the per-slot cache: same adapter
+// binding, not mixed, not shifted.  Ends with the host check of the sharing invariant.
+void Engine::share_prefixes(const std::vector<size_t>& seqs_in) {
+  std::vector<size_t> seqs = seqs_in;
+  std::sort(seqs.begin(), seqs.end());
+  std::vector<char> in_batch(slots_.size(), 0), done(slots_.size(), 0);
+  for (size_t i : seqs) in_batch[i] = 1;
+  auto common = [](const std::vector<int32_t>& a, const std::vector<int32_t>& b) {
+    size_t n = 0;
+    while (n < a.size() && n < b.size() && a[n] == b[n]) ++n;
+    return n;
+  };
+  for (size_t i : seqs) {
+    Slot& s = slots_[i];
+    const int n = (int)s.prompt.size();
+    const KvTag now = bind_tag(i);
+    const bool same_bind = s.kv_tag.serial == now.serial && s.kv_tag.scale == now.scale;
+    // (a slot released since the last round still lists the tokens of pages it gave back)
+    s.kv_toks.resize(std::min(s.kv_toks.size(), (size_t)pager_.owned((int)i) * 64));
+    const int own =same_bind ? (int)std::min(common(s.kv_toks, s.prompt), (size_t)n - 1) : 0;
+    int best = 0, donor = -1;
+    for (size_t j = 0; j < slots_.size(); ++j) {
+      const Slot& d = slots_[j];
+      if (j == i || !d.active || d.n_shifts > 0 || (in_batch[j] && !done[j])) continue;
+      const KvTag dt = in_batch[j] ? bind_tag(j) : d.kv_tag;
+      if (dt.serial != now.serial || dt.scale != now.scale || dt.serial == kMixedTag) continue;
+      const std::vector<int32_t>& toks = in_batch[j] ? d.prompt : d.kv_toks;
+      const int pages = std::min({(int)common(toks, s.prompt), n - 1, pager_.owned((int)j) * 64}) / 64;
+      if (pages > best) { best = pages; donor = (int)j; }
+    }
+    int first = own;   // where prefill_items starts this slot's prefill
+    if (donor >= 0 && best * 64 > own) {
+      pager_.release((int)i);
+      pager_.share((int)i, donor, best);
+      s.kv_toks.assign(s.prompt.begin(), s.prompt.begin() + best * 64);
+      s.kv_tag = now;
+      shared_skipped_ += best * 64 - own;
+      first = best * 64;
+    } else if (own < pager_.write_floor((int)i)) {   // pages left from an earlier sequence that others still read
+      pager_.release((int)i);
+      s.kv_toks.clear();
+      first = 0;
+    }
+    kv_grant(i, first, n + 1);   // the tail it prefills + one decode position, all in private pages
+    done[i] = 1;
+  }
+  kv_sync();
 }
 
 void Engine::kv_sync() {
@@ -2020,7 +2095,7 @@ void Engine::admit(const std::vector<int>& slots, const std::vector<std::vector<
     if (!slot_in_range(i)) throw std::runtime_error("admit: bad slot");
     if (slots_[i].active) throw std::runtime_error("admit: slot " + std::to_string(i) + " is busy");
     if (prompts[k].empty() || (int)prompts[k].size() >= max_ctx_) throw std::runtime_error("bad prompt length");
-    kv_grant((size_t)i, (int)prompts[k].size() + 1);
+    if (!shared_prefix_) kv_grant((size_t)i, 0, (int)prompts[k].size() + 1);   // (else: share_prefixes, below)
     begin_sequence((size_t)i, prompts[k]);
     seqs.push_back((size_t)i);
     mbs[i / B_] = 1;
@@ -2030,6 +2105,7 @@ void Engine::admit(const std::vector<int>& slots, const std::vector<std::vector<
   for (size_t i : seqs) upload_tokens(i, 0, slots_[i].prompt.data(), slots_[i].prompt.size());
   for (int mb = 0; mb < M_; ++mb)
     if (mbs[mb]) push_positions(mb);
+  if (shared_prefix_) share_prefixes(seqs);
   std::vector<Item> items = prefill_items(seqs, true);
   forget_kv_toks();
   run_all(items);
@@ -2075,11 +2151,12 @@ StepStats Engine::decode_steps(int k) {
     if (s.active) throw std::runtime_error("context capacity exhausted (prompt + generated tokens > max_ctx)");
     s.prompt.clear();
     s.base_round = rounds_done_;
+    kv_restart(i);   // it restarts at 0: not in a page that others read
     push_positions((int)(i / B_));
   }
   // KV pages for the k positions every running sequence is about to write
   for (size_t i = 0; i < slots_.size(); ++i)
-    if (slots_[i].active) kv_grant(i, slot_pos(i) + k + 1);
+    if (slots_[i].active) kv_grant(i, slot_pos(i), slot_pos(i) + k + 1);   // (decode appends land in private pages)
   kv_sync();
   for_each_last_stage([&](Worker& w) {
     if (w.cpu) return w.tok_t.clear();
@@ -2192,8 +2269,9 @@ void Engine::score(const std::vector<std::vector<int32_t>>& prompts, int n_top, 
   forget_kv_toks();
   reset_slots(0);
   for (size_t i = n; i < slots_.size(); ++i) pager_.release((int)i);
+  for (size_t i = 0; i < n; ++i) kv_restart(i);   // every prompt is written from position 0
   for (size_t i = 0; i < n; ++i)
-    if (prompts[i].size() > 1) kv_grant(i, (int)prompts[i].size() - 1);
+    if (prompts[i].size() > 1) kv_grant(i, 0, (int)prompts[i].size() - 1);
   kv_sync();
   for (size_t i = 0; i < n; ++i) upload_tokens(i, 0, prompts[i].data(), prompts[i].size());
   out->assign(n, {});
@@ -2288,7 +2366,8 @@ void Engine::embed(const std::vector<int>& slots, const std::vector<std::vector<
   Worker* wl = last_worker();
   // KV pages for the prompts (all or none: a pool too small for this call leaves the slots as they were)
   try {
-    for (size_t k = 0; k < n; ++k) kv_grant((size_t)slots[k], (int)prompts[k].size());
+    for (size_t k = 0; k < n; ++k) kv_restart((size_t)slots[k]);
+    for (size_t k = 0; k < n; ++k) kv_grant((size_t)slots[k], 0, (int)prompts[k].size());
   } catch (...) {
     for (size_t k = 0; k < n; ++k) pager_.release(slots[k]);
     throw;
@@ -2473,7 +2552,7 @@ Json Engine::spec_generate(const std::vector<std::vector<int32_t>>& prompts, int
         if ((int)d.size() > room) d.resize(std::max(0, room));
         chunk[i].push_back(ctx[i].back());
         chunk[i].insert(chunk[i].end(), d.begin(), d.end());
-        kv_grant(i, pos + (int)chunk[i].size());
+        kv_grant(i, pos, pos + (int)chunk[i].size());
         drafted += (long)d.size();
         upload_tokens(i, pos, chunk[i].data(), chunk[i].size());
         PrefillSeg sg;
@@ -2600,6 +2679,9 @@ Json Engine::info() const {
     j["device_speed"] = ds;
   }
   j["kv_free_pages"] = pager_.free_pages();
+  j["shared_prefix"] = shared_prefix_;
+  j["kv_shared_pages"] = pager_.shared_total();
+  j["shared_prefix_skipped_tokens"] = (int64_t)shared_skipped_;
   j["context_shift"] = auto_shift_;
   j["n_keep"] = n_keep_;
   j["context_shifts"] = (int64_t)context_shifts_;

@@ -400,12 +400,20 @@ class Engine {
   size_t bcast_cap_ = 0;
   bool prefix_cache_ = true;   // Slot::kv_toks
   long reused_tokens_ = 0;
+  // "shared_prefix": a new prompt takes the whole pages of its longest common prefix with a live
+  // slot's KV (KvPager::share) and prefills only its tail
+  bool shared_prefix_ = false;
+  long shared_skipped_ = 0;   // prompt tokens whose prefill sharing skipped
+  void share_prefixes(const std::vector<size_t>& seqs);
   void refresh_slot_cache();
   KvPager pager_;           // paged KV: one logical table, installed on every stage
   int kv_pages_ = 0;         // pool pages per stage
   std::vector<double> device_speed_;   // partitioner weights per stage (given or probed)
   int failed_stage_ = -1;    // stage whose worker raised the fault (health()["failed_stage"])
-  void kv_grant(size_t slot, int n_tokens);   // throws when the pool is exhausted
+  // pages for a write of positions [first_pos, n_tokens) of `slot`: throws when the pool is
+  // exhausted or the write would touch a shared page (every grant before a prefill or decode)
+  void kv_grant(size_t slot, int first_pos, int n_tokens);
+  void kv_restart(size_t slot);   // the slot is rewritten from position 0: shared pages go back first
   void kv_sync();            // push a changed table to the stages (between engine calls)
   // the next decode position: prompt + rounds since the admission - discarded positions
   int slot_pos(size_t i) const {

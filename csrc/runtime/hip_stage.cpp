@@ -541,6 +541,28 @@ void HipStage::alloc_runtime() {
     ml_part_ = (float*)zalloc((size_t)n_split_ * B * Hq * 2 * 4);
   }
   attn_cnt_ = (int32_t*)zalloc((size_t)std::max(B, 16) * Hkv * 4);
+  if (opt_.shared_prefix) {
+    if (!opt_.fused_attn) throw std::runtime_error("\"shared_prefix\" needs the fused decode attention (\"fused_attn\": false contradicts it)");
+    if (B < 2) throw std::runtime_error("\"shared_prefix\" needs \"mb_size\" >= 2 (a group has two rows)");
+    // page splits of the prefix phase: fixed here, the captured launch's grid depends on it; the
+    // decode kernel merges at most 128 partials per (row, kv head)
+    n_psplit_ = attn_shared_splits(1, Hkv, opt_.max_ctx / 64, std::min(8, 128 - n_split_));
+    if (n_psplit_ < 1) throw std::runtime_error("\"shared_prefix\": no room for prefix partials beside the decode splits");
+    pfx_o_ = (float*)zalloc((size_t)n_psplit_ * B * Hq * Dp_ * 4);
+    pfx_ml_ = (float*)zalloc((size_t)n_psplit_ * B * Hq * 2 * 4);
+    if (!o_part_) {   // a row with prefix partials always merges
+      o_part_ = (float*)zalloc((size_t)n_split_ * B * Hq * Dp_ * 4);
+      ml_part_ = (float*)zalloc((size_t)n_split_ * B * Hq * 2 * 4);
+    }
+    for (int mb = 0; mb < NM; ++mb) {
+      SharedMb s;
+      s.groups = (SharedAttnGroup*)zalloc((size_t)(B / 2) * sizeof(SharedAttnGroup));
+      s.rows = (int32_t*)zalloc((size_t)B * 4);
+      s.kv_begin = (int32_t*)zalloc((size_t)B * 4);
+      s.pfx_row = (int32_t*)zalloc((size_t)B * 4);
+      shared_mb_.push_back(s);
+    }
+  }
   if (opt_.prefill_flash && opt_.max_ctx > 256) {   // prefill KV-split partials (attn_prefill.hip)
     pf_opart_ = (float*)zalloc((size_t)kPrefillMaxSplit * opt_.prefill_chunk * Hq * Dp_ * 4);
     pf_ml_ = (float*)zalloc((size_t)kPrefillMaxSplit * opt_.prefill_chunk * Hq * 2 * 4);
@@ -641,6 +663,48 @@ void HipStage::set_block_table(const std::vector<int32_t>& t) {
   HIP_OK(hipStreamSynchronize(stream_));   // no launch may still read the old table
   host_bt_ = t;
   HIP_OK(hipMemcpy(block_table_, host_bt_.data(), host_bt_.size() * 4, hipMemcpyHostToDevice));
+  if (opt_.shared_prefix) build_group_tables();
+}
+
+// shared_prefix: the group table of every micro-batch from the block table just installed.  Rows
+// whose slots name the same first page form a group; its shared run is the leading entries all of
+// them agree on (whole, full pages: KvPager::share), read through the first member's slot.  The
+// captured decode graphs read these arrays from device memory: nothing is re-captured.
+void HipStage::build_group_tables() {
+  const int B = opt_.mb_size;
+  for (int mb = 0; mb < (int)shared_mb_.size(); ++mb) {
+    std::vector<SharedAttnGroup> groups((size_t)B / 2, SharedAttnGroup{0, 0, 0, 0});
+    std::vector<int32_t> rows, kv_begin(B, 0), pfx_row(B, -1);
+    std::vector<char> taken(B, 0);
+    int ng = 0;
+    auto row_of = [&](int b) { return &host_bt_[(size_t)slot_of(mb, b) * max_pages_]; };
+    for (int b = 0; b < B; ++b) {
+      if (taken[b] || row_of(b)[0] == n_pages_) continue;
+      std::vector<int> members{b};
+      int run = max_pages_;
+      for (int c = b + 1; c < B; ++c) {
+        if (taken[c] || row_of(c)[0] != row_of(b)[0]) continue;
+        int k = 0;
+        while (k < run && row_of(c)[k] == row_of(b)[k] && row_of(b)[k] != n_pages_) ++k;
+        run = k;
+        members.push_back(c);
+      }
+      if (members.size() < 2) continue;
+      groups[ng++] = SharedAttnGroup{run, (int32_t)members.size(), (int32_t)rows.size(), slot_of(mb, b)};
+      for (int m : members) {
+        taken[m] = 1;
+        pfx_row[m] = (int32_t)rows.size();
+        kv_begin[m] = 64 * run;
+        rows.push_back(m);
+      }
+    }
+    rows.resize(B, 0);
+    const SharedMb& s = shared_mb_[mb];
+    HIP_OK(hipMemcpy(s.groups, groups.data(), groups.size() * sizeof(SharedAttnGroup), hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(s.rows, rows.data(), (size_t)B * 4, hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(s.kv_begin, kv_begin.data(), (size_t)B * 4, hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(s.pfx_row, pfx_row.data(), (size_t)B * 4, hipMemcpyHostToDevice));
+  }
 }
 
 // Context shift: the new table, then one launch_kv_shift per layer (and per kKvShiftMaxRec records)
@@ -1226,6 +1290,12 @@ DecodeAttnParams HipStage::decode_attn_params(int li, const Fwd& f, bool qkv_def
   dp.hd = cfg_.head_dim; dp.Dp = Dp_; dp.split_len = opt_.attn_split_len; dp.n_split = n_split_;
   dp.o_part = o_part_; dp.ml_part = ml_part_; dp.counters = attn_cnt_; dp.out = attn_; dp.ldo = Ko_;
   if (qkv_deferred) { dp.ssq = ssq_; dp.eps = cfg_.eps; dp.d_model = cfg_.d_model; dp.bias = L.qkv_bias; }
+  // shared_prefix: a whole micro-batch's decode step runs in two phases (any other call reads every
+  // key through the row's own table, shared pages included)
+  if (opt_.shared_prefix && f.decode && f.M == opt_.mb_size && f.slot0 >= 0 && f.slot0 % opt_.mb_size == 0) {
+    const SharedMb& s = shared_mb_[f.slot0 / opt_.mb_size];
+    dp.kv_begin = s.kv_begin; dp.pfx_row = s.pfx_row; dp.pfx_o = pfx_o_; dp.pfx_ml = pfx_ml_; dp.n_psplit = n_psplit_;
+  }
   return dp;
 }
 
@@ -1241,6 +1311,13 @@ void HipStage::attention(int li, const Fwd& f, bool qkv_deferred, bool pre) {
 #ifdef MIPIPE_TIMING_PROBES
     dp.probe = knob(KNOB_ATTN_PROBE);
 #endif
+    if (dp.kv_begin) {   // phase 1: the pages the rows share, once per group
+      SharedAttnParams sp{};
+      sp.d = dp;
+      const SharedMb& s = shared_mb_[f.slot0 / opt_.mb_size];
+      sp.groups = s.groups; sp.rows = s.rows; sp.max_groups = opt_.mb_size / 2;
+      launch_attn_shared(sp, st);
+    }
     launch_attn_decode(dp, st);
   } else {
     RopeKvParams rp{};

@@ -318,6 +318,12 @@ class HipStage : public Stage {
   SkPending sk_pend_;
   float* o_part_ = nullptr; float* ml_part_ = nullptr; int n_split_ = 1;
   int32_t* attn_cnt_ = nullptr;   // fused decode attention: split arrival counters
+  // shared_prefix: per micro-batch the group table attn_shared reads (rebuilt from the block table in
+  // set_block_table, outside the captured graphs) and the prefix partials the decode kernel merges
+  struct SharedMb { SharedAttnGroup* groups = nullptr; int32_t* rows = nullptr; int32_t* kv_begin = nullptr; int32_t* pfx_row = nullptr; };
+  std::vector<SharedMb> shared_mb_;
+  float* pfx_o_ = nullptr; float* pfx_ml_ = nullptr; int n_psplit_ = 0;
+  void build_group_tables();
   // MoE scratch
   float* moe_logits_ = nullptr; int32_t* moe_counts_ = nullptr; int32_t* moe_lists_ = nullptr;
   float* moe_w_ = nullptr; f16* moe_h_ = nullptr;

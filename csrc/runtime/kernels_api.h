@@ -310,8 +310,38 @@ struct DecodeAttnParams {
   int probe = 0;                   // timing probes only (knob ATTN_PROBE): bit 0 skips the global V append,
                                    // bit 1 the K append (results wrong; never in production runs)
   int v_kb = 0, v_d = 0;           // V page strides (0 = legacy)
+  // Shared prompt prefixes (all null / 0: off).  Row t attends keys [kv_begin[t], pos[t]] here (kv_begin a
+  // multiple of 64); a row with pfx_row[t] >= 0 also folds the n_psplit partials attn_shared wrote for the
+  // keys below kv_begin into its final merge: pfx_o [n_psplit][M*Hq][Dp], pfx_ml [n_psplit][M*Hq][2], row
+  // index pfx_row[t] * Hq + h, the exp2-domain (m, l) of o_part / ml_part.  Workgroup forms only.
+  const int32_t* kv_begin = nullptr; const int32_t* pfx_row = nullptr;
+  float* pfx_o = nullptr; float* pfx_ml = nullptr; int n_psplit = 0;
 };
 void launch_attn_decode(const DecodeAttnParams& p, hipStream_t st);
+
+// Attention over a shared prompt prefix (attn_shared.hip): rows of a decode micro-batch whose slots
+// name the same leading KV pages form a group; one workgroup = (group, block of <= 128 query rows,
+// kv head, page split) stages each shared K / V page in LDS once and multiplies it with the G heads
+// of every member row.  Writes unnormalised partials (O, m, l) per (member row, head, page split)
+// for launch_attn_decode to merge (DecodeAttnParams::pfx_*).  The grid is sized from capacities
+// (max_groups, d.M, n_psplit), so a captured launch serves any table contents.
+struct SharedAttnGroup {   // one record per group; n_rows == 0: unused
+  int32_t n_pages;         // shared 64-key pages (>= 1), read through the leader's block-table row
+  int32_t n_rows;          // member rows (>= 2)
+  int32_t row_off;         // first entry of the group's rows in SharedAttnParams::rows
+  int32_t leader;          // slot whose block-table row names the pages
+};
+struct SharedAttnParams {
+  DecodeAttnParams d;              // the decode launch's inputs: qkv, pos, block_table, rope_cs, q_scale, caches,
+                                   // shapes, deferred norm, v strides, pfx_row; d.pfx_o / d.pfx_ml / d.n_psplit
+  const SharedAttnGroup* groups;   // [max_groups]
+  const int32_t* rows;             // [<= d.M] member rows of the micro-batch, group after group
+  int max_groups;
+};
+void launch_attn_shared(const SharedAttnParams& p, hipStream_t st);
+// page splits of the prefix phase for groups of up to max_pages shared pages: enough workgroups to
+// cover the CUs, >= 2 pages per split, at most max_split
+int attn_shared_splits(int n_groups, int Hkv, int max_pages, int max_split);
 // the device form launch_attn_decode takes for p (host only: M, Hkv, n_split and the knobs decide)
 enum AttnDecodeForm {
   ATTN_FORM_PF4 = 0,    // attn_decode_kernel: 4 waves, next-chunk prefetch (one split)

@@ -12,6 +12,13 @@
 // The allocator is deterministic (LIFO free list seeded 0, 1, 2, ...), so every rank of a
 // multi-process pipeline that replays the same engine calls derives the same tables without any
 // exchange.
+//
+// Shared prompt prefixes: every physical page carries a reference count.  share() lets a slot that
+// owns nothing name the leading pages of another slot's row; the pages return to the free list when
+// the last holder releases them.  INVARIANT: only whole 64-token pages are ever shared, shared
+// pages (count > 1) are read-only, and they form a leading run of a slot's row -- every write a
+// sequence makes (decode append, speculative draft, prefill of its tail) lands in a private page,
+// at or above write_floor(slot) = shared_pages(slot) * 64.  check_write() enforces it on the host.
 #pragma once
 #include <cstdint>
 #include <stdexcept>
@@ -31,6 +38,8 @@ class KvPager {
     n_pages_ = n_pages;
     table_.assign((size_t)n_slots * max_pages, n_pages);   // everything -> TRASH
     owned_.assign(n_slots, 0);
+    refs_.assign(n_pages, 0);
+    n_shared_ = 0;
     free_.clear();
     for (int p = n_pages - 1; p >= 0; --p) free_.push_back(p);   // pop_back() yields 0, 1, 2, ...
     dirty_ = true;
@@ -47,6 +56,7 @@ class KvPager {
     if (miss > (int)free_.size()) return false;
     for (int k = owned_[slot]; k < need; ++k) {
       table_[(size_t)slot * max_pages_ + k] = free_.back();
+      refs_[free_.back()] = 1;
       free_.pop_back();
     }
     owned_[slot] = need;
@@ -54,11 +64,55 @@ class KvPager {
     return true;
   }
 
+  // `dst` (owning nothing) takes the first n_pages entries of `src`'s row, read-only; ensure(dst)
+  // then grants private pages after them
+  void share(int dst, int src, int n_pages) {
+    check(dst);
+    check(src);
+    if (dst == src) throw std::runtime_error("KvPager::share: slot " + std::to_string(dst) + " with itself");
+    if (owned_[dst] != 0)
+      throw std::runtime_error("KvPager::share: slot " + std::to_string(dst) + " already owns " +
+                               std::to_string(owned_[dst]) + " pages");
+    if (n_pages < 1 || n_pages > owned_[src])
+      throw std::runtime_error("KvPager::share: " + std::to_string(n_pages) + " pages of the " +
+                               std::to_string(owned_[src]) + " slot " + std::to_string(src) + " owns");
+    for (int k = 0; k < n_pages; ++k) {
+      const int32_t e = table_[(size_t)src * max_pages_ + k];
+      table_[(size_t)dst * max_pages_ + k] = e;
+      if (refs_[e]++ == 1) ++n_shared_;
+    }
+    owned_[dst] = n_pages;
+    dirty_ = true;
+  }
+
+  // length of the leading run of `slot`'s entries that other slots hold too
+  int shared_pages(int slot) const {
+    check(slot);
+    int n = 0;
+    while (n < owned_[slot] && refs_[table_[(size_t)slot * max_pages_ + n]] > 1) ++n;
+    return n;
+  }
+  int write_floor(int slot) const { return shared_pages(slot) * kPage; }
+  // the sharing invariant: a write of `slot` at position first_pos must land in a private page
+  void check_write(int slot, int first_pos) const {
+    const int floor = write_floor(slot);
+    if (first_pos < floor)
+      throw std::runtime_error("KvPager: slot " + std::to_string(slot) + " would write position " +
+                               std::to_string(first_pos) + " into a shared page (private from " +
+                               std::to_string(floor) + ")");
+  }
+  // ensure() for a write of positions [first_pos, n_tokens): throws where it would touch a shared page
+  bool grant(int slot, int first_pos, int n_tokens) {
+    check_write(slot, first_pos);
+    return ensure(slot, n_tokens);
+  }
+  int shared_total() const { return n_shared_; }   // pool-wide: pages with count > 1
+
   void release(int slot) {
     check(slot);
     for (int k = owned_[slot] - 1; k >= 0; --k) {
       int32_t& e = table_[(size_t)slot * max_pages_ + k];
-      free_.push_back(e);
+      unref(e);
       e = n_pages_;
     }
     if (owned_[slot]) dirty_ = true;
@@ -83,10 +137,13 @@ class KvPager {
       throw std::runtime_error("KvPager::shift: n_keep + n_discard exceeds the " + std::to_string(owned_[slot]) +
                                " pages slot " + std::to_string(slot) + " owns");
     int32_t* row = &table_[(size_t)slot * max_pages_];
+    for (int k = 0; k < owned_[slot]; ++k)
+      if (refs_[row[k]] > 1)
+        throw std::runtime_error("KvPager::shift: slot " + std::to_string(slot) + " holds shared pages");
     const int nd = n_discard / kPage, r0 = n_keep % kPage;
     const int first = n_keep / kPage + (r0 ? 1 : 0);   // first entry that leaves the row
     const int merge = r0 ? row[first + nd - 1] : -1;
-    for (int k = first + nd - 1; k >= first; --k) free_.push_back(row[k]);
+    for (int k = first + nd - 1; k >= first; --k) unref(row[k]);
     for (int k = first + nd; k < owned_[slot]; ++k) row[k - nd] = row[k];
     for (int k = owned_[slot] - nd; k < owned_[slot]; ++k) row[k] = n_pages_;
     owned_[slot] -= nd;
@@ -108,9 +165,15 @@ class KvPager {
   void check(int slot) const {
     if (slot < 0 || slot >= n_slots_) throw std::runtime_error("KvPager: bad slot " + std::to_string(slot));
   }
-  int n_slots_ = 0, max_pages_ = 0, n_pages_ = 0;
+  // one holder less; the last one returns the page to the free list
+  void unref(int32_t page) {
+    const int left = --refs_[page];
+    if (left == 1) --n_shared_;
+    if (left == 0) free_.push_back(page);
+  }
+  int n_slots_ = 0, max_pages_ = 0, n_pages_ = 0, n_shared_ = 0;
   std::vector<int32_t> table_, free_;
-  std::vector<int> owned_;
+  std::vector<int> owned_, refs_;
   bool dirty_ = false;
 };
 

@@ -128,6 +128,9 @@ inline void print_common_usage(FILE* f) {
           "  --context-shift           when a sequence fills the context (-c), drop half of what follows the first\n"
           "                            --keep tokens of its prompt (in whole 64-token pages) and go on generating:\n"
           "                            -n is no longer capped by -c.  --no-context-shift (default): it ends there\n"
+          "  --shared-prefix           prompts that begin with the tokens a running sequence already holds share its\n"
+          "                            whole 64-token KV pages and prefill only their tail; decode reads the shared\n"
+          "                            pages once per group of rows.  Not with --context-shift, --world, --rpc or CPU stages\n"
           "  --keep N                  prompt tokens a context shift keeps (default 0; -1: the whole prompt)\n"
           "  --draft-max K             speculative decoding by prompt lookup: up to K drafted tokens per\n"
           "                            verify round (greedy; --lookup-ngram N, default 3)\n"
@@ -200,6 +203,7 @@ inline CliOptions parse_cli(int argc, char** argv,
     else if (a == "--prefill-chunk" || a == "-ub" || a == "--ubatch-size") e["prefill_chunk"] = std::atoi(val().c_str());
     else if (a == "--no-graphs") e["graphs"] = false;
     else if (a == "--draft-max" || a == "--draft") e["draft_max"] = std::atoi(val().c_str());   // prompt-lookup speculation
+    else if (a == "--shared-prefix") e["shared_prefix"] = true;
     else if (a == "--context-shift") e["context_shift"] = true;
     else if (a == "--no-context-shift") e["context_shift"] = false;
     else if (a == "--keep") e["n_keep"] = std::atoi(val().c_str());

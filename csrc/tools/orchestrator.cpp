@@ -1393,6 +1393,11 @@ void handle_metrics(Server& S, int fd) {
       }
     snprintf(b, sizeof(b), "# TYPE mipipe_engine_ok gauge\nmipipe_engine_ok %d\n", h.get_bool("ok", false) ? 1 : 0);
     m += b;
+    snprintf(b, sizeof(b),
+             "# TYPE mipipe_kv_shared_pages gauge\nmipipe_kv_shared_pages %lld\n"
+             "# TYPE mipipe_shared_prefix_skipped_tokens_total counter\nmipipe_shared_prefix_skipped_tokens_total %lld\n",
+             (long long)h.get_num("kv_shared_pages", 0), (long long)h.get_num("shared_prefix_skipped_tokens", 0));
+    m += b;
   }
   respond(fd, 200, "text/plain; version=0.0.4", m);
 }

@@ -93,6 +93,14 @@ _SIGS = {
                       c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
                       c_void_p, c_int, c_void_p, c_float, c_int, c_void_p, c_int, c_int,
                       c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p], c_int),
+    "mp_op_attn_decode_shared": ([c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_float,
+                                  c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p,
+                                  c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_float, c_int, c_void_p, c_int,
+                                  c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p], c_int),
+    "mp_op_attn_shared": ([c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_float, c_void_p, c_void_p, c_int,
+                           c_int, c_int, c_int, c_int, c_void_p, c_float, c_int, c_void_p, c_int, c_void_p, c_void_p,
+                           c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p], c_int),
+    "mp_kvpager_script": ([c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p], c_int),
     "mp_attn_decode_form": ([c_int, c_int, c_int], c_int),
     "mp_op_v_layout": ([c_int], c_int),
     "mp_op_gemvs_qkv": ([c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p,

@@ -18,7 +18,9 @@ chosen token's only, 1..20 plus that many alternatives; read with logprobs()), r
 sampling: every sequence slot has its own record, see set_slot_sampling), row_masks (a token mask per
 sequence slot for constrained output, see set_slot_masks and mipipe.grammar; switches row_sampling on),
 lora_adapters (LoRA adapter capacity, 0 off, at most 8; see load_adapter / set_slot_adapters) and
-lora_max_rank (largest rank of an adapter tensor pair, default 64, at most 128), context_shift (default
+lora_max_rank (largest rank of an adapter tensor pair, default 64, at most 128), shared_prefix (default
+false: prompts that begin with tokens a running slot already holds share its whole KV pages, see
+docs/USAGE.md --shared-prefix), context_shift (default
 False: a sequence that fills max_ctx ends; True: decode() / generate() first drop half of what follows the
 first n_keep prompt tokens, in whole 64-token pages, and go on, see context_shift) and n_keep (default 0;
 -1: the whole prompt).
@@ -234,7 +236,9 @@ class Engine:
     def kv_stats(self):
         """Live paged-KV numbers: pool pages, free pages (the `info` dict is a load-time snapshot)."""
         j = N.jcall(N.lib().mp_engine_info, self._h, what="engine info")
-        return {"kv_pages": j["kv_pages"], "kv_free_pages": j["kv_free_pages"]}
+        return {"kv_pages": j["kv_pages"], "kv_free_pages": j["kv_free_pages"],
+                "kv_shared_pages": j["kv_shared_pages"],   # Engine(shared_prefix=True): pages several slots read
+                "shared_prefix_skipped_tokens": j["shared_prefix_skipped_tokens"]}
 
     def context_shift(self, slots, n_keep, n_discard):
         """Context shift, between decode() calls: for each running slot slots[i], the cached positions

@@ -861,3 +861,62 @@ def attn_o(w: PackedWeight, y, qkv, pos, block_table, rope_cs, k_cache, v_cache,
     N.check(N.lib().mp_op_attn_o(*a, _ptr(w.dev), w.ptype, w.ntiles, w.nsb, _ptr(y), y.stride(0), w.n, _stream()),
             "attn_o")
     return y
+
+
+class SharedAttnTable:
+    """The group table of a decode micro-batch with shared prefix pages, as the engine uploads it
+    before a round: groups = [(leader_slot, n_pages, [member rows])], each with >= 2 rows of the
+    micro-batch (row t in slot slots[t]) and >= 1 shared page.  Holds the device arrays
+    attn_shared / attn_decode take, and the prefix partial buffers (poisoned with NaN)."""
+
+    def __init__(self, M, Hq, Dp, n_psplit, groups, slots, block_table, max_groups=None, device="cuda"):
+        max_groups = max(M // 2, 1) if max_groups is None else max_groups
+        bt = block_table.cpu()
+        assert 1 <= len(groups) <= max_groups and n_psplit >= 1
+        rec = np.zeros((max_groups, 4), dtype=np.int32)
+        rows, kv_begin, pfx_row = [], np.zeros(M, np.int32), np.full(M, -1, np.int32)
+        for i, (leader, n_pages, members) in enumerate(groups):
+            assert len(members) >= 2 and 1 <= n_pages <= bt.shape[1] and 0 <= leader < bt.shape[0]
+            rec[i] = (n_pages, len(members), len(rows), leader)
+            for t in members:
+                assert 0 <= t < M and pfx_row[t] < 0, "a row belongs to one group"
+                assert torch.equal(bt[slots[t], :n_pages], bt[leader, :n_pages]), "members share the leader's pages"
+                pfx_row[t] = len(rows)
+                kv_begin[t] = 64 * n_pages
+                rows.append(t)
+        dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)
+        self.n_psplit, self.max_groups = n_psplit, max_groups
+        self.groups, self.rows = dev(rec), dev(np.array(rows + [0] * (M - len(rows)), np.int32))
+        self.kv_begin, self.pfx_row = dev(kv_begin), dev(pfx_row)
+        self.pfx_o = torch.full((n_psplit, M * Hq, Dp), float("nan"), dtype=torch.float32, device=device)
+        self.pfx_ml = torch.full((n_psplit, M * Hq, 2), float("nan"), dtype=torch.float32, device=device)
+
+
+def attn_shared(qkv, pos, block_table, rope_cs, k_cache, v_cache, Hq, Hkv, hd, Dp, q_scale, table: SharedAttnTable, *,
+                ssq=None, eps=0.0, d_model=0, bias=None, kv_fp8=False) -> None:
+    """The prefix phase of decode attention over shared prompt pages (attn_shared.hip): the same
+    inputs as attn_decode; writes table.pfx_o / table.pfx_ml for the attn_decode(shared=table) that
+    follows on the stream."""
+    assert qkv.dtype == torch.float32 and qkv.stride(1) == 1 and pos.dtype == torch.int32
+    assert block_table.dtype == torch.int32 and block_table.is_contiguous() and rope_cs.is_contiguous()
+    assert k_cache.dtype == v_cache.dtype == (torch.uint8 if kv_fp8 else torch.float16)
+    N.check(N.lib().mp_op_attn_shared(_ptr(qkv), qkv.stride(0), _ptr(pos), _ptr(block_table), block_table.shape[1],
+                                      _ptr(rope_cs), q_scale, _ptr(k_cache), _ptr(v_cache), qkv.shape[0], Hq, Hkv, hd,
+                                      Dp, _ptr(ssq), eps, d_model, _ptr(bias), int(kv_fp8), _ptr(table.pfx_row),
+                                      _ptr(table.pfx_o), _ptr(table.pfx_ml), table.n_psplit, _ptr(table.groups),
+                                      _ptr(table.rows), table.max_groups, _stream()), "attn_shared")
+
+
+def attn_decode_shared(qkv, pos, block_table, rope_cs, k_cache, v_cache, Hq, Hkv, hd, Dp, q_scale, split_len, n_split,
+                       scratch, table: SharedAttnTable, *, slot=None, slot0=None, ssq=None, eps=0.0, d_model=0,
+                       bias=None, kv_fp8=False, out=None):
+    """attn_decode over the rows' private suffixes [kv_begin, pos] (the workgroup forms), its merge
+    folding in the prefix partials attn_shared left in `table`."""
+    M = qkv.shape[0]
+    if out is None:
+        out = torch.zeros(M, Hq * hd, dtype=torch.float16, device=qkv.device)
+    a = _decode_attn_args(qkv, pos, block_table, rope_cs, k_cache, v_cache, Hq, Hkv, hd, Dp, q_scale, split_len,
+                          n_split, scratch, out, slot, slot0, ssq, eps, d_model, bias, kv_fp8, False)[:-1]
+    N.check(N.lib().mp_op_attn_decode_shared(*a, _ptr(table.kv_begin), _ptr(table.pfx_row), _ptr(table.pfx_o),
+                                             _ptr(table.pfx_ml), table.n_psplit, _stream()), "attn_decode_shared")
+    return out
