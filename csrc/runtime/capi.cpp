@@ -165,6 +165,7 @@ const char* mp_model_config_json(const char* gguf_path) {
   j["qk_norm"] = c.qk_norm;
   j["expert_ff"] = c.expert_ff;
   j["pooling_type"] = c.pooling_type;
+  j["causal_attn"] = c.causal_attn;
   g_str = j.dump();
   return g_str.c_str();
   API_CATCH(nullptr)
@@ -660,6 +661,40 @@ int mp_op_attn_prefill(const void* q, const void* pos, const void* slot, const v
       p.tiles[p.n_tiles++] = (uint32_t)(segs[2 * s] + r) | ((uint32_t)std::min(bt, segs[2 * s + 1] - r) << 16);
     }
   launch_attn_prefill(p, (hipStream_t)stream);
+  HIP_OK(hipGetLastError());
+  return 0;
+  API_CATCH(-1)
+}
+
+// non-causal flash attention over a packed embed chunk (attn_encode.hip): segs as above, kv_len[s] the
+// length of segment s's prompt (its rows attend to keys [0, kv_len[s]) of their slot; the kernel reads
+// no positions); the tiles are cut here exactly as HipStage::attention_encode cuts them
+int mp_op_attn_encode(const void* q, const void* slot, const void* block_table, int max_pages, const void* k_cache,
+                      const void* v_cache, int Hq, int Hkv, int hd, int Dp, const int32_t* segs, const int32_t* kv_len,
+                      int n_segs, void* out, int ldo, int n_split, int split_pages, void* o_part, void* ml_part, int M,
+                      int kv_fp8, void* stream) {
+  API_TRY
+  if (Hkv < 1 || Hq < Hkv || Hq % Hkv || Hq / Hkv > 128) throw std::runtime_error("attn_encode: bad GQA group");
+  EncodeAttnParams p{};
+  p.q = (const f16*)q; p.slot = (const int32_t*)slot;
+  p.block_table = (const int32_t*)block_table; p.max_pages = max_pages;
+  p.k_cache = (const f16*)k_cache; p.v_cache = (const f16*)v_cache;
+  p.Hq = Hq; p.Hkv = Hkv; p.hd = hd; p.Dp = Dp; p.out = (f16*)out; p.ldo = ldo;
+  p.M = M; p.n_split = n_split; p.split_pages = split_pages; p.o_part = (float*)o_part; p.ml_part = (float*)ml_part;
+  p.kv_fp8 = kv_fp8;
+  op_v_strides(Dp, p.v_kb, p.v_d);
+  const int bt = prefill_attn_rows_per_tile(Hq / Hkv);
+  for (int s = 0; s < n_segs; ++s)
+    for (int r = 0; r < segs[2 * s + 1]; r += bt) {
+      if (p.n_tiles == kEncodeAttnMaxTiles) {
+        if (n_split > 1) throw std::runtime_error("attn_encode: a split chunk must fit one launch");
+        launch_attn_encode(p, (hipStream_t)stream);
+        p.n_tiles = 0;
+      }
+      p.kv_len[p.n_tiles] = kv_len[s];
+      p.tiles[p.n_tiles++] = (uint32_t)(segs[2 * s] + r) | ((uint32_t)std::min(bt, segs[2 * s + 1] - r) << 16);
+    }
+  launch_attn_encode(p, (hipStream_t)stream);
   HIP_OK(hipGetLastError());
   return 0;
   API_CATCH(-1)

@@ -418,7 +418,7 @@ void CpuStage::rmsnorm(const float* x, const std::vector<float>& w, float* y, in
   }
 }
 
-void CpuStage::layer_forward(int li, int M, float* x, const int32_t* pos, const int32_t* slot) {
+void CpuStage::layer_forward(int li, int M, float* x, const int32_t* pos, const int32_t* slot, const int32_t* kvlen) {
   const Layer& L = layers_[li];
   const int d = cfg_.d_model, qd = cfg_.q_dim(), kvd = cfg_.kv_dim(), hd = cfg_.head_dim;
   const int Hq = cfg_.n_head, Hkv = cfg_.n_head_kv, G = Hq / Hkv, ctx = opt_.max_ctx;
@@ -470,14 +470,15 @@ void CpuStage::layer_forward(int li, int M, float* x, const int32_t* pos, const 
     std::memcpy(&kc_[li][kv_off], row + qd, (size_t)kvd * 4);
     std::memcpy(&vc_[li][kv_off], row + qd + kvd, (size_t)kvd * 4);
   }
-  // causal attention over the slot's cache (tokens of this chunk are already appended)
+  // causal attention over the slot's cache (tokens of this chunk are already appended); with kvlen
+  // (non-causal embed chunks: whole prompts) every row of a prompt over all of its keys
   const float scale = 1.0f / std::sqrt((float)hd);
   pool_->parallel_for((int64_t)M * Hq, [&](int64_t i0, int64_t i1) {
     std::vector<float> sc((size_t)ctx);
     for (int64_t i = i0; i < i1; ++i) {
       const int m = (int)(i / Hq), h = (int)(i % Hq), kh = h / G;
       const float* q = qkv_.data() + (size_t)m * ldq + (size_t)h * hd;
-      const int n = pos[m] + 1;
+      const int n = kvlen ? kvlen[m] : pos[m] + 1;
       const float* kb = &kc_[li][(size_t)kh * hd];
       const float* vb = &vc_[li][(size_t)kh * hd];
       float mx = -INFINITY;
@@ -881,14 +882,17 @@ void CpuStage::head(int mb, int M, const float* x, int32_t* tok_out, uint64_t sa
 void CpuStage::prefill(int mb, const std::vector<PrefillSeg>& segs, hipStream_t) {
   const int d = cfg_.d_model;
   float* x = act_[mb].data();
-  std::vector<int32_t> pos, slot;
+  std::vector<int32_t> pos, slot, kvlen;   // kvlen: non-causal chunks only
+  const bool bidir = !segs.empty() && segs[0].bidir;
   for (const PrefillSeg& s : segs) {
     if (s.p0 + s.T > opt_.max_ctx) throw std::runtime_error("prompt exceeds context");
+    if (bidir && (!s.bidir || s.p0 != 0)) throw std::runtime_error("non-causal chunk: a segment that is not a whole prompt");
     const int sl = mb * opt_.mb_size + s.b;
     for (int t = 0; t < s.T; ++t) {
       const int row = (int)pos.size();
       pos.push_back(s.p0 + t);
       slot.push_back(sl);
+      if (bidir) kvlen.push_back(s.T);
       if (spec_.first()) {
         const int32_t tok = prompt_[(size_t)sl * opt_.max_ctx + s.p0 + t];
         if (tok < 0 || tok >= cfg_.vocab) throw std::runtime_error("token id out of range");
@@ -900,7 +904,8 @@ void CpuStage::prefill(int mb, const std::vector<PrefillSeg>& segs, hipStream_t)
   if (T > opt_.prefill_chunk) throw std::runtime_error("prefill chunk too large");
   // rows carry their own slot and position, so the packed chunk runs as one batch (the causal
   // mask per row is its position; other sequences' rows are in other slots)
-  for (size_t li = 0; li < layers_.size(); ++li) layer_forward((int)li, T, x, pos.data(), slot.data());
+  for (size_t li = 0; li < layers_.size(); ++li)
+    layer_forward((int)li, T, x, pos.data(), slot.data(), bidir ? kvlen.data() : nullptr);
   if (spec_.last() && !segs.empty() && segs[0].verify) {
     // speculative verification: greedy next token after every row of the chunk
     if (vtok_.size() < (size_t)opt_.n_mb) vtok_.resize(opt_.n_mb);

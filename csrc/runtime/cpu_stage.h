@@ -71,7 +71,8 @@ class CpuStage : public Stage {
   // Y[m][n] (+)= sum_k W[n][k] X[m][k]
   void matmul(const CpuMat& W, const float* X, int ldx, int M, float* Y, int ldy, bool accumulate);
   void rmsnorm(const float* x, const std::vector<float>& w, float* y, int M);
-  void layer_forward(int li, int M, float* x, const int32_t* pos, const int32_t* slot);
+  // kvlen: keys row m attends to (null: the causal pos[m] + 1; PrefillSeg::bidir rows: their prompt's length)
+  void layer_forward(int li, int M, float* x, const int32_t* pos, const int32_t* slot, const int32_t* kvlen = nullptr);
   void ffn(const Layer& L, int li, int M, const float* xn, float* x, const int32_t* slot);
   // LoRA (opt_.lora_adapters > 0), plain f32: Y[m] += scale * B (A X[m]) for every row whose slot is bound
   // to an adapter that has a pair for (layer li of this stage, target)

@@ -435,6 +435,15 @@ Engine::Engine(const Json& j) : jcfg_(j) {
   if (n_keep_ < -1) throw std::runtime_error("\"n_keep\" must be >= 0, or -1 for the whole prompt");
   if (auto_shift_) check_shift_supported("\"context_shift\"");
   packed_prefill_ = j.get_bool("packed_prefill", true);
+  {
+    const std::string ea = j.get_str("embed_attention", "auto");
+    if (ea != "auto" && ea != "causal" && ea != "non-causal")
+      throw std::runtime_error("\"embed_attention\" must be \"auto\", \"causal\" or \"non-causal\", not \"" + ea + "\"");
+    embed_bidir_ = ea == "auto" ? !cfg_.causal_attn : ea == "non-causal";
+    if (!cfg_.causal_attn)
+      MP_LOGW("the model is trained without the causal mask (attention.causal = false): embeddings run %s attention, "
+              "generation and scoring stay causal", embed_bidir_ ? "non-causal" : "causal (embed_attention)");
+  }
   prefix_cache_ = j.get_bool("prefix_cache", true);
   shared_prefix_ = j.get_bool("shared_prefix", false);
   if (shared_prefix_) {
@@ -1849,7 +1858,10 @@ std::vector<Item> Engine::pack_chunks(int mb, const std::vector<PackRow>& rows, 
     it.segs.clear();
     it.T = 0;
   };
-  for (const PackRow& r : rows)
+  for (const PackRow& r : rows) {
+    // non-causal: every row needs every key of its prompt in the cache before it attends, so a prompt
+    // (at most chunk_ rows: embed() checked) sits wholly in one chunk
+    if (flags.bidir && r.len > chunk_ - it.T) flush();
     for (int p0 = r.p0, end = r.p0 + r.len; p0 < end;) {
       PrefillSeg sg = flags;
       sg.b = r.b; sg.p0 = p0; sg.T = std::min(chunk_ - it.T, end - p0);
@@ -1859,6 +1871,7 @@ std::vector<Item> Engine::pack_chunks(int mb, const std::vector<PackRow>& rows, 
       p0 += sg.T;
       if (it.T == chunk_ || !packed_prefill_) flush();
     }
+  }
   flush();
   return chunks;
 }
@@ -2356,6 +2369,10 @@ void Engine::embed(const std::vector<int>& slots, const std::vector<std::vector<
     if ((int)prompts[k].size() > max_ctx_)
       throw std::runtime_error("embed: prompt " + std::to_string(k) + " has " + std::to_string(prompts[k].size()) +
                                " tokens, more than max_ctx = " + std::to_string(max_ctx_));
+    if (embed_bidir_ && (int)prompts[k].size() > chunk_)
+      throw std::runtime_error("embed: prompt " + std::to_string(k) + " has " + std::to_string(prompts[k].size()) +
+                               " tokens, more than prefill_chunk = " + std::to_string(chunk_) +
+                               " (non-causal attention needs the whole prompt in one chunk)");
     for (int32_t t : prompts[k])
       if (t < 0 || t >= cfg_.vocab)
         throw std::runtime_error("embed: token id " + std::to_string(t) + " out of range (vocab " + std::to_string(cfg_.vocab) + ")");
@@ -2383,6 +2400,7 @@ void Engine::embed(const std::vector<int>& slots, const std::vector<std::vector<
   std::vector<std::vector<Item>> chunks(M_);
   PrefillSeg embedded;
   embedded.embed = true;
+  embedded.bidir = embed_bidir_;
   for (int mb = 0; mb < M_; ++mb) {
     std::vector<PackRow> rows;
     for (int b = 0; b < B_; ++b)
@@ -2715,6 +2733,8 @@ Json Engine::info() const {
   if (cfg_.expert_ff) m["expert_d_ff"] = cfg_.d_ff;
   m["pooling_type"] = cfg_.pooling_type;   // the file's (-1: none); embed() pools by "pooling" unless told otherwise
   j["pooling"] = std::string(pooling_name(default_pooling()));
+  m["causal_attn"] = cfg_.causal_attn;     // the file's <arch>.attention.causal
+  j["embed_attention"] = embed_bidir_ ? "non-causal" : "causal";   // what embed() runs
   m["describe"] = cfg_.describe();
   j["model"] = m;
   size_t wb = 0, kb = 0;

@@ -126,7 +126,9 @@ class Engine {
   // calls, for idle slots only; the other slots keep their state and the used slots are idle again
   // (their KV pages returned, their prefix-cache entry dropped) when the call returns.  Every stage
   // in this process.  Throws naming the cause: a busy slot, an empty prompt, a prompt over max_ctx,
-  // a token id out of range, a pooling that is not supported.
+  // a token id out of range, a pooling that is not supported.  A non-causal engine ("embed_attention")
+  // attends every row to its whole prompt, which then has to fit one chunk: a prompt over
+  // prefill_chunk throws too.
   struct EmbedResult { std::vector<float> v; int n_rows = 1; };
   void embed(const std::vector<int>& slots, const std::vector<std::vector<int32_t>>& prompts, int pooling,
              bool normalize, std::vector<EmbedResult>* out);
@@ -371,6 +373,8 @@ class Engine {
   // The chunks of one micro-batch, in order: the rows [p0, p0 + len) of sequence row b, cut into
   // packed chunks of at most chunk_ rows (a chunk may hold several sequences; without packed_prefill
   // every segment is its own chunk).  `flags` gives every segment its score / verify / embed marks.
+  // flags.bidir: a prompt is never split (each has at most chunk_ rows); one that does not fit the
+  // chunk being filled starts the next.
   struct PackRow { int b, p0, len; };
   std::vector<Item> pack_chunks(int mb, const std::vector<PackRow>& rows, const PrefillSeg& flags) const;
   int32_t* out_host_ = nullptr;                    // pinned [rounds_cap][M*B]
@@ -388,6 +392,9 @@ class Engine {
   bool kv_fp8_ = false;      // kv_dtype "fp8" (checkpoint fingerprint: the KV bytes' element type)
   bool trace_ = false, failed_ = false;
   bool packed_prefill_ = true;   // several sequences per prefill chunk (config "packed_prefill")
+  // embed() runs non-causal attention (PrefillSeg::bidir): config "embed_attention" = "auto" (the file's
+  // <arch>.attention.causal), "causal" or "non-causal".  Nothing else reads it.
+  bool embed_bidir_ = false;
   int act_dtype_ = 0;            // stage-boundary activation wire format (ActDtype; config "act_dtype")
   std::string link_fallback_;    // why local mode's requested RCCL links became LocalLinks (empty: none)
   double trace_t0_ = 0, watchdog_s_ = 600;

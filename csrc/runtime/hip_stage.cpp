@@ -1327,7 +1327,9 @@ void HipStage::attention(int li, const Fwd& f, bool qkv_deferred, bool pre) {
     rp.q_out = q_; rp.k_cache = kc_[li]; rp.v_cache = vc_[li]; rp.kv_fp8 = opt_.kv_fp8;
     set_v_strides(rp.v_kb, rp.v_d);
     launch_rope_kv(rp, st);
-    if (!decode && opt_.prefill_flash) {
+    if (!decode && segs && !segs->empty() && (*segs)[0].bidir) {
+      attention_encode(li, f);   // every key of every prompt of the chunk is in the pages now
+    } else if (!decode && opt_.prefill_flash) {
       PrefillAttnParams pa{};
       pa.q = q_; pa.pos = pos; pa.slot = slot; pa.block_table = block_table_; pa.max_pages = max_pages_;
       pa.k_cache = kc_[li]; pa.v_cache = vc_[li]; pa.Hq = cfg_.n_head; pa.Hkv = cfg_.n_head_kv;
@@ -1396,6 +1398,39 @@ void HipStage::attention(int li, const Fwd& f, bool qkv_deferred, bool pre) {
     }
     }
   }
+}
+
+// non-causal embed chunk: whole prompts (PrefillSeg::bidir), each row over all keys of its prompt
+void HipStage::attention_encode(int li, const Fwd& f) {
+  EncodeAttnParams pa{};
+  pa.q = q_; pa.slot = f.slot; pa.block_table = block_table_; pa.max_pages = max_pages_;
+  pa.k_cache = kc_[li]; pa.v_cache = vc_[li]; pa.Hq = cfg_.n_head; pa.Hkv = cfg_.n_head_kv;
+  pa.kv_fp8 = opt_.kv_fp8;
+  set_v_strides(pa.v_kb, pa.v_d);
+  pa.hd = cfg_.head_dim; pa.Dp = Dp_; pa.out = attn_; pa.ldo = Ko_; pa.M = f.M;
+  const int bt = prefill_attn_rows_per_tile(cfg_.n_head / cfg_.n_head_kv);
+  int pages_needed = 0, n_tiles = 0;
+  for (const PrefillSeg& sg : *f.segs) {
+    if (!sg.bidir || sg.p0 != 0) throw std::runtime_error("non-causal chunk: a segment that is not a whole prompt");
+    pages_needed = std::max(pages_needed, (sg.T + 63) / 64);
+    n_tiles += (sg.T + bt - 1) / bt;
+  }
+  // few tiles over long prompts: split every tile's pages over grid.z so the chunk fills the CUs (one
+  // workgroup list per launch, so only when it fits one)
+  if (pf_opart_ && n_tiles <= kEncodeAttnMaxTiles) {
+    pa.n_split = prefill_attn_splits(n_tiles, cfg_.n_head_kv, pages_needed, kPrefillMaxSplit, &pa.split_pages);
+    pa.o_part = pf_opart_; pa.ml_part = pf_ml_;
+  }
+  int row = 0;
+  for (const PrefillSeg& sg : *f.segs) {
+    for (int r = 0; r < sg.T; r += bt) {
+      if (pa.n_tiles == kEncodeAttnMaxTiles) { launch_attn_encode(pa, f.st); pa.n_tiles = 0; }
+      pa.kv_len[pa.n_tiles] = sg.T;
+      pa.tiles[pa.n_tiles++] = (uint32_t)(row + r) | ((uint32_t)std::min(bt, sg.T - r) << 16);
+    }
+    row += sg.T;
+  }
+  launch_attn_encode(pa, f.st);
 }
 
 bool HipStage::fuse_norm(int M) const { return opt_.fused_norm && M <= 4; }

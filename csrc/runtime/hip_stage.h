@@ -223,6 +223,8 @@ class HipStage : public Stage {
   const void* xq_src_ = nullptr; int xq_rows_ = 0;   // the f16 rows xq_ currently holds (set by norm_x / the quant)
   bool attention_o(int li, const Fwd& f, float* x, bool pre = false);
   void attention(int li, const Fwd& f, bool qkv_deferred, bool pre = false);
+  // a chunk of PrefillSeg::bidir segments, after rope_kv: launch_attn_encode over q_ and the layer's pages
+  void attention_encode(int li, const Fwd& f);
   DecodeAttnParams decode_attn_params(int li, const Fwd& f, bool qkv_deferred) const;
   bool small_path(int M) const { return opt_.small_gemv && M <= 4; }
   size_t kv_eb() const { return opt_.kv_fp8 ? 1 : 2; }   // bytes per cached K/V element

@@ -286,6 +286,33 @@ void launch_attn_prefill(const PrefillAttnParams& p, hipStream_t st);
 int prefill_attn_splits(int n_tiles, int Hkv, int max_pages_needed, int max_split, int* split_pages);
 int prefill_attn_rows_per_tile(int G);   // tokens per tile: 128 / G
 
+// non-causal (bidirectional) flash attention over a packed embed chunk (attn_encode.hip): every row of
+// a tile attends to keys [0, kv_len) of its slot, whatever its own position.  Tiles as above (m0 | n << 16,
+// n <= 128 / G consecutive rows of ONE prompt, the tiles of a prompt next to each other) with the
+// prompt's length beside each; the whole prompt's K / V rows are in the pages before the launch.  One
+// workgroup per (tile, kv head, split) walks ceil(kv_len / 64) pages, or pages [z, z + 1) * split_pages of
+// them; the splits' partials have the attn_combine layout and are merged in the launcher.
+constexpr int kEncodeAttnMaxTiles = 256;
+struct EncodeAttnParams {
+  const f16* q;                  // [M][Hq][Dp], q_scale applied
+  const int32_t* slot;           // [M]
+  const int32_t* block_table; int max_pages;
+  const f16* k_cache; const f16* v_cache;
+  int Hq, Hkv, hd, Dp;
+  f16* out; int ldo;             // [M][ldo], head h at columns h * hd
+  int M = 0;                     // rows of the chunk (partial-buffer layout)
+  int n_split = 1, split_pages = 1;
+  float* o_part = nullptr; float* ml_part = nullptr;   // [n_split][M*Hq][Dp], [n_split][M*Hq][2]
+  int kv_fp8 = 0;
+  int v_kb = 0, v_d = 0;         // V page strides (0 = legacy)
+  int n_tiles;
+  uint32_t tiles[kEncodeAttnMaxTiles];
+  int32_t kv_len[kEncodeAttnMaxTiles];   // 1 <= kv_len <= max_pages * 64, host-checked
+};
+static_assert(sizeof(EncodeAttnParams) < 4096, "kernel arguments: 4 KB");
+// throws, naming it, on a shape or tile the kernel cannot take (host-side checks only)
+void launch_attn_encode(const EncodeAttnParams& p, hipStream_t st);
+
 // fused decode step of attention: RoPE(q, k) + KV append + split-K flash-decoding + last-arriver
 // merge (replaces rope_kv + attention + combine for tq = 1)
 struct DecodeAttnParams {

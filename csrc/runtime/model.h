@@ -43,6 +43,10 @@ struct ModelConfig {
   // <arch>.pooling_type of an embedding model (llama.cpp's ids: 0 none, 1 mean, 2 cls, 3 last, 4 rank);
   // -1: the file has none.  Engine::embed pools by it when it is 1..3 and by `last` otherwise.
   int pooling_type = -1;
+  // <arch>.attention.causal (default true).  false: an embedding model trained without the causal mask
+  // (gte-Qwen2, GritLM, LLM2Vec conversions); Engine::embed then runs non-causal attention unless
+  // "embed_attention" says otherwise.  Generation, scoring and verification stay causal.
+  bool causal_attn = true;
 
   int q_dim() const { return n_head * head_dim; }
   int kv_dim() const { return n_head_kv * head_dim; }

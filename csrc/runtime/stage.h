@@ -75,6 +75,8 @@ struct PrefillSeg {
   bool embed = false;   // embedding chunk (every segment from position 0 of its prompt on, no prefix reuse): the
                         // last stage norms and pools the rows by set_embed (-> copy_embeddings /
                         // copy_token_embeddings); no LM head, nothing kept for prefill_finish, no sampler state
+  bool bidir = false;   // embed segment of a non-causal engine: the segment is a WHOLE prompt (p0 = 0, T = its
+                        // length) and every row attends to all T keys (attn_encode.hip; CpuStage: key bound T)
 };
 
 inline const char* pooling_name(int p) {

@@ -119,6 +119,9 @@ inline void print_common_usage(FILE* f) {
           "  --pooling none|mean|cls|last   how a prompt's rows become its vector (default: the model's\n"
           "                            pooling_type, else last: in a causal model only the last row has seen the\n"
           "                            whole prompt); none prints one vector per token\n"
+          "  --attention causal|non-causal   attention of the embedding prompts (engine key embed_attention; default:\n"
+          "                            the model's attention.causal).  non-causal: every row sees its whole prompt,\n"
+          "                            which must fit --prefill-chunk; generation stays causal either way\n"
           "  --embd-normalize N        2: scale each vector to unit L2 length (default); -1: leave it as it is\n"
           "  --lora FILE               LoRA adapter GGUF (llama.cpp's format); --lora-scaled FILE SCALE applies it at\n"
           "                            SCALE.  mi-cli: exactly one, bound to every sequence; orchestrator: repeatable\n"
@@ -239,6 +242,7 @@ inline CliOptions parse_cli(int argc, char** argv,
         throw std::runtime_error("--pooling " + o.pooling + ": must be none, mean, cls or last" +
                                  (o.pooling == "rank" ? " (rank pooling is not supported)" : ""));
     }
+    else if (a == "--attention") e["embed_attention"] = val();   // causal | non-causal (the engine checks the name)
     else if (a == "--embd-normalize") {
       o.embd_normalize = std::atoi(val().c_str());
       if (o.embd_normalize != 2 && o.embd_normalize != -1) throw std::runtime_error("--embd-normalize must be 2 (L2) or -1 (none)");

@@ -22,8 +22,9 @@ lora_max_rank (largest rank of an adapter tensor pair, default 64, at most 128),
 false: prompts that begin with tokens a running slot already holds share its whole KV pages, see
 docs/USAGE.md --shared-prefix), context_shift (default
 False: a sequence that fills max_ctx ends; True: decode() / generate() first drop half of what follows the
-first n_keep prompt tokens, in whole 64-token pages, and go on, see context_shift) and n_keep (default 0;
--1: the whole prompt).
+first n_keep prompt tokens, in whole 64-token pages, and go on, see context_shift), n_keep (default 0;
+-1: the whole prompt) and embed_attention ("auto": the file's <arch>.attention.causal | "causal" |
+"non-causal": what embed() runs; non-causal prompts must fit one prefill_chunk).
 """
 from __future__ import annotations
 
@@ -338,7 +339,9 @@ class Engine:
         vector to unit L2 length (the zero vector stays zero).  The output RMSNorm is applied, the LM
         head is not run.  Legal before start() and between decode() calls: the prompts run in idle
         slots (`slots`, or as many idle ones as needed, in groups when there are more prompts than
-        idle slots), running sequences are untouched and the slots are idle again afterwards."""
+        idle slots), running sequences are untouched and the slots are idle again afterwards.  The
+        attention is the engine's embed_attention (info["embed_attention"]): non-causal for a file with
+        <arch>.attention.causal = false, and then a prompt over prefill_chunk tokens raises."""
         d = self.info["model"]["d_model"]
         prompts = [list(map(int, p)) for p in prompts]
         res = []

@@ -42,6 +42,9 @@ class LlamaConfig:
     # -1 = the key is not written.  Engine.embed pools by it when it is 1..3, by `last` otherwise.
     pooling_type: int = -1
     add_eos: bool = False       # tokenizer.ggml.add_eos_token (Qwen3-Embedding files set it)
+    # <arch>.attention.causal: False = an embedding model trained without the causal mask (gte-Qwen2,
+    # GritLM, LLM2Vec conversions); the key is written only then.  Engine.embed follows it.
+    causal: bool = True
 
     @property
     def hd(self) -> int:

@@ -86,10 +86,12 @@ class RefLlama:
         self.router_margins = []
 
     @torch.no_grad()
-    def forward(self, tokens, start_pos: int, layers=None, x_in=None, want_logits=True):
+    def forward(self, tokens, start_pos: int, layers=None, x_in=None, want_logits=True, causal=True):
         """tokens: list[int] (T new tokens at positions start_pos..start_pos+T-1).
         layers: optional (a, b) half-open layer range (pipeline-stage oracle).
         x_in: hidden state input instead of embedding (stage > 0).
+        causal=False: every row attends to every key in the cache (a bidirectional embedding model:
+        the whole prompt in one call from start_pos 0).
         Returns logits [T, vocab] (or hidden state if want_logits is False)."""
         t = self.t
         T = len(tokens) if x_in is None else x_in.shape[0]
@@ -125,7 +127,8 @@ class RefLlama:
             sc = torch.einsum("thd,shd->hts", q, Kx) / np.sqrt(hd)
             qpos = torch.as_tensor(pos, device=self.device)[:, None]
             kpos = torch.arange(S, device=self.device)[None, :]
-            sc = sc.masked_fill((kpos > qpos)[None], float("-inf"))
+            if causal:
+                sc = sc.masked_fill((kpos > qpos)[None], float("-inf"))
             pr = torch.softmax(sc, dim=-1)
             o = torch.einsum("hts,shd->thd", pr, Vx).reshape(T, H * hd)
             x = x + o @ t[p + "attn_output.weight"].T

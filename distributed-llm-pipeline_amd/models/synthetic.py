@@ -110,6 +110,8 @@ def write_synthetic_gguf(path: str, cfg: LlamaConfig, ftype: str = "Q4_K_M", see
         w.add(f"{arch}.expert_used_count", cfg.n_expert_used, U32)
     if cfg.pooling_type >= 0:
         w.add(f"{arch}.pooling_type", cfg.pooling_type, U32)
+    if not cfg.causal:
+        w.add(f"{arch}.attention.causal", False)
     if with_tokenizer:
         tokenizer_data.add_tokenizer_kv(w, cfg)
 

@@ -409,6 +409,27 @@ def attn_prefill(q, pos, slot, block_table, k_cache, v_cache, Hkv, hd, segs=None
     return out
 
 
+def attn_encode(q, slot, block_table, k_cache, v_cache, Hkv, hd, segs, kv_len, n_split=1, split_pages=1,
+                kv_fp8=False):
+    """Non-causal flash attention (attn_encode.hip): q [M][Hq][Dp] f16 (q_scale applied); the rows of
+    segs[s] = (row0, T), consecutive rows of one prompt, attend to keys [0, kv_len[s]) of their slot.
+    n_split / split_pages / kv_fp8 as attn_prefill."""
+    M, Hq, Dp = q.shape
+    sa = np.asarray(segs, np.int32).reshape(-1)
+    la = np.asarray(kv_len, np.int32).reshape(-1)
+    assert len(la) == len(segs)
+    out = torch.zeros(M, Hq * hd, dtype=torch.float16, device=q.device)
+    op = ml = None
+    if n_split > 1:
+        op = torch.full((n_split, M * Hq, Dp), float("nan"), dtype=torch.float32, device=q.device)
+        ml = torch.full((n_split, M * Hq, 2), float("nan"), dtype=torch.float32, device=q.device)
+    N.check(N.lib().mp_op_attn_encode(_ptr(q), _ptr(slot), _ptr(block_table), block_table.shape[1],
+                                      _ptr(k_cache), _ptr(v_cache), Hq, Hkv, hd, Dp, sa.ctypes.data, la.ctypes.data,
+                                      len(segs), _ptr(out), out.stride(0), n_split, split_pages, _ptr(op), _ptr(ml), M,
+                                      int(kv_fp8), _stream()), "attn_encode")
+    return out
+
+
 ARGMAX_CHUNKS = 64
 
 
