@@ -15,7 +15,7 @@ __global__ __launch_bounds__(ST) void sample_kernel(const SampleParams p) {
   const int row = blockIdx.x;
   const int32_t step = p.step ? p.step[0] : 0;
   const uint64_t r = mix64(p.seed ^ mix64(((uint64_t)step << 20) ^ (uint64_t)row));
-  sample_chain(p.logits + (size_t)row * p.ld, p.n, p.temp, p.top_k, p.top_p, p.min_p, r, p.tokens + row);
+  sample_chain(p.logits + (size_t)row * p.ld, p.n, p.temp, p.top_k, p.top_p, p.min_p, ChainExtra{}, r, p.tokens + row);
 }
 
 __global__ __launch_bounds__(256) void penalize_kernel(const PenaltyParams p) {

@@ -3,7 +3,9 @@
 // greedy and sampled requests, each with its own cuts, penalties, logit bias and random stream, and
 // the captured decode graphs never change when a request is admitted.
 //   row_adjust_kernel:  logit bias, then the repetition penalties of penalize_kernel, per row
-//   sample_rows_kernel: the chain of sample_kernel (sample_chain.h) with the row's parameters
+//   sample_rows_kernel: the chain of sample_kernel (sample_chain.h) with the row's parameters, among
+//                       them the cuts only a record can switch on (top-n-sigma, typical-p, XTC) and the
+//                       dynamic temperature
 // The record is uniform per workgroup: the compiler reads it with a handful of scalar loads.
 #include <stdexcept>
 
@@ -62,7 +64,9 @@ __global__ __launch_bounds__(ST) void sample_rows_kernel(const SampleRowsParams 
   const int32_t d = p.draw[row];
   if (temp > 0.f) {
     const uint64_t r = mix64(rs.seed ^ mix64((uint64_t)(uint32_t)d << 20));
-    sample_chain(p.logits + (size_t)row * p.ld, p.n, temp, rs.top_k, rs.top_p, rs.min_p, r, p.tokens + row);
+    const ChainExtra x{rs.top_n_sigma, rs.typical_p, rs.xtc_probability, rs.xtc_threshold, rs.dynatemp_range,
+                       rs.dynatemp_exponent};
+    sample_chain(p.logits + (size_t)row * p.ld, p.n, temp, rs.top_k, rs.top_p, rs.min_p, x, r, p.tokens + row);
   }
   // (every thread read draw[row] before the chain's first barrier; a greedy row's other threads do
   // not use it)

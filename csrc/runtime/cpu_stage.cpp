@@ -557,37 +557,101 @@ int CpuStage::sample_row(const float* lg, uint64_t salt, int row) {
 }
 
 // the chain for one row with the uniform variate u01 in [0, 1) given (temp_ > 0)
-int CpuStage::sample_chain(const float* lg, float temp_, int top_k_, float top_p_, float min_p_, double u01) const {
+// x: the record whose top-n-sigma, typical-p, XTC (variate u2) and dynamic temperature also apply
+// (null: none).  s lists the survivors as positions of the sorted row, most probable first; every
+// stage works on the survivors of the one before (the order of sample_chain.h).
+int CpuStage::sample_chain(const float* lg, float temp_, int top_k_, float top_p_, float min_p_, double u01,
+                           const RowSampling* x, double u2) const {
   const int n = cfg_.vocab;
   std::vector<std::pair<float, int>> v(n);
   for (int i = 0; i < n; ++i) v[i] = {lg[i], i};
   std::sort(v.begin(), v.end(), [](auto& a, auto& b) { return a.first > b.first || (a.first == b.first && a.second < b.second); });
-  int keep = (top_k_ > 0 && top_k_ < n) ? top_k_ : n;
   const float mx = v[0].first;
-  std::vector<double> p1(keep);
-  for (int i = 0; i < keep; ++i) p1[i] = std::exp((double)v[i].first - mx);
+  std::vector<int> s(n);
+  for (int i = 0; i < n; ++i) s[i] = i;
+  auto p1 = [&](int k) { return std::exp((double)v[k].first - mx); };
+  auto total = [&]() { double t = 0; for (int k : s) t += p1(k); return t; };
+  // entropy of the survivors (finite logits); *cnt: how many
+  auto entropy = [&](int* cnt) {
+    double z = 0, a = 0;
+    *cnt = 0;
+    for (int k : s) {
+      if (!std::isfinite(v[k].first)) continue;
+      const double d = (double)v[k].first - mx, e = std::exp(d);
+      z += e; a += e > 0 ? e * d : 0.0; ++*cnt;
+    }
+    return z > 0 ? std::log(z) - a / z : 0.0;
+  };
+  if (x && x->top_n_sigma > 0.f) {
+    double s1 = 0, s2 = 0, c = 0;
+    for (int i = 0; i < n; ++i)
+      if (std::isfinite(lg[i])) { const double d = (double)lg[i] - mx; s1 += d; s2 += d * d; c += 1; }
+    if (c > 0) {
+      const double mean = s1 / c, floor_l = (double)mx - x->top_n_sigma * std::sqrt(std::max(s2 / c - mean * mean, 0.0));
+      size_t j = 1;
+      while (j < s.size() && v[s[j]].first >= floor_l) ++j;
+      s.resize(j);
+    }
+  }
+  if (top_k_ > 0 && (size_t)top_k_ < s.size()) s.resize(top_k_);
+  if (x && x->typical_p > 0.f && x->typical_p < 1.f) {
+    const double z = total();
+    int cnt;
+    const double H = entropy(&cnt);
+    if (z > 0) {
+      std::vector<std::pair<double, int>> sc;   // (|-ln p - H|, position), -inf logits left out
+      for (int k : s)
+        if (p1(k) > 0) sc.emplace_back(std::fabs(std::log(z) - ((double)v[k].first - mx) - H), k);
+      std::stable_sort(sc.begin(), sc.end(), [](auto& a, auto& b) { return a.first < b.first; });
+      double c = 0;
+      s.clear();
+      for (const auto& e : sc) {
+        s.push_back(e.second);
+        c += p1(e.second);
+        if (c >= x->typical_p * z) break;
+      }
+      std::sort(s.begin(), s.end());
+    }
+  }
   if (top_p_ > 0.f && top_p_ < 1.f) {
-    double tot = 0, c = 0;
-    for (int i = 0; i < keep; ++i) tot += p1[i];
-    int j = 0;
-    while (j < keep) { c += p1[j++]; if (c >= top_p_ * tot) break; }
-    keep = std::max(1, j);
+    const double tot = total();
+    double c = 0;
+    size_t j = 0;
+    while (j < s.size()) { c += p1(s[j++]); if (c >= top_p_ * tot) break; }
+    s.resize(std::max<size_t>(1, j));
   }
   if (min_p_ > 0) {
-    int j = 0;
-    while (j < keep && p1[j] >= min_p_) ++j;
-    keep = std::max(1, j);
+    const double top = p1(s[0]);
+    size_t j = 0;
+    while (j < s.size() && p1(s[j]) >= min_p_ * top) ++j;
+    s.resize(std::max<size_t>(1, j));
   }
-  std::vector<double> p(keep);
+  if (x && x->xtc_probability > 0.f && x->xtc_threshold <= 0.5f && u2 < x->xtc_probability) {
+    const double z = total();
+    size_t j = 0;   // the survivors with p >= threshold lead the list; the last of them stays
+    while (j < s.size() && p1(s[j]) >= x->xtc_threshold * z) ++j;
+    if (j >= 2) s.erase(s.begin(), s.begin() + (j - 1));
+  }
+  double T = temp_;
+  if (x && x->dynatemp_range > 0.f) {
+    int cnt;
+    const double H = std::max(entropy(&cnt), 0.0);
+    if (cnt > 1) {
+      const double t_lo = std::max(0.0, (double)temp_ - x->dynatemp_range), t_hi = (double)temp_ + x->dynatemp_range;
+      T = std::max(t_lo + (t_hi - t_lo) * std::pow(std::min(H / std::log((double)cnt), 1.0), (double)x->dynatemp_exponent), 1e-6);
+    }
+  }
+  const double top = v[s[0]].first;
+  std::vector<double> p(s.size());
   double sum = 0;
-  for (int i = 0; i < keep; ++i) { p[i] = std::exp(((double)v[i].first - mx) / temp_); sum += p[i]; }
+  for (size_t i = 0; i < s.size(); ++i) { p[i] = std::exp(((double)v[s[i]].first - top) / T); sum += p[i]; }
   const double u = u01 * sum;
   double c = 0;
-  for (int i = 0; i < keep; ++i) {
+  for (size_t i = 0; i < s.size(); ++i) {
     c += p[i];
-    if (u < c) return v[i].second;
+    if (u < c) return v[s[i]].second;
   }
-  return v[keep - 1].second;
+  return v[s.back()].second;
 }
 
 // KV of one slot: per layer, K rows then V rows [n_tok][kv_dim] f32 (gathered through the slot's
@@ -809,7 +873,9 @@ void CpuStage::head_rows(int mb, int M, int32_t* tok_out, bool advance) {
       tok_out[m] = (int32_t)(std::max_element(lg, lg + V) - lg);
     } else {
       const uint64_t r = mix64(rs.seed ^ mix64((uint64_t)(uint32_t)draws_[s] << 20));
-      tok_out[m] = sample_chain(lg, rs.temp, rs.top_k, rs.top_p, rs.min_p, (double)(r >> 40) * (1.0 / 16777216.0));
+      const uint64_t r2 = mix64(r ^ 0x9E3779B97F4A7C15ULL);   // XTC's variate: the draw's stays as it is
+      tok_out[m] = sample_chain(lg, rs.temp, rs.top_k, rs.top_p, rs.min_p, (double)(r >> 40) * (1.0 / 16777216.0), &rs,
+                                (double)(r2 >> 40) * (1.0 / 16777216.0));
     }
     if (advance) ++draws_[s];
     if (lp) {

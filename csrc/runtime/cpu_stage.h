@@ -95,7 +95,8 @@ class CpuStage : public Stage {
   void set_sample_step(uint64_t s) override { step_ = s; }
   const char* backend_name() const override { return "cpu"; }
   int sample_row(const float* logits, uint64_t salt, int row);
-  int sample_chain(const float* logits, float temp, int top_k, float top_p, float min_p, double u01) const;
+  int sample_chain(const float* logits, float temp, int top_k, float top_p, float min_p, double u01,
+                   const RowSampling* x = nullptr, double u2 = 0) const;
   CpuMat own_random(int type, int64_t N, int64_t K, uint64_t seed);
 
   ModelConfig cfg_;

@@ -26,6 +26,14 @@
 namespace mp {
 
 namespace {
+// the members of the chain only a slot record switches on (the engine-wide sampler has no such
+// stages): name in the sampling dict and of the engine key of its default, member, neutral value
+struct ChainField { const char* name; float RowSampling::* member; float neutral; };
+const ChainField kChainFields[] = {
+    {"top_n_sigma", &RowSampling::top_n_sigma, 0.f},         {"typical_p", &RowSampling::typical_p, 1.f},
+    {"xtc_probability", &RowSampling::xtc_probability, 0.f}, {"xtc_threshold", &RowSampling::xtc_threshold, 0.1f},
+    {"dynatemp_range", &RowSampling::dynatemp_range, 0.f},   {"dynatemp_exponent", &RowSampling::dynatemp_exponent, 1.f}};
+
 // host memory a CPU stage's KV pool may plan with: the "host_mem_gib" option, else MemAvailable from
 // /proc/meminfo (physical pages as a fallback), instead of assuming a 64 GiB host
 double host_mem_bytes(const Json& j) {
@@ -468,8 +476,12 @@ Engine::Engine(const Json& j) : jcfg_(j) {
     row_default_.repeat = (float)j.get_num("repeat_penalty", 1.0);
     row_default_.freq = (float)j.get_num("frequency_penalty", 0.0);
     row_default_.presence = (float)j.get_num("presence_penalty", 0.0);
+    for (const ChainField& f : kChainFields) row_default_.*f.member = (float)j.get_num(f.name, f.neutral);
     row_default_.seed = seed;
     check_row_sampling(row_default_, cfg_.vocab);
+  } else {
+    for (const ChainField& f : kChainFields)
+      if (j.has(f.name)) throw std::runtime_error(std::string("\"") + f.name + "\" needs \"row_sampling\": the engine-wide sampler has no such stage");
   }
   {
     Slot idle;   // every slot starts at the engine's values
@@ -1487,10 +1499,12 @@ void Engine::push_row_draws(int mb) {
   for_each_last_stage([&](Worker& w) { w.stage->set_row_draws(mb, d); });
 }
 
-RowSampling Engine::sampling_from_json(const Json& j, bool* has_seed) const {
+RowSampling Engine::sampling_from_json(const Json& j, bool* has_seed, bool absent_neutral) const {
   if (!row_sampling_) throw std::runtime_error("per-request sampling needs an engine built with row_sampling");
   if (!j.is_obj()) throw std::runtime_error("sampling: an object of fields is expected");
   RowSampling r = row_default_;
+  if (absent_neutral)   // what sampling_to_json wrote: a field it left out was neutral
+    for (const ChainField& f : kChainFields) r.*f.member = f.neutral;
   auto num = [&](const char* k, double d) {
     if (!j.has(k)) return d;
     if (!j[k].is_num()) throw std::runtime_error(std::string("sampling: ") + k + " must be a number");
@@ -1502,7 +1516,9 @@ RowSampling Engine::sampling_from_json(const Json& j, bool* has_seed) const {
     return v;
   };
   for (const auto& kv : j.obj()) {
-    static const char* known[] = {"temp", "top_k", "top_p", "min_p", "repeat", "freq", "presence", "seed", "draw0", "logit_bias"};
+    static const char* known[] = {"temp", "top_k", "top_p", "min_p", "repeat", "freq", "presence", "seed", "draw0", "logit_bias",
+                                  "top_n_sigma", "typical_p", "xtc_probability", "xtc_threshold", "dynatemp_range",
+                                  "dynatemp_exponent"};
     bool ok = false;
     for (const char* k : known) ok |= kv.first == k;
     if (!ok) throw std::runtime_error("sampling: unknown field " + kv.first);
@@ -1514,6 +1530,8 @@ RowSampling Engine::sampling_from_json(const Json& j, bool* has_seed) const {
   r.repeat = (float)num("repeat", r.repeat);
   r.freq = (float)num("freq", r.freq);
   r.presence = (float)num("presence", r.presence);
+  for (const ChainField& f : kChainFields) r.*f.member = (float)num(f.name, r.*f.member);
+  if (r.top_n_sigma <= 0.f) r.top_n_sigma = 0.f;   // llama.cpp's clients send -1 for "off"
   r.draw0 = (int32_t)integer("draw0", 0, 0, 2147483647.0);
   bool seeded = false;
   if (j.has("seed") && !j["seed"].is_null()) {
@@ -1578,6 +1596,8 @@ Json Engine::sampling_to_json(const RowSampling& r) {
     lb.push(e);
   }
   o["logit_bias"] = lb;
+  for (const ChainField& f : kChainFields)   // only when set: the dict of a plain request stays as it was
+    if (r.*f.member != f.neutral) o[f.name] = (double)(r.*f.member);
   return o;
 }
 
@@ -1820,7 +1840,7 @@ Json Engine::load_state(const std::string& dir) {
     for (size_t i = 0; i < n; ++i) {
       Slot& s = slots_[i];
       bool seeded = false;
-      s.rec = sampling_from_json(sj["sampling"].arr()[i], &seeded);
+      s.rec = sampling_from_json(sj["sampling"].arr()[i], &seeded, true);
       s.seed_given = true;
       if (sj.has("draws") && (int)sj["draws"].arr()[i].num() != s.rec.draw0 + (int)s.gen.size())
         throw std::runtime_error("load_state: bad session (draws)");

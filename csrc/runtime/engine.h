@@ -161,13 +161,17 @@ class Engine {
   // slot_sampling() reports the record with the seed in use.  Throws naming the field on a value
   // out of range.  JSON form (C API, sessions, HTTP): {"temp", "top_k", "top_p", "min_p", "repeat",
   // "freq", "presence", "seed" (number or decimal string), "draw0", "logit_bias": [[id, bias | false], ..]},
-  // absent fields = the engine's values.
+  // absent fields = the engine's values.  The chain members beyond the engine-wide sampler's,
+  // "top_n_sigma", "typical_p", "xtc_probability", "xtc_threshold", "dynatemp_range" and
+  // "dynatemp_exponent" (engine keys of the same names give their defaults), are written by
+  // sampling_to_json only where they differ from neutral (0, 1, 0, 0.1, 0, 1); absent_neutral reads
+  // such a dict back (a saved session).
   bool row_sampling() const { return row_sampling_; }
   // for_start: the record is for a start(), which resets every slot, so a busy slot takes it too
   void set_slot_sampling(int slot, const RowSampling& r, bool has_seed = true, bool for_start = false);
   RowSampling slot_sampling(int slot) const;
   const RowSampling& sampling_defaults() const { return row_default_; }
-  RowSampling sampling_from_json(const Json& j, bool* has_seed) const;
+  RowSampling sampling_from_json(const Json& j, bool* has_seed, bool absent_neutral = false) const;
   static Json sampling_to_json(const RowSampling& r);
   // Per-slot token masks (config "row_masks": true; needs row_sampling and switches it on when that
   // key is absent; local mode).  bits[i]: ceil(vocab / 32) words for slot slots[i], token t allowed iff

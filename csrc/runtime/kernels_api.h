@@ -449,10 +449,13 @@ void launch_hist_push(int32_t* hist, int32_t* cnt, int last_n, const int32_t* to
 
 // Per-request sampling (sample_rows.hip; engine key "row_sampling"): one record per sequence slot in a
 // device table the captured decode graphs read, so an admit copies records and never re-captures.
-// Chain of a row: raw logits -> logit bias -> penalties -> cuts at T = 1 (top-k, top-p, min-p) ->
-// draw at temperature T.  The d-th token a request generates (d = draw0, draw0 + 1, ..) uses
-//   u = (mix64(seed ^ mix64(d << 20)) >> 40) / 2^24
-// whatever its slot, row, micro-batch or round of admission.
+// Chain of a row: raw logits -> logit bias -> penalties -> cuts at T = 1 (top-n-sigma, top-k,
+// typical-p, top-p, min-p, XTC; each over the survivors of the one before) -> draw at temperature T
+// (dynatemp_range > 0: T moves in [T - range, T + range] with the survivors' entropy).  The d-th token
+// a request generates (d = draw0, draw0 + 1, ..) uses, with r = mix64(seed ^ mix64(d << 20)),
+//   u = (r >> 40) / 2^24   for the draw,   u2 = (mix64(r ^ 0x9E3779B97F4A7C15) >> 40) / 2^24   for XTC
+// whatever its slot, row, micro-batch or round of admission.  A record of zero words past `presence`
+// has every one of the later members off.
 constexpr int kMaxLogitBias = 32;
 struct RowSampling {
   float temp = 0.f; int32_t top_k = 0; float top_p = 1.f; float min_p = 0.f;   // temp <= 0: greedy
@@ -460,11 +463,15 @@ struct RowSampling {
   int32_t n_bias = 0;
   uint64_t seed = 0;
   int32_t draw0 = 0;      // draws the request consumed before this admission (failover, resume)
-  int32_t pad_ = 0;
+  float top_n_sigma = 0.f;              // <= 0: off
   int32_t bias_id[kMaxLogitBias] = {};
   float bias_val[kMaxLogitBias] = {};   // -inf bans the token
+  float typical_p = 1.f;                // 0 or 1: off
+  float xtc_probability = 0.f, xtc_threshold = 0.1f;   // probability 0 or threshold > 0.5: off
+  float dynatemp_range = 0.f, dynatemp_exponent = 1.f;  // range 0: off
+  int32_t pad_ = 0;                     // (the record holds a uint64: its size is a multiple of 8)
 };
-static_assert(sizeof(RowSampling) == 304, "RowSampling is a device record");
+static_assert(sizeof(RowSampling) == 328, "RowSampling is a device record");
 // bias, then penalties, in place; one workgroup per row; a row without bias and with neutral
 // penalties (repeat 1, freq 0, presence 0) returns before touching its logits.  The window of row m
 // is hist[m * hist_ld .. + last_n) (-1 = empty); penalty maths as launch_penalize.  An id listed

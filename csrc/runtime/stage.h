@@ -95,6 +95,12 @@ inline void check_row_sampling(const RowSampling& r, int vocab) {
   if (!std::isfinite(r.freq)) bad("freq");
   if (!std::isfinite(r.presence)) bad("presence");
   if (r.draw0 < 0) bad("draw0");
+  if (!std::isfinite(r.top_n_sigma)) bad("top_n_sigma");
+  if (!(r.typical_p > 0.f && r.typical_p <= 1.f)) bad("typical_p");
+  if (!(r.xtc_probability >= 0.f && r.xtc_probability <= 1.f)) bad("xtc_probability");
+  if (!(r.xtc_threshold >= 0.f)) bad("xtc_threshold");
+  if (!(r.dynatemp_range >= 0.f) || std::isinf(r.dynatemp_range)) bad("dynatemp_range");
+  if (!(r.dynatemp_exponent > 0.f) || std::isinf(r.dynatemp_exponent)) bad("dynatemp_exponent");
   if (r.n_bias < 0 || r.n_bias > kMaxLogitBias) bad("n_bias");
   for (int i = 0; i < r.n_bias; ++i) {
     if (r.bias_id[i] < 0 || r.bias_id[i] >= vocab) bad("logit_bias id");

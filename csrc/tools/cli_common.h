@@ -100,6 +100,9 @@ inline void print_common_usage(FILE* f) {
           "  --temp T --top-k K --top-p P --min-p P --seed S   sampling (default greedy, temp 0)\n"
           "  --repeat-penalty R --repeat-last-n N --frequency-penalty F --presence-penalty P\n"
           "                            penalties over the last N tokens (default 1.0 / 64 / 0 / 0)\n"
+          "  --top-nsigma S --typical P --xtc-probability Q --xtc-threshold T --dynatemp-range R --dynatemp-exp E\n"
+          "                            further stages of the sampler chain, in llama.cpp's order (default off: 0 / 1 /\n"
+          "                            0 / 0.1 / 0 / 1); they run in the per-row sampler and imply --row-sampling\n"
           "  --sampling greedy         force greedy\n"
           "  --n-probs N               record token log-probabilities (raw log-softmax): -1 the chosen token's\n"
           "                            only, 1..20 plus that many alternatives (default 0: off)\n"
@@ -160,6 +163,16 @@ inline void print_common_usage(FILE* f) {
           "  --verbose, --log-file FILE, --trace FILE (Chrome trace of the pipeline)\n");
 }
 
+// llama-cli's flags of the sampler stages beyond top-k / top-p / min-p -> the engine key of the default
+inline const char* chain_flag_key(const std::string& a) {
+  static const char* const kFlags[][2] = {{"--typical", "typical_p"},           {"--top-nsigma", "top_n_sigma"},
+                                          {"--xtc-probability", "xtc_probability"}, {"--xtc-threshold", "xtc_threshold"},
+                                          {"--dynatemp-range", "dynatemp_range"},   {"--dynatemp-exp", "dynatemp_exponent"}};
+  for (auto& f : kFlags)
+    if (a == f[0]) return f[1];
+  return nullptr;
+}
+
 // Parses the shared flags; unknown flags are offered to `extra_flag(name, next_value_fn)` which
 // returns true if it consumed them.
 inline CliOptions parse_cli(int argc, char** argv,
@@ -191,6 +204,10 @@ inline CliOptions parse_cli(int argc, char** argv,
     else if (a == "--top-k") e["top_k"] = std::atoi(val().c_str());
     else if (a == "--top-p") e["top_p"] = std::atof(val().c_str());
     else if (a == "--min-p") e["min_p"] = std::atof(val().c_str());
+    else if (const char* key = chain_flag_key(a)) {   // stages of the per-row sampler only
+      e[key] = std::atof(val().c_str());
+      e["row_sampling"] = true;
+    }
     else if (a == "--repeat-penalty") e["repeat_penalty"] = std::atof(val().c_str());
     else if (a == "--repeat-last-n") e["repeat_last_n"] = std::atoi(val().c_str());
     else if (a == "--frequency-penalty") e["frequency_penalty"] = std::atof(val().c_str());

@@ -868,7 +868,8 @@ void spawn_job(Server& S, std::shared_ptr<Job> job) {
 }
 
 // The sampling fields every llama.cpp-server client sends: temperature, top_k, top_p, min_p, seed,
-// repeat_penalty, frequency_penalty, presence_penalty, logit_bias ([[id, bias | false], ..] or {"id": bias})
+// repeat_penalty, frequency_penalty, presence_penalty, logit_bias ([[id, bias | false], ..] or {"id": bias}),
+// top_n_sigma, typical_p, xtc_probability, xtc_threshold, dynatemp_range, dynatemp_exponent
 // -> the request's slot record (Engine::sampling_from_json).  They need a server started with
 // --row-sampling; repeat_last_n is the server's (a request may only repeat it).  false: a 400 was sent.
 struct ReqSampling {
@@ -947,7 +948,10 @@ bool parse_sampling(Server& S, int fd, const Json& body, const std::string& mode
   static const char* const kFields[][2] = {{"temperature", "temp"}, {"top_k", "top_k"}, {"top_p", "top_p"},
                                            {"min_p", "min_p"}, {"seed", "seed"}, {"repeat_penalty", "repeat"},
                                            {"frequency_penalty", "freq"}, {"presence_penalty", "presence"},
-                                           {"logit_bias", "logit_bias"}};
+                                           {"logit_bias", "logit_bias"}, {"top_n_sigma", "top_n_sigma"},
+                                           {"typical_p", "typical_p"}, {"xtc_probability", "xtc_probability"},
+                                           {"xtc_threshold", "xtc_threshold"}, {"dynatemp_range", "dynatemp_range"},
+                                           {"dynatemp_exponent", "dynatemp_exponent"}};
   Json j = Json::object();
   bool any = body.has("repeat_last_n");
   for (auto& f : kFields)
@@ -969,7 +973,8 @@ bool parse_sampling(Server& S, int fd, const Json& body, const std::string& mode
     if (ModelSlot* m = find_model(S, model)) e = m->eng.get();
   if (!e || !e->row_sampling()) {
     respond_text(fd, 400, "per-request sampling fields (temperature, top_k, top_p, min_p, seed, repeat_penalty, "
-                          "frequency_penalty, presence_penalty, logit_bias) need a server started with --row-sampling");
+                          "frequency_penalty, presence_penalty, logit_bias, top_n_sigma, typical_p, xtc_probability, "
+                          "xtc_threshold, dynatemp_range, dynatemp_exponent) need a server started with --row-sampling");
     return false;
   }
   if (body.has("repeat_last_n")) {
@@ -1182,6 +1187,11 @@ void handle_completion(Server& S, int fd, const Request& r) {
   if (g.has_seed) {   // --row-sampling: the seed of this request's stream (a string above 2^53, which a number cannot hold)
     if (g.seed <= (1ULL << 53)) o["seed"] = (double)g.seed;
     else o["seed"] = std::to_string(g.seed);
+  }
+  if (rs.has) {   // the record the request was sampled by (fields of the chain that are off are left out)
+    RowSampling rec = rs.rec;
+    if (g.has_seed) rec.seed = g.seed;
+    o["generation_settings"] = Engine::sampling_to_json(rec);
   }
   if (n_probs > 0) {   // llama.cpp's field: one entry per generated token, n_probs alternatives each
     Json cp = Json::array();

@@ -92,7 +92,10 @@ class Engine:
         idle slot `slot` uses.  Fields: temp, top_k, top_p, min_p, repeat, freq, presence (absent = the
         engine's values; temp <= 0 = greedy), seed (the request's own random stream; absent = a default
         one, reported by slot_sampling), draw0 (draws already consumed: the request continues its
-        stream there), logit_bias ([[id, bias], ..], bias False or -inf bans the token; at most 32).
+        stream there), logit_bias ([[id, bias], ..], bias False or -inf bans the token; at most 32), and
+        the further stages of llama.cpp's chain: top_n_sigma (<= 0 off), typical_p (1 off),
+        xtc_probability / xtc_threshold (0 / 0.1; off at probability 0 or threshold > 0.5),
+        dynatemp_range / dynatemp_exponent (0 / 1); slot_sampling reports these only where they are on.
         The d-th token a request generates is drawn with u = (mix64(seed ^ mix64(d << 20)) >> 40) / 2^24
         whatever slot, micro-batch or round it runs in.  release() puts the slot back to the defaults."""
         f = dict(fields)

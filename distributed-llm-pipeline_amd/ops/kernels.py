@@ -501,15 +501,20 @@ MAX_LOGIT_BIAS = 32
 # the device record of one row (RowSampling, csrc/runtime/kernels_api.h)
 ROW_SAMPLING_DTYPE = np.dtype([("temp", "<f4"), ("top_k", "<i4"), ("top_p", "<f4"), ("min_p", "<f4"), ("repeat", "<f4"),
                                ("freq", "<f4"), ("presence", "<f4"), ("n_bias", "<i4"), ("seed", "<u8"), ("draw0", "<i4"),
-                               ("pad", "<i4"), ("bias_id", "<i4", (MAX_LOGIT_BIAS,)), ("bias_val", "<f4", (MAX_LOGIT_BIAS,))])
+                               ("top_n_sigma", "<f4"), ("bias_id", "<i4", (MAX_LOGIT_BIAS,)),
+                               ("bias_val", "<f4", (MAX_LOGIT_BIAS,)), ("typical_p", "<f4"), ("xtc_probability", "<f4"),
+                               ("xtc_threshold", "<f4"), ("dynatemp_range", "<f4"), ("dynatemp_exponent", "<f4"),
+                               ("pad", "<i4")])
 
 
 def row_records(rows, device) -> torch.Tensor:
-    """Device table (uint8 [M][304]) of per-row sampling records from dicts with the keys temp, top_k,
-    top_p, min_p, repeat, freq, presence, seed, draw0 and bias (a list of (id, value) pairs, <= 32)."""
+    """Device table (uint8 [M][328]) of per-row sampling records from dicts with the keys temp, top_k,
+    top_p, min_p, repeat, freq, presence, seed, draw0, top_n_sigma, typical_p, xtc_probability,
+    xtc_threshold, dynatemp_range, dynatemp_exponent and bias (a list of (id, value) pairs, <= 32)."""
     assert ROW_SAMPLING_DTYPE.itemsize == N.lib().mp_row_sampling_bytes()
     a = np.zeros(len(rows), ROW_SAMPLING_DTYPE)
     a["top_p"], a["repeat"] = 1.0, 1.0
+    a["typical_p"], a["xtc_threshold"], a["dynatemp_exponent"] = 1.0, 0.1, 1.0
     for i, r in enumerate(rows):
         r = dict(r)
         bias = list(r.pop("bias", ()))
