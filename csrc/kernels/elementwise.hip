@@ -2,6 +2,7 @@
 // (K5+K6 fused), argmax (K12 greedy), decode-step advance, SwiGLU (K8, unfused fallback).
 // All loads/stores of bf16/f16/f32 rows are vectorised (guide Guideline 13).
 #include "kcommon.h"
+#include "mx8.h"
 #include <stdexcept>
 #include "../runtime/kernels_api.h"
 #include "../runtime/qtypes.h"
@@ -31,7 +32,7 @@ __global__ __launch_bounds__(1024) void rmsnorm_kernel(const float* x, int ldx, 
                                                        float eps, f16* out, int ldo, float* zero,
                                                        int64_t zero_n, int M, const float* bias, int bias_n,
                                                        const float* part, int nsplit, int64_t pstride, int ldp,
-                                                       int8_t* q8, int ldq8, float* q8s) {
+                                                       int8_t* q8, int ldq8, float* q8s, bool q8_mx) {
   __shared__ float red[16], red2[16];
   const int row = blockIdx.x;
   const int tid = threadIdx.x;
@@ -100,7 +101,24 @@ __global__ __launch_bounds__(1024) void rmsnorm_kernel(const float* x, int ldx, 
                              fmaxf(fabsf((float)hv[k][1].x), fabsf((float)hv[k][1].y))));
       }
     }
-    if (q8) {   // int8_gemm: the same f16 row quantized per row (quant_rows_i8_kernel's rounding)
+    if (q8 && q8_mx) {   // mx8_gemm: the same f16 row as MX-FP8 blocks (quant_rows_mx8_kernel's rounding)
+      // a block is 8 adjacent lanes x 4 elements (d % 32 == 0: they are in or out of the row together)
+      uint8_t* se = reinterpret_cast<uint8_t*>(q8s) + (size_t)row * (ldq8 >> 5);
+#pragma unroll
+      for (int k = 0; k < 2; ++k) {
+        const int i = (tid + 1024 * k) * 4;
+        float bm = fmaxf(fmaxf(fabsf((float)hv[k][0].x), fabsf((float)hv[k][0].y)),
+                         fmaxf(fabsf((float)hv[k][1].x), fabsf((float)hv[k][1].y)));
+        bm = fmaxf(bm, __shfl_xor(bm, 1));
+        bm = fmaxf(bm, __shfl_xor(bm, 2));
+        bm = fmaxf(bm, __shfl_xor(bm, 4));
+        if (i < d) {
+          const uint32_t e = mx8_scale_e(bm);
+          *reinterpret_cast<uint32_t*>(q8 + (size_t)row * ldq8 + i) = mx8_pack4(hv[k][0], hv[k][1], mx8_scale_f32(e));
+          if ((tid & 7) == 0) se[i >> 5] = (uint8_t)e;
+        }
+      }
+    } else if (q8) {   // int8_gemm: the same f16 row quantized per row (quant_rows_i8_kernel's rounding)
       qm = wave_max(qm);
       if ((tid & 63) == 0) red2[tid >> 6] = qm;
       __syncthreads();
@@ -594,17 +612,18 @@ void launch_rmsnorm(const float* x, int ldx, const float* w, int d, float eps, f
                     float* zero, int64_t zero_n, hipStream_t st, const float* bias, int bias_n) {
   const int zb = zero ? (int)((zero_n + 16383) / 16384) : 0;
   hipLaunchKernelGGL(mpk::rmsnorm_kernel, dim3(M > zb ? M : zb), dim3(1024), 0, st, x, ldx, w, d, eps, out, ldo, zero,
-                     zero_n, M, bias, bias_n, nullptr, 0, 0, 0, nullptr, 0, nullptr);
+                     zero_n, M, bias, bias_n, nullptr, 0, 0, 0, nullptr, 0, nullptr, false);
 }
 
 void launch_rmsnorm_acc(float* x, int ldx, const float* w, int d, float eps, f16* out, int ldo, int M,
                         float* zero, int64_t zero_n, const float* part, int nsplit, int64_t ss, int ldp, hipStream_t st,
-                        const float* bias, int bias_n, int8_t* q8, int ldq8, float* q8s) {
-  if ((d & 3) || d > 8192 || (ldx & 3) || (part && ((ldp & 3) || (ss & 3))) || (q8 && (ldq8 & 3)))
+                        const float* bias, int bias_n, int8_t* q8, int ldq8, float* q8s, bool q8_mx) {
+  if ((d & 3) || d > 8192 || (ldx & 3) || (part && ((ldp & 3) || (ss & 3))) || (q8 && (ldq8 & 3)) ||
+      (q8 && q8_mx && ((d & 31) || (ldq8 & 31))))
     throw std::runtime_error("launch_rmsnorm_acc: needs d <= 8192 and 4-aligned rows");
   const int zb = zero ? (int)((zero_n + 16383) / 16384) : 0;
   hipLaunchKernelGGL(mpk::rmsnorm_kernel, dim3(M > zb ? M : zb), dim3(1024), 0, st, x, ldx, w, d, eps, out, ldo, zero,
-                     zero_n, M, bias, bias_n, part, part ? nsplit : 0, ss, ldp, q8, ldq8, q8s);
+                     zero_n, M, bias, bias_n, part, part ? nsplit : 0, ss, ldp, q8, ldq8, q8s, q8_mx);
 }
 
 void launch_embed(int t, const uint8_t* table, int64_t rb, int d, const int32_t* tokens, int M, float* x,

@@ -1,0 +1,291 @@
+// MX-FP8 GEMM (opt-in mx8_gemm mode, M > 64): Y[M][N] (+)= X[M][K] W[N][K]^T with both operands in
+// OCP MXFP8 -- e4m3 bytes with one e8m0 power-of-two scale per 32 k of a row -- on
+// v_mfma_scale_f32_32x32x64_f8f6f4, which applies both block scales inside the instruction.
+//
+// Operand layout of the instruction (fp8 x fp8, measured with one-hot rows and per-block scales):
+// lane l supplies row (A) / column (B) l % 32; its VGPRs 0-3 hold k = 16 (l / 32) .. + 15 and its
+// VGPRs 4-7 k = 32 + 16 (l / 32) .. + 15 of the MFMA's 64.  The scale operand is a dword whose byte
+// op_sel picks; the byte of lane l scales k-block l / 32 (k = 32 (l / 32) .. + 31), i.e. one MX block,
+// whose values sit in the SAME register half of the two lanes l % 32 and l % 32 + 32.
+//
+// Work split: a workgroup of 8 waves computes BM (128 | 256) rows x 256 columns; every wave owns 32
+// columns for all BM rows (BM / 32 accumulator fragments of 16 f32).  K runs in stages of 128 (two
+// MFMAs per fragment), two stages per 256-k super-block.
+//   W  never touches LDS: requant_mx8_kernel lays each wave's B operand of a 64-k block out as 2 KB
+//      in fragment order, so a stage is four 1 KB wave loads global -> VGPR, one stage ahead.  The
+//      column's 8 scale bytes of a super-block arrive as one dword per lane, already ordered so that
+//      op_sel = 2 q + kk (stage q, MFMA kk) selects the lane's block.
+//   X  (e4m3 rows, 128 B per row per stage) is shared by the 8 waves through LDS: global -> VGPR one
+//      stage ahead, ds_write into the other of two stage buffers behind the MFMAs, one barrier per
+//      stage.  Rows keep gemm3's 16-byte chunk swizzle (g3_off), so a fragment's two ds_read_b128 are
+//      bank-conflict free.  The rows' scale dwords (4 blocks of the stage) ride along in the stage
+//      buffer; a lane shifts its dword by 8 (l / 32), so op_sel = 2 kk selects its k-block.
+// The global loads and the LDS writes are plain C++ (the compiler's own vmcnt waits: the prefetch
+// registers are written at the top of a stage and first read behind its MFMAs); the LDS reads are
+// asm with counted lgkmcnt waits, one fragment ahead of the MFMAs.
+// EPI_ATOMIC splits the super-block range over blockIdx.y; epilogues and output layouts are gemm3's
+// (SwiGLU: tile rows 0-7 gate, 8-15 up of the same 8 outputs).
+#include "kcommon.h"
+#include "mx8.h"
+#include "gemm_lds.h"
+#include "../runtime/kernels_api.h"
+#include "../runtime/tuning.h"
+
+#include <algorithm>
+#include <stdexcept>
+
+namespace mpk {
+using namespace mp;
+
+typedef int i32x8 __attribute__((ext_vector_type(8)));
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+
+template <int OFF>   // ds_read_b32 with an immediate byte offset (asm, as gemm_lds.h's ds_b128o)
+__device__ __forceinline__ void ds_b32o(uint32_t& v, uint32_t addr) {
+  static_assert(OFF >= 0 && OFF < 65536, "ds offset");
+  asm volatile("ds_read_b32 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "i"(OFF) : "memory");
+}
+
+// f16 rows -> MX-FP8 rows: one workgroup per row, 8 f16 (one 16-byte load) per lane per step, so a
+// block is 4 adjacent lanes (cross-lane max), 8-byte stores, one scale byte per block
+__global__ __launch_bounds__(256) void quant_rows_mx8_kernel(const f16* X, int ldx, int K, uint8_t* Q, int ldq, uint8_t* S,
+                                                             int lds) {
+  const int m = blockIdx.x, tid = threadIdx.x;
+  const f16* x = X + (size_t)m * ldx;
+  for (int k = tid * 8; k < K; k += 2048) {   // K % 32 == 0: the 4 lanes of a block run the same trips
+    const half8_t v = *reinterpret_cast<const half8_t*>(x + k);
+    float mx = amax8(v);
+    mx = fmaxf(mx, __shfl_xor(mx, 1));
+    mx = fmaxf(mx, __shfl_xor(mx, 2));
+    const uint32_t e = mx8_scale_e(mx);
+    *reinterpret_cast<u32x2*>(Q + (size_t)m * ldq + k) = mx8_pack8(v, mx8_scale_f32(e));
+    if ((tid & 3) == 0) S[(size_t)m * lds + (k >> 5)] = (uint8_t)e;
+  }
+}
+
+// Dense f16 weight -> the GEMM's B image (kernels_api.h): one lane per (column, 32-k block b of the
+// chunk's two); the block's halves go to register half b of the lanes col and col + 32, so a wave
+// writes one 2 KB chunk as two stores of 2 x 512 B
+__global__ __launch_bounds__(256) void requant_mx8_kernel(const f16* W, int ldw, int n, int nsb, int nchunks, uint8_t* out,
+                                                          uint8_t* scales) {
+  const int chunk = blockIdx.x * 4 + (threadIdx.x >> 6), l = threadIdx.x & 63;
+  if (chunk >= nchunks) return;
+  const int nkb = 4 * nsb, c = chunk / nkb, kb = chunk - c * nkb;
+  const int col = 32 * c + (l & 31), k0 = 64 * kb + 32 * (l >> 5);
+  half8_t v[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    if (col < n) v[j] = *reinterpret_cast<const half8_t*>(W + (size_t)col * ldw + k0 + 8 * j);
+    else v[j] = half8_t{0, 0, 0, 0, 0, 0, 0, 0};
+  }
+  const uint32_t e = mx8_scale_e(fmaxf(fmaxf(amax8(v[0]), amax8(v[1])), fmaxf(amax8(v[2]), amax8(v[3]))));
+  const float s = mx8_scale_f32(e);
+  uint8_t* dst = out + (size_t)chunk * 2048 + 1024 * (l >> 5) + (l & 31) * 16;
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {   // k-half h of the block: lane 32 h + col % 32
+    const u32x2 a = mx8_pack8(v[2 * h], s), b = mx8_pack8(v[2 * h + 1], s);
+    *reinterpret_cast<u32x4*>(dst + 512 * h) = u32x4{a.x, a.y, b.x, b.y};
+  }
+  scales[((size_t)(c * nsb + (kb >> 2)) * 64 + l) * 4 + (kb & 3)] = (uint8_t)e;
+}
+
+template <int EPI, int BM>
+__global__ __launch_bounds__(512) void gemm_mx_kernel(const Mx8Params p, const int n_mb, const int sb_per_split) {
+  constexpr int FM = BM / 32;        // accumulator fragments (32 rows each) per wave
+  constexpr int AP = BM / 64;        // 16-byte x pieces per thread per stage
+  constexpr int A_BYTES = BM * 128, STAGE = A_BYTES + 2048;   // x rows + a scale dword slot per thread (BM used)
+  __shared__ __attribute__((aligned(16))) char smem[2 * STAGE];
+
+  const int tid = threadIdx.x, lane = tid & 63, cl = lane & 31, h = lane >> 5;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  // XCD-aware logical id (bijective for any grid size): the row blocks of one column group share an XCD
+  const int nwg = gridDim.x, bx = blockIdx.x;
+  const int xcd = bx & 7, q8 = nwg >> 3, r8 = nwg & 7;
+  const int lid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bx >> 3);
+  const int cg = lid / n_mb, mb = lid - cg * n_mb;
+  const int m0 = mb * BM, M = p.M;
+  const int sb_begin = blockIdx.y * sb_per_split, sb_end = min(sb_begin + sb_per_split, p.nsb);
+  if (sb_begin >= sb_end) return;   // uniform over the workgroup
+
+  // this wave's 32 columns: group grp of the B image (clamped: a wave past the last group computes a
+  // copy of it and stores nothing)
+  const int grp = min(cg * 8 + wave, (p.ntiles + 1) / 2 - 1);
+  const uint8_t* wb = p.W + (size_t)grp * p.nsb * 8192 + lane * 16;
+  const uint32_t* wsp = reinterpret_cast<const uint32_t*>(p.wscale) + (size_t)grp * p.nsb * 64 + lane;
+  // x piece i of this thread: row (tid + 512 i) >> 3, 16-byte chunk tid & 7 (rows clamped to M - 1)
+  const int xrow = tid >> 3, xch = tid & 7;
+  // (threads >= BM fetch a clamped row's dword into their own, unread slot: no branch in the loop, which
+  // would split its block and let the MFMAs sink past the scheduling fences)
+  const uint8_t* xsa = p.xscale + (size_t)min(m0 + min(tid, BM - 1), M - 1) * p.ldxs;
+
+  // stage s (128 k): this thread's x pieces and x scale dword, this lane's four B half-fragments
+  auto fetch = [&](int s, u32x4 (&a)[AP], uint32_t& as, u32x4 (&b)[4]) {
+#pragma unroll
+    for (int i = 0; i < AP; ++i) a[i] = ld16(p.X + (size_t)min(m0 + xrow + 64 * i, M - 1) * p.ldx + 16 * xch + (size_t)s * 128);
+    as = *reinterpret_cast<const uint32_t*>(xsa + 4 * s);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) b[j] = ld16(wb + (size_t)s * 4096 + 1024 * j);
+  };
+  auto store_a = [&](int buf, const u32x4 (&a)[AP], uint32_t as) {
+    char* A = smem + buf * STAGE;
+#pragma unroll
+    for (int i = 0; i < AP; ++i) *reinterpret_cast<u32x4*>(A + g3_off(xrow + 64 * i, xch)) = a[i];
+    reinterpret_cast<uint32_t*>(A + A_BYTES)[tid] = as;
+  };
+
+  f32x16 acc[FM];
+#pragma unroll
+  for (int i = 0; i < FM; ++i)
+#pragma unroll
+    for (int v = 0; v < 16; ++v) acc[i][v] = 0.f;
+
+  // stage q of a super-block from buffer q: fragment i's rows 32 i + cl; MFMA kk's register half e holds
+  // k = 64 kk + 32 e + 16 h .. + 15 (chunk 4 kk + 2 e + h of the row).
+  // Row 32 i + cl has the swizzle of cl, so a lane's four chunk addresses (MFMA kk, register half e)
+  // are fixed and fragment / buffer are immediate offsets.  The LDS reads are asm (ds_b128o): left to
+  // the compiler, every fragment's reads are hoisted to the top of the stage (16 VGPRs each, 300
+  // spilled); fragment i + 1 is read ahead of fragment i's two MFMAs under a counted lgkmcnt.
+  uint32_t fa[4];
+#pragma unroll
+  for (int c = 0; c < 4; ++c) fa[c] = lds_addr(smem) + g3_off(cl, 4 * (c >> 1) + 2 * (c & 1) + h);
+  const uint32_t sa = lds_addr(smem) + A_BYTES + 4 * cl;
+  auto compute = [&](auto qc, const u32x4 (&b)[4], uint32_t wsc) {
+    constexpr int Q = decltype(qc)::value;
+    i32x8 bf[2];
+#pragma unroll
+    for (int kk = 0; kk < 2; ++kk) {
+      const u32x4 bl = b[2 * kk], bh = b[2 * kk + 1];
+      bf[kk] = i32x8{(int)bl.x, (int)bl.y, (int)bl.z, (int)bl.w, (int)bh.x, (int)bh.y, (int)bh.z, (int)bh.w};
+    }
+    u32x4 fr[2][4];
+    uint32_t asc[2];
+    auto read = [&](auto ic, u32x4 (&f)[4], uint32_t& sc) {   // 5 LDS reads
+      constexpr int I = decltype(ic)::value;
+      ds_b32o<Q * STAGE + 128 * I>(sc, sa);
+      static_for<4>([&](auto cc) { ds_b128o<Q * STAGE + 4096 * I>(f[decltype(cc)::value], fa[decltype(cc)::value]); });
+    };
+    read(std::integral_constant<int, 0>{}, fr[0], asc[0]);
+    static_for<FM>([&](auto ic) {
+      constexpr int I = decltype(ic)::value;
+      if constexpr (I + 1 < FM) {
+        read(std::integral_constant<int, I + 1>{}, fr[(I + 1) & 1], asc[(I + 1) & 1]);
+        wait_lgkm<5>();   // fragment I in, I + 1's five reads in flight
+      } else {
+        wait_lgkm<0>();
+      }
+      const int as_i = (int)(asc[I & 1] >> (8 * h));
+      static_for<2>([&](auto kc) {
+        constexpr int KK = decltype(kc)::value;
+        const u32x4 lo = fr[I & 1][2 * KK], hi = fr[I & 1][2 * KK + 1];
+        const i32x8 af = {(int)lo.x, (int)lo.y, (int)lo.z, (int)lo.w, (int)hi.x, (int)hi.y, (int)hi.z, (int)hi.w};
+        acc[I] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(af, bf[KK], acc[I], 0, 0, 2 * KK, as_i, 2 * Q + KK, (int)wsc);
+      });
+      __builtin_amdgcn_sched_barrier(0);   // the next fragment's reads stay behind these MFMAs
+    });
+  };
+
+  u32x4 an[AP], b[2][4];
+  uint32_t asn, wsc = wsp[(size_t)sb_begin * 64];
+  fetch(2 * sb_begin, an, asn, b[0]);
+  store_a(0, an, asn);
+  __syncthreads();
+  for (int sb = sb_begin; sb < sb_end; ++sb) {
+    fetch(2 * sb + 1, an, asn, b[1]);
+    compute(std::integral_constant<int, 0>{}, b[0], wsc);
+    store_a(1, an, asn);   // buffer 1's last readers passed the barrier that ended the previous stage
+    __syncthreads();
+    const int nx = min(sb + 1, sb_end - 1);   // (the last trip re-reads its own super-block: in bounds, unused)
+    fetch(2 * nx, an, asn, b[0]);
+    const uint32_t wsn = wsp[(size_t)nx * 64];
+    compute(std::integral_constant<int, 1>{}, b[1], wsc);
+    store_a(0, an, asn);
+    __syncthreads();
+    wsc = wsn;
+  }
+
+  // epilogue: lane holds C[row 32 i + 8 (v >> 2) + 4 h + (v & 3)][col cl] of the wave's 32 columns
+  const int rowb = m0 + 4 * h;
+  const int n = (cg * 8 + wave) * 32 + cl;
+  if constexpr (EPI == EPI_SWIGLU) {
+    const int o = (n >> 4) * 8 + (cl & 15);   // tile rows 0-7 gate, 8-15 up of the same 8 outputs
+#pragma unroll
+    for (int i = 0; i < FM; ++i)
+#pragma unroll
+      for (int v = 0; v < 16; ++v) {
+        const float other = __shfl_xor(acc[i][v], 8);
+        const int m = rowb + 32 * i + 8 * (v >> 2) + (v & 3);
+        if ((cl & 8) == 0 && m < M && o < p.n_valid) p.H[(size_t)m * p.ldh + o] = sat_f16(silu(acc[i][v]) * other);
+      }
+  } else if (n < p.n_valid) {
+#pragma unroll
+    for (int i = 0; i < FM; ++i)
+#pragma unroll
+      for (int v = 0; v < 16; ++v) {
+        const int m = rowb + 32 * i + 8 * (v >> 2) + (v & 3);
+        if (m < M) {
+          float* dst = p.Y + (size_t)m * p.ldy + n;
+          if constexpr (EPI == EPI_ATOMIC) unsafeAtomicAdd(dst, acc[i][v]);
+          else *dst = acc[i][v];
+        }
+      }
+  }
+}
+
+}  // namespace mpk
+
+namespace mp {
+
+void launch_quant_rows_mx8(const f16* X, int ldx, int M, int K, uint8_t* Q, int ldq, uint8_t* S, int lds, hipStream_t st) {
+  if (M <= 0 || K <= 0 || (K & 31) || (ldx & 7) || (ldq & 7) || ldx < K || ldq < K || lds < K / 32 ||
+      (reinterpret_cast<uintptr_t>(X) & 15) || (reinterpret_cast<uintptr_t>(Q) & 7))
+    throw std::runtime_error("quant_rows_mx8: K must be a multiple of 32, rows 16-byte aligned");
+  hipLaunchKernelGGL(mpk::quant_rows_mx8_kernel, dim3(M), dim3(256), 0, st, X, ldx, K, Q, ldq, S, lds);
+}
+
+void launch_requant_mx8(const f16* W, int ldw, int n, int ntiles, int nsb, uint8_t* out, uint8_t* scales, hipStream_t st) {
+  if (n <= 0 || n > ntiles * 16 || nsb <= 0 || ldw < nsb * 256 || (ldw & 7) || (reinterpret_cast<uintptr_t>(W) & 15) ||
+      (reinterpret_cast<uintptr_t>(out) & 15))
+    throw std::runtime_error("requant_mx8: bad weight shape or alignment");
+  const int nchunks = mx8_groups(ntiles) * 4 * nsb;
+  hipLaunchKernelGGL(mpk::requant_mx8_kernel, dim3((nchunks + 3) / 4), dim3(256), 0, st, W, ldw, n, nsb, nchunks, out,
+                     scales);
+}
+
+template <int EPI, int BM>
+static void gemm_mx_go(const Mx8Params& p, bool allow_split, hipStream_t st) {
+  const int n_cg = (p.ntiles + 15) / 16, n_mb = (p.M + BM - 1) / BM, wgs = n_cg * n_mb;
+  int nsplit = 1;
+  // split-K by gemm3's rule: fill the grid up to the split target, >= 1024 k (4 super-blocks) per split
+  const int split_wg = knob(KNOB_GEMM2_SPLIT_WG);
+  if (EPI == EPI_ATOMIC && allow_split && wgs < split_wg) nsplit = std::max(1, std::min(split_wg / wgs, p.nsb / 4));
+  const int per = (p.nsb + nsplit - 1) / nsplit;
+  nsplit = (p.nsb + per - 1) / per;
+  hipLaunchKernelGGL((mpk::gemm_mx_kernel<EPI, BM>), dim3(wgs, nsplit), dim3(512), 0, st, p, n_mb, per);
+}
+
+template <int EPI>
+static void gemm_mx_shape(const Mx8Params& p, bool allow_split, hipStream_t st) {
+  // 128-row tiles when one holds M, or when 256-row tiles would leave more than half the CUs without
+  // a workgroup and the epilogue cannot split K to fill them
+  const int wg256 = (p.ntiles + 15) / 16 * ((p.M + 255) / 256);
+  const bool splits = EPI == EPI_ATOMIC && allow_split;
+  if (p.M <= 128 || (wg256 < 128 && !splits)) gemm_mx_go<EPI, 128>(p, allow_split, st);
+  else gemm_mx_go<EPI, 256>(p, allow_split, st);
+}
+
+void launch_gemm_mx8(int epi, const Mx8Params& p, hipStream_t st, bool allow_split) {
+  const bool swiglu = epi == EPI_SWIGLU;
+  if (p.M <= 0 || p.ntiles <= 0 || p.nsb <= 0 || p.ldx < p.nsb * 256 || (p.ldx & 15) || p.ldxs < p.nsb * 8 || (p.ldxs & 3) ||
+      (reinterpret_cast<uintptr_t>(p.X) & 15) || (reinterpret_cast<uintptr_t>(p.xscale) & 3) ||
+      (reinterpret_cast<uintptr_t>(p.W) & 15) || (reinterpret_cast<uintptr_t>(p.wscale) & 3) || !(swiglu ? (void*)p.H : (void*)p.Y) ||
+      p.n_valid > (swiglu ? p.ntiles * 8 : p.ntiles * 16))
+    throw std::runtime_error("gemm_mx8: bad operand shape or alignment");
+  switch (epi) {
+    case EPI_STORE: return gemm_mx_shape<EPI_STORE>(p, allow_split, st);
+    case EPI_ATOMIC: return gemm_mx_shape<EPI_ATOMIC>(p, allow_split, st);
+    case EPI_SWIGLU: return gemm_mx_shape<EPI_SWIGLU>(p, allow_split, st);
+    default: throw std::runtime_error("gemm_mx8: unknown epilogue");
+  }
+}
+
+}  // namespace mp

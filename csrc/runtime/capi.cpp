@@ -319,6 +319,35 @@ int mp_op_gemm3_i8(int epi, const void* W, int ntiles, int nsb, const void* Q, i
   API_CATCH(-1)
 }
 
+// MX-FP8 GEMM mode (gemm_mx.hip): X f16 [M][ldx] -> e4m3 rows Q [M][ldq] + e8m0 block scales S [M][lds];
+// a dense f16 weight -> the GEMM's operand image; Y = X W^T on v_mfma_scale_f32_32x32x64_f8f6f4
+int mp_op_quant_mx8(const void* X, int ldx, int M, int K, void* Q, int ldq, void* S, int lds, void* stream) {
+  API_TRY
+  launch_quant_rows_mx8((const f16*)X, ldx, M, K, (uint8_t*)Q, ldq, (uint8_t*)S, lds, (hipStream_t)stream);
+  HIP_OK(hipGetLastError());
+  return 0;
+  API_CATCH(-1)
+}
+
+int mp_op_requant_mx8(const void* W, int ldw, int n, int ntiles, int nsb, void* out, void* scales, void* stream) {
+  API_TRY
+  launch_requant_mx8((const f16*)W, ldw, n, ntiles, nsb, (uint8_t*)out, (uint8_t*)scales, (hipStream_t)stream);
+  HIP_OK(hipGetLastError());
+  return 0;
+  API_CATCH(-1)
+}
+
+int mp_op_gemm_mx8(int epi, const void* W, const void* ws, int ntiles, int nsb, const void* Q, int ldq, const void* S, int lds,
+                   int M, void* Y, int ldy, void* H, int ldh, int n_valid, int allow_split, void* stream) {
+  API_TRY
+  const Mx8Params p{(const uint8_t*)W, (const uint8_t*)ws, (const uint8_t*)Q, ldq, (const uint8_t*)S, lds, M,
+                    (float*)Y, ldy, (f16*)H, ldh, ntiles, nsb, n_valid};
+  launch_gemm_mx8(epi, p, (hipStream_t)stream, allow_split != 0);
+  HIP_OK(hipGetLastError());
+  return 0;
+  API_CATCH(-1)
+}
+
 int mp_set_knob(const char* name, int value) {
   API_TRY
   set_knob(name, value);

@@ -117,21 +117,30 @@ double i8_copy_bytes(int t, int64_t n, int64_t k) {
   return np * kp + np * 4;
 }
 
-double synth_layer_i8_bytes(const ModelConfig& c, const std::string& ftype, int li) {
+// mx8_gemm (HipStage::build_mx8_copies): the same matrices as MX-FP8, one e4m3 byte per weight plus
+// one e8m0 scale byte per 32, rows padded to the GEMM's 32-column groups: (1 + 1/32) B per padded weight
+double mx8_copy_bytes(int t, int64_t n, int64_t k) {
+  if (t == T_F32 || t == T_F16 || t == T_BF16) return 0;
+  const double np = (double)((n + 31) / 32 * 32), kp = (double)((k + 255) / 256 * 256);
+  return np * kp * 33.0 / 32.0;
+}
+
+using CopyBytes = double (*)(int, int64_t, int64_t);
+
+double synth_layer_copy_bytes(const ModelConfig& c, const std::string& ftype, int li, CopyBytes cb) {
   if (c.n_expert > 0) return 0;   // MoE experts keep their own kernels (no copy)
   const SyntheticTypes t = SyntheticTypes::from_ftype(ftype, li, c.n_layer);
   const int64_t d = c.d_model, q = c.q_dim(), kv = c.kv_dim(), f = c.d_ff;
-  return i8_copy_bytes(t.q, q, d) + i8_copy_bytes(t.k, kv, d) + i8_copy_bytes(t.v, kv, d) + i8_copy_bytes(t.o, d, q) +
-         i8_copy_bytes(t.gate, f, d) + i8_copy_bytes(t.up, f, d) + i8_copy_bytes(t.down, d, f);
+  return cb(t.q, q, d) + cb(t.k, kv, d) + cb(t.v, kv, d) + cb(t.o, d, q) + cb(t.gate, f, d) + cb(t.up, f, d) + cb(t.down, d, f);
 }
 
-double gguf_layer_i8_bytes(const GgufFile& g, int li) {
+double gguf_layer_copy_bytes(const GgufFile& g, int li, CopyBytes cb) {
   double b = 0;
   const std::string p = "blk." + std::to_string(li) + ".";
-  if (g.tensor(p + "ffn_gate_inp.weight")) return 0;   // MoE layer: build_i8_copies skips it whole
+  if (g.tensor(p + "ffn_gate_inp.weight")) return 0;   // MoE layer: build_i8_copies / build_mx8_copies skip it whole
   for (const char* nm : {"attn_q", "attn_k", "attn_v", "attn_output", "ffn_gate", "ffn_up", "ffn_down"}) {
     const GgufTensor* t = g.tensor(p + nm + ".weight");
-    if (t && t->ne.size() >= 2) b += i8_copy_bytes(t->type, t->ne[1], t->ne[0]);
+    if (t && t->ne.size() >= 2) b += cb(t->type, t->ne[1], t->ne[0]);
   }
   return b;
 }
@@ -162,9 +171,12 @@ Engine::Engine(const Json& j) : jcfg_(j) {
   const uint64_t seed = (uint64_t)j.get_num("seed", 1234);
 
   std::vector<double> layer_cost;
-  std::vector<double> layer_extra;   // HBM bytes per layer beyond its weights (int8_gemm copies)
-  const bool i8_copies = j.get_bool("int8_gemm", false) && j.get_bool("prefill_gemm", true) &&
-                         j.get_str("backend", "hip") != "cpu";
+  std::vector<double> layer_extra;   // HBM bytes per layer beyond its weights (int8_gemm / mx8_gemm copies)
+  if (j.get_bool("int8_gemm", false) && j.get_bool("mx8_gemm", false))
+    throw std::runtime_error("int8_gemm and mx8_gemm are mutually exclusive");
+  const bool copies_on = j.get_bool("prefill_gemm", true) && j.get_str("backend", "hip") != "cpu";
+  const CopyBytes copy_bytes = !copies_on ? nullptr : j.get_bool("int8_gemm", false) ? i8_copy_bytes :
+                               j.get_bool("mx8_gemm", false) ? mx8_copy_bytes : nullptr;
   double head_cost = 0, embd_cost = 0;
   if (j.has("gguf")) {
     gguf_.reset(new GgufFile(j.get_str("gguf", "")));
@@ -175,7 +187,7 @@ Engine::Engine(const Json& j) : jcfg_(j) {
       for (auto& t : gguf_->tensors())
         if (t.name.compare(0, p.size(), p) == 0) bytes += (double)t.nbytes;
       layer_cost.push_back(bytes);
-      layer_extra.push_back(i8_copies ? gguf_layer_i8_bytes(*gguf_, li) : 0.0);
+      layer_extra.push_back(copy_bytes ? gguf_layer_copy_bytes(*gguf_, li, copy_bytes) : 0.0);
     }
     const GgufTensor* out = gguf_->tensor("output.weight");
     head_cost = (double)(out ? out->nbytes : gguf_->tensor("token_embd.weight")->nbytes);
@@ -183,7 +195,7 @@ Engine::Engine(const Json& j) : jcfg_(j) {
     cfg_ = config_from_json(j["synthetic"]);
     for (int li = 0; li < cfg_.n_layer; ++li) {
       layer_cost.push_back(synth_layer_bytes(cfg_, ftype, li));
-      layer_extra.push_back(i8_copies ? synth_layer_i8_bytes(cfg_, ftype, li) : 0.0);
+      layer_extra.push_back(copy_bytes ? synth_layer_copy_bytes(cfg_, ftype, li, copy_bytes) : 0.0);
     }
     const SyntheticTypes t = SyntheticTypes::from_ftype(ftype, 0, cfg_.n_layer);
     head_cost = (double)cfg_.vocab * cfg_.d_model * block_bytes(t.out) / block_elems(t.out);
@@ -407,6 +419,7 @@ Engine::Engine(const Json& j) : jcfg_(j) {
   so.prefill_gemm_v = j.get_int("prefill_gemm_v", 0);
   so.gemm_splitk_store = j.get_bool("gemm_splitk_store", true);
   so.int8_gemm = j.get_bool("int8_gemm", false);
+  so.mx8_gemm = j.get_bool("mx8_gemm", false);
   so.deterministic = j.get_bool("deterministic", false);
   so.prefill_flash = j.get_bool("prefill_flash", true);
   so.kv_fp8 = j.get_str("kv_dtype", "f16") == "fp8";

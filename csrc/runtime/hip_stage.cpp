@@ -469,9 +469,47 @@ void HipStage::build_i8_copies() {
   MP_LOGI("stage %d: int8_gemm: %.2f GiB of per-row int8 weight copies", spec_.stage, bytes / 1073741824.0);
 }
 
+// mx8_gemm: an MX-FP8 copy of every quantized projection (the wide GEMMs then run gemm_mx_kernel):
+// unpacked to dense f16 like the int8 copies, re-quantized per 32-k block into the GEMM's operand image
+void HipStage::build_mx8_copies() {
+  auto each = [&](const std::function<void(PackedMat&)>& f) {
+    for (LayerW& L : layers_) {
+      if (L.moe) continue;
+      for (MatSeg& sg : L.qkv) f(sg.m);
+      f(L.wo);
+      if (L.fused_gateup) f(L.gateup);
+      else { f(L.gate); f(L.up); }
+      f(L.down);
+    }
+  };
+  size_t maxe = 0;
+  each([&](PackedMat& m) {
+    if (m.d && !is16(m.ptype)) maxe = std::max(maxe, (size_t)m.dims.ntiles * 16 * m.dims.nsb * 256);
+  });
+  if (!maxe) return;
+  f16* tmp = nullptr;
+  HIP_OK(hipMalloc(&tmp, maxe * 2));
+  size_t bytes = 0;
+  each([&](PackedMat& m) {
+    if (!m.d || is16(m.ptype)) return;
+    const int nt = (int)m.dims.ntiles, nsb = (int)m.dims.nsb;
+    launch_unpack(m.ptype, m.d, nt, nsb, tmp, nsb * 256, stream_);
+    m.mx = (uint8_t*)dmalloc(mx8_weight_bytes(nt, nsb));
+    m.mx_s = (uint8_t*)dmalloc(mx8_scale_bytes(nt, nsb));
+    launch_requant_mx8(tmp, nsb * 256, (int)m.dims.N, nt, nsb, m.mx, m.mx_s, stream_);
+    bytes += mx8_weight_bytes(nt, nsb) + mx8_scale_bytes(nt, nsb);
+  });
+  HIP_OK(hipStreamSynchronize(stream_));
+  HIP_OK(hipFree(tmp));
+  weight_bytes_ += bytes;
+  MP_LOGI("stage %d: mx8_gemm: %.2f GiB of MX-FP8 weight copies", spec_.stage, bytes / 1073741824.0);
+}
+
 void HipStage::alloc_runtime() {
   HIP_OK(hipSetDevice(spec_.device));
+  if (opt_.int8_gemm && opt_.mx8_gemm) throw std::runtime_error("int8_gemm and mx8_gemm are mutually exclusive");
   if (opt_.int8_gemm && opt_.prefill_gemm) build_i8_copies();
+  if (opt_.mx8_gemm && opt_.prefill_gemm) build_mx8_copies();
   // MoE routers as dense f16 (E x d x 2 B per layer: 64 KB at Mixtral): the router-logits kernel
   // reads them row-major, one launch of M / 4 workgroups for any micro-batch width
   for (LayerW& L : layers_) {
@@ -493,10 +531,11 @@ void HipStage::alloc_runtime() {
     return p;
   };
   xn_ = (f16*)zalloc((size_t)scratch_rows_ * Kd_ * 2);
-  if (opt_.int8_gemm && opt_.prefill_gemm && std::max(B, opt_.prefill_chunk) > 64) {
+  if ((opt_.int8_gemm || opt_.mx8_gemm) && opt_.prefill_gemm && std::max(B, opt_.prefill_chunk) > 64) {
     xq_ld_ = std::max({Kd_, Ko_, Kff_});
     xq_ = (int8_t*)zalloc((size_t)scratch_rows_ * xq_ld_);
-    xqs_ = (float*)zalloc((size_t)scratch_rows_ * 4);
+    if (opt_.mx8_gemm) xqe_ = (uint8_t*)zalloc((size_t)scratch_rows_ * (xq_ld_ / 32));
+    else xqs_ = (float*)zalloc((size_t)scratch_rows_ * 4);
   }
   attn_ = (f16*)zalloc((size_t)scratch_rows_ * Ko_ * 2);
   h_ = (f16*)zalloc((size_t)scratch_rows_ * Kff_ * 2);
@@ -891,6 +930,7 @@ HipStage::GemmRoute HipStage::gemm_route(const MatCall& c) const {
   }
   if (c.M <= 64 || !opt_.prefill_gemm) return GemmRoute::GEMV;
   if (m.i8 && xq_ && c.X) return GemmRoute::I8;
+  if (m.mx && xqe_ && c.X) return GemmRoute::MX8;
   const int gv = opt_.prefill_gemm_v == 2 ? 4 : opt_.prefill_gemm_v != 0 ? opt_.prefill_gemm_v : is16(m.ptype) ? 3 : 4;
   if (gv == 4 && gemm4_supported(m.ptype)) return GemmRoute::GEMM4;
   if (gv == 3) return GemmRoute::GEMM3;
@@ -959,6 +999,18 @@ void HipStage::gemv(const MatCall& c, hipStream_t st) {
       launch_gemm3(P_I8, c.epi, p, st, atomics);
       return;
     }
+    case GemmRoute::MX8: {
+      // mx8_gemm: x rows quantized per 32-k block, scaled fp8 MFMA against the MX-FP8 copy (gemm_mx_kernel)
+      if (c.X != xq_src_ || c.M != xq_rows_) {   // not already quantized by norm_x / the previous GEMM on X
+        launch_quant_rows_mx8(c.X, c.ldx, c.M, p.nsb * 256, reinterpret_cast<uint8_t*>(xq_), xq_ld_, xqe_, xq_ld_ / 32, st);
+        xq_src_ = c.X;
+        xq_rows_ = c.M;
+      }
+      Mx8Params q{m.mx, m.mx_s, reinterpret_cast<const uint8_t*>(xq_), xq_ld_, xqe_, xq_ld_ / 32, c.M,
+                  p.Y, p.ldy, p.H, p.ldh, p.ntiles, p.nsb, p.n_valid};
+      launch_gemm_mx8(c.epi, q, st, atomics);
+      return;
+    }
     case GemmRoute::GEMM4:
       if (!r.g4.ok) throw std::runtime_error("gemv: no gemm4 launch plan for this projection");
       if (!r.store) return run_gemm4(m.ptype, r.g4, c.epi, p, st);
@@ -1003,11 +1055,12 @@ void HipStage::norm_x(float* x, const float* w, int M, float* zero, int64_t zero
                       int bias_n) {
   const int d = cfg_.d_model;
   const bool pend = sk_pend_.x == x && sk_pend_.M == M && sk_pend_.n == d && sk_pend_.ldy == d;
-  // int8_gemm: the wide GEMMs reading xn_ take its int8 rows from this launch (no separate quant)
-  const bool q8 = xq_ && M > 64 && M <= scratch_rows_;
+  // int8_gemm / mx8_gemm: the wide GEMMs reading xn_ take its quantized rows from this launch (no separate quant)
+  const bool q8 = xq_ && M > 64 && M <= scratch_rows_ && (!xqe_ || (d & 31) == 0);   // (MX blocks: whole in d)
   if ((pend || q8) && d <= 8192 && (d & 3) == 0) {
     launch_rmsnorm_acc(x, d, w, d, cfg_.eps, xn_, Kd_, M, zero, zero_n, pend ? sk_part_ : nullptr, sk_pend_.ns,
-                       sk_pend_.ss, sk_pend_.ldp, st, bias, bias_n, q8 ? xq_ : nullptr, xq_ld_, q8 ? xqs_ : nullptr);
+                       sk_pend_.ss, sk_pend_.ldp, st, bias, bias_n, q8 ? xq_ : nullptr, xq_ld_,
+                       !q8 ? nullptr : xqe_ ? reinterpret_cast<float*>(xqe_) : xqs_, q8 && xqe_);
     if (pend) sk_pend_ = SkPending{};
     xq_src_ = q8 ? (const void*)xn_ : nullptr;
     xq_rows_ = M;

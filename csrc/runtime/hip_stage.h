@@ -62,6 +62,8 @@ struct PackedMat {
   PackedDims dims{};
   uint8_t* i8 = nullptr;    // int8_gemm: per-row int8 re-quantized copy (P_I8 chunks) ...
   float* i8_ws = nullptr;   // ... and its row scales
+  uint8_t* mx = nullptr;    // mx8_gemm: MX-FP8 re-quantized copy (launch_requant_mx8's image) ...
+  uint8_t* mx_s = nullptr;  // ... and its e8m0 block scales
   size_t bytes() const { return dims.bytes; }
 };
 
@@ -219,7 +221,10 @@ class HipStage : public Stage {
   // Qwen3: per-head RMSNorm of the q and k heads of the complete q|k|v rows in qkv_ (no-op without weights)
   void qk_norm(const LayerW& L, int M, hipStream_t st);
   void build_i8_copies();
-  int8_t* xq_ = nullptr; float* xqs_ = nullptr; int xq_ld_ = 0;   // int8_gemm: quantized activation rows
+  void build_mx8_copies();
+  // int8_gemm: quantized activation rows and row scales; mx8_gemm: e4m3 rows in xq_, block scales in xqe_
+  int8_t* xq_ = nullptr; float* xqs_ = nullptr; int xq_ld_ = 0;
+  uint8_t* xqe_ = nullptr;   // [rows][xq_ld_ / 32] e8m0 bytes
   const void* xq_src_ = nullptr; int xq_rows_ = 0;   // the f16 rows xq_ currently holds (set by norm_x / the quant)
   bool attention_o(int li, const Fwd& f, float* x, bool pre = false);
   void attention(int li, const Fwd& f, bool qkv_deferred, bool pre = false);
@@ -243,7 +248,7 @@ class HipStage : public Stage {
   // stores split-K partials to sk_part_.  GEMV: the split count handed to launch_gemv, and whether the
   // splits store to det_part_ for the fixed-order reduction (deterministic mode).  part_n: floats of
   // stored partials, either way
-  enum class GemmRoute { I8, GEMM4, GEMM3, GEMM1, GEMV, GEMVS };
+  enum class GemmRoute { I8, MX8, GEMM4, GEMM3, GEMM1, GEMV, GEMVS };
   struct MatRoute {
     GemmRoute family = GemmRoute::GEMV;
     Gemm4Plan g4{}; bool store = false;

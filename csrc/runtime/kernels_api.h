@@ -140,11 +140,13 @@ void launch_rmsnorm(const float* x, int ldx, const float* w, int d, float eps, f
 // launch_rmsnorm that first adds nsplit split-K partials (part + s * ss + row * ldp) into x and
 // writes x back (gemm_splitk_store: the deferred reduction of the o / down GEMMs into the residual)
 // part may be null (nothing to absorb); q8 (optional): the normalised f16 row also quantized to int8
-// per row (q8 + row * ldq8, scale q8s[row]) for the int8_gemm consumer
+// per row (q8 + row * ldq8, scale q8s[row]) for the int8_gemm consumer; q8_mx: q8 takes the row's
+// MX-FP8 bytes instead (launch_quant_rows_mx8's rounding, d % 32 == 0) and q8s is its scale bytes,
+// ldq8 / 32 per row (the mx8_gemm consumer)
 void launch_rmsnorm_acc(float* x, int ldx, const float* w, int d, float eps, f16* out, int ldo, int M,
                         float* zero, int64_t zero_n, const float* part, int nsplit, int64_t ss, int ldp, hipStream_t st,
                         const float* bias = nullptr, int bias_n = 0, int8_t* q8 = nullptr, int ldq8 = 0,
-                        float* q8s = nullptr);
+                        float* q8s = nullptr, bool q8_mx = false);
 
 // Embedding pooling (pool.hip): the output RMSNorm of a prefill chunk's residual rows, pooled per
 // prompt.  Pooling ids are llama.cpp's (<arch>.pooling_type); rank is not implemented.
@@ -239,6 +241,33 @@ void launch_quant_rows_i8(const f16* X, int ldx, int M, int K, int8_t* Q, int ld
 // per-row int8 re-quantization of a dense f16 weight [n_pad][nsb * 256] (launch_unpack output) into
 // P_I8 chunks (4096 B per 16 rows x 256 k) + per-row scales ws[n_pad]
 void launch_requant_i8(const f16* W, int ldw, int n, int n_pad, int nsb, uint8_t* out, float* ws, hipStream_t st);
+
+// MX-FP8 GEMM mode (gemm_mx.hip; OCP MXFP8): a block is 32 consecutive k of one row, its scale an
+// e8m0 byte E (value 2^(E - 127)), the smallest power of two s with amax / s <= 448 (E = 127 for an
+// all-zero block), its elements OCP e4m3 bytes of x / s rounded to nearest even.
+// Rows: X f16 [M][ldx] -> Q [M][ldq] e4m3 bytes + S [M][lds] scale bytes (K / 32 per row; K % 32 == 0)
+void launch_quant_rows_mx8(const f16* X, int ldx, int M, int K, uint8_t* Q, int ldq, uint8_t* S, int lds, hipStream_t st);
+// Weights: dense f16 [n][ldw] (launch_unpack output; columns >= n of the image are zero blocks)
+// -> the GEMM's operand image.  Column group c (32 columns), 64-k block kb: 2 KB at
+// (c * 4 nsb + kb) * 2048, byte e * 1024 + l * 16 + j = column 32 c + l % 32, k 64 kb + 32 e +
+// 16 (l / 32) + j (register half e of lane l's MFMA B fragment: two 1 KB wave loads).  Scales: group c,
+// super-block sb: 256 B at (c * nsb + sb) * 256, byte 4 l + e = the scale of column 32 c + l % 32,
+// block 8 sb + 2 e + l / 32 (one dword per lane per 256 k; the MFMA's op_sel picks byte e)
+inline int mx8_groups(int ntiles) { return (ntiles + 1) / 2; }
+inline size_t mx8_weight_bytes(int ntiles, int nsb) { return (size_t)mx8_groups(ntiles) * nsb * 8192; }
+inline size_t mx8_scale_bytes(int ntiles, int nsb) { return (size_t)mx8_groups(ntiles) * nsb * 256; }
+void launch_requant_mx8(const f16* W, int ldw, int n, int ntiles, int nsb, uint8_t* out, uint8_t* scales, hipStream_t st);
+// Y[M][n] (+)= X W^T on v_mfma_scale_f32_32x32x64_f8f6f4; epilogues and output layouts as launch_gemm3
+struct Mx8Params {
+  const uint8_t* W; const uint8_t* wscale;   // launch_requant_mx8's images
+  const uint8_t* X; int ldx;                  // e4m3 rows [M][ldx] (nsb * 256 columns used)
+  const uint8_t* xscale; int ldxs;            // scale bytes [M][ldxs] (ldxs % 4 == 0)
+  int M;
+  float* Y; int ldy;                          // EPI_STORE / EPI_ATOMIC
+  f16* H; int ldh;                            // EPI_SWIGLU
+  int ntiles, nsb, n_valid;
+};
+void launch_gemm_mx8(int epi, const Mx8Params& p, hipStream_t st, bool allow_split = true);
 
 struct AttnParams {
   const f16* q;          // [M][Hq][Dp]

@@ -34,6 +34,8 @@ struct StageOptions {
   bool prefill_gemm = true; // prompt chunks > 16 rows: MFMA dequant-GEMM instead of 16-row GEMVs
   bool int8_gemm = false;   // M > 64 GEMMs on v_mfma_i32_16x16x64_i8: per-row int8 activations x per-row int8
                             // re-quantized weights (+1 B/weight of HBM; reduced precision, opt-in)
+  bool mx8_gemm = false;    // M > 64 GEMMs on v_mfma_scale_f32_32x32x64_f8f6f4: MX-FP8 activations x MX-FP8
+                            // re-quantized weights (+33/32 B/weight of HBM; reduced precision, opt-in; not with int8_gemm)
   bool gemm_splitk_store = true;   // M > 64 split-K GEMMs: per-split partial stores + a fixed-order reduction
                                    // (into the residual: absorbed by the next RMSNorm) instead of float atomics
   int prefill_gemm_v = 0;    // 0: auto (16-bit weights: gemm3; the quantized types gemm4 takes: gemm4; the rest: the

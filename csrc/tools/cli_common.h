@@ -153,6 +153,8 @@ inline void print_common_usage(FILE* f) {
           "  --kv-pool TOKENS          paged KV pool per stage;  --kv-dtype f16|fp8 (-ctk/-ctv) KV cache element type\n"
           "  --int8-gemm               batches > 64 rows on the int8 MFMA (per-row int8 activations and weights:\n"
           "                            faster, reduced precision);  --deterministic  bitwise-reproducible logits\n"
+          "  --mx8-gemm                batches > 64 rows on the scaled fp8 MFMA (MX-FP8 activations and weights, one\n"
+          "                            power-of-two scale per 32 values: reduced precision, robust to outlier channels)\n"
           "  --world N --rank R        one process per stage (multi-process / multi-host)\n"
           "  --next HOST --master HOST --base-port P   TCP ring neighbours (prima.cpp style)\n"
           "  --gpu-mem GiB [--force]   per-GPU memory budget (caps auto KV; fail if a stage exceeds it)\n"
@@ -241,6 +243,7 @@ inline CliOptions parse_cli(int argc, char** argv,
       e["kv_dtype"] = val();                                                     // f16 | fp8 (K and V together)
     else if (a == "--force") e["force"] = true;
     else if (a == "--int8-gemm") e["int8_gemm"] = true;
+    else if (a == "--mx8-gemm") e["mx8_gemm"] = true;
     else if (a == "--deterministic") e["deterministic"] = true;
     else if (a == "--base-port") e["base_port"] = std::atoi(val().c_str());
     else if (a == "--rpc") rpc = val();

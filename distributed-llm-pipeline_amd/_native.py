@@ -66,6 +66,10 @@ _SIGS = {
     "mp_op_quant_i8": ([c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p], c_int),
     "mp_op_gemm3_i8": ([c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int,
                         c_void_p, c_void_p, c_int, c_void_p], c_int),
+    "mp_op_quant_mx8": ([c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p], c_int),
+    "mp_op_requant_mx8": ([c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p], c_int),
+    "mp_op_gemm_mx8": ([c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_int,
+                        c_void_p, c_int, c_int, c_int, c_void_p], c_int),
     "mp_set_knob": ([c_char_p, c_int], c_int),
     "mp_reset_knob": ([c_char_p], c_int),
     "mp_op_unpack": ([c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p], c_int),

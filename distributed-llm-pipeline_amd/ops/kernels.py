@@ -291,6 +291,64 @@ def gemm_i8(w: I8Weight, x: torch.Tensor | None = None, epi: int = EPI_STORE, y:
     return y
 
 
+class Mx8Weight:
+    """MX-FP8 re-quantization of a packed weight for the mx8_gemm mode (csrc/kernels/gemm_mx.hip):
+    per 32 consecutive k of a row one e8m0 scale byte E (2^(E - 127), the smallest power of two s with
+    amax / s <= 448; 127 for a zero block) and 32 e4m3 bytes of w / s, in the GEMM's operand image
+    (requant_mx8_kernel; layout in csrc/runtime/kernels_api.h).  Rows pad to groups of 32 columns."""
+
+    def __init__(self, w: PackedWeight):
+        self.n, self.k, self.k_pad, self.ntiles, self.nsb = w.n, w.k, w.k_pad, w.ntiles, w.nsb
+        self.ng = (w.ntiles + 1) // 2
+        dense = torch.zeros(w.n_pad, w.k_pad, dtype=torch.float16, device=w.dev.device)
+        L = N.lib()
+        N.check(L.mp_op_unpack(w.ptype, _ptr(w.dev), w.ntiles, w.nsb, _ptr(dense), w.k_pad, _stream()), "unpack")
+        self.dev = torch.empty(self.ng * w.nsb * 8192, dtype=torch.uint8, device=dense.device)
+        self.scales = torch.empty(self.ng * w.nsb * 256, dtype=torch.uint8, device=dense.device)
+        N.check(L.mp_op_requant_mx8(_ptr(dense), w.k_pad, w.n, w.ntiles, w.nsb, _ptr(self.dev), _ptr(self.scales),
+                                    _stream()), "requant_mx8")
+
+    def dense(self) -> torch.Tensor:
+        """The values the image encodes, f32 [n][k_pad] (image byte and scale positions undone)."""
+        g, nsb = self.ng, self.nsb
+        q = self.dev.view(g, 4 * nsb, 2, 2, 32, 16).permute(0, 4, 1, 2, 3, 5)        # g, col, kb, e, l / 32, j
+        e = self.scales.view(g, nsb, 2, 32, 4).permute(0, 3, 1, 4, 2)                # g, col, sb, e, l / 32
+        q = q.reshape(g * 32, self.k_pad).view(torch.float8_e4m3fn).float()
+        s = torch.exp2(e.reshape(g * 32, self.k_pad // 32).float() - 127.0)
+        return (q * s.repeat_interleave(32, dim=1))[: self.n]
+
+
+def quant_rows_mx8(x: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+    """f16 [M][K] (K % 32 == 0) -> (e4m3 bytes uint8 [M][K], e8m0 scale bytes uint8 [M][K / 32])."""
+    assert x.dtype == torch.float16 and x.is_contiguous()
+    M, K = x.shape
+    q = torch.empty(M, K, dtype=torch.uint8, device=x.device)
+    s = torch.empty(M, K // 32, dtype=torch.uint8, device=x.device)
+    N.check(N.lib().mp_op_quant_mx8(_ptr(x), K, M, K, _ptr(q), K, _ptr(s), K // 32, _stream()), "quant_mx8")
+    return q, s
+
+
+def gemm_mx8(w: Mx8Weight, x: torch.Tensor | None = None, epi: int = EPI_STORE, y: torch.Tensor | None = None,
+             xq: tuple[torch.Tensor, torch.Tensor] | None = None, allow_split: bool = True) -> torch.Tensor:
+    """MX-FP8 GEMM: x f16 [M][K_pad] quantized per 32-k block (or xq = quant_rows_mx8(x) given),
+    v_mfma_scale_f32_32x32x64_f8f6f4 against Mx8Weight; outputs as gemm (ATOMIC adds into y)."""
+    q, s = xq if xq is not None else quant_rows_mx8(x)
+    assert q.shape[1] == w.k_pad and s.shape[1] == w.k_pad // 32
+    M = q.shape[0]
+    L = N.lib()
+    if epi == EPI_SWIGLU:
+        F = w.n // 2
+        h = torch.zeros(M, F, dtype=torch.float16, device=q.device) if y is None else y
+        N.check(L.mp_op_gemm_mx8(epi, _ptr(w.dev), _ptr(w.scales), w.ntiles, w.nsb, _ptr(q), w.k_pad, _ptr(s), s.stride(0),
+                                 M, None, 0, _ptr(h), h.stride(0), F, int(allow_split), _stream()), "gemm_mx8")
+        return h
+    if y is None:
+        y = torch.zeros(M, w.n, dtype=torch.float32, device=q.device)
+    N.check(L.mp_op_gemm_mx8(epi, _ptr(w.dev), _ptr(w.scales), w.ntiles, w.nsb, _ptr(q), w.k_pad, _ptr(s), s.stride(0),
+                             M, _ptr(y), y.stride(0), None, 0, w.n, int(allow_split), _stream()), "gemm_mx8")
+    return y
+
+
 def set_gemm3_tuning(bm: int = 0, bn: int = 0, nsplit: int = 0, split_wg: int = 0) -> None:
     """Force the v3 GEMM's tile rows / columns (128 | 256) and ATOMIC split-K factor (0 = auto);
     split_wg: workgroup target of the automatic split.  0 restores a knob to the process's own value
