@@ -500,6 +500,49 @@ template <> struct Deq<P_IQ4_XS> {
   }
 };
 
+// ------------------------------------------------------------------ MXFP4 (17 B / 32 w, e2m1 codes)
+// No table: an e2m1 code (e1 e0 m) put at bits 9-11 of an f16, sign at bit 15, IS the f16 -- exponent
+// field 0 a subnormal, else a normal -- of value e2m1 2^-14.  A dword holds elements j = 0..3 in its
+// low nibbles and j = 4..7 in its high ones (the codebook types' order), so two shift-and pairs turn
+// either set into four high bytes (sign at bit 7, code at bits 1-3), two v_perm spread them over
+// zero low bytes into half2 pairs, and the 2^14 folds into the block multiplier 2^(e - 127 + 14),
+// whose f16 bits are (e - 98) << 10 (pack keeps e in [99, 128]).  The product is exact wherever the
+// weight is an f16 (code 2^(e - 127) >= 2^-24).
+__device__ __forceinline__ half2_t mx4_mult(uint32_t ee) {   // ee = e(2q) | e(2q + 1) << 8
+  return as_h2((((ee & 0xFFu) | ((ee & 0xFF00u) << 8)) - 0x00620062u) << 10);
+}
+__device__ __forceinline__ half8_t mx4_frag(uint32_t w, half2_t S) {
+  const uint32_t a = ((w << 4) & 0x80808080u) | ((w << 1) & 0x0E0E0E0Eu);
+  const uint32_t b = (w & 0x80808080u) | ((w >> 3) & 0x0E0E0E0Eu);
+  return pack8(as_u32(as_h2(__builtin_amdgcn_perm(0u, a, 0x010C000Cu)) * S),
+               as_u32(as_h2(__builtin_amdgcn_perm(0u, a, 0x030C020Cu)) * S),
+               as_u32(as_h2(__builtin_amdgcn_perm(0u, b, 0x010C000Cu)) * S),
+               as_u32(as_h2(__builtin_amdgcn_perm(0u, b, 0x030C020Cu)) * S));
+}
+
+// chunk: quants [h][lane] 16 B | scale bytes [r] 8 B (byte b = block b)
+template <> struct Deq<P_MXFP4> {
+  static constexpr int CB = chunk_bytes(P_MXFP4);
+  struct Raw { u32x4 q0, q1; uint32_t ee; };
+  __device__ static __forceinline__ void load(Raw& r, const uint8_t* c, int lane) { load(r, PtrSrc{c}, lane); }
+  template <class S>
+  __device__ static __forceinline__ void load(Raw& r, const S& c, int lane) {
+    r.q0 = c.q16nt(lane * 16);
+    r.q1 = c.q16nt(1024 + lane * 16);
+    r.ee = c.q2(2048 + (lane & 15) * 8 + 2 * (lane >> 4));   // blocks 2g, 2g + 1
+  }
+  template <int H>
+  __device__ static __forceinline__ void dequant(const Raw& r, half8_t b[4], int lane, const Consts&) { dequant<H>(r, b, lane); }
+  template <int H>
+  __device__ static __forceinline__ void dequant(const Raw& r, half8_t b[4], int) {
+    const u32x4 q = H == 0 ? r.q0 : r.q1;
+    const half2_t S2 = mx4_mult(r.ee);
+    const half2_t S = H ? h2hi(S2) : h2lo(S2);
+#pragma unroll
+    for (int s = 0; s < 4; ++s) b[s] = mx4_frag(q[s], S);
+  }
+};
+
 // bf16 pair (low, high halves of w) -> f16 pair (dense unpack only: the GEMV/GEMM kernels keep bf16):
 // exact inside f16's normal range; v_cvt_pkrtz rounds toward zero, so a bf16 beyond 65504 becomes
 // +-65504 (saturation) instead of an infinity

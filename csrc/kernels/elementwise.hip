@@ -184,6 +184,13 @@ __device__ float deq_elem(int t, const uint8_t* row, int e) {
       const int ls = ((b[4 + ib / 2] >> (4 * (ib % 2))) & 15) | (((sh >> (2 * ib)) & 3) << 4);
       return h2f(*reinterpret_cast<const uint16_t*>(b)) * (float)(ls - 32) * (float)kv[i];
     }
+    case T_MXFP4: {   // 2 e2m1(nibble) times 2^(e - 128) (e = 0, 1: subnormal floats)
+      const int8_t kv[16] = {0, 1, 2, 3, 4, 6, 8, 12, 0, -1, -2, -3, -4, -6, -8, -12};
+      const uint8_t* b = row + (e / 32) * 17;
+      const int l = e % 32;
+      const int i = l < 16 ? (b[1 + l] & 15) : (b[1 + l - 16] >> 4);
+      return __uint_as_float(b[0] < 2 ? 0x00200000u << b[0] : (uint32_t)(b[0] - 1) << 23) * (float)kv[i];
+    }
     case T_Q4_K: case T_Q5_K: {
       const int bb = t == T_Q4_K ? 144 : 176;
       const uint8_t* b = row + (e / 256) * bb;

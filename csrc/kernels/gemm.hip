@@ -136,6 +136,7 @@ void launch_gemm(int ptype, int epi, GemvParams p, hipStream_t st) {
     case P_Q5_1: gemm_pt<P_Q5_1>(epi, p, st); break;
     case P_IQ4_NL: gemm_pt<P_IQ4_NL>(epi, p, st); break;
     case P_IQ4_XS: gemm_pt<P_IQ4_XS>(epi, p, st); break;
+    case P_MXFP4: gemm_pt<P_MXFP4>(epi, p, st); break;
     case P_F16: gemm_pt<P_F16>(epi, p, st); break;
     case P_BF16: gemm_pt<P_BF16>(epi, p, st); break;
   }

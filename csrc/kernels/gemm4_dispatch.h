@@ -124,6 +124,7 @@ extern template void gemm4_run<P_Q5_0>(const Gemm4Plan&, int, const GemvParams&,
 extern template void gemm4_run<P_Q5_1>(const Gemm4Plan&, int, const GemvParams&, const mpk::G4Moe*, hipStream_t);
 extern template void gemm4_run<P_IQ4_NL>(const Gemm4Plan&, int, const GemvParams&, const mpk::G4Moe*, hipStream_t);
 extern template void gemm4_run<P_IQ4_XS>(const Gemm4Plan&, int, const GemvParams&, const mpk::G4Moe*, hipStream_t);
+extern template void gemm4_run<P_MXFP4>(const Gemm4Plan&, int, const GemvParams&, const mpk::G4Moe*, hipStream_t);
 extern template void gemm4_run<P_F16>(const Gemm4Plan&, int, const GemvParams&, const mpk::G4Moe*, hipStream_t);
 extern template void gemm4_run<P_BF16>(const Gemm4Plan&, int, const GemvParams&, const mpk::G4Moe*, hipStream_t);
 

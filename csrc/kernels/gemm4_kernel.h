@@ -304,6 +304,21 @@ template <int PT> struct W4_IQ4 {
 };
 template <> struct W4<P_IQ4_NL> : W4_IQ4<P_IQ4_NL> {};
 template <> struct W4<P_IQ4_XS> : W4_IQ4<P_IQ4_XS> {};
+// MXFP4: IQ4_XS's loads (the 8-B tail of a row holds its scale bytes), table-free fragments (dequant.h)
+template <> struct W4<P_MXFP4> : W4_IQ4<P_IQ4_XS> {
+  __device__ static __forceinline__ Prep prep(const Raw& w, int q) {
+    return Prep{mx4_mult(((q & 2) ? w.hdr.y : w.hdr.x) >> (16 * (q & 1)))};
+  }
+  __device__ static __forceinline__ half8_t frag(const Raw& w, const Prep& p, int t, int, const Consts&) {
+    const int kk = t >> 1, e = t & 1;
+    return mx4_frag(w.q[kk][e], kk ? h2hi(p.S2) : h2lo(p.S2));
+  }
+  // (repeated, not inherited: the base's fragp names the base's frag, the codebook lookup)
+  template <int P, class RW, class PR>
+  __device__ static __forceinline__ uint32_t fragp(const RW& w, const PR& p, int t, int h, const Consts& k) {
+    return __builtin_bit_cast(u32x4, frag(w, p, t, h, k))[P];
+  }
+};
 
 // Q8_0: piece (u, kk, r) = 32 int8 (+128) at R + ((u*2 + kk)*16 + r)*32; bytes 16h .. 16h+15 hold
 // dwords g = 2h, 2h+1 of the 16x16 map (one b128 per kk); block scales [u][r] = (d(2q), d(2q+1))
@@ -367,7 +382,8 @@ template <> struct W4<P_BF16> : W4_16<P_BF16> {};
 
 template <int PT> constexpr bool g4_supported() {
   return PT == P_Q4_K || PT == P_Q5_K || PT == P_Q6_K || PT == P_Q8_0 || PT == P_F16 || PT == P_BF16 ||
-         PT == P_Q3_K || PT == P_Q2_K || PT == P_Q5_0 || PT == P_Q5_1 || PT == P_IQ4_NL || PT == P_IQ4_XS;
+         PT == P_Q3_K || PT == P_Q2_K || PT == P_Q5_0 || PT == P_Q5_1 || PT == P_IQ4_NL || PT == P_IQ4_XS ||
+         PT == P_MXFP4;
 }
 
 // MoE mode (grouped GEMM over the routed experts): blockIdx.z = expert e, whose rows are

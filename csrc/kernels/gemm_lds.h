@@ -668,6 +668,21 @@ template <> struct W3<P_IQ4_XS> {
   }
 };
 
+// MXFP4: IQ4_XS's raw image (quants [u][h][r] 16 B, the tile's 128 contiguous tail bytes [u][r] 8 B, here
+// the rows' eight scale bytes); the quarter's two bytes become the multiplier pair
+template <> struct W3<P_MXFP4> : W3<P_IQ4_XS> {
+  static constexpr int CB = chunk_bytes(P_MXFP4);
+  static_assert(CB == W3<P_IQ4_XS>::CB, "MXFP4 shares the IQ4_XS chunk geometry");
+  template <int TW>
+  __device__ static __forceinline__ Prep prep(const Raw<TW>& w, int u, int q, int) {
+    return Prep{mx4_mult(((q & 2) ? w.hdr[u].y : w.hdr[u].x) >> (16 * (q & 1)))};
+  }
+  template <int TW>
+  __device__ static __forceinline__ half8_t frag(const Raw<TW>& w, const Prep& p, int u, int kk, int, const Consts&) {
+    return mx4_frag(w.q[u][kk], kk ? h2hi(p.S2) : h2lo(p.S2));
+  }
+};
+
 // 16-bit weights (F16, or BF16 for the bf16 MFMA: the A fragments go to bf16): the fragment bytes themselves,
 // [u][kk][lane] 16 B = element 4 kk + g of lane (q, r) of the T16 chunk
 template <int PT> struct W3_16 {

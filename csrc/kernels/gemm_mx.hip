@@ -7,6 +7,11 @@
 // VGPRs 4-7 k = 32 + 16 (l / 32) .. + 15 of the MFMA's 64.  The scale operand is a dword whose byte
 // op_sel picks; the byte of lane l scales k-block l / 32 (k = 32 (l / 32) .. + 31), i.e. one MX block,
 // whose values sit in the SAME register half of the two lanes l % 32 and l % 32 + 32.
+// An fp4 (e2m1) B operand (blgp = 4; measured the same way: one-hot fp8 rows against fp4 columns whose
+// nibble codes spell their position, scale bytes differing per lane half): lane l supplies column
+// l % 32 from its VGPRs 0-3 only (4-7 are ignored), 32 nibbles = k 32 (l / 32) .. + 31 in order, k even
+// in the low nibble of byte k / 2.  The lane's scale byte scales exactly those 32 k: one lane, one
+// MX block, and op_sel picks the byte as for fp8.
 //
 // Work split: a workgroup of 8 waves computes BM (128 | 256) rows x 256 columns; every wave owns 32
 // columns for all BM rows (BM / 32 accumulator fragments of 16 f32).  K runs in stages of 128 (two
@@ -14,7 +19,10 @@
 //   W  never touches LDS: requant_mx8_kernel lays each wave's B operand of a 64-k block out as 2 KB
 //      in fragment order, so a stage is four 1 KB wave loads global -> VGPR, one stage ahead.  The
 //      column's 8 scale bytes of a super-block arrive as one dword per lane, already ordered so that
-//      op_sel = 2 q + kk (stage q, MFMA kk) selects the lane's block.
+//      op_sel = 2 q + kk (stage q, MFMA kk) selects the lane's block.  An MXFP4 tensor's B image
+//      (relayout_mx4_kernel: the file's nibbles and scale bytes, permuted) is 1 KB per 64-k block, so
+//      the fp4 variant (BF = 1) loads two 1 KB pieces per stage and keeps 8 instead of 16 VGPRs of B
+//      per stage in flight; the scale image and op_sel are the same.
 //   X  (e4m3 rows, 128 B per row per stage) is shared by the 8 waves through LDS: global -> VGPR one
 //      stage ahead, ds_write into the other of two stage buffers behind the MFMAs, one barrier per
 //      stage.  Rows keep gemm3's 16-byte chunk swizzle (g3_off), so a fragment's two ds_read_b128 are
@@ -89,8 +97,34 @@ __global__ __launch_bounds__(256) void requant_mx8_kernel(const f16* W, int ldw,
   scales[((size_t)(c * nsb + (kb >> 2)) * 64 + l) * 4 + (kb & 3)] = (uint8_t)e;
 }
 
-template <int EPI, int BM>
+// P_MXFP4 T16 image -> the fp4 B image (kernels_api.h): a permutation.  One lane per (column, 32-k
+// block): its 16 source bytes are the T16 piece of lane 16 g + r, half h (block 2 g + h of the chunk),
+// whose dwords hold elements j = 0..3 in the low and 4..7 in the high nibbles of their bytes
+__global__ __launch_bounds__(256) void relayout_mx4_kernel(const uint8_t* W, int ntiles, int nsb, int nchunks, uint8_t* out,
+                                                           uint8_t* scales) {
+  const int chunk = blockIdx.x * 4 + (threadIdx.x >> 6), l = threadIdx.x & 63;
+  if (chunk >= nchunks) return;
+  const int nkb = 4 * nsb, c = chunk / nkb, kb = chunk - c * nkb;
+  const int tile = 2 * c + ((l & 31) >> 4), r = l & 15, sb = kb >> 2, bi = 2 * (kb & 3) + (l >> 5);
+  u32x4 o = {0u, 0u, 0u, 0u};
+  uint32_t e = 127;
+  if (tile < ntiles) {   // (an odd tile count leaves the last group's upper 16 columns empty)
+    const uint8_t* src = W + ((size_t)tile * nsb + sb) * chunk_bytes(P_MXFP4);
+    const u32x4 q = *reinterpret_cast<const u32x4*>(src + (bi & 1) * 1024 + (16 * (bi >> 1) + r) * 16);
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+      const uint32_t lo = q[s] & 0x0F0F0F0Fu, hi = (q[s] >> 4) & 0x0F0F0F0Fu;
+      o[s] = __builtin_amdgcn_perm(hi | (hi >> 4), lo | (lo >> 4), 0x06040200u);   // bytes (j0 j1, j2 j3, j4 j5, j6 j7)
+    }
+    e = src[2048 + 8 * r + bi];
+  }
+  *reinterpret_cast<u32x4*>(out + (size_t)chunk * 1024 + l * 16) = o;
+  scales[((size_t)(c * nsb + sb) * 64 + l) * 4 + (kb & 3)] = (uint8_t)e;
+}
+
+template <int EPI, int BM, int BF>   // BF: B operand format, 0 = e4m3 (2 KB per 64-k block), 1 = fp4 (1 KB)
 __global__ __launch_bounds__(512) void gemm_mx_kernel(const Mx8Params p, const int n_mb, const int sb_per_split) {
+  constexpr int NB = BF ? 2 : 4;     // 16-byte B pieces per lane per stage
   constexpr int FM = BM / 32;        // accumulator fragments (32 rows each) per wave
   constexpr int AP = BM / 64;        // 16-byte x pieces per thread per stage
   constexpr int A_BYTES = BM * 128, STAGE = A_BYTES + 2048;   // x rows + a scale dword slot per thread (BM used)
@@ -110,7 +144,7 @@ __global__ __launch_bounds__(512) void gemm_mx_kernel(const Mx8Params p, const i
   // this wave's 32 columns: group grp of the B image (clamped: a wave past the last group computes a
   // copy of it and stores nothing)
   const int grp = min(cg * 8 + wave, (p.ntiles + 1) / 2 - 1);
-  const uint8_t* wb = p.W + (size_t)grp * p.nsb * 8192 + lane * 16;
+  const uint8_t* wb = p.W + (size_t)grp * p.nsb * (2048 * NB) + lane * 16;
   const uint32_t* wsp = reinterpret_cast<const uint32_t*>(p.wscale) + (size_t)grp * p.nsb * 64 + lane;
   // x piece i of this thread: row (tid + 512 i) >> 3, 16-byte chunk tid & 7 (rows clamped to M - 1)
   const int xrow = tid >> 3, xch = tid & 7;
@@ -118,13 +152,13 @@ __global__ __launch_bounds__(512) void gemm_mx_kernel(const Mx8Params p, const i
   // would split its block and let the MFMAs sink past the scheduling fences)
   const uint8_t* xsa = p.xscale + (size_t)min(m0 + min(tid, BM - 1), M - 1) * p.ldxs;
 
-  // stage s (128 k): this thread's x pieces and x scale dword, this lane's four B half-fragments
-  auto fetch = [&](int s, u32x4 (&a)[AP], uint32_t& as, u32x4 (&b)[4]) {
+  // stage s (128 k): this thread's x pieces and x scale dword, this lane's four B half-fragments (fp4: two fragments)
+  auto fetch = [&](int s, u32x4 (&a)[AP], uint32_t& as, u32x4 (&b)[NB]) {
 #pragma unroll
     for (int i = 0; i < AP; ++i) a[i] = ld16(p.X + (size_t)min(m0 + xrow + 64 * i, M - 1) * p.ldx + 16 * xch + (size_t)s * 128);
     as = *reinterpret_cast<const uint32_t*>(xsa + 4 * s);
 #pragma unroll
-    for (int j = 0; j < 4; ++j) b[j] = ld16(wb + (size_t)s * 4096 + 1024 * j);
+    for (int j = 0; j < NB; ++j) b[j] = ld16(wb + (size_t)s * (1024 * NB) + 1024 * j);
   };
   auto store_a = [&](int buf, const u32x4 (&a)[AP], uint32_t as) {
     char* A = smem + buf * STAGE;
@@ -149,13 +183,18 @@ __global__ __launch_bounds__(512) void gemm_mx_kernel(const Mx8Params p, const i
 #pragma unroll
   for (int c = 0; c < 4; ++c) fa[c] = lds_addr(smem) + g3_off(cl, 4 * (c >> 1) + 2 * (c & 1) + h);
   const uint32_t sa = lds_addr(smem) + A_BYTES + 4 * cl;
-  auto compute = [&](auto qc, const u32x4 (&b)[4], uint32_t wsc) {
+  auto compute = [&](auto qc, const u32x4 (&b)[NB], uint32_t wsc) {
     constexpr int Q = decltype(qc)::value;
     i32x8 bf[2];
 #pragma unroll
     for (int kk = 0; kk < 2; ++kk) {
-      const u32x4 bl = b[2 * kk], bh = b[2 * kk + 1];
-      bf[kk] = i32x8{(int)bl.x, (int)bl.y, (int)bl.z, (int)bl.w, (int)bh.x, (int)bh.y, (int)bh.z, (int)bh.w};
+      if constexpr (BF) {   // the lane's 32 nibbles; the operand's upper four registers are not read
+        const u32x4 bl = b[kk];
+        bf[kk] = i32x8{(int)bl.x, (int)bl.y, (int)bl.z, (int)bl.w, 0, 0, 0, 0};
+      } else {
+        const u32x4 bl = b[2 * kk], bh = b[2 * kk + 1];
+        bf[kk] = i32x8{(int)bl.x, (int)bl.y, (int)bl.z, (int)bl.w, (int)bh.x, (int)bh.y, (int)bh.z, (int)bh.w};
+      }
     }
     u32x4 fr[2][4];
     uint32_t asc[2];
@@ -178,13 +217,13 @@ __global__ __launch_bounds__(512) void gemm_mx_kernel(const Mx8Params p, const i
         constexpr int KK = decltype(kc)::value;
         const u32x4 lo = fr[I & 1][2 * KK], hi = fr[I & 1][2 * KK + 1];
         const i32x8 af = {(int)lo.x, (int)lo.y, (int)lo.z, (int)lo.w, (int)hi.x, (int)hi.y, (int)hi.z, (int)hi.w};
-        acc[I] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(af, bf[KK], acc[I], 0, 0, 2 * KK, as_i, 2 * Q + KK, (int)wsc);
+        acc[I] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(af, bf[KK], acc[I], 0, BF ? 4 : 0, 2 * KK, as_i, 2 * Q + KK, (int)wsc);
       });
       __builtin_amdgcn_sched_barrier(0);   // the next fragment's reads stay behind these MFMAs
     });
   };
 
-  u32x4 an[AP], b[2][4];
+  u32x4 an[AP], b[2][NB];
   uint32_t asn, wsc = wsp[(size_t)sb_begin * 64];
   fetch(2 * sb_begin, an, asn, b[0]);
   store_a(0, an, asn);
@@ -251,6 +290,13 @@ void launch_requant_mx8(const f16* W, int ldw, int n, int ntiles, int nsb, uint8
                      scales);
 }
 
+void launch_relayout_mx4(const uint8_t* W, int ntiles, int nsb, uint8_t* out, uint8_t* scales, hipStream_t st) {
+  if (ntiles <= 0 || nsb <= 0 || (reinterpret_cast<uintptr_t>(W) & 15) || (reinterpret_cast<uintptr_t>(out) & 15))
+    throw std::runtime_error("relayout_mx4: bad weight shape or alignment");
+  const int nchunks = mx8_groups(ntiles) * 4 * nsb;
+  hipLaunchKernelGGL(mpk::relayout_mx4_kernel, dim3((nchunks + 3) / 4), dim3(256), 0, st, W, ntiles, nsb, nchunks, out, scales);
+}
+
 template <int EPI, int BM>
 static void gemm_mx_go(const Mx8Params& p, bool allow_split, hipStream_t st) {
   const int n_cg = (p.ntiles + 15) / 16, n_mb = (p.M + BM - 1) / BM, wgs = n_cg * n_mb;
@@ -260,7 +306,8 @@ static void gemm_mx_go(const Mx8Params& p, bool allow_split, hipStream_t st) {
   if (EPI == EPI_ATOMIC && allow_split && wgs < split_wg) nsplit = std::max(1, std::min(split_wg / wgs, p.nsb / 4));
   const int per = (p.nsb + nsplit - 1) / nsplit;
   nsplit = (p.nsb + per - 1) / per;
-  hipLaunchKernelGGL((mpk::gemm_mx_kernel<EPI, BM>), dim3(wgs, nsplit), dim3(512), 0, st, p, n_mb, per);
+  if (p.bfmt) hipLaunchKernelGGL((mpk::gemm_mx_kernel<EPI, BM, 1>), dim3(wgs, nsplit), dim3(512), 0, st, p, n_mb, per);
+  else hipLaunchKernelGGL((mpk::gemm_mx_kernel<EPI, BM, 0>), dim3(wgs, nsplit), dim3(512), 0, st, p, n_mb, per);
 }
 
 template <int EPI>
@@ -278,7 +325,7 @@ void launch_gemm_mx8(int epi, const Mx8Params& p, hipStream_t st, bool allow_spl
   if (p.M <= 0 || p.ntiles <= 0 || p.nsb <= 0 || p.ldx < p.nsb * 256 || (p.ldx & 15) || p.ldxs < p.nsb * 8 || (p.ldxs & 3) ||
       (reinterpret_cast<uintptr_t>(p.X) & 15) || (reinterpret_cast<uintptr_t>(p.xscale) & 3) ||
       (reinterpret_cast<uintptr_t>(p.W) & 15) || (reinterpret_cast<uintptr_t>(p.wscale) & 3) || !(swiglu ? (void*)p.H : (void*)p.Y) ||
-      p.n_valid > (swiglu ? p.ntiles * 8 : p.ntiles * 16))
+      p.n_valid > (swiglu ? p.ntiles * 8 : p.ntiles * 16) || (p.bfmt != 0 && p.bfmt != 1))
     throw std::runtime_error("gemm_mx8: bad operand shape or alignment");
   switch (epi) {
     case EPI_STORE: return gemm_mx_shape<EPI_STORE>(p, allow_split, st);

@@ -308,6 +308,7 @@ void launch_gemv2(int ptype, int epi, const GemvParams& p, int nsplit, int nw, i
     case P_Q5_1: gemv2_pt<P_Q5_1>(epi, p, nsplit, nw, tw, st); break;
     case P_IQ4_NL: gemv2_pt<P_IQ4_NL>(epi, p, nsplit, nw, tw, st); break;
     case P_IQ4_XS: gemv2_pt<P_IQ4_XS>(epi, p, nsplit, nw, tw, st); break;
+    case P_MXFP4: gemv2_pt<P_MXFP4>(epi, p, nsplit, nw, tw, st); break;
     case P_F16: gemv2_pt<P_F16>(epi, p, nsplit, nw, tw, st); break;
     case P_BF16: gemv2_pt<P_BF16>(epi, p, nsplit, nw, tw, st); break;
   }

@@ -105,6 +105,16 @@ __global__ void init_packed_kernel(uint8_t* W, size_t nbytes, int pt, float scal
       v[0] = (v[0] & 0xFFFF0000u) | h;
       v[2] = (v[2] & 0xFFFF0000u) | h;
     }
+  } else if (pt == P_MXFP4) {
+    if (in_chunk >= 2048) {   // 16 scale bytes (two rows): each drawn from its own random byte
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        uint32_t o = 0;
+#pragma unroll
+        for (int b = 0; b < 4; ++b) o |= (uint32_t)mxfp4_rand_e(scale, v[k] >> (8 * b)) << (8 * b);
+        v[k] = o;
+      }
+    }
   } else if (pt == P_Q4_0) {
     if (in_chunk >= 2048) {
 #pragma unroll
@@ -141,6 +151,7 @@ __global__ void init_raw_kernel(uint8_t* W, int64_t nblocks, int t, float scale,
     case T_Q5_1: h[0] = f2h(scale / 9.2f); h[1] = f2h(-15.5f * scale / 9.2f); break;
     case T_IQ4_NL: h[0] = f2h(scale / 67.f); break;
     case T_IQ4_XS: h[0] = f2h(scale / (18.5f * 67.f)); break;
+    case T_MXFP4: p[0] = (uint8_t)mxfp4_rand_e(scale, p[0]); break;
     case T_Q2_K:
       *reinterpret_cast<uint16_t*>(p + 80) = f2h(scale / 13.5f);
       *reinterpret_cast<uint16_t*>(p + 82) = f2h(scale / 9.f);

@@ -348,6 +348,27 @@ int mp_op_gemm_mx8(int epi, const void* W, const void* ws, int ntiles, int nsb, 
   API_CATCH(-1)
 }
 
+// MXFP4 weights on the same GEMM with an fp4 B operand: the P_MXFP4 T16 image -> the B image (a
+// permutation of the file's nibbles and scale bytes), then mp_op_gemm_mx8's arguments
+int mp_op_relayout_mx4(const void* W, int ntiles, int nsb, void* out, void* scales, void* stream) {
+  API_TRY
+  launch_relayout_mx4((const uint8_t*)W, ntiles, nsb, (uint8_t*)out, (uint8_t*)scales, (hipStream_t)stream);
+  HIP_OK(hipGetLastError());
+  return 0;
+  API_CATCH(-1)
+}
+
+int mp_op_gemm_mx4(int epi, const void* W, const void* ws, int ntiles, int nsb, const void* Q, int ldq, const void* S, int lds,
+                   int M, void* Y, int ldy, void* H, int ldh, int n_valid, int allow_split, void* stream) {
+  API_TRY
+  const Mx8Params p{(const uint8_t*)W, (const uint8_t*)ws, (const uint8_t*)Q, ldq, (const uint8_t*)S, lds, M,
+                    (float*)Y, ldy, (f16*)H, ldh, ntiles, nsb, n_valid, 1};
+  launch_gemm_mx8(epi, p, (hipStream_t)stream, allow_split != 0);
+  HIP_OK(hipGetLastError());
+  return 0;
+  API_CATCH(-1)
+}
+
 int mp_set_knob(const char* name, int value) {
   API_TRY
   set_knob(name, value);

@@ -82,6 +82,24 @@ float dot_q4_0_scalar(const uint8_t* w, const Q8Act& x, int64_t K) {
   return s;
 }
 
+// MXFP4: the codes as integers 2 e2m1 (ggml's kvalues_mxfp4), the block scale 2^(e - 128) (e = 0, 1:
+// subnormal floats), both exact in f32; the integer sum is at most 32 x 12 x 127
+float dot_mxfp4_scalar(const uint8_t* w, const Q8Act& x, int64_t K) {
+  static const int8_t kv[16] = {0, 1, 2, 3, 4, 6, 8, 12, 0, -1, -2, -3, -4, -6, -8, -12};
+  float s = 0.f;
+  for (int64_t b = 0; b < K / 32; ++b) {
+    const uint8_t* blk = w + 17 * b;
+    const int8_t* a = x.q + 32 * b;
+    int acc = 0;
+    for (int i = 0; i < 16; ++i) acc += kv[blk[1 + i] & 15] * a[i] + kv[blk[1 + i] >> 4] * a[16 + i];
+    const uint32_t u = blk[0] < 2 ? 0x00200000u << blk[0] : (uint32_t)(blk[0] - 1) << 23;
+    float d;
+    std::memcpy(&d, &u, 4);
+    s += d * x.d[b] * (float)acc;
+  }
+  return s;
+}
+
 template <bool Q5>
 float dot_q45k_scalar(const uint8_t* w, const Q8Act& x, int64_t K) {
   constexpr int BB = Q5 ? 176 : 144;
@@ -271,10 +289,10 @@ bool have_avx2() {
 }  // namespace
 
 bool qdot_supported(int type) {
-  return type == T_Q8_0 || type == T_Q4_0 || type == T_Q4_K || type == T_Q5_K || type == T_Q6_K;
+  return type == T_Q8_0 || type == T_Q4_0 || type == T_Q4_K || type == T_Q5_K || type == T_Q6_K || type == T_MXFP4;
 }
 
-int64_t qdot_block(int type) { return type == T_Q8_0 || type == T_Q4_0 ? 32 : 256; }
+int64_t qdot_block(int type) { return type == T_Q8_0 || type == T_Q4_0 || type == T_MXFP4 ? 32 : 256; }
 
 void quantize_q8_rows(const float* X, int ldx, int M, int64_t K, Q8Buf& buf) {
   if (K % 32) throw std::runtime_error("quantize_q8_rows: K must be a multiple of 32");
@@ -329,6 +347,7 @@ float qdot_row_scalar(int type, const uint8_t* w, const Q8Act& x, int64_t K) {
     case T_Q4_K: return dot_q45k_scalar<false>(w, x, K);
     case T_Q5_K: return dot_q45k_scalar<true>(w, x, K);
     case T_Q6_K: return dot_q6k_scalar(w, x, K);
+    case T_MXFP4: return dot_mxfp4_scalar(w, x, K);   // (no AVX2 form: qdot_row falls through to this one)
   }
   throw std::runtime_error("qdot_row: unsupported type");
 }

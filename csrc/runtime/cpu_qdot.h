@@ -23,7 +23,7 @@ inline Q8Act q8_row(const Q8Buf& b, int m) {
   return Q8Act{b.q.data() + (size_t)m * b.K, b.d.data() + (size_t)m * (b.K / 32), b.s.data() + (size_t)m * (b.K / 16)};
 }
 
-// ggml types with an integer dot (Q8_0, Q4_0, Q4_K, Q5_K, Q6_K) and their block length in weights
+// ggml types with an integer dot (Q8_0, Q4_0, Q4_K, Q5_K, Q6_K, MXFP4) and their block length in weights
 bool qdot_supported(int ggml_type);
 int64_t qdot_block(int ggml_type);
 // X [M][ldx] f32 -> buf (K a multiple of 32)

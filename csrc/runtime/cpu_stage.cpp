@@ -86,6 +86,7 @@ void fill_random(int type, int64_t nblocks, float scale, uint64_t seed, uint8_t*
         break;
       case T_IQ4_NL: put_f16(p, scale / 72.f); break;            // a random codebook entry has rms ~67
       case T_IQ4_XS: put_f16(p, scale / (20.f * 72.f)); break;   // random 6-bit scales: rms(ls - 32) ~ 18.5
+      case T_MXFP4: p[0] = (uint8_t)mxfp4_rand_e(scale, p[0]); break;
       default: throw std::runtime_error("cpu synthetic: unsupported type");
     }
   }

@@ -122,6 +122,7 @@ double i8_copy_bytes(int t, int64_t n, int64_t k) {
 double mx8_copy_bytes(int t, int64_t n, int64_t k) {
   if (t == T_F32 || t == T_F16 || t == T_BF16) return 0;
   const double np = (double)((n + 31) / 32 * 32), kp = (double)((k + 255) / 256 * 256);
+  if (t == T_MXFP4) return np * kp * 17.0 / 32.0;   // its own nibbles as the fp4 operand image: 4.25 bits per weight
   return np * kp * 33.0 / 32.0;
 }
 

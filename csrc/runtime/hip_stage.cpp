@@ -55,6 +55,7 @@ SyntheticTypes SyntheticTypes::from_ftype(const std::string& ftype_in, int layer
   } else if (f == "Q5_0") all(T_Q5_0);
   else if (f == "Q5_1") all(T_Q5_1);
   else if (f == "IQ4_NL") all(T_IQ4_NL);
+  else if (f == "MXFP4") { all(T_MXFP4); t.embd = t.out = T_Q8_0; }   // llama.cpp keeps token_embd / output at Q8_0
   else if (f == "IQ4_XS") {   // the mix of models/config.py tensor_type
     all(T_IQ4_XS);
     t.out = T_Q6_K;
@@ -470,7 +471,9 @@ void HipStage::build_i8_copies() {
 }
 
 // mx8_gemm: an MX-FP8 copy of every quantized projection (the wide GEMMs then run gemm_mx_kernel):
-// unpacked to dense f16 like the int8 copies, re-quantized per 32-k block into the GEMM's operand image
+// unpacked to dense f16 like the int8 copies, re-quantized per 32-k block into the GEMM's operand image.
+// An MXFP4 tensor is MX already: its nibbles and scale bytes are laid out as an fp4 B image instead
+// (4.25 bits per weight, nothing re-quantized)
 void HipStage::build_mx8_copies() {
   auto each = [&](const std::function<void(PackedMat&)>& f) {
     for (LayerW& L : layers_) {
@@ -484,15 +487,22 @@ void HipStage::build_mx8_copies() {
   };
   size_t maxe = 0;
   each([&](PackedMat& m) {
-    if (m.d && !is16(m.ptype)) maxe = std::max(maxe, (size_t)m.dims.ntiles * 16 * m.dims.nsb * 256);
+    if (m.d && !is16(m.ptype) && m.ptype != P_MXFP4) maxe = std::max(maxe, (size_t)m.dims.ntiles * 16 * m.dims.nsb * 256);
   });
-  if (!maxe) return;
   f16* tmp = nullptr;
-  HIP_OK(hipMalloc(&tmp, maxe * 2));
-  size_t bytes = 0;
+  if (maxe) HIP_OK(hipMalloc(&tmp, maxe * 2));
+  size_t bytes = 0, bytes4 = 0;
   each([&](PackedMat& m) {
     if (!m.d || is16(m.ptype)) return;
     const int nt = (int)m.dims.ntiles, nsb = (int)m.dims.nsb;
+    if (m.ptype == P_MXFP4) {
+      m.mx = (uint8_t*)dmalloc(mx4_weight_bytes(nt, nsb));
+      m.mx_s = (uint8_t*)dmalloc(mx8_scale_bytes(nt, nsb));
+      m.mx_fmt = 1;
+      launch_relayout_mx4(m.d, nt, nsb, m.mx, m.mx_s, stream_);
+      bytes4 += mx4_weight_bytes(nt, nsb) + mx8_scale_bytes(nt, nsb);
+      return;
+    }
     launch_unpack(m.ptype, m.d, nt, nsb, tmp, nsb * 256, stream_);
     m.mx = (uint8_t*)dmalloc(mx8_weight_bytes(nt, nsb));
     m.mx_s = (uint8_t*)dmalloc(mx8_scale_bytes(nt, nsb));
@@ -500,9 +510,10 @@ void HipStage::build_mx8_copies() {
     bytes += mx8_weight_bytes(nt, nsb) + mx8_scale_bytes(nt, nsb);
   });
   HIP_OK(hipStreamSynchronize(stream_));
-  HIP_OK(hipFree(tmp));
-  weight_bytes_ += bytes;
-  MP_LOGI("stage %d: mx8_gemm: %.2f GiB of MX-FP8 weight copies", spec_.stage, bytes / 1073741824.0);
+  if (tmp) HIP_OK(hipFree(tmp));
+  weight_bytes_ += bytes + bytes4;
+  if (bytes) MP_LOGI("stage %d: mx8_gemm: %.2f GiB of MX-FP8 weight copies", spec_.stage, bytes / 1073741824.0);
+  if (bytes4) MP_LOGI("stage %d: mx8_gemm: %.3f GiB of MXFP4 fp4 operand images", spec_.stage, bytes4 / 1073741824.0);
 }
 
 void HipStage::alloc_runtime() {
@@ -1007,7 +1018,7 @@ void HipStage::gemv(const MatCall& c, hipStream_t st) {
         xq_rows_ = c.M;
       }
       Mx8Params q{m.mx, m.mx_s, reinterpret_cast<const uint8_t*>(xq_), xq_ld_, xqe_, xq_ld_ / 32, c.M,
-                  p.Y, p.ldy, p.H, p.ldh, p.ntiles, p.nsb, p.n_valid};
+                  p.Y, p.ldy, p.H, p.ldh, p.ntiles, p.nsb, p.n_valid, m.mx_fmt};
       launch_gemm_mx8(c.epi, q, st, atomics);
       return;
     }

@@ -64,6 +64,7 @@ struct PackedMat {
   float* i8_ws = nullptr;   // ... and its row scales
   uint8_t* mx = nullptr;    // mx8_gemm: MX-FP8 re-quantized copy (launch_requant_mx8's image) ...
   uint8_t* mx_s = nullptr;  // ... and its e8m0 block scales
+  int mx_fmt = 0;           // mx's B format (Mx8Params::bfmt): 1 = an MXFP4 tensor's own nibbles, no fp8 copy
   size_t bytes() const { return dims.bytes; }
 };
 

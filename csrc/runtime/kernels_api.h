@@ -110,7 +110,7 @@ void launch_gemm(int ptype, int epi, GemvParams p, hipStream_t st);
 void launch_gemm3(int ptype, int epi, GemvParams p, hipStream_t st, bool allow_split = true);
 // Prompt / wide-decode GEMM v4 (gemm4*.hip): gemm3's LDS-DMA stream on v_mfma_f32_32x32x16 (BM 128 |
 // 256 rows x 256 columns, each wave owning 32 columns, and the opt-in forms of the geometry table).
-// Q4_K, Q5_K, Q6_K, Q8_0, Q3_K, Q2_K, Q5_0, Q5_1, IQ4_NL, IQ4_XS, F16, BF16; false = type not supported (nothing launched).  Every launch
+// Q4_K, Q5_K, Q6_K, Q8_0, Q3_K, Q2_K, Q5_0, Q5_1, IQ4_NL, IQ4_XS, MXFP4, F16, BF16; false = type not supported (nothing launched).  Every launch
 // runs plan_gemm4 / plan_moe_gemm4 (gemm4_plan.h).  _splitk: split-K partial stores, split s into
 // scratch + s * M * ntiles * 16 (false: the shape does not split or scratch_n floats are too few),
 // then (reduce) added into p.Y in split order.
@@ -257,15 +257,24 @@ inline int mx8_groups(int ntiles) { return (ntiles + 1) / 2; }
 inline size_t mx8_weight_bytes(int ntiles, int nsb) { return (size_t)mx8_groups(ntiles) * nsb * 8192; }
 inline size_t mx8_scale_bytes(int ntiles, int nsb) { return (size_t)mx8_groups(ntiles) * nsb * 256; }
 void launch_requant_mx8(const f16* W, int ldw, int n, int ntiles, int nsb, uint8_t* out, uint8_t* scales, hipStream_t st);
+// MXFP4 weights need no re-quantization: the P_MXFP4 T16 image's nibbles and scale bytes, permuted, ARE
+// the fp4 B operand.  Column group c, 64-k block kb: 1 KB at (c * 4 nsb + kb) * 1024, lane l's 16 bytes
+// at l * 16 = column 32 c + l % 32, block 2 kb + l / 32, byte i = code(k 2 i) | code(k 2 i + 1) << 4
+// (the MFMA's fp4 operand order, gemm_mx.hip).  Scales: the same image as launch_requant_mx8's.  The source
+// is the T16 image, so the scale bytes are the ones pack_t16 clamped to [99, 128] (qtypes.h): the instruction
+// could carry all of e8m0, but both routes of a tensor then compute from the same weights.
+inline size_t mx4_weight_bytes(int ntiles, int nsb) { return (size_t)mx8_groups(ntiles) * nsb * 4096; }
+void launch_relayout_mx4(const uint8_t* W, int ntiles, int nsb, uint8_t* out, uint8_t* scales, hipStream_t st);
 // Y[M][n] (+)= X W^T on v_mfma_scale_f32_32x32x64_f8f6f4; epilogues and output layouts as launch_gemm3
 struct Mx8Params {
-  const uint8_t* W; const uint8_t* wscale;   // launch_requant_mx8's images
+  const uint8_t* W; const uint8_t* wscale;   // launch_requant_mx8's images (bfmt 1: launch_relayout_mx4's)
   const uint8_t* X; int ldx;                  // e4m3 rows [M][ldx] (nsb * 256 columns used)
   const uint8_t* xscale; int ldxs;            // scale bytes [M][ldxs] (ldxs % 4 == 0)
   int M;
   float* Y; int ldy;                          // EPI_STORE / EPI_ATOMIC
   f16* H; int ldh;                            // EPI_SWIGLU
   int ntiles, nsb, n_valid;
+  int bfmt = 0;                               // B operand format: 0 = e4m3, 1 = fp4 (e2m1)
 };
 void launch_gemm_mx8(int epi, const Mx8Params& p, hipStream_t st, bool allow_split = true);
 

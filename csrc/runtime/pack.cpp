@@ -1,6 +1,8 @@
 #include "pack.h"
+#include "log.h"
 
 #include <algorithm>
+#include <atomic>
 #include <cstring>
 #include <stdexcept>
 #include <thread>
@@ -123,6 +125,14 @@ static inline void put_hi5(uint8_t* chunk, const Pos& p, int v) {
 // element l of a 32-weight block's 16 nibble bytes
 static inline int nib32(const uint8_t* qs, int l) { return l < 16 ? (qs[l] & 15) : (qs[l - 16] >> 4); }
 static const int8_t kIq4Values[16] = {-127, -104, -83, -65, -49, -35, -22, -10, 1, 13, 25, 38, 53, 69, 89, 113};
+// MXFP4: 2 e2m1(nibble) (ggml's kvalues_mxfp4), times 2^(e - 128)
+static const int8_t kMxfp4Values[16] = {0, 1, 2, 3, 4, 6, 8, 12, 0, -1, -2, -3, -4, -6, -8, -12};
+static inline float mxfp4_half_scale(int e) {   // 2^(e - 128): e = 0, 1 are subnormal floats
+  const uint32_t u = e < 2 ? 0x00200000u << e : (uint32_t)(e - 1) << 23;
+  float f;
+  std::memcpy(&f, &u, 4);
+  return f;
+}
 
 // 2-bit field of (h, s, j) inside the lane's ONE 16-B piece: dword 2 (s >> 1) + h, bit
 // 16 (j & 1) + 8 (s & 1) + 2 (j >> 1)
@@ -131,7 +141,7 @@ static inline void put_2bit(uint8_t* chunk, const Pos& p, int v) {
   chunk[p.lane * 16 + bit / 8] |= (uint8_t)((v & 3) << (bit % 8));
 }
 
-static void pack_chunk(int t, int pt, const uint8_t* src, int64_t K, int64_t k0, uint8_t* chunk, int r) {
+static void pack_chunk(int t, int pt, const uint8_t* src, int64_t K, int64_t k0, uint8_t* chunk, int r, int64_t& clamped) {
   // src: row bytes at k0 (super-block start); K: total row length (elements)
   switch (pt) {
     case P_Q4_K: {
@@ -238,6 +248,20 @@ static void pack_chunk(int t, int pt, const uint8_t* src, int64_t K, int64_t k0,
       }
       break;
     }
+    case P_MXFP4: {   // scale bytes clamped to what the f16 multiplier 2^(e - 113) can carry (qtypes.h)
+      for (int b = 0; b < 8; ++b) {
+        if (k0 + 32 * b >= K) break;
+        const uint8_t* blk = src + 17 * b;
+        const int e = blk[0];
+        bool any = false;
+        for (int l = 0; l < 16; ++l) any |= (blk[1 + l] & 0x77) != 0;
+        if (any && (e < 99 || e > 128)) ++clamped;
+        chunk[2048 + 8 * r + b] = (uint8_t)std::min(std::max(e, 99), 128);
+        if (e >= 99)
+          for (int l = 0; l < 32; ++l) put_nib_cb(chunk, pos_of(32 * b + l, r), nib32(blk + 1, l));
+      }
+      break;
+    }
     case P_IQ4_XS: {
       for (int w = 0; w < 256; ++w) put_nib_cb(chunk, pos_of(w, r), nib32(src + 8 + 16 * (w / 32), w % 32));
       std::memcpy(chunk + 2048 + 8 * r, src, 8);
@@ -283,7 +307,11 @@ int pack_t16_tiles(int t, int64_t N, int64_t K, const RowFn& row, uint8_t* dst, 
   if (K % be) throw std::runtime_error("pack: K not a block multiple");
   if (tile0 < 0 || tile1 > d.ntiles || tile0 > tile1) throw std::runtime_error("pack: bad tile range");
   std::memset(dst, 0, (size_t)(tile1 - tile0) * d.nsb * cb);
+  if (pt == P_MXFP4)   // padding blocks too keep a scale byte the f16 multiplier can carry (their codes are zero)
+    for (int64_t c = 0; c < (tile1 - tile0) * d.nsb; ++c) std::memset(dst + (size_t)c * cb + 2048, 99, 128);
+  std::atomic<int64_t> clamped{0};
   auto work = [&](int64_t t0, int64_t t1) {
+    int64_t nclamp = 0;
     for (int64_t tile = t0; tile < t1; ++tile) {
       for (int r = 0; r < 16; ++r) {
         const int64_t n = tile * 16 + r;
@@ -294,10 +322,11 @@ int pack_t16_tiles(int t, int64_t N, int64_t K, const RowFn& row, uint8_t* dst, 
           const int64_t k0 = sb * 256;
           uint8_t* chunk = dst + (size_t)((tile - tile0) * d.nsb + sb) * cb;
           const uint8_t* s = src + (size_t)(k0 / be) * bb;
-          pack_chunk(t, pt, s, K, k0, chunk, r);
+          pack_chunk(t, pt, s, K, k0, chunk, r, nclamp);
         }
       }
     }
+    clamped += nclamp;
   };
   const int64_t nt = tile1 - tile0;
   if (n_threads <= 0) n_threads = (int)std::min<unsigned>(16, std::max(1u, std::thread::hardware_concurrency()));
@@ -312,6 +341,8 @@ int pack_t16_tiles(int t, int64_t N, int64_t K, const RowFn& row, uint8_t* dst, 
     }
     for (auto& x : th) x.join();
   }
+  if (clamped) MP_LOGW("pack: %lld MXFP4 blocks of a %lld x %lld tensor have a scale outside 2^-28 .. 2^1 and were clamped",
+                       (long long)clamped.load(), (long long)N, (long long)K);
   return pt;
 }
 
@@ -355,6 +386,13 @@ MP_HOST_AVX2_CLONES void dequant_row(int t, const uint8_t* src, float* dst, int6
         const uint8_t* blk = src + 18 * b;
         const float d = f16_to_f32(rd16(blk));
         for (int l = 0; l < 32; ++l) dst[32 * b + l] = d * (float)kIq4Values[nib32(blk + 2, l)];
+      }
+      return;
+    case T_MXFP4:
+      for (int64_t b = 0; b < K / 32; ++b) {
+        const uint8_t* blk = src + 17 * b;
+        const float d = mxfp4_half_scale(blk[0]);
+        for (int l = 0; l < 32; ++l) dst[32 * b + l] = d * (float)kMxfp4Values[nib32(blk + 1, l)];
       }
       return;
     case T_IQ4_XS:

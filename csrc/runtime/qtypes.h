@@ -50,8 +50,17 @@
 //   P_Q5_1 (3072 B):   as P_Q5_0 | m [r] 16 B (same order as d)
 //   P_IQ4_NL (2304 B): quants [h][lane] 16 B | d [r] 16 B (as P_Q5_0)
 //   P_IQ4_XS (2176 B): quants [h][lane] 16 B | header [r] 8 B as in GGUF (d, scales_h, scales_l)
-// A block past a ragged K stays zero (d = 0, m = 0: w = 0).
+//
+// MXFP4 (ggml type 39, OCP microscaling fp4), 17 B / 32: u8 e, qs[16].  A nibble is e2m1: bit 3 the
+// sign, magnitudes {0, 0.5, 1, 1.5, 2, 3, 4, 6}; w = e2m1(nibble) 2^(e - 127) (ggml: kvalues_mxfp4 =
+// 2 e2m1 times 2^(e - 128), the same number; e = 0, 1 are the subnormal floats 2^-128, 2^-127).
+//   P_MXFP4 (2176 B): quants [h][lane] 16 B in the codebook types' nibble order | scale bytes [r] 8 B
+//                     (byte b = block b's e).  The f16 kernels build the block multiplier 2^(e - 113)
+//                     from the byte, so pack clamps e to [99, 128]: a block below 99 (every weight
+//                     under 2^-25) is stored as zeros, one above 128 keeps its codes at e = 128.
+// A block past a ragged K stays zero (d = 0, m = 0: w = 0; MXFP4: zero codes).
 #pragma once
+#include <math.h>
 #include <stdint.h>
 #include <stddef.h>
 
@@ -66,7 +75,7 @@ namespace mp {
 enum GgmlType : int {
   T_F32 = 0, T_F16 = 1, T_Q4_0 = 2, T_Q4_1 = 3, T_Q5_0 = 6, T_Q5_1 = 7, T_Q8_0 = 8, T_Q8_1 = 9,
   T_Q2_K = 10, T_Q3_K = 11, T_Q4_K = 12, T_Q5_K = 13, T_Q6_K = 14, T_Q8_K = 15, T_IQ4_NL = 20, T_IQ4_XS = 23,
-  T_BF16 = 30,
+  T_BF16 = 30, T_MXFP4 = 39,
 };
 
 inline const char* type_name(int t) {
@@ -76,7 +85,8 @@ inline const char* type_name(int t) {
     case T_Q5_K: return "Q5_K"; case T_Q6_K: return "Q6_K";
     case T_Q2_K: return "Q2_K"; case T_Q3_K: return "Q3_K";
     case T_Q5_0: return "Q5_0"; case T_Q5_1: return "Q5_1";
-    case T_IQ4_NL: return "IQ4_NL"; case T_IQ4_XS: return "IQ4_XS"; default: return "?";
+    case T_IQ4_NL: return "IQ4_NL"; case T_IQ4_XS: return "IQ4_XS";
+    case T_MXFP4: return "MXFP4"; default: return "?";
   }
 }
 
@@ -84,7 +94,7 @@ inline const char* type_name(int t) {
 MP_HD inline int block_elems(int t) {
   switch (t) {
     case T_F32: case T_F16: case T_BF16: return 1;
-    case T_Q8_0: case T_Q4_0: case T_Q5_0: case T_Q5_1: case T_IQ4_NL: return 32;
+    case T_Q8_0: case T_Q4_0: case T_Q5_0: case T_Q5_1: case T_IQ4_NL: case T_MXFP4: return 32;
     case T_Q2_K: case T_Q3_K: case T_Q4_K: case T_Q5_K: case T_Q6_K: case T_IQ4_XS: return 256;
     default: return 0;
   }
@@ -95,6 +105,7 @@ MP_HD inline int block_bytes(int t) {
     case T_Q8_0: return 34; case T_Q4_0: return 18;
     case T_Q2_K: return 84; case T_Q3_K: return 110;
     case T_Q5_0: return 22; case T_Q5_1: return 24; case T_IQ4_NL: return 18; case T_IQ4_XS: return 136;
+    case T_MXFP4: return 17;
     case T_Q4_K: return 144; case T_Q5_K: return 176; case T_Q6_K: return 210;
     default: return 0;
   }
@@ -106,7 +117,7 @@ inline size_t row_bytes(int t, int64_t n) { return (size_t)(n / block_elems(t)) 
 // the bf16 MFMA on them.  P_I8 is not a GGUF type: per-row int8 re-quantized weights (one f32 scale
 // per output row, kept beside the matrix) for the int8-activation GEMM prototype (gemm3.hip, K15).
 enum PackType : int { P_F16 = 0, P_Q8_0 = 1, P_Q4_K = 2, P_Q5_K = 3, P_Q6_K = 4, P_Q4_0 = 5, P_BF16 = 6, P_I8 = 7,
-                      P_Q3_K = 8, P_Q2_K = 9, P_Q5_0 = 10, P_Q5_1 = 11, P_IQ4_NL = 12, P_IQ4_XS = 13 };
+                      P_Q3_K = 8, P_Q2_K = 9, P_Q5_0 = 10, P_Q5_1 = 11, P_IQ4_NL = 12, P_IQ4_XS = 13, P_MXFP4 = 14 };
 constexpr bool is16(int p) { return p == P_F16 || p == P_BF16; }
 
 inline int pack_type_of(int ggml_type) {
@@ -118,6 +129,7 @@ inline int pack_type_of(int ggml_type) {
     case T_Q3_K: return P_Q3_K; case T_Q2_K: return P_Q2_K;
     case T_Q5_0: return P_Q5_0; case T_Q5_1: return P_Q5_1;
     case T_IQ4_NL: return P_IQ4_NL; case T_IQ4_XS: return P_IQ4_XS;
+    case T_MXFP4: return P_MXFP4;
     default: return -1;
   }
 }
@@ -127,7 +139,17 @@ constexpr int chunk_bytes(int p) {
   return is16(p) ? 8192 : p == P_Q8_0 ? 4352 : p == P_Q4_K ? 2304 : p == P_Q5_K ? 2816
        : p == P_Q6_K ? 3360 : p == P_Q4_0 ? 2304 : p == P_I8 ? 4096
        : p == P_Q3_K ? 1760 : p == P_Q2_K ? 1344 : p == P_Q5_0 ? 2816 : p == P_Q5_1 ? 3072
-       : p == P_IQ4_NL ? 2304 : p == P_IQ4_XS ? 2176 : 0;
+       : p == P_IQ4_NL ? 2304 : p == P_IQ4_XS ? 2176 : p == P_MXFP4 ? 2176 : 0;
+}
+
+// Random MXFP4 init: a uniformly drawn e2m1 code has rms 2.93, and a power-of-two scale cannot hit
+// every target, so the byte is e0 or e0 + 1 with the probability (from the random byte rnd8) that
+// makes the mean square of the weights scale^2
+MP_HD inline int mxfp4_rand_e(float scale, uint32_t rnd8) {
+  const float l = log2f(scale / 2.926f), fl = floorf(l);
+  const float p = (exp2f(2.f * (l - fl)) - 1.f) * (1.f / 3.f);
+  const int e = 127 + (int)fl + ((float)(rnd8 & 255u) < 256.f * p ? 1 : 0);
+  return e < 99 ? 99 : e > 128 ? 128 : e;
 }
 
 inline int64_t round_up(int64_t a, int64_t b) { return (a + b - 1) / b * b; }

@@ -101,8 +101,8 @@ def use_more_bits(i: int, n: int) -> bool:
     return i < n // 8 or i >= 7 * n // 8 or (i - n // 8) % 3 == 2
 
 
-def tensor_type(ftype: str, name: str, layer: int, n_layer: int, k_dim: int) -> int:
-    """ggml type of a 2-D weight under a named file type (mix)."""
+def tensor_type(ftype: str, name: str, layer: int, n_layer: int, k_dim: int, expert: bool = False) -> int:
+    """ggml type of a 2-D weight under a named file type (mix); expert: a stacked MoE expert tensor."""
     ftype = ftype.upper()
     plain = {"F32": Q.F32, "F16": Q.F16, "BF16": Q.BF16, "Q8_0": Q.Q8_0, "Q6_K": Q.Q6_K,
              "Q5_K": Q.Q5_K, "Q4_0": Q.Q4_0, "Q5_0": Q.Q5_0, "Q5_1": Q.Q5_1, "IQ4_NL": Q.IQ4_NL}
@@ -153,6 +153,13 @@ def tensor_type(ftype: str, name: str, layer: int, n_layer: int, k_dim: int) -> 
         if not kq:   # upstream's rule for the two low-bit types; the others as above
             return Q.Q4_0 if t in (Q.Q2_K, Q.Q3_K) else Q.Q8_0
         return t
+    if ftype in ("MXFP4", "MXFP4_MOE"):
+        # llama.cpp's rule: MXFP4 wherever the row is a multiple of 32 (MXFP4_MOE: the expert tensors
+        # only), Q8_0 for everything else, token_embd / output included
+        moe_only = ftype == "MXFP4_MOE"
+        if name in ("token_embd", "output") or k_dim % 32 or (moe_only and not expert):
+            return Q.Q8_0
+        return Q.MXFP4
     if ftype == "IQ4_XS":
         # (as recalled from upstream) the base type beside a Q6_K output, Q5_K attn_v and early ffn_down;
         # rows that are no multiple of 256 fall to the 32-weight-block type of the same width

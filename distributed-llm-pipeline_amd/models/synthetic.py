@@ -44,11 +44,11 @@ def llama_tensor_specs(cfg: LlamaConfig, ftype: str):
         if cfg.n_expert:
             yield (p + "ffn_gate_inp.weight", (d, cfg.n_expert), Q.F32, "router")
             yield (p + "ffn_gate_exps.weight", (d, cfg.d_ff, cfg.n_expert),
-                   tensor_type(ftype, "ffn_gate", i, L, d), "w")
+                   tensor_type(ftype, "ffn_gate", i, L, d, expert=True), "w")
             yield (p + "ffn_up_exps.weight", (d, cfg.d_ff, cfg.n_expert),
-                   tensor_type(ftype, "ffn_up", i, L, d), "w")
+                   tensor_type(ftype, "ffn_up", i, L, d, expert=True), "w")
             yield (p + "ffn_down_exps.weight", (cfg.d_ff, d, cfg.n_expert),
-                   tensor_type(ftype, "ffn_down", i, L, cfg.d_ff), "wo")
+                   tensor_type(ftype, "ffn_down", i, L, cfg.d_ff, expert=True), "wo")
         else:
             yield (p + "ffn_gate.weight", (d, cfg.d_ff), tensor_type(ftype, "ffn_gate", i, L, d), "w")
             yield (p + "ffn_up.weight", (d, cfg.d_ff), tensor_type(ftype, "ffn_up", i, L, d), "w")

@@ -17,6 +17,7 @@ EPI_STORE, EPI_ATOMIC, EPI_SWIGLU = 0, 1, 2
 P_F16, P_Q8_0, P_Q4_K, P_Q5_K, P_Q6_K, P_Q4_0, P_BF16, P_I8 = 0, 1, 2, 3, 4, 5, 6, 7
 P_Q3_K, P_Q2_K = 8, 9
 P_Q5_0, P_Q5_1, P_IQ4_NL, P_IQ4_XS = 10, 11, 12, 13
+P_MXFP4 = 14
 
 
 def _ptr(t: torch.Tensor | None):
@@ -318,6 +319,22 @@ class Mx8Weight:
         return (q * s.repeat_interleave(32, dim=1))[: self.n]
 
 
+class Mx4Weight:
+    """An MXFP4 packed weight as the fp4 B operand of the mx8_gemm GEMM (relayout_mx4_kernel): the
+    file's nibbles and e8m0 bytes permuted into fragment order, nothing re-quantized (layout in
+    csrc/runtime/kernels_api.h).  gemm_mx8 takes it in place of an Mx8Weight."""
+    fp4 = True
+
+    def __init__(self, w: PackedWeight):
+        assert w.ptype == P_MXFP4
+        self.n, self.k, self.k_pad, self.ntiles, self.nsb = w.n, w.k, w.k_pad, w.ntiles, w.nsb
+        self.ng = (w.ntiles + 1) // 2
+        self.dev = torch.empty(self.ng * w.nsb * 4096, dtype=torch.uint8, device=w.dev.device)
+        self.scales = torch.empty(self.ng * w.nsb * 256, dtype=torch.uint8, device=w.dev.device)
+        N.check(N.lib().mp_op_relayout_mx4(_ptr(w.dev), w.ntiles, w.nsb, _ptr(self.dev), _ptr(self.scales), _stream()),
+                "relayout_mx4")
+
+
 def quant_rows_mx8(x: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
     """f16 [M][K] (K % 32 == 0) -> (e4m3 bytes uint8 [M][K], e8m0 scale bytes uint8 [M][K / 32])."""
     assert x.dtype == torch.float16 and x.is_contiguous()
@@ -328,23 +345,26 @@ def quant_rows_mx8(x: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
     return q, s
 
 
-def gemm_mx8(w: Mx8Weight, x: torch.Tensor | None = None, epi: int = EPI_STORE, y: torch.Tensor | None = None,
-             xq: tuple[torch.Tensor, torch.Tensor] | None = None, allow_split: bool = True) -> torch.Tensor:
+def gemm_mx8(w: "Mx8Weight | Mx4Weight", x: torch.Tensor | None = None, epi: int = EPI_STORE,
+             y: torch.Tensor | None = None, xq: tuple[torch.Tensor, torch.Tensor] | None = None,
+             allow_split: bool = True) -> torch.Tensor:
     """MX-FP8 GEMM: x f16 [M][K_pad] quantized per 32-k block (or xq = quant_rows_mx8(x) given),
-    v_mfma_scale_f32_32x32x64_f8f6f4 against Mx8Weight; outputs as gemm (ATOMIC adds into y)."""
+    v_mfma_scale_f32_32x32x64_f8f6f4 against Mx8Weight (e4m3 B) or Mx4Weight (fp4 B); outputs as gemm
+    (ATOMIC adds into y)."""
     q, s = xq if xq is not None else quant_rows_mx8(x)
     assert q.shape[1] == w.k_pad and s.shape[1] == w.k_pad // 32
     M = q.shape[0]
     L = N.lib()
+    op = L.mp_op_gemm_mx4 if getattr(w, "fp4", False) else L.mp_op_gemm_mx8
     if epi == EPI_SWIGLU:
         F = w.n // 2
         h = torch.zeros(M, F, dtype=torch.float16, device=q.device) if y is None else y
-        N.check(L.mp_op_gemm_mx8(epi, _ptr(w.dev), _ptr(w.scales), w.ntiles, w.nsb, _ptr(q), w.k_pad, _ptr(s), s.stride(0),
+        N.check(op(epi, _ptr(w.dev), _ptr(w.scales), w.ntiles, w.nsb, _ptr(q), w.k_pad, _ptr(s), s.stride(0),
                                  M, None, 0, _ptr(h), h.stride(0), F, int(allow_split), _stream()), "gemm_mx8")
         return h
     if y is None:
         y = torch.zeros(M, w.n, dtype=torch.float32, device=q.device)
-    N.check(L.mp_op_gemm_mx8(epi, _ptr(w.dev), _ptr(w.scales), w.ntiles, w.nsb, _ptr(q), w.k_pad, _ptr(s), s.stride(0),
+    N.check(op(epi, _ptr(w.dev), _ptr(w.scales), w.ntiles, w.nsb, _ptr(q), w.k_pad, _ptr(s), s.stride(0),
                              M, _ptr(y), y.stride(0), None, 0, w.n, int(allow_split), _stream()), "gemm_mx8")
     return y
 

@@ -5,7 +5,7 @@ synthetic-GGUF generator.  The block layouts follow the GGUF/ggml spec recorded 
 SURVEY.md §2.8 (the reference delegates these formats to its llama.cpp submodule,
 `.gitmodules:1-3`, which is not in the mount; the spec is reconstructed there).
 
-Formats: F32, F16, BF16, Q8_0, Q4_0, Q5_0, Q5_1, IQ4_NL, IQ4_XS, Q2_K, Q3_K, Q4_K, Q5_K, Q6_K.  Quantizers are simple
+Formats: F32, F16, BF16, Q8_0, Q4_0, Q5_0, Q5_1, IQ4_NL, IQ4_XS, MXFP4, Q2_K, Q3_K, Q4_K, Q5_K, Q6_K.  Quantizers are simple
 (min/max based) but produce valid blocks; dequantizers are exact implementations of
 the block math, so `dequant(bytes)` is the ground truth a kernel must reproduce.
 """
@@ -18,19 +18,20 @@ F32, F16, Q4_0, Q4_1, Q5_0, Q5_1, Q8_0, Q8_1 = 0, 1, 2, 3, 6, 7, 8, 9
 Q2_K, Q3_K, Q4_K, Q5_K, Q6_K, Q8_K = 10, 11, 12, 13, 14, 15
 IQ4_NL, IQ4_XS = 20, 23
 BF16 = 30
+MXFP4 = 39
 
 QK_K = 256
 
 TYPE_NAMES = {F32: "F32", F16: "F16", BF16: "BF16", Q8_0: "Q8_0", Q4_0: "Q4_0",
               Q2_K: "Q2_K", Q3_K: "Q3_K", Q4_K: "Q4_K", Q5_K: "Q5_K", Q6_K: "Q6_K",
-              Q5_0: "Q5_0", Q5_1: "Q5_1", IQ4_NL: "IQ4_NL", IQ4_XS: "IQ4_XS"}
+              Q5_0: "Q5_0", Q5_1: "Q5_1", IQ4_NL: "IQ4_NL", IQ4_XS: "IQ4_XS", MXFP4: "MXFP4"}
 NAME_TO_TYPE = {v: k for k, v in TYPE_NAMES.items()}
 
 # (block_elems, block_bytes)
 BLOCK = {
     F32: (1, 4), F16: (1, 2), BF16: (1, 2),
     Q8_0: (32, 34), Q4_0: (32, 18),
-    Q5_0: (32, 22), Q5_1: (32, 24), IQ4_NL: (32, 18), IQ4_XS: (256, 136),
+    Q5_0: (32, 22), Q5_1: (32, 24), IQ4_NL: (32, 18), IQ4_XS: (256, 136), MXFP4: (32, 17),
     Q2_K: (256, 84), Q3_K: (256, 110),
     Q4_K: (256, 144), Q5_K: (256, 176), Q6_K: (256, 210),
 }
@@ -546,6 +547,36 @@ def dequantize_iq4_xs(b: np.ndarray) -> np.ndarray:
     return (dl[:, :, None] * kv).reshape(-1)
 
 
+# ----------------------------------------------------------------------------- MXFP4
+# OCP microscaling fp4: a nibble is e2m1 (bit 3 the sign), the block scale one e8m0 byte.
+E2M1 = np.array([0, 0.5, 1, 1.5, 2, 3, 4, 6], np.float32)
+KVALUES_MXFP4 = np.concatenate([E2M1, -E2M1])
+
+
+def quantize_mxfp4(x: np.ndarray) -> np.ndarray:
+    """MXFP4, 17 bytes / 32 weights: u8 e, qs[16]; w = e2m1(nibble) 2^(e - 127).  OCP rounding: the
+    scale is the smallest power of two with amax / scale <= 6, each weight goes to the nearest e2m1."""
+    x = np.asarray(x, np.float32).reshape(-1, 32)
+    amax = np.abs(x).max(axis=1).astype(np.float64)
+    ex = np.where(amax > 0, np.ceil(np.log2(np.where(amax > 0, amax, 1.0) / 6.0)), 0.0)
+    e = np.clip(ex + 127, 0, 254).astype(np.int32)
+    y = np.abs(x.astype(np.float64)) * np.ldexp(1.0, 127 - e)[:, None]
+    idx = np.abs(y[..., None] - E2M1.astype(np.float64)).argmin(axis=-1).astype(np.uint8)
+    idx |= (np.signbit(x) & (idx > 0)).astype(np.uint8) << 3
+    out = np.zeros((x.shape[0], 17), np.uint8)
+    out[:, 0] = e
+    out[:, 1:] = idx[:, :16] | (idx[:, 16:] << 4)
+    return out.reshape(-1)
+
+
+def dequantize_mxfp4(b: np.ndarray) -> np.ndarray:
+    b = np.asarray(b, np.uint8).reshape(-1, 17)
+    # ggml's form: 2 e2m1 times 2^(e - 128), exact in f32 down to the subnormal e = 0, 1
+    half = np.ldexp(np.float32(1.0), b[:, 0].astype(np.int32) - 128)
+    with np.errstate(over="ignore"):   # e = 254: 12 * 2^126 is inf in f32, as in ggml
+        return (half[:, None] * (2.0 * KVALUES_MXFP4)[_nibbles32(b[:, 1:])]).astype(np.float32).reshape(-1)
+
+
 # ----------------------------------------------------------------------------- dispatch
 def quantize(x: np.ndarray, qtype: int) -> np.ndarray:
     x = np.ascontiguousarray(x, np.float32)
@@ -557,7 +588,7 @@ def quantize(x: np.ndarray, qtype: int) -> np.ndarray:
         return f32_to_bf16_bits(x.reshape(-1)).view(np.uint8).copy()
     return {Q8_0: quantize_q8_0, Q4_0: quantize_q4_0, Q2_K: quantize_q2_k, Q3_K: quantize_q3_k, Q4_K: quantize_q4_k,
             Q5_K: quantize_q5_k, Q6_K: quantize_q6_k, Q5_0: quantize_q5_0, Q5_1: quantize_q5_1,
-            IQ4_NL: quantize_iq4_nl, IQ4_XS: quantize_iq4_xs}[qtype](x)
+            IQ4_NL: quantize_iq4_nl, IQ4_XS: quantize_iq4_xs, MXFP4: quantize_mxfp4}[qtype](x)
 
 
 def dequantize(b: np.ndarray, qtype: int, shape=None) -> np.ndarray:
@@ -572,7 +603,7 @@ def dequantize(b: np.ndarray, qtype: int, shape=None) -> np.ndarray:
         y = {Q8_0: dequantize_q8_0, Q4_0: dequantize_q4_0, Q2_K: dequantize_q2_k, Q3_K: dequantize_q3_k,
              Q4_K: dequantize_q4_k,
              Q5_K: dequantize_q5_k, Q6_K: dequantize_q6_k, Q5_0: dequantize_q5_0, Q5_1: dequantize_q5_1,
-             IQ4_NL: dequantize_iq4_nl, IQ4_XS: dequantize_iq4_xs}[qtype](b)
+             IQ4_NL: dequantize_iq4_nl, IQ4_XS: dequantize_iq4_xs, MXFP4: dequantize_mxfp4}[qtype](b)
     return y.reshape(shape) if shape is not None else y
 
 
@@ -621,4 +652,10 @@ def random_blocks(rng: np.random.Generator, qtype: int, n_rows: int, n_cols: int
     elif qtype == IQ4_XS:
         # ls - 32 uniform in [-32, 31] (rms ~18.5) times a codebook entry (rms ~67)
         raw[:, 0:2] = np.full((nblk, 1), scale / (18.5 * 67.0), np.float16).view(np.uint8)
+    elif qtype == MXFP4:
+        # a uniformly drawn e2m1 code has rms 2.93; the scale byte is e0 or e0 + 1 with the odds that
+        # make the mean square of the weights scale^2
+        l = np.log2(scale / 2.926)
+        p = (4.0 ** (l - np.floor(l)) - 1.0) / 3.0
+        raw[:, 0] = np.clip(127 + int(np.floor(l)) + (rng.random(nblk) < p), 99, 128).astype(np.uint8)
     return raw.reshape(-1)

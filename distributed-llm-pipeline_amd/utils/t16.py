@@ -13,11 +13,12 @@ from . import quants as Q
 P_F16, P_Q8_0, P_Q4_K, P_Q5_K, P_Q6_K, P_Q4_0, P_BF16 = 0, 1, 2, 3, 4, 5, 6
 P_Q3_K, P_Q2_K = 8, 9   # (7 is P_I8, which has no GGUF type)
 P_Q5_0, P_Q5_1, P_IQ4_NL, P_IQ4_XS = 10, 11, 12, 13
+P_MXFP4 = 14
 CHUNK = {P_F16: 8192, P_Q8_0: 4352, P_Q4_K: 2304, P_Q5_K: 2816, P_Q6_K: 3360, P_Q4_0: 2304, P_BF16: 8192,
-         P_Q3_K: 1760, P_Q2_K: 1344, P_Q5_0: 2816, P_Q5_1: 3072, P_IQ4_NL: 2304, P_IQ4_XS: 2176}
+         P_Q3_K: 1760, P_Q2_K: 1344, P_Q5_0: 2816, P_Q5_1: 3072, P_IQ4_NL: 2304, P_IQ4_XS: 2176, P_MXFP4: 2176}
 PACK_OF = {Q.F32: P_F16, Q.F16: P_F16, Q.BF16: P_BF16, Q.Q8_0: P_Q8_0, Q.Q4_0: P_Q4_0,
            Q.Q4_K: P_Q4_K, Q.Q5_K: P_Q5_K, Q.Q6_K: P_Q6_K, Q.Q3_K: P_Q3_K, Q.Q2_K: P_Q2_K,
-           Q.Q5_0: P_Q5_0, Q.Q5_1: P_Q5_1, Q.IQ4_NL: P_IQ4_NL, Q.IQ4_XS: P_IQ4_XS}
+           Q.Q5_0: P_Q5_0, Q.Q5_1: P_Q5_1, Q.IQ4_NL: P_IQ4_NL, Q.IQ4_XS: P_IQ4_XS, Q.MXFP4: P_MXFP4}
 
 
 def _f16(b2):
@@ -109,6 +110,11 @@ def unpack_t16(packed: np.ndarray, ptype: int, n: int, k: int) -> np.ndarray:
                                 ls = ((hdr[lane, 4 + blk // 2] >> (4 * (blk % 2))) & 15) | (((sh >> (2 * blk)) & 3) << 4)
                                 d = _f16(hdr[:, 0:2]) * (ls.astype(np.float32) - 32)
                             v = d * Q.KVALUES_IQ4[idx]
+                        elif ptype == P_MXFP4:
+                            # the codebook types' nibble order; scale bytes [r] 8 B, byte 2g + h
+                            idx = (c[h * 1024 + lane * 16 + s * 4 + (j & 3)] >> (4 * (j >> 2))) & 15
+                            e = c[2048 + 8 * r + 2 * g + h].astype(np.int32)
+                            v = np.ldexp(Q.KVALUES_MXFP4[idx], e - 127)
                         elif ptype == P_Q6_K:
                             i = j >> 1
                             bit = 16 * s + ((8 + 2 * i) if (j & 1) else 2 * i)
