@@ -30,12 +30,13 @@
 //      buffer; a lane shifts its dword by 8 (l / 32), so op_sel = 2 kk selects its k-block.
 // The global loads and the LDS writes are plain C++ (the compiler's own vmcnt waits: the prefetch
 // registers are written at the top of a stage and first read behind its MFMAs); the LDS reads are
-// asm with counted lgkmcnt waits, one fragment ahead of the MFMAs.
+// asm with counted lgkmcnt waits, one fragment ahead of the MFMAs (gemm_mx_core.h: the stage, the image
+// addressing and the workgroup id remap, shared with the grouped MoE kernel of moe_mx.hip).
 // EPI_ATOMIC splits the super-block range over blockIdx.y; epilogues and output layouts are gemm3's
 // (SwiGLU: tile rows 0-7 gate, 8-15 up of the same 8 outputs).
 #include "kcommon.h"
 #include "mx8.h"
-#include "gemm_lds.h"
+#include "gemm_mx_core.h"
 #include "../runtime/kernels_api.h"
 #include "../runtime/tuning.h"
 
@@ -44,15 +45,6 @@
 
 namespace mpk {
 using namespace mp;
-
-typedef int i32x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-template <int OFF>   // ds_read_b32 with an immediate byte offset (asm, as gemm_lds.h's ds_b128o)
-__device__ __forceinline__ void ds_b32o(uint32_t& v, uint32_t addr) {
-  static_assert(OFF >= 0 && OFF < 65536, "ds offset");
-  asm volatile("ds_read_b32 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "i"(OFF) : "memory");
-}
 
 // f16 rows -> MX-FP8 rows: one workgroup per row, 8 f16 (one 16-byte load) per lane per step, so a
 // block is 4 adjacent lanes (cross-lane max), 8-byte stores, one scale byte per block
@@ -124,7 +116,7 @@ __global__ __launch_bounds__(256) void relayout_mx4_kernel(const uint8_t* W, int
 
 template <int EPI, int BM, int BF>   // BF: B operand format, 0 = e4m3 (2 KB per 64-k block), 1 = fp4 (1 KB)
 __global__ __launch_bounds__(512) void gemm_mx_kernel(const Mx8Params p, const int n_mb, const int sb_per_split) {
-  constexpr int NB = BF ? 2 : 4;     // 16-byte B pieces per lane per stage
+  constexpr int NB = MxB<BF>::NB;    // 16-byte B pieces per lane per stage
   constexpr int FM = BM / 32;        // accumulator fragments (32 rows each) per wave
   constexpr int AP = BM / 64;        // 16-byte x pieces per thread per stage
   constexpr int A_BYTES = BM * 128, STAGE = A_BYTES + 2048;   // x rows + a scale dword slot per thread (BM used)
@@ -133,9 +125,7 @@ __global__ __launch_bounds__(512) void gemm_mx_kernel(const Mx8Params p, const i
   const int tid = threadIdx.x, lane = tid & 63, cl = lane & 31, h = lane >> 5;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   // XCD-aware logical id (bijective for any grid size): the row blocks of one column group share an XCD
-  const int nwg = gridDim.x, bx = blockIdx.x;
-  const int xcd = bx & 7, q8 = nwg >> 3, r8 = nwg & 7;
-  const int lid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bx >> 3);
+  const int lid = mx_xcd_lid(blockIdx.x, gridDim.x);
   const int cg = lid / n_mb, mb = lid - cg * n_mb;
   const int m0 = mb * BM, M = p.M;
   const int sb_begin = blockIdx.y * sb_per_split, sb_end = min(sb_begin + sb_per_split, p.nsb);
@@ -144,8 +134,8 @@ __global__ __launch_bounds__(512) void gemm_mx_kernel(const Mx8Params p, const i
   // this wave's 32 columns: group grp of the B image (clamped: a wave past the last group computes a
   // copy of it and stores nothing)
   const int grp = min(cg * 8 + wave, (p.ntiles + 1) / 2 - 1);
-  const uint8_t* wb = p.W + (size_t)grp * p.nsb * (2048 * NB) + lane * 16;
-  const uint32_t* wsp = reinterpret_cast<const uint32_t*>(p.wscale) + (size_t)grp * p.nsb * 64 + lane;
+  const uint8_t* wb = MxB<BF>::pieces(p.W, grp, p.nsb, lane);
+  const uint32_t* wsp = MxB<BF>::scales(p.wscale, grp, p.nsb, lane);
   // x piece i of this thread: row (tid + 512 i) >> 3, 16-byte chunk tid & 7 (rows clamped to M - 1)
   const int xrow = tid >> 3, xch = tid & 7;
   // (threads >= BM fetch a clamped row's dword into their own, unread slot: no branch in the loop, which
@@ -157,8 +147,7 @@ __global__ __launch_bounds__(512) void gemm_mx_kernel(const Mx8Params p, const i
 #pragma unroll
     for (int i = 0; i < AP; ++i) a[i] = ld16(p.X + (size_t)min(m0 + xrow + 64 * i, M - 1) * p.ldx + 16 * xch + (size_t)s * 128);
     as = *reinterpret_cast<const uint32_t*>(xsa + 4 * s);
-#pragma unroll
-    for (int j = 0; j < NB; ++j) b[j] = ld16(wb + (size_t)s * (1024 * NB) + 1024 * j);
+    MxB<BF>::fetch(wb, s, b);
   };
   auto store_a = [&](int buf, const u32x4 (&a)[AP], uint32_t as) {
     char* A = smem + buf * STAGE;
@@ -167,79 +156,35 @@ __global__ __launch_bounds__(512) void gemm_mx_kernel(const Mx8Params p, const i
     reinterpret_cast<uint32_t*>(A + A_BYTES)[tid] = as;
   };
 
-  f32x16 acc[FM];
+  f32x16 acc[FM][1];
 #pragma unroll
   for (int i = 0; i < FM; ++i)
 #pragma unroll
-    for (int v = 0; v < 16; ++v) acc[i][v] = 0.f;
+    for (int v = 0; v < 16; ++v) acc[i][0][v] = 0.f;
 
-  // stage q of a super-block from buffer q: fragment i's rows 32 i + cl; MFMA kk's register half e holds
-  // k = 64 kk + 32 e + 16 h .. + 15 (chunk 4 kk + 2 e + h of the row).
-  // Row 32 i + cl has the swizzle of cl, so a lane's four chunk addresses (MFMA kk, register half e)
-  // are fixed and fragment / buffer are immediate offsets.  The LDS reads are asm (ds_b128o): left to
-  // the compiler, every fragment's reads are hoisted to the top of the stage (16 VGPRs each, 300
-  // spilled); fragment i + 1 is read ahead of fragment i's two MFMAs under a counted lgkmcnt.
-  uint32_t fa[4];
-#pragma unroll
-  for (int c = 0; c < 4; ++c) fa[c] = lds_addr(smem) + g3_off(cl, 4 * (c >> 1) + 2 * (c & 1) + h);
-  const uint32_t sa = lds_addr(smem) + A_BYTES + 4 * cl;
-  auto compute = [&](auto qc, const u32x4 (&b)[NB], uint32_t wsc) {
-    constexpr int Q = decltype(qc)::value;
-    i32x8 bf[2];
-#pragma unroll
-    for (int kk = 0; kk < 2; ++kk) {
-      if constexpr (BF) {   // the lane's 32 nibbles; the operand's upper four registers are not read
-        const u32x4 bl = b[kk];
-        bf[kk] = i32x8{(int)bl.x, (int)bl.y, (int)bl.z, (int)bl.w, 0, 0, 0, 0};
-      } else {
-        const u32x4 bl = b[2 * kk], bh = b[2 * kk + 1];
-        bf[kk] = i32x8{(int)bl.x, (int)bl.y, (int)bl.z, (int)bl.w, (int)bh.x, (int)bh.y, (int)bh.z, (int)bh.w};
-      }
-    }
-    u32x4 fr[2][4];
-    uint32_t asc[2];
-    auto read = [&](auto ic, u32x4 (&f)[4], uint32_t& sc) {   // 5 LDS reads
-      constexpr int I = decltype(ic)::value;
-      ds_b32o<Q * STAGE + 128 * I>(sc, sa);
-      static_for<4>([&](auto cc) { ds_b128o<Q * STAGE + 4096 * I>(f[decltype(cc)::value], fa[decltype(cc)::value]); });
-    };
-    read(std::integral_constant<int, 0>{}, fr[0], asc[0]);
-    static_for<FM>([&](auto ic) {
-      constexpr int I = decltype(ic)::value;
-      if constexpr (I + 1 < FM) {
-        read(std::integral_constant<int, I + 1>{}, fr[(I + 1) & 1], asc[(I + 1) & 1]);
-        wait_lgkm<5>();   // fragment I in, I + 1's five reads in flight
-      } else {
-        wait_lgkm<0>();
-      }
-      const int as_i = (int)(asc[I & 1] >> (8 * h));
-      static_for<2>([&](auto kc) {
-        constexpr int KK = decltype(kc)::value;
-        const u32x4 lo = fr[I & 1][2 * KK], hi = fr[I & 1][2 * KK + 1];
-        const i32x8 af = {(int)lo.x, (int)lo.y, (int)lo.z, (int)lo.w, (int)hi.x, (int)hi.y, (int)hi.z, (int)hi.w};
-        acc[I] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(af, bf[KK], acc[I], 0, BF ? 4 : 0, 2 * KK, as_i, 2 * Q + KK, (int)wsc);
-      });
-      __builtin_amdgcn_sched_barrier(0);   // the next fragment's reads stay behind these MFMAs
-    });
+  // stage q of a super-block from buffer q: gemm_mx_core.h's mx_stage (fragment i's rows 32 i + cl)
+  const MxLdsAddr la(smem, A_BYTES, cl, h);
+  auto compute = [&](auto qc, const u32x4 (&b)[1][NB], const uint32_t (&wsc)[1]) {
+    mx_stage<BF, FM, 1, STAGE, decltype(qc)::value, false>(la, h, b, wsc, acc, FM);
   };
 
-  u32x4 an[AP], b[2][NB];
-  uint32_t asn, wsc = wsp[(size_t)sb_begin * 64];
-  fetch(2 * sb_begin, an, asn, b[0]);
+  u32x4 an[AP], b[2][1][NB];
+  uint32_t asn, wsc[1] = {wsp[(size_t)sb_begin * 64]};
+  fetch(2 * sb_begin, an, asn, b[0][0]);
   store_a(0, an, asn);
   __syncthreads();
   for (int sb = sb_begin; sb < sb_end; ++sb) {
-    fetch(2 * sb + 1, an, asn, b[1]);
+    fetch(2 * sb + 1, an, asn, b[1][0]);
     compute(std::integral_constant<int, 0>{}, b[0], wsc);
     store_a(1, an, asn);   // buffer 1's last readers passed the barrier that ended the previous stage
     __syncthreads();
     const int nx = min(sb + 1, sb_end - 1);   // (the last trip re-reads its own super-block: in bounds, unused)
-    fetch(2 * nx, an, asn, b[0]);
+    fetch(2 * nx, an, asn, b[0][0]);
     const uint32_t wsn = wsp[(size_t)nx * 64];
     compute(std::integral_constant<int, 1>{}, b[1], wsc);
     store_a(0, an, asn);
     __syncthreads();
-    wsc = wsn;
+    wsc[0] = wsn;
   }
 
   // epilogue: lane holds C[row 32 i + 8 (v >> 2) + 4 h + (v & 3)][col cl] of the wave's 32 columns
@@ -251,9 +196,9 @@ __global__ __launch_bounds__(512) void gemm_mx_kernel(const Mx8Params p, const i
     for (int i = 0; i < FM; ++i)
 #pragma unroll
       for (int v = 0; v < 16; ++v) {
-        const float other = __shfl_xor(acc[i][v], 8);
+        const float other = __shfl_xor(acc[i][0][v], 8);
         const int m = rowb + 32 * i + 8 * (v >> 2) + (v & 3);
-        if ((cl & 8) == 0 && m < M && o < p.n_valid) p.H[(size_t)m * p.ldh + o] = sat_f16(silu(acc[i][v]) * other);
+        if ((cl & 8) == 0 && m < M && o < p.n_valid) p.H[(size_t)m * p.ldh + o] = sat_f16(silu(acc[i][0][v]) * other);
       }
   } else if (n < p.n_valid) {
 #pragma unroll
@@ -263,8 +208,8 @@ __global__ __launch_bounds__(512) void gemm_mx_kernel(const Mx8Params p, const i
         const int m = rowb + 32 * i + 8 * (v >> 2) + (v & 3);
         if (m < M) {
           float* dst = p.Y + (size_t)m * p.ldy + n;
-          if constexpr (EPI == EPI_ATOMIC) unsafeAtomicAdd(dst, acc[i][v]);
-          else *dst = acc[i][v];
+          if constexpr (EPI == EPI_ATOMIC) unsafeAtomicAdd(dst, acc[i][0][v]);
+          else *dst = acc[i][0][v];
         }
       }
   }

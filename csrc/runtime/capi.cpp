@@ -369,6 +369,26 @@ int mp_op_gemm_mx4(int epi, const void* W, const void* ws, int ntiles, int nsb, 
   API_CATCH(-1)
 }
 
+// grouped expert GEMM on the scaled MFMA (moe_mx.hip): mp_op_moe_gemm4's operands with the packed
+// weights replaced by E B images (bfmt 0: mp_op_requant_mx8's, 1: mp_op_relayout_mx4's) and the f16 rows
+// by mp_op_quant_mx8's e4m3 rows + scale bytes
+int mp_op_moe_gemm_mx(int epi, const void* W, int64_t estride_w, const void* ws, int64_t estride_s, int bfmt, int ntiles,
+                      int nsb, const void* Q, int ldq, const void* S, int lds, int x_per_slot, int M, int E, int k,
+                      const void* counts, const void* lists, int list_cap, const void* weights, void* Y, int ldy, void* H,
+                      int ldh, int n_valid, void* stream) {
+  API_TRY
+  MoeMxParams q{};
+  q.W = (const uint8_t*)W; q.estride_w = (size_t)estride_w; q.wscale = (const uint8_t*)ws; q.estride_s = (size_t)estride_s;
+  q.bfmt = bfmt; q.ntiles = ntiles; q.nsb = nsb; q.X = (const uint8_t*)Q; q.ldx = ldq; q.xscale = (const uint8_t*)S; q.ldxs = lds;
+  q.x_per_slot = x_per_slot; q.M = M; q.E = E; q.k = k;
+  q.counts = (const int32_t*)counts; q.lists = (const int32_t*)lists; q.list_cap = list_cap;
+  q.weights = (const float*)weights; q.Y = (float*)Y; q.ldy = ldy; q.H = (f16*)H; q.ldh = ldh; q.n_valid = n_valid;
+  launch_moe_gemm_mx(epi, q, (hipStream_t)stream);
+  HIP_OK(hipGetLastError());
+  return 0;
+  API_CATCH(-1)
+}
+
 int mp_set_knob(const char* name, int value) {
   API_TRY
   set_knob(name, value);

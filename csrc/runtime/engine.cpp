@@ -108,7 +108,7 @@ double synth_layer_bytes(const ModelConfig& c, const std::string& ftype, int li)
   return b(t.q, q, d) + b(t.k, kv, d) + b(t.v, kv, d) + b(t.o, d, q) + ffn * std::max(1, c.n_expert);
 }
 
-// int8_gemm (HipStage::build_i8_copies): an int8 copy of every quantized non-MoE projection, one
+// int8_gemm (HipStage::build_i8_copies): an int8 copy of every quantized projection of the dense layers, one
 // byte per weight of the 16-row x 256-k padded packing plus a float row scale.  These bytes live
 // next to the weights, so the KV budget and the --gpu-mem check must see them.
 double i8_copy_bytes(int t, int64_t n, int64_t k) {
@@ -128,22 +128,39 @@ double mx8_copy_bytes(int t, int64_t n, int64_t k) {
 
 using CopyBytes = double (*)(int, int64_t, int64_t);
 
+// A MoE layer: int8_gemm skips it whole (build_i8_copies); mx8_gemm (build_mx8_copies) images its attention
+// projections like a dense layer's and every expert's fused gate/up [2F][d] and down [d][F]
 double synth_layer_copy_bytes(const ModelConfig& c, const std::string& ftype, int li, CopyBytes cb) {
-  if (c.n_expert > 0) return 0;   // MoE experts keep their own kernels (no copy)
   const SyntheticTypes t = SyntheticTypes::from_ftype(ftype, li, c.n_layer);
   const int64_t d = c.d_model, q = c.q_dim(), kv = c.kv_dim(), f = c.d_ff;
-  return cb(t.q, q, d) + cb(t.k, kv, d) + cb(t.v, kv, d) + cb(t.o, d, q) + cb(t.gate, f, d) + cb(t.up, f, d) + cb(t.down, d, f);
+  const double attn = cb(t.q, q, d) + cb(t.k, kv, d) + cb(t.v, kv, d) + cb(t.o, d, q);
+  if (c.n_expert > 0) return cb == mx8_copy_bytes ? attn + c.n_expert * (cb(t.gate, 2 * f, d) + cb(t.down, d, f)) : 0;
+  return attn + cb(t.gate, f, d) + cb(t.up, f, d) + cb(t.down, d, f);
 }
 
 double gguf_layer_copy_bytes(const GgufFile& g, int li, CopyBytes cb) {
   double b = 0;
   const std::string p = "blk." + std::to_string(li) + ".";
-  if (g.tensor(p + "ffn_gate_inp.weight")) return 0;   // MoE layer: build_i8_copies / build_mx8_copies skip it whole
+  const bool moe = g.tensor(p + "ffn_gate_inp.weight") != nullptr;
+  if (moe && cb != mx8_copy_bytes) return 0;
   for (const char* nm : {"attn_q", "attn_k", "attn_v", "attn_output", "ffn_gate", "ffn_up", "ffn_down"}) {
     const GgufTensor* t = g.tensor(p + nm + ".weight");
     if (t && t->ne.size() >= 2) b += cb(t->type, t->ne[1], t->ne[0]);
   }
-  return b;
+  if (!moe) return b;
+  // experts: stacked ffn_*_exps [E][F][d] tensors, or legacy per-expert ffn_*.<e>.weight (as load_layer)
+  if (const GgufTensor* sg = g.tensor(p + "ffn_gate_exps.weight")) {
+    const GgufTensor* dn = g.tensor(p + "ffn_down_exps.weight");
+    if (!dn || sg->ne.size() < 3 || dn->ne.size() < 3) return b;
+    return b + (double)sg->ne[2] * (cb(sg->type, 2 * sg->ne[1], sg->ne[0]) + cb(dn->type, dn->ne[1], dn->ne[0]));
+  }
+  for (int e = 0;; ++e) {
+    const std::string s = "." + std::to_string(e) + ".weight";
+    const GgufTensor* gt = g.tensor(p + "ffn_gate" + s);
+    const GgufTensor* dn = g.tensor(p + "ffn_down" + s);
+    if (!gt || !dn || gt->ne.size() < 2 || dn->ne.size() < 2) return b;
+    b += cb(gt->type, 2 * gt->ne[1], gt->ne[0]) + cb(dn->type, dn->ne[1], dn->ne[0]);
+  }
 }
 
 }  // namespace

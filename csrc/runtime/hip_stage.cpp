@@ -475,39 +475,49 @@ void HipStage::build_i8_copies() {
 // An MXFP4 tensor is MX already: its nibbles and scale bytes are laid out as an fp4 B image instead
 // (4.25 bits per weight, nothing re-quantized)
 void HipStage::build_mx8_copies() {
-  auto each = [&](const std::function<void(PackedMat&)>& f) {
+  // f(matrix, count, source stride, image stride out, scale stride out): a dense projection (count 1) or a
+  // MoE layer's E expert matrices, whose images are stacked at a fixed stride for the grouped kernel
+  // (moe_mx.hip); the experts' T16 images stay (the M <= 64 MoE GEMV and the deterministic mode read them)
+  auto each = [&](const std::function<void(PackedMat&, int, size_t, size_t*, size_t*)>& f) {
     for (LayerW& L : layers_) {
-      if (L.moe) continue;
-      for (MatSeg& sg : L.qkv) f(sg.m);
-      f(L.wo);
-      if (L.fused_gateup) f(L.gateup);
-      else { f(L.gate); f(L.up); }
-      f(L.down);
+      for (MatSeg& sg : L.qkv) f(sg.m, 1, 0, nullptr, nullptr);
+      f(L.wo, 1, 0, nullptr, nullptr);
+      if (L.moe) {
+        f(L.ex.gateup, cfg_.n_expert, L.ex.gateup_stride, &L.ex.gateup_mx_stride, &L.ex.gateup_mxs_stride);
+        f(L.ex.down, cfg_.n_expert, L.ex.down_stride, &L.ex.down_mx_stride, &L.ex.down_mxs_stride);
+        continue;
+      }
+      if (L.fused_gateup) f(L.gateup, 1, 0, nullptr, nullptr);
+      else { f(L.gate, 1, 0, nullptr, nullptr); f(L.up, 1, 0, nullptr, nullptr); }
+      f(L.down, 1, 0, nullptr, nullptr);
     }
   };
   size_t maxe = 0;
-  each([&](PackedMat& m) {
+  each([&](PackedMat& m, int, size_t, size_t*, size_t*) {
     if (m.d && !is16(m.ptype) && m.ptype != P_MXFP4) maxe = std::max(maxe, (size_t)m.dims.ntiles * 16 * m.dims.nsb * 256);
   });
   f16* tmp = nullptr;
   if (maxe) HIP_OK(hipMalloc(&tmp, maxe * 2));
   size_t bytes = 0, bytes4 = 0;
-  each([&](PackedMat& m) {
-    if (!m.d || is16(m.ptype)) return;
+  each([&](PackedMat& m, int E, size_t src_stride, size_t* wstride, size_t* sstride) {
+    if (!m.d || is16(m.ptype)) return;   // (16-bit experts get no image: they stay on gemm4)
     const int nt = (int)m.dims.ntiles, nsb = (int)m.dims.nsb;
-    if (m.ptype == P_MXFP4) {
-      m.mx = (uint8_t*)dmalloc(mx4_weight_bytes(nt, nsb));
-      m.mx_s = (uint8_t*)dmalloc(mx8_scale_bytes(nt, nsb));
-      m.mx_fmt = 1;
-      launch_relayout_mx4(m.d, nt, nsb, m.mx, m.mx_s, stream_);
-      bytes4 += mx4_weight_bytes(nt, nsb) + mx8_scale_bytes(nt, nsb);
-      return;
+    const bool fp4 = m.ptype == P_MXFP4;
+    const size_t wb = fp4 ? mx4_weight_bytes(nt, nsb) : mx8_weight_bytes(nt, nsb), sb = mx8_scale_bytes(nt, nsb);
+    m.mx = (uint8_t*)dmalloc(wb * E);
+    m.mx_s = (uint8_t*)dmalloc(sb * E);
+    m.mx_fmt = fp4 ? 1 : 0;
+    if (wstride) { *wstride = wb; *sstride = sb; }
+    for (int e = 0; e < E; ++e) {
+      const uint8_t* src = m.d + (size_t)e * src_stride;
+      if (fp4) {
+        launch_relayout_mx4(src, nt, nsb, m.mx + e * wb, m.mx_s + e * sb, stream_);
+      } else {
+        launch_unpack(m.ptype, src, nt, nsb, tmp, nsb * 256, stream_);
+        launch_requant_mx8(tmp, nsb * 256, (int)m.dims.N, nt, nsb, m.mx + e * wb, m.mx_s + e * sb, stream_);
+      }
     }
-    launch_unpack(m.ptype, m.d, nt, nsb, tmp, nsb * 256, stream_);
-    m.mx = (uint8_t*)dmalloc(mx8_weight_bytes(nt, nsb));
-    m.mx_s = (uint8_t*)dmalloc(mx8_scale_bytes(nt, nsb));
-    launch_requant_mx8(tmp, nsb * 256, (int)m.dims.N, nt, nsb, m.mx, m.mx_s, stream_);
-    bytes += mx8_weight_bytes(nt, nsb) + mx8_scale_bytes(nt, nsb);
+    (fp4 ? bytes4 : bytes) += (wb + sb) * E;
   });
   HIP_OK(hipStreamSynchronize(stream_));
   if (tmp) HIP_OK(hipFree(tmp));
@@ -571,6 +581,10 @@ void HipStage::alloc_runtime() {
     moe_w_ = (float*)zalloc((size_t)scratch_rows_ * k * 4);
     moe_h_ = (f16*)zalloc((size_t)scratch_rows_ * k * Kff_ * 2);
     if (opt_.deterministic) moe_yslot_ = (float*)zalloc((size_t)std::min(scratch_rows_, 64) * k * cfg_.d_model * 4);
+    if (xqe_) {   // mx8_gemm with wide rounds: the grouped down GEMM reads moe_h_ as MX-FP8 rows
+      moe_hq_ = (uint8_t*)zalloc((size_t)scratch_rows_ * k * Kff_);
+      moe_hqe_ = (uint8_t*)zalloc((size_t)scratch_rows_ * k * (Kff_ / 32));
+    }
   }
   int split = opt_.attn_split_len;
   if (split <= 0) {
@@ -1130,6 +1144,31 @@ void HipStage::moe_ffn_rows(const LayerW& L, int r0, int M, hipStream_t st, floa
   dp.ntiles = (int)L.ex.down.dims.ntiles; dp.nsb = (int)L.ex.down.dims.nsb;
   dp.X = moe_h_; dp.ldx = Kff_; dp.x_per_slot = 1; dp.H = nullptr; dp.ldh = 0;
   dp.Y = x + (size_t)r0 * d; dp.ldy = d; dp.weights = moe_w_; dp.n_valid = d;
+  if (grouped && moe_hq_ && L.ex.gateup.mx && L.ex.down.mx && moe_mx_route(M, k, E)) {
+    // mx8_gemm, from 128 routed rows per expert on average (moe_mx_route: below, gemm4's MoE mode measured
+    // faster): both projections on the scaled MFMA (moe_mx.hip) against the experts' B images.  xn_'s M rows
+    // as MX-FP8 once (norm_x's side output when it ran), then moe_h_'s M k slot rows for the down GEMM: the
+    // columns past F are zero (moe_h_ is zero-allocated, the epilogue writes o < F only)
+    const int gk = gp.nsb * 256;
+    uint8_t* xq = reinterpret_cast<uint8_t*>(xq_);
+    if (xq_src_ != (const void*)xn || xq_rows_ != M) {
+      launch_quant_rows_mx8(xn, Kd_, M, gk, xq, xq_ld_, xqe_, xq_ld_ / 32, st);
+      xq_src_ = xn;
+      xq_rows_ = M;
+    }
+    MoeMxParams q{};
+    q.W = L.ex.gateup.mx; q.estride_w = L.ex.gateup_mx_stride; q.wscale = L.ex.gateup.mx_s; q.estride_s = L.ex.gateup_mxs_stride;
+    q.bfmt = L.ex.gateup.mx_fmt; q.X = xq; q.ldx = xq_ld_; q.xscale = xqe_; q.ldxs = xq_ld_ / 32; q.x_per_slot = 0;
+    q.M = M; q.E = E; q.k = k; q.counts = moe_counts_; q.lists = moe_lists_; q.list_cap = rp.list_cap; q.weights = moe_w_;
+    q.H = moe_h_; q.ldh = Kff_; q.ntiles = gp.ntiles; q.nsb = gp.nsb; q.n_valid = F;
+    launch_moe_gemm_mx(EPI_SWIGLU, q, st);
+    launch_quant_rows_mx8(moe_h_, Kff_, M * k, dp.nsb * 256, moe_hq_, Kff_, moe_hqe_, Kff_ / 32, st);
+    q.W = L.ex.down.mx; q.estride_w = L.ex.down_mx_stride; q.wscale = L.ex.down.mx_s; q.estride_s = L.ex.down_mxs_stride;
+    q.bfmt = L.ex.down.mx_fmt; q.X = moe_hq_; q.ldx = Kff_; q.xscale = moe_hqe_; q.ldxs = Kff_ / 32; q.x_per_slot = 1;
+    q.H = nullptr; q.ldh = 0; q.Y = dp.Y; q.ldy = d; q.ntiles = dp.ntiles; q.nsb = dp.nsb; q.n_valid = d;
+    launch_moe_gemm_mx(EPI_ATOMIC, q, st);
+    return;
+  }
   if (grouped) {
     if (!launch_moe_gemm4(L.ex.gateup.ptype, EPI_SWIGLU, gp, st) || !launch_moe_gemm4(L.ex.down.ptype, EPI_ATOMIC, dp, st))
       throw std::runtime_error("moe_ffn: grouped GEMM does not support the expert weight type");

@@ -78,7 +78,9 @@ struct ExpertW {  // MoE layer weights (Mixtral); experts stored back to back
   size_t gateup_stride = 0;
   PackedMat down;              // E down matrices
   size_t down_stride = 0;
-  PackedMat router;            // [E][d] router (f16 packed)
+  // mx8_gemm: gateup.mx / down.mx hold E B images (mx_s: E scale images) at these strides
+  size_t gateup_mx_stride = 0, gateup_mxs_stride = 0, down_mx_stride = 0, down_mxs_stride = 0;
+  PackedMat router;           // [E][d] router (f16 packed)
   f16* router_dense = nullptr;  // the router unpacked to dense f16 [E_pad][nsb*256] (launch_router_logits)
 };
 
@@ -227,6 +229,8 @@ class HipStage : public Stage {
   int8_t* xq_ = nullptr; float* xqs_ = nullptr; int xq_ld_ = 0;
   uint8_t* xqe_ = nullptr;   // [rows][xq_ld_ / 32] e8m0 bytes
   const void* xq_src_ = nullptr; int xq_rows_ = 0;   // the f16 rows xq_ currently holds (set by norm_x / the quant)
+  // mx8_gemm on a MoE stage: moe_h_'s rows as MX-FP8 for the grouped down GEMM, [scratch_rows_ * k][Kff_] + scales
+  uint8_t* moe_hq_ = nullptr; uint8_t* moe_hqe_ = nullptr;
   bool attention_o(int li, const Fwd& f, float* x, bool pre = false);
   void attention(int li, const Fwd& f, bool qkv_deferred, bool pre = false);
   // a chunk of PrefillSeg::bidir segments, after rope_kv: launch_attn_encode over q_ and the layer's pages

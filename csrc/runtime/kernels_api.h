@@ -277,6 +277,27 @@ struct Mx8Params {
   int bfmt = 0;                               // B operand format: 0 = e4m3, 1 = fp4 (e2m1)
 };
 void launch_gemm_mx8(int epi, const Mx8Params& p, hipStream_t st, bool allow_split = true);
+// Grouped MoE expert GEMM on the same instruction (moe_mx.hip): expert e's routed rows (lists[e][0 ..
+// counts[e]), slot ids token * k + j) times its B image, E images estride_w / estride_s bytes apart.
+// EPI_SWIGLU: H[slot] = SwiGLU(x[slot / k] W_e^T); EPI_ATOMIC: Y[slot / k] += weights[slot] * (x[slot] W_e^T)
+// (x_per_slot: x rows are slots).  Throws, naming the problem, on operands the kernel cannot take.
+struct MoeMxParams {
+  const uint8_t* W; size_t estride_w;         // E images of launch_requant_mx8 (bfmt 1: launch_relayout_mx4)
+  const uint8_t* wscale; size_t estride_s;
+  int bfmt;                                   // 0 = e4m3, 1 = fp4 (e2m1)
+  const uint8_t* X; int ldx;                  // e4m3 rows (nsb * 256 columns used)
+  const uint8_t* xscale; int ldxs;            // scale bytes per row (ldxs % 4 == 0)
+  int x_per_slot;                             // x row = x_per_slot ? slot : slot / k
+  int M, E, k;                                // tokens of the call, experts (<= 128), experts per token (<= 8)
+  const int32_t* counts; const int32_t* lists; int list_cap;   // list_cap >= M
+  const float* weights;                       // [M * k] router weights (EPI_ATOMIC)
+  float* Y; int ldy;                          // EPI_ATOMIC
+  f16* H; int ldh;                            // EPI_SWIGLU
+  int ntiles, nsb, n_valid;
+};
+int moe_mx_tile_rows(int M, int k, int E);    // the kernel's row tile (128 | 64) for a launch shape
+bool moe_mx_route(int M, int k, int E);       // the stages' choice: this kernel (true) or gemm4's MoE mode (host-only)
+void launch_moe_gemm_mx(int epi, const MoeMxParams& p, hipStream_t st);
 
 struct AttnParams {
   const f16* q;          // [M][Hq][Dp]

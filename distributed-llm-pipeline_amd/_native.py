@@ -73,6 +73,9 @@ _SIGS = {
     "mp_op_relayout_mx4": ([c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p], c_int),
     "mp_op_gemm_mx4": ([c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_int,
                         c_void_p, c_int, c_int, c_int, c_void_p], c_int),
+    "mp_op_moe_gemm_mx": ([c_int, c_void_p, ctypes.c_longlong, c_void_p, ctypes.c_longlong, c_int, c_int, c_int, c_void_p,
+                           c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p,
+                           c_void_p, c_int, c_void_p, c_int, c_int, c_void_p], c_int),
     "mp_set_knob": ([c_char_p, c_int], c_int),
     "mp_reset_knob": ([c_char_p], c_int),
     "mp_op_unpack": ([c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p], c_int),

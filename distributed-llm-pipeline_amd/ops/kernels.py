@@ -369,6 +369,30 @@ def gemm_mx8(w: "Mx8Weight | Mx4Weight", x: torch.Tensor | None = None, epi: int
     return y
 
 
+def stack_mx_experts(ws: "list[Mx8Weight] | list[Mx4Weight]"):
+    """The B images of E experts of one shape as (images, estride_w, scales, estride_s): one uint8 tensor each,
+    expert e at e * estride bytes (moe_gemm_mx's weight operands)."""
+    assert len({(w.ntiles, w.nsb, bool(getattr(w, "fp4", False))) for w in ws}) == 1
+    return (torch.stack([w.dev for w in ws]).view(-1), ws[0].dev.numel(),
+            torch.stack([w.scales for w in ws]).view(-1), ws[0].scales.numel())
+
+
+def moe_gemm_mx(w_dev: torch.Tensor, estride_w: int, w_scales: torch.Tensor, estride_s: int, fp4: bool, ntiles: int,
+                nsb: int, n_valid: int, epi: int, xq: tuple[torch.Tensor, torch.Tensor], M: int, E: int, k: int, counts,
+                lists, weights=None, *, x_per_slot: bool = False, h: torch.Tensor | None = None,
+                y: torch.Tensor | None = None, list_cap: int | None = None, bfmt: int | None = None) -> None:
+    """Grouped expert GEMM on the scaled MFMA (moe_mx.hip) over E B images (stack_mx_experts): outputs and
+    routing operands as moe_gemm; xq = quant_rows_mx8 of the f16 rows moe_gemm would take.  list_cap / bfmt
+    override what the tensors imply (the launcher's own checks then answer)."""
+    q, s = xq
+    N.check(N.lib().mp_op_moe_gemm_mx(epi, _ptr(w_dev), estride_w, _ptr(w_scales), estride_s,
+                                      int(fp4) if bfmt is None else bfmt, ntiles, nsb, _ptr(q), q.stride(0), _ptr(s),
+                                      s.stride(0), int(x_per_slot), M, E, k, _ptr(counts), _ptr(lists),
+                                      lists.shape[1] if list_cap is None else list_cap, _ptr(weights), _ptr(y),
+                                      y.stride(0) if y is not None else 0, _ptr(h), h.stride(0) if h is not None else 0,
+                                      n_valid, _stream()), "moe_gemm_mx")
+
+
 def set_gemm3_tuning(bm: int = 0, bn: int = 0, nsplit: int = 0, split_wg: int = 0) -> None:
     """Force the v3 GEMM's tile rows / columns (128 | 256) and ATOMIC split-K factor (0 = auto);
     split_wg: workgroup target of the automatic split.  0 restores a knob to the process's own value
